@@ -11,8 +11,13 @@ re-linearisation (K1 + K2).  Inputs are resident in HBM when the timed region st
 N GPUs: weak scaling — the graph is N x C3 (N*100k poses / N*300k edges), edges sharded contiguously across ranks,
 one RCCL all-reduce per CG matvec inside libpgo; `value` = LM iterations/s x N (C3-sized graph-iterations per second).
 
-Extra JSON objects: `roofline` (K1, HIP events on the library's own stream) and `cpu_baseline` (the CPU oracle = a
-restatement of the reference's Ceres path, timed on the host cores on a bounded sample; rank 0, N = 1 only).
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the timed solve's chi2 against the
+independent CPU trajectory).  `--full` adds everything that takes runs of its own: the per-kernel / `roofline` figures (HIP events on
+the library's own stream), the leg including transfers, K1 out of cache, Ceres' decision rule, the solve to convergence, `cpu_baseline`
+(the CPU oracle = a restatement of the reference's Ceres path, timed on the host cores on a bounded sample; rank 0, N = 1 only) and,
+with several ranks, the `c5_strong` leg.
+
+`--dump-outputs DIR` writes what the timed path hands its caller after the last timed step (dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -172,11 +177,38 @@ def cpu_baseline(sample_poses, max_iters, budget_s):
     }
 
 
+DUMP_BYTES_MAX = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, q, t, s, summ):
+    """--dump-outputs: what a caller of the timed path receives from pgo_solve_end after the last timed step — the state (quaternions
+    x, y, z, w and translations per keyframe, one weight per switchable loop) and the summary's costs — as float64 DIR/<name>.npy.  The
+    inputs are the same for the same arguments (seeded generator, odometry initial guess), so two builds compare array by array.  Above
+    64 MB in all (graphs larger than C3 x 2) the keyframes and the switches are a fixed sample: seed 0, the same for the same graph."""
+    n, m = q.size // 4, s.size
+    arrays = {"quaternions": q.reshape(n, 4), "translations": t.reshape(n, 3), "switches": s,
+              "cost_per_iteration": np.array([summ.iterations[k].cost for k in range(summ.num_logged)]),     # entry 0 = the initial cost
+              "final_cost": np.array([summ.final_cost])}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        keep = 0.98 * DUMP_BYTES_MAX / total      # (room for the .npy headers)
+        rng = np.random.default_rng(0)
+        kp = np.sort(rng.choice(n, int(n * keep), replace=False))
+        ks = np.sort(rng.choice(m, int(m * keep), replace=False))
+        arrays.update(quaternions=arrays["quaternions"][kp], translations=arrays["translations"][kp], switches=s[ks])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)     # the reference's LM budget per trigger: max_num_iterations = 10
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure as well: per-kernel / roofline timings, the leg including transfers, K1 out of cache, "
+                    "Ceres' decision rule, the solve to convergence, the CPU baseline and (several ranks) the c5_strong leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they computed (final state and costs) as DIR/<name>.npy, float64, at most 64 MB")
     ap.add_argument("--cg-tol", type=float, default=None, help="PCG relative tolerance (default: library default)")
     ap.add_argument("--cg-max", type=int, default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -369,51 +401,56 @@ def main():
         elapsed = float(tt.item())
 
     shard_counters = P.sharding_stats().as_dict() if world > 1 else None
-    # ---- roofline of the dominant data-parallel kernel (K1), measured live with HIP events on the library stream
-    k1_ms, k1_bytes = P.time_kernel(0, 50)
-    k2_ms, k2_bytes = P.time_kernel(1, 20)
-    if world == 1:
-        cg_ms, cg_bytes = P.time_kernel(2, 50)
-        mv_ms, mv_bytes = P.time_kernel(4, 50)
-        try:
-            up_ms, up_bytes = P.time_kernel(5, 50)
-        except capi.PgoError:      # single-reduction form: the update cannot run without its matvec (its head would see stale partial sums): iteration minus matvec
-            up_ms, up_bytes = cg_ms - mv_ms, cg_bytes - mv_bytes
-    else:      # (the single-GPU form of the PCG iteration is not what several ranks run: no such figure for them)
-        cg_ms = cg_bytes = mv_ms = mv_bytes = up_ms = up_bytes = None
-    k1c_ms, k1c_bytes = P.time_kernel(3, 50)
+    cg_ms = cg_bytes = mv_ms = mv_bytes = up_ms = up_bytes = None
     mg_ms = mg_bytes = mgc_ms = mgc_bytes = None
-    try:      # one multigrid-preconditioned PCG iteration on the current LM system (graphs with a hierarchy: >= mg_min_keyframes keyframes, one GPU)
+    if args.full:      # (pgo_time_kernel leaves the keyframe state of the open solve as it is: what solve_end returns below is the timed steps' result)
+        # ---- roofline of the dominant data-parallel kernel (K1), measured live with HIP events on the library stream
+        k1_ms, k1_bytes = P.time_kernel(0, 50)
+        k2_ms, k2_bytes = P.time_kernel(1, 20)
         if world == 1:
-            mg_ms, mg_bytes = P.time_kernel(6, 50)
-            mgc_ms, mgc_bytes = P.time_kernel(7, 50)
-    except capi.PgoError:
-        pass
+            cg_ms, cg_bytes = P.time_kernel(2, 50)
+            mv_ms, mv_bytes = P.time_kernel(4, 50)
+            try:
+                up_ms, up_bytes = P.time_kernel(5, 50)
+            except capi.PgoError:      # single-reduction form: the update cannot run without its matvec (its head would see stale partial sums): iteration minus matvec
+                up_ms, up_bytes = cg_ms - mv_ms, cg_bytes - mv_bytes
+        # (several ranks: the single-GPU form of the PCG iteration is not what they run: no such figure for them)
+        k1c_ms, k1c_bytes = P.time_kernel(3, 50)
+        try:      # one multigrid-preconditioned PCG iteration on the current LM system (graphs with a hierarchy: >= mg_min_keyframes keyframes, one GPU)
+            if world == 1:
+                mg_ms, mg_bytes = P.time_kernel(6, 50)
+                mgc_ms, mgc_bytes = P.time_kernel(7, 50)
+        except capi.PgoError:
+            pass
     qf, tf, sf, summ = P.solve_end()
     P_linear_solver, P_cg_tol, P_cg_max = P.options.linear_solver, P.options.cg_rel_tolerance, P.options.cg_max_iterations
     summ_cg_total = int(summ.cg_iterations)
     summ_cg_mg = int(summ.cg_iterations_multigrid)
     if fresh:
         drop_problem(P)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, qf, tf, sf, summ)
 
     # ---- the same K iterations once more INCLUDING the host<->device transfers and the write-back; never `value`
-    if fresh:
-        P = make_problem()   # cold handle: the edge upload and the device graph build of a first solve are part of this figure
-    barrier(); sync()
-    t_incl = time.perf_counter()
-    P.solve_begin(q0, t0_, s0)
-    for _ in range(args.steps):
-        P.lm_step(ignore_termination=True)
-    P.solve_end()
-    sync(); barrier()
-    elapsed_incl = time.perf_counter() - t_incl
-
-    drop_problem(P)
+    elapsed_incl = None
+    if args.full:
+        if fresh:
+            P = make_problem()   # cold handle: the edge upload and the device graph build of a first solve are part of this figure
+        barrier(); sync()
+        t_incl = time.perf_counter()
+        P.solve_begin(q0, t0_, s0)
+        for _ in range(args.steps):
+            P.lm_step(ignore_termination=True)
+        P.solve_end()
+        sync(); barrier()
+        elapsed_incl = time.perf_counter() - t_incl
+    if args.full or not fresh:
+        drop_problem(P)
 
     # ---- K1 once more where its output cannot sit in the 256 MiB Infinity Cache: C3's 194 MB of Jacobian blocks are absorbed by it (plain
     # stores), so the C3 figure is an HBM + cache number; 400k keyframes / 1.2M edges write 775 MB with non-temporal stores
     k1_big = None
-    if scale == 1 and world == 1 and not strong and rank == 0 and not args.no_k1_out_of_cache:
+    if args.full and scale == 1 and world == 1 and not strong and rank == 0 and not args.no_k1_out_of_cache:
         gb = graphgen.generate(400000, 400000, odom_f_max=2, seed=3)
         Pb = capi.problem_from_graph(gb, switchable=True, device_id=device_index)
         Pb.solve_begin(gb.init_q, gb.init_t, np.full(gb.n_loops, 0.99))
@@ -426,7 +463,7 @@ def main():
     # ---- the same K iterations under Ceres' EXACT decision rule: cg_early_tolerance = cg_mid_tolerance = 0 — every step's linear system is solved to
     # cg_rel_tolerance before it is accepted or rejected, as an exact factorisation would.  Outside the timed `value`; reported beside it.
     ceres_rule = None
-    if scale == 1 and world == 1 and not strong and not args.no_ceres_rule:
+    if args.full and scale == 1 and world == 1 and not strong and not args.no_ceres_rule:
         try:
             Pe = capi.problem_from_graph(g, switchable=True, device_id=device_index, max_num_iterations=10 ** 6, cg_early_tolerance=0.0, cg_mid_tolerance=0.0, **opt)
             Pe.solve_begin(q0, t0_, s0)
@@ -465,7 +502,7 @@ def main():
     # region, with the reference's options left at Ceres' defaults (function_tolerance 1e-6) until the minimiser stops by itself, against the independent CPU run to
     # convergence (tests/golden/c3_converged.json: oracle Jacobians + scipy CG to 1e-12 + Python restatement of the Ceres loop; nothing of libpgo)
     chi2_conv = None
-    if scale == 1 and world == 1 and not strong and args.poses_per_gpu == C3_POSES:
+    if args.full and scale == 1 and world == 1 and not strong and args.poses_per_gpu == C3_POSES:
         try:
             with open(os.path.join(ROOT, "tests", "golden", "c3_converged.json")) as f:
                 gold = json.load(f)
@@ -494,8 +531,8 @@ def main():
     traffic_note = {}
 
     def static_traffic(name, getter):
-        if not (scale == 1 and world == 1 and not strong and args.poses_per_gpu == C3_POSES):
-            return None        # the PMC passes were taken on C3 x 1 only
+        if not (args.full and scale == 1 and world == 1 and not strong and args.poses_per_gpu == C3_POSES):
+            return None        # the PMC passes were taken on C3 x 1 only (and stand beside the rooflines of --full)
         try:
             with open(os.path.join(ROOT, "profiles", name)) as f:
                 pj = json.load(f)
@@ -575,15 +612,12 @@ def main():
             "weak_graph_note": ("N x C3 as ONE graph is a harder problem at every N: 10 LM iterations on one MI355X take 0.092 / 0.43 / 0.98 / 2.25 / 10.7 s at N = 1 / 2 / 4 / 6 / 8 "
                                 "(every step of the 800 000-keyframe graph is accepted, the trust region opens to 2.4e7, 20 441 PCG iterations instead of 798); the c5_strong leg — the same "
                                 "graph at every N — isolates the solver's scaling") if world > 1 and not strong else None,
-            "libpgo_sha256": lib_sha, "static_traffic_notes": traffic_note or None,
+            "libpgo_sha256": lib_sha,
             # the hash of the sources the loaded library was built from (compiled in by _build.py) next to the hash of this checkout's sources: equal = built from this tree
             "libpgo_sources_sha256": capi.build_info()[0], "checkout_sources_sha256": capi.build_info()[1],
-            "lm_iters_per_s_raw": ips, "c5_strong": None,
-            "value_ceres_decision_rule": ceres_rule,
-            "lm_iters_per_s_including_transfers": args.steps / elapsed_incl * scale,   # upload of the state, K iterations, write-back (rank 0's clock)
+            "lm_iters_per_s_raw": ips,
             "chi2_initial": 2.0 * summ.initial_cost, "chi2_final": 2.0 * summ.final_cost,
             "chi2_ref": chi2_ref, "chi2_rel_diff": chi2_rel,   # reference = the CPU trajectory after the same number of LM iterations (null: no golden for this workload / step count)
-            "chi2_converged_rel_diff": None if not chi2_conv or "error" in chi2_conv else chi2_conv["chi2_converged_rel_diff"], "converged": chi2_conv,
             "lm_successful_steps": summ.num_successful_steps, "cg_iterations_total": int(summ.cg_iterations),
             "cg_iterations_per_step": [it.cg_iterations for it in its[1:]],
             # what the K counted LM iterations were: a step rejected at an early-rejection pause costs a fraction of a fully solved one (Ceres pays a full factorisation for each)
@@ -601,6 +635,13 @@ def main():
                 "pcg_s_beyond_iterations_x_iteration_time": None if cg_ms is None or mg_ms is None else
                     sum(it.seconds_pcg for it in steps) - 1e-3 * (summ_cg_mg * mg_ms + (summ_cg_total - summ_cg_mg) * cg_ms),
                 "note": "pcg_s includes the early-rejection pauses' candidate evaluations, the drain of the chunk in flight when a PCG stops, and multigrid operators built after a PCG has started (in-flight switch)"})(its[1:args.steps + 1]),
+        }
+    if rank == 0 and args.full:
+        out.update({
+            "static_traffic_notes": traffic_note or None, "c5_strong": None,
+            "value_ceres_decision_rule": ceres_rule,
+            "lm_iters_per_s_including_transfers": args.steps / elapsed_incl * scale,   # upload of the state, K iterations, write-back (rank 0's clock)
+            "chi2_converged_rel_diff": None if not chi2_conv or "error" in chi2_conv else chi2_conv["chi2_converged_rel_diff"], "converged": chi2_conv,
             "roofline": {"bound": "hbm", "kernel": "k1_edges_kernel<true> (residual + Jacobian blocks, all edges, one launch)",
                          "achieved": k1_bytes / (k1_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": k1_bytes / (k1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
@@ -627,13 +668,13 @@ def main():
                 "note": "latency-bound: the coarse levels hold 12 %, 4 %, 1 % and 0.4 % of the keyframes, every level kernel starts on cold L2s (DESIGN.md)"},
             "other_kernels": {"k2_assembly": {"ms": k2_ms, "GBps": k2_bytes / k2_ms / 1e6}, "pcg_iteration": None if cg_ms is None else {"ms": cg_ms, "GBps": cg_bytes / cg_ms / 1e6},
                               "k1_cost_only": {"ms": k1c_ms, "GBps": k1c_bytes / k1c_ms / 1e6}},
-        }
+        })
         if scale == 1 and world == 1 and not strong and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.cpu_sample_poses, args.cpu_iters, 30.0)
             except Exception as e:   # the baseline is reported, never required for the GPU number
                 out["cpu_baseline"] = {"value": None, "unit": "LM iters/s (C3-equivalent)", "cores": 1, "kind": "port", "sample": "failed: %r" % (e,)}
-    if world > 1 and not strong and not args.no_c5_strong:
+    if args.full and world > 1 and not strong and not args.no_c5_strong:
         # The C5 leg runs LAST, after everything the contract asks for has been measured, under a watchdog on every rank: a collective that does not come back on some
         # multi-GPU box must cost this leg, not the bench line — after --c5-timeout seconds rank 0 prints the line without it and every rank leaves.
         import threading

@@ -37,8 +37,8 @@ for c in SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU; do pmc_s
 # 3b. condense the PMC passes NOW (on this box) so that the bench below reports the static traffic figures of exactly this build, then the bench line (driver's command)
 python scripts/pmc_r03_summary.py $OUT > $OUT/pmc_summary.log 2>&1
 cp profiles/k1_pmc_latest.json profiles/k1_pmc_r03.json profiles/pcg_pmc_latest.json profiles/mg_pmc_latest.json profiles/r03_pcg_pmc.txt $OUT/ 2>/dev/null
-python bench.py --steps 20 --warmup 5 > $OUT/r03_bench.json 2> $OUT/bench.err
-rocprofv3 --kernel-trace --stats -d gpurun_out/r03_final/trace_bench -o t -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-k1-out-of-cache > $OUT/r03_bench_under_rocprof.json 2> $OUT/bench_rocprof.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/r03_bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats -d $OUT/trace_bench -o t -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-k1-out-of-cache > $OUT/r03_bench_under_rocprof.json 2> $OUT/bench_rocprof.err
 python scripts/rocpd_summary.py stats $(find gpurun_out/r03_final/trace_bench -name "*.db" | head -1) > $OUT/r03_bench_kernel_stats.txt; stamp $OUT/r03_bench_kernel_stats.txt
 rm -rf gpurun_out/r03_final/trace_bench
 # 4. all configs, graph types, smoothed-prolongator A/B, session replay, multi-rank overhead, the 2-rank bench through gloo on this one GPU
@@ -52,6 +52,6 @@ python scripts/gpu_mg_crossover.py 4000,6000,8000,12000,18000 2>&1 | grep -v "^\
 python scripts/research/session_step_times.py 400,1000,3000 2>&1 | grep -v "^\[pgo\]" > $OUT/r03_session_step_times.txt; stamp $OUT/r03_session_step_times.txt
 python scripts/gpu_multi_overhead.py > $OUT/multi_overhead.log 2>&1
 python scripts/gpu_multi_overhead.py mg > $OUT/multi_overhead_mg.log 2>&1
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 --collective gloo > $OUT/r03_bench_gloo2.json 2> $OUT/bench_gloo2.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 10 --warmup 2 --collective gloo > $OUT/r03_bench_gloo2.json 2> $OUT/bench_gloo2.err
 cp gpurun_out/multi_overhead.json $OUT/r03_multi_overhead.json 2>/dev/null; cp gpurun_out/multi_overhead_mg.json $OUT/r03_multi_overhead_mg.json 2>/dev/null
 ls -la $OUT $PM

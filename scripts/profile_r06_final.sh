@@ -54,8 +54,8 @@ for c in SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU; do pmc_s
 
 python scripts/pmc_r06_summary.py $OUT > $OUT/pmc_summary.log 2>&1
 cp profiles/k1_pmc_latest.json profiles/k1_pmc_r06.json profiles/pcg_pmc_latest.json profiles/mg_pmc_latest.json profiles/r06_pcg_pmc.txt $OUT/ 2>/dev/null
-python bench.py --steps 20 --warmup 5 > $OUT/r06_bench.json 2> $OUT/bench.err
-rocprofv3 --kernel-trace --stats -d gpurun_out/r06_final/trace_bench -o t -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-k1-out-of-cache > $OUT/r06_bench_under_rocprof.json 2> $OUT/bench_rocprof.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/r06_bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats -d $OUT/trace_bench -o t -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-k1-out-of-cache > $OUT/r06_bench_under_rocprof.json 2> $OUT/bench_rocprof.err
 python scripts/rocpd_summary.py stats $(find gpurun_out/r06_final/trace_bench -name "*.db" | head -1) > $OUT/r06_bench_kernel_stats.txt; stamp $OUT/r06_bench_kernel_stats.txt
 rm -rf gpurun_out/r06_final/trace_bench
 # idle gaps of the timed region (bench.py's K LM steps, the device idle for 0.3 s on both sides) and of a 400-keyframe trigger
@@ -80,8 +80,8 @@ python scripts/gpu_session_replay.py 3000 600 100 2 > $OUT/r06_session_replay_2d
 python scripts/research/session_step_times.py 400,1000,3000 2>&1 | grep -v "^\[pgo\]" > $OUT/r06_session_step_times.txt; stamp $OUT/r06_session_step_times.txt
 python scripts/gpu_multi_overhead.py > $OUT/multi_overhead.log 2>&1
 python scripts/gpu_multi_overhead.py mg > $OUT/multi_overhead_mg.log 2>&1
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 --collective gloo > $OUT/r06_bench_gloo2.json 2> $OUT/bench_gloo2.err
-python bench.py --config C5 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/r06_bench_c5_strong_1gpu.json 2> $OUT/bench_c5.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 10 --warmup 2 --collective gloo > $OUT/r06_bench_gloo2.json 2> $OUT/bench_gloo2.err
+python bench.py --full --config C5 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/r06_bench_c5_strong_1gpu.json 2> $OUT/bench_c5.err
 cp gpurun_out/multi_overhead.json $OUT/r06_multi_overhead.json 2>/dev/null; cp gpurun_out/multi_overhead_mg.json $OUT/r06_multi_overhead_mg.json 2>/dev/null
 python scripts/pmc_r06_summary.py $OUT > $OUT/pmc_summary.log 2>&1
 ls -la $OUT $PM
