@@ -426,7 +426,8 @@ int pgo_apply_normal_operator(pgo_problem* p, const double* x, double* y);
  * rank without edges is fine.  pgo_solve returns the COMPLETE solution on every rank (each
  * keyframe from its owner, each switch from the rank holding its edge).  At most 52 ranks.  Calls that issue
  * collectives (solve*, evaluate, get_normal_blocks, apply_normal_operator, time_kernel) must be
- * made by all ranks in the same order. */
+ * made by all ranks in the same order.  A handle holds one communicator at a time: any pgo_comm_init* on a handle that already has one fails with
+ * PGO_ERR_INVALID_ARG (call pgo_comm_destroy first).  pgo_destroy releases an attached communicator too (an in-process rank then aborts its group instead of waiting for it). */
 int pgo_comm_get_unique_id(uint8_t id[PGO_COMM_ID_BYTES]);
 int pgo_comm_init(pgo_problem* p, int32_t rank, int32_t world_size, const uint8_t id[PGO_COMM_ID_BYTES]);
 int pgo_comm_destroy(pgo_problem* p);

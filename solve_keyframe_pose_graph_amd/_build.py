@@ -10,8 +10,8 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIBPGO = os.path.join(_HERE, "libpgo.so")
 LIBGEN = os.path.join(_HERE, "libpgo_graphgen.so")
 
-HIP_SOURCES = ["pgo_kernels.hip", "pgo_solver.hip"]
-HIP_HEADERS = ["pgo_internal.hpp", "pgo_device_math.hpp", "pgo_mg_kernels.hpp", "pgo_mg_host.hpp", "pgo_comm_local.hpp"]
+HIP_SOURCES = ["pgo_kernels.hip", "pgo_solver.hip", "pgo_comm.hip"]
+HIP_HEADERS = ["pgo_internal.hpp", "pgo_device_math.hpp", "pgo_mg_kernels.hpp", "pgo_mg_host.hpp", "pgo_comm.hpp"]
 
 
 def _stale(target, deps):
@@ -58,7 +58,7 @@ def source_tree_hash(extra_flags=()):
 def compile_libpgo(target, extra_flags=(), verbose=False, obj_dir=None):
     """Reproducible build: every translation unit to an object of its own with a FIXED compilation-unit id (clang otherwise draws a random one per run: two builds of the
     same sources differed in a few hundred bytes), source paths mapped relative to the repo root, no linker build-id — the same sources and flags give the same bytes whatever
-    the checkout's path.  The two objects are compiled side by side."""
+    the checkout's path.  The objects are compiled side by side."""
     obj_dir = obj_dir or OBJ_DIR
     os.makedirs(obj_dir, exist_ok=True)
     sha = source_tree_hash(extra_flags)

@@ -1,5 +1,5 @@
-// pgo_internal.hpp — device data layout and kernel launch interface shared by pgo_kernels.hip (device code)
-// and pgo_solver.hip (host LM controller + C-ABI).  gfx950 only.
+// pgo_internal.hpp — device data layout and kernel launch interface shared by pgo_kernels.hip (device code),
+// pgo_solver.hip (host LM controller + C-ABI) and pgo_comm.hip (the multi-rank transports: the in-process group's kernels).  gfx950 only.
 //
 // HBM layout (all fp64 unless noted; "tile" = 64 consecutive edges of one class = one wavefront of K1):
 //   pose8   [N][8]            qx qy qz qw tx ty tz pad — one 64-B record per keyframe (coalesced 16-B/lane loads,
@@ -21,6 +21,16 @@
 #include <stdint.h>
 
 #include "pgo_device_math.hpp"
+
+// host code: a failed HIP call returns its PGO_* code from the calling function, with the call and HIP's text in `err` (a std::string)
+#define PGO_HIPCHK(err, expr)                                                                      \
+    do {                                                                                           \
+        hipError_t e__ = (expr);                                                                   \
+        if (e__ != hipSuccess) {                                                                   \
+            (err) = std::string(#expr) + ": " + hipGetErrorString(e__);                            \
+            return e__ == hipErrorOutOfMemory ? PGO_ERR_OUT_OF_MEMORY : PGO_ERR_HIP;               \
+        }                                                                                          \
+    } while (0)
 
 namespace pgo {
 
@@ -247,7 +257,7 @@ void launch_gather_rows(double* buf, const double* a1, int k1, const double* a2,
 void launch_scatter_rows(const double* buf, double* a1, int k1, double* a2, int k2, int64_t n, const int32_t* idx, const int32_t* stop, hipStream_t st);
 void launch_scatter_rows_dinv(const double* buf, double* r, double* x, const double* Dinv, int64_t n, const int32_t* idx, const int32_t* stop, hipStream_t st);      // r rows in, x = Dinv r formed on the spot
 void launch_sum_rows(const double* buf, double* a1, int k1, double* a2, int k2, int64_t n_sh, const int32_t* sh_loc, const int32_t* sum_ptr, const int32_t* sum_src, const int32_t* stop, hipStream_t st);
-// in-process communicator (pgo_comm_init_local): out[i] = sum / max over the ranks' staged buffers in rank order; peers' segments copied into the receive buffer
+// in-process communicator (pgo_comm.hip: LocalComm): out[i] = sum / max over the ranks' staged buffers in rank order; peers' segments copied into the receive buffer
 struct LocalPeers { const double* src[16]; int64_t off[16]; int64_t cnt[16]; int n; };      // off: destination offset (copy) — unused by the reduction
 void launch_local_reduce(double* out, const LocalPeers& P, int64_t n, int op, hipStream_t st);
 void launch_local_copy(double* recv, const LocalPeers& P, hipStream_t st);

@@ -7,8 +7,6 @@
 // Ceres' trust_region_minimizer.cc / levenberg_marquardt_strategy.cc control flow; the
 // linear solve is a device PCG instead of SPARSE_NORMAL_CHOLESKY.  There is NO CPU fallback: without a HIP
 // device pgo_create fails.
-#include <dlfcn.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -22,8 +20,8 @@
 
 #include "pgo.h"
 #include "pgo_internal.hpp"
+#include "pgo_comm.hpp"
 #include "pgo_mg_host.hpp"
-#include "pgo_comm_local.hpp"
 
 using namespace pgo;
 
@@ -88,21 +86,6 @@ struct HostClass {
 
 // scalar slots
 enum { S_COST = 0, S_PRIOR_COST = 1, S_MODEL = 2, S_SW_STEP2 = 3, S_SW_XNORM2 = 4, S_GMAX = 5, S_STEP2 = 6, S_XNORM2 = 7, S_N = 8 };
-
-// ---- RCCL through dlopen (only touched when pgo_comm_* is used) ----
-struct Rccl {
-    struct Uid { char b[128]; };   // ncclUniqueId (NCCL_UNIQUE_ID_BYTES = 128), passed BY VALUE to ncclCommInitRank
-    void* h = nullptr;
-    int (*GetUniqueId)(void*) = nullptr;
-    int (*CommInitRank)(void**, int, Uid, int) = nullptr;
-    int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*Send)(const void*, size_t, int, int, void*, hipStream_t) = nullptr;      // ncclSend(buf, count, type, peer, comm, stream)
-    int (*Recv)(void*, size_t, int, int, void*, hipStream_t) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    int (*CommDestroy)(void*) = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-};
 
 // Host half of a multigrid build (pgo_mg_host.hpp's hierarchy + the pooled index arrays and offsets of its device image): no HIP call, no collective in here when the handle is a
 // single rank's — that half can therefore run on a worker thread while the stream works on other LM steps (regroup, below); mg_install() uploads it.
@@ -261,12 +244,10 @@ struct pgo_problem {
     double t_begin = 0, t_device0 = 0;
     pgo_summary sum;
 
-    // comm
-    Rccl nccl; void* comm = nullptr; int rank = 0, world = 1;
-    pgo_allreduce_fn custom_allreduce = nullptr; void* custom_ctx = nullptr;
-    pgo_exchange_fn custom_exchange = nullptr;
-    pgo_local::Group* local_group = nullptr; uint64_t lc_count = 0;      // in-process communicator: collectives issued so far (parity = count & 1)
-    std::vector<int64_t> x_off_send, x_off_recv;                          // scratch: segment bounds in doubles of the exchange in flight
+    // the multi-rank transport (pgo_comm.hpp); none on one GPU
+    std::unique_ptr<pgo_comm::Comm> comm;
+    int rank() const { return comm ? comm->rank() : 0; }
+    int world() const { return comm ? comm->world() : 1; }
 
     // pipelined convergence polling: pinned host copies of {flags[4], scal[4]} for two chunks in flight
     struct Poll { int32_t flags[4]; double scal[4]; };
@@ -289,14 +270,7 @@ struct pgo_problem {
 
 namespace {
 
-#define HIPCHK(p, expr)                                                                            \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            (p)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                         \
-            return e__ == hipErrorOutOfMemory ? PGO_ERR_OUT_OF_MEMORY : PGO_ERR_HIP;               \
-        }                                                                                          \
-    } while (0)
+#define HIPCHK(p, expr) PGO_HIPCHK((p)->err, expr)
 
 int set_device(pgo_problem* p) { HIPCHK(p, hipSetDevice(p->device)); return PGO_OK; }
 
@@ -435,11 +409,11 @@ int mg_prepare_impl(pgo_problem* p, const double* sw_now, MgPrepared& Q) {
     } else {
         // Several ranks: every rank gathers the endpoints and weights of ALL edges (one all-reduce of a zero-padded buffer: 24 B per edge, once per graph build)
         // and builds the same hierarchy from the global graph; its own edges and owned keyframes are what it contributes to level 1 (pgo_mg_host.hpp).
-        std::vector<double> cnt((size_t)2 * p->world, 0.0);
-        cnt[(size_t)2 * p->rank] = (double)Er; cnt[(size_t)2 * p->rank + 1] = (double)Es;
+        std::vector<double> cnt((size_t)2 * p->world(), 0.0);
+        cnt[(size_t)2 * p->rank()] = (double)Er; cnt[(size_t)2 * p->rank() + 1] = (double)Es;
         if ((rc = host_allreduce(p, cnt, 0)) != PGO_OK) return rc;
         int64_t ErT = 0, EsT = 0, my_r = 0, my_s = 0;
-        for (int r = 0; r < p->world; ++r) { if (r == p->rank) { my_r = ErT; my_s = EsT; } ErT += (int64_t)(cnt[(size_t)2 * r] + 0.5); EsT += (int64_t)(cnt[(size_t)2 * r + 1] + 0.5); }
+        for (int r = 0; r < p->world(); ++r) { if (r == p->rank()) { my_r = ErT; my_s = EsT; } ErT += (int64_t)(cnt[(size_t)2 * r] + 0.5); EsT += (int64_t)(cnt[(size_t)2 * r + 1] + 0.5); }
         std::vector<double> buf((size_t)3 * (ErT + EsT), 0.0);
         double* b_rc1 = buf.data(); double* b_rc2 = b_rc1 + ErT; double* b_rw = b_rc2 + ErT; double* b_sc1 = b_rw + ErT; double* b_sc2 = b_sc1 + EsT; double* b_sw = b_sc2 + EsT;
         for (int64_t e = 0; e < Er; ++e) { b_rc1[my_r + e] = p->rel.c1[e]; b_rc2[my_r + e] = p->rel.c2[e]; b_rw[my_r + e] = p->rel.meas[(size_t)8 * e + 7]; }
@@ -454,15 +428,15 @@ int mg_prepare_impl(pgo_problem* p, const double* sw_now, MgPrepared& Q) {
         for (int32_t c : p->constant_nodes) if (c >= 0 && c < Ng) gfree[c] = 0;
         const pgo_mg::LocalContrib local{&p->l2g, &p->h_own, &p->rel.c1, &p->rel.c2, &p->swe.c1, &p->swe.c2};
         // distributed cycle: aggregates never mix owners, every level is numbered owner-major (pgo_mg_host.hpp: Owners)
-        pgo_mg::Owners OW; OW.touch_mask = &p->h_touch_mask; OW.owner = &p->h_owner; OW.world = p->world; OW.dist_min_rows = p->opt.mg_dist_min_rows > 0 ? p->opt.mg_dist_min_rows : 8192;
+        pgo_mg::Owners OW; OW.touch_mask = &p->h_touch_mask; OW.owner = &p->h_owner; OW.world = p->world(); OW.dist_min_rows = p->opt.mg_dist_min_rows > 0 ? p->opt.mg_dist_min_rows : 8192;
         ok = pgo_mg::build_hierarchy(Ng, gfree, grc1, grc2, grw.data(), 1, gsc1, gsc2, (sw_now && S > 0) ? gsw.data() : nullptr, passes0, passes, dense_max, MG_TILE_ROWS, MG_MAX_LEVELS, H, false, 0, &local, n_smoothed, loop_discount, &p->mg_cache,
-                                     nullptr, nullptr, p->world > 1 ? &OW : nullptr);
-        if (ok && p->world > 1) {
+                                     nullptr, nullptr, p->world() > 1 ? &OW : nullptr);
+        if (ok && p->world() > 1) {
             // the cycle's plans, and beside them on a thread of its own — the two read the finished hierarchy and write their own results — the set-up's (the set-up distributed
             // like the cycle: who contributes to / needs which blocks; the gathered edge lists are rank by rank)
             const bool want_setup = p->opt.mg_dist_setup != 0;
-            std::vector<int64_t> rel_off((size_t)p->world + 1, 0), sw_off((size_t)p->world + 1, 0);
-            for (int r = 0; r < p->world; ++r) { rel_off[(size_t)r + 1] = rel_off[(size_t)r] + (int64_t)(cnt[(size_t)2 * r] + 0.5); sw_off[(size_t)r + 1] = sw_off[(size_t)r] + (int64_t)(cnt[(size_t)2 * r + 1] + 0.5); }
+            std::vector<int64_t> rel_off((size_t)p->world() + 1, 0), sw_off((size_t)p->world() + 1, 0);
+            for (int r = 0; r < p->world(); ++r) { rel_off[(size_t)r + 1] = rel_off[(size_t)r] + (int64_t)(cnt[(size_t)2 * r] + 0.5); sw_off[(size_t)r + 1] = sw_off[(size_t)r] + (int64_t)(cnt[(size_t)2 * r + 1] + 0.5); }
             const bool tm = pgo_mg::timing();
             std::atomic<bool> worker_failed{false};      // (declared before the thread and its joiner: destroyed after them)
             std::thread worker;
@@ -470,13 +444,13 @@ int mg_prepare_impl(pgo_problem* p, const double* sw_now, MgPrepared& Q) {
             bool started = false;
             if (want_setup && pgo_mg::host_threads() > 1) {
                 try {
-                    worker = std::thread([&]() { try { pgo_mg::timing() = tm; pgo_mg::build_setup_plans(H, p->rank, p->world, grc1, grc2, rel_off, gsc1, gsc2, sw_off, Q.setup); } catch (...) { worker_failed.store(true); } });
+                    worker = std::thread([&]() { try { pgo_mg::timing() = tm; pgo_mg::build_setup_plans(H, p->rank(), p->world(), grc1, grc2, rel_off, gsc1, gsc2, sw_off, Q.setup); } catch (...) { worker_failed.store(true); } });
                     started = true;
                 } catch (...) {}
             }
-            pgo_mg::build_level_plans(H, OW, p->rank, Q.plans);
+            pgo_mg::build_level_plans(H, OW, p->rank(), Q.plans);
             if (started) { worker.join(); if (worker_failed.load()) throw std::bad_alloc(); }
-            else if (want_setup) pgo_mg::build_setup_plans(H, p->rank, p->world, grc1, grc2, rel_off, gsc1, gsc2, sw_off, Q.setup);
+            else if (want_setup) pgo_mg::build_setup_plans(H, p->rank(), p->world(), grc1, grc2, rel_off, gsc1, gsc2, sw_off, Q.setup);
         }
         if (ok) {
             const int32_t n1g = (int32_t)H.mem0_ptr.size() - 1;
@@ -504,10 +478,10 @@ int mg_prepare_impl(pgo_problem* p, const double* sw_now, MgPrepared& Q) {
         MgPrepared::Share& sh = Q.share[(size_t)l];
         const int32_t tiles = A.tile_agg0.empty() ? 0 : (int32_t)A.tile_agg0.size() - 1;
         sh.distributed = dist && A.distributed;
-        if (sh.distributed) { sh.tile0 = A.tile_ptr[(size_t)p->rank]; sh.tiles_own = A.tile_ptr[(size_t)p->rank + 1] - sh.tile0; sh.rT_row0 = H.L[(size_t)l + 1].own_ptr[(size_t)p->rank]; sh.rT_row1 = H.L[(size_t)l + 1].own_ptr[(size_t)p->rank + 1]; }
+        if (sh.distributed) { sh.tile0 = A.tile_ptr[(size_t)p->rank()]; sh.tiles_own = A.tile_ptr[(size_t)p->rank() + 1] - sh.tile0; sh.rT_row0 = H.L[(size_t)l + 1].own_ptr[(size_t)p->rank()]; sh.rT_row1 = H.L[(size_t)l + 1].own_ptr[(size_t)p->rank() + 1]; }
         else { sh.tile0 = 0; sh.tiles_own = tiles; sh.rT_row0 = 0; sh.rT_row1 = H.L[(size_t)l + 1].n; }
     }
-    Q.a0 = dist ? H.L[0].own_ptr[(size_t)p->rank] : 0; Q.a1 = dist ? H.L[0].own_ptr[(size_t)p->rank + 1] : H.L[0].n;
+    Q.a0 = dist ? H.L[0].own_ptr[(size_t)p->rank()] : 0; Q.a1 = dist ? H.L[0].own_ptr[(size_t)p->rank() + 1] : H.L[0].n;
     // pooled arrays: (offset, count) per array; doubles rounded up to even counts (16-B loads)
     std::vector<int32_t>& pi32 = Q.pi32; std::vector<int64_t>& pi64 = Q.pi64;
     {   // one allocation per pool (the arrays are appended one by one: without the reservation the 10-MB pools are reallocated and copied a dozen times)
@@ -748,7 +722,7 @@ int mg_install(pgo_problem* p, MgPrepared& Q) {
         {   // what the rank's cycle kernels read of the level (pgo_mg_level_norms: the same ranges whichever way the set-up ran)
             pgo_problem::OwnRange R;
             const bool mine = l + 1 < nl && Q.share[(size_t)l].distributed;
-            const int32_t r0 = mine ? A.own_ptr[(size_t)p->rank] : 0, r1 = mine ? A.own_ptr[(size_t)p->rank + 1] : A.n;
+            const int32_t r0 = mine ? A.own_ptr[(size_t)p->rank()] : 0, r1 = mine ? A.own_ptr[(size_t)p->rank() + 1] : A.n;
             R.row0 = r0; R.row1 = r1; R.blk0 = A.rowptr[(size_t)r0]; R.blk1 = A.rowptr[(size_t)r1];
             if (A.smoothed) {
                 R.ps0 = A.ps_rowptr[(size_t)r0]; R.ps1 = A.ps_rowptr[(size_t)r1]; R.w0 = A.w_rowptr[(size_t)r0]; R.w1 = A.w_rowptr[(size_t)r1];
@@ -758,7 +732,7 @@ int mg_install(pgo_problem* p, MgPrepared& Q) {
         }
         {   // the set-up's share of the level: a distributed level under the distributed set-up forms its own rows, every other one all of them
             const bool part = l < Q.setup.first_whole;
-            const int32_t r0 = part ? A.own_ptr[(size_t)p->rank] : 0, r1 = part ? A.own_ptr[(size_t)p->rank + 1] : A.n;
+            const int32_t r0 = part ? A.own_ptr[(size_t)p->rank()] : 0, r1 = part ? A.own_ptr[(size_t)p->rank() + 1] : A.n;
             D.su_row0 = r0; D.su_row1 = r1; D.su_blk0 = A.rowptr[(size_t)r0]; D.su_blk1 = A.rowptr[(size_t)r1];
             D.su_ps0 = A.smoothed ? A.ps_rowptr[(size_t)r0] : 0; D.su_ps1 = A.smoothed ? A.ps_rowptr[(size_t)r1] : 0;
             D.su_w0 = A.smoothed ? A.w_rowptr[(size_t)r0] : 0; D.su_w1 = A.smoothed ? A.w_rowptr[(size_t)r1] : 0;
@@ -773,7 +747,7 @@ int mg_install(pgo_problem* p, MgPrepared& Q) {
                 const int64_t blocks = (int64_t)A.col.size() + (A.smoothed ? 2 * (int64_t)A.w_col.size() : 0);
                 int64_t own_rows = A.n, own_blocks = blocks;
                 if (sh.distributed) {
-                    const int32_t r0 = A.own_ptr[(size_t)p->rank], r1 = A.own_ptr[(size_t)p->rank + 1];
+                    const int32_t r0 = A.own_ptr[(size_t)p->rank()], r1 = A.own_ptr[(size_t)p->rank() + 1];
                     own_rows = r1 - r0;
                     own_blocks = A.rowptr[(size_t)r1] - A.rowptr[(size_t)r0];
                     if (A.smoothed) own_blocks += (int64_t)(A.w_rowptr[(size_t)r1] - A.w_rowptr[(size_t)r0]) + (int64_t)(A.rT_rowptr[(size_t)sh.rT_row1] - A.rT_rowptr[(size_t)sh.rT_row0]);
@@ -835,7 +809,7 @@ int mg_install(pgo_problem* p, MgPrepared& Q) {
     p->mg_first_whole = Q.setup.first_whole;
     if (p->mg_first_whole > 0) {
         const pgo_mg::HostLevel& W = H.L[(size_t)p->mg_first_whole];
-        p->mg_fw_row0 = W.own_ptr[(size_t)p->rank]; p->mg_fw_row1 = W.own_ptr[(size_t)p->rank + 1];
+        p->mg_fw_row0 = W.own_ptr[(size_t)p->rank()]; p->mg_fw_row1 = W.own_ptr[(size_t)p->rank() + 1];
         p->mg_fw_blk0 = W.rowptr[(size_t)p->mg_fw_row0]; p->mg_fw_blk1 = W.rowptr[(size_t)p->mg_fw_row1];
     }
     p->mg_setup = std::move(Q.setup);
@@ -998,7 +972,7 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
     // ---- multi-GPU: rank-local subgraph.  This rank works on the keyframes its own residual blocks touch, renumbered densely; keyframes
     // touched by >= 2 ranks are "shared" (their rows are summed over ranks by exchange_rows), the lowest touching rank is the owner.
     const int64_t Ng = N;
-    p->local_ids = p->comm != nullptr || p->custom_allreduce != nullptr || p->local_group != nullptr;   // also with a 1-rank communicator: the same code path, every collective issued
+    p->local_ids = p->comm != nullptr;   // also with a 1-rank communicator: the same code path, every collective issued
     p->n_sh_mine = p->n_sh_global = 0;
     if (p->local_ids) {
         std::vector<uint8_t> touched((size_t)Ng, 0);
@@ -1011,9 +985,9 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
         // Two all-reduces of Ng doubles, once per graph build.  Sum: every rank adds 2^rank for the keyframes it touches — the set of touching ranks (exact in a double up to
         // 52 ranks): how many they are, and who exchanges the keyframe's rows with whom.  Max of (blocks + 1) * 64 + 63 - rank: the OWNER — the rank holding most of the
         // keyframe's residual blocks, the lowest of them on a tie (pgo_mg_host.hpp: Owners).
-        if (p->world > 52) { p->err = "more than 52 ranks"; return PGO_ERR_INVALID_ARG; }
+        if (p->world() > 52) { p->err = "more than 52 ranks"; return PGO_ERR_INVALID_ARG; }
         std::vector<double> buf((size_t)Ng), obuf((size_t)Ng);
-        for (int64_t g = 0; g < Ng; ++g) { buf[g] = touched[g] ? std::ldexp(1.0, p->rank) : 0.0; obuf[g] = touched[g] ? (double)(((int64_t)deg[g] + 1) * 64 + 63 - p->rank) : 0.0; }
+        for (int64_t g = 0; g < Ng; ++g) { buf[g] = touched[g] ? std::ldexp(1.0, p->rank()) : 0.0; obuf[g] = touched[g] ? (double)(((int64_t)deg[g] + 1) * 64 + 63 - p->rank()) : 0.0; }
         int rc2;
         if ((rc2 = host_allreduce(p, buf, 0)) != PGO_OK) return rc2;
         if ((rc2 = host_allreduce(p, obuf, 2)) != PGO_OK) return rc2;
@@ -1027,11 +1001,11 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
             if (m) { p->h_owner[g] = 63 - (int32_t)((int64_t)(obuf[g] + 0.5) % 64); if (!((m >> p->h_owner[g]) & 1)) { p->err = "graph build: a keyframe's owner does not touch it (the ranks' all-reduces disagree)"; return PGO_ERR_COMM; } }
             p->h_touched_any[g] = cnt > 0;
             if (touched[g]) {
-                if (!((m >> p->rank) & 1)) { p->err = "touch masks: the all-reduce did not return this rank's own bit"; return PGO_ERR_COMM; }
+                if (!((m >> p->rank()) & 1)) { p->err = "touch masks: the all-reduce did not return this rank's own bit"; return PGO_ERR_COMM; }
                 p->g2l[g] = (int32_t)p->l2g.size();
                 if (cnt >= 2) ++n_mine;
                 p->l2g.push_back((int32_t)g);
-                p->h_own.push_back(p->h_owner[g] == p->rank ? 1.0 : 0.0);
+                p->h_own.push_back(p->h_owner[g] == p->rank() ? 1.0 : 0.0);
             }
             if (cnt >= 2) ++pos;
         }
@@ -1041,7 +1015,7 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
         HIPCHK(p, hipMemcpyAsync(p->d_l2g.p, p->l2g.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
         HIPCHK(p, hipMemcpyAsync(p->d_own.p, p->h_own.data(), N * sizeof(double), hipMemcpyHostToDevice, p->st));
         {   // the keyframes' neighbour exchange: segments per peer, and for every shared keyframe the order its parts are summed in (pgo_mg_host.hpp: build_fine_plan)
-            pgo_mg::build_fine_plan(p->h_touch_mask, p->l2g, p->rank, p->world, p->fine_plan);
+            pgo_mg::build_fine_plan(p->h_touch_mask, p->l2g, p->rank(), p->world(), p->fine_plan);
             const pgo_mg::FinePlan& F = p->fine_plan;
             auto up = [&](DBuf<int32_t>& d, const std::vector<int32_t>& v) -> int {
                 HIPCHK(p, d.ensure(std::max<size_t>(v.size(), 1)));
@@ -1308,128 +1282,27 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
 }
 
 // ---- collectives (no-ops without a communicator; a 1-rank communicator still issues every call) ----
-// in-process communicator (pgo_comm_local.hpp): step 1 of its protocol — the parity buffers of this collective may be overwritten once the peers' reads of two collectives ago are done
-int local_pre(pgo_problem* p) {
-    pgo_local::Group* G = p->local_group;
-    const int par = (int)(p->lc_count & 1);
-    for (int q = 0; q < G->world; ++q) if (q != p->rank && G->slot[q].done[par]) HIPCHK(p, hipStreamWaitEvent(p->st, G->slot[q].done[par], 0));
-    return PGO_OK;
-}
-int local_allreduce(pgo_problem* p, double* buf, size_t n, int op) {
-    pgo_local::Group* G = p->local_group;
-    pgo_local::Group::Slot& me = G->slot[p->rank];
-    const int par = (int)(p->lc_count & 1);
-    int rc;
-    if ((rc = local_pre(p)) != PGO_OK) return rc;
-    if (me.stage_cap[par] < n) {
-        HIPCHK(p, hipStreamSynchronize(p->st));
-        if (me.stage[par]) (void)hipFree(me.stage[par]);
-        me.stage[par] = nullptr; me.stage_cap[par] = 0;
-        const size_t want = n + n / 4 + 64;
-        HIPCHK(p, hipMalloc((void**)&me.stage[par], want * sizeof(double)));
-        me.stage_cap[par] = want;
-    }
-    HIPCHK(p, hipMemcpyAsync(me.stage[par], buf, n * sizeof(double), hipMemcpyDeviceToDevice, p->st));
-    HIPCHK(p, hipEventRecord(me.ready[par], p->st));
-    me.ptr[par] = me.stage[par];
-    if (!G->barrier()) { p->err = "in-process communicator: a rank did not reach the collective (failed, left, or out of step)"; return PGO_ERR_COMM; }
-    LocalPeers P{};
-    P.n = G->world;
-    for (int q = 0; q < G->world; ++q) {
-        P.src[q] = G->slot[q].ptr[par]; P.off[q] = 0; P.cnt[q] = (int64_t)n;
-        if (q != p->rank) HIPCHK(p, hipStreamWaitEvent(p->st, G->slot[q].ready[par], 0));
-    }
-    launch_local_reduce(buf, P, (int64_t)n, op, p->st);
-    HIPCHK(p, hipEventRecord(me.done[par], p->st));
-    ++p->lc_count;
-    return PGO_OK;
-}
+// a graph built for several ranks whose communicator has gone since (pgo_comm_destroy inside a solve): its collectives fail
+int no_comm(pgo_problem* p) { p->err = "no communicator: the graph was built for several ranks (pgo_comm_destroy inside a solve?)"; return PGO_ERR_STATE; }
 int allreduce(pgo_problem* p, double* buf, size_t n, int op /*0 sum, 2 max*/) {
-    if (p->local_ids || p->comm || p->custom_allreduce || p->local_group) { ++p->st_allreduces; p->st_bytes_allreduce += (double)n * sizeof(double); }
-    if (p->local_group) return local_allreduce(p, buf, n, op);
-    if (p->custom_allreduce) {
-        const int rc = p->custom_allreduce(p->custom_ctx, buf, (int64_t)n, op, (void*)p->st);
-        if (rc != 0) { p->err = "custom all-reduce callback failed"; return PGO_ERR_COMM; }
-        return PGO_OK;
-    }
-    if (!p->comm) return PGO_OK;
-    const int rc = p->nccl.AllReduce(buf, buf, n, /*ncclDouble*/ 8, op, p->comm, p->st);
-    if (rc != 0) { p->err = std::string("ncclAllReduce: ") + (p->nccl.GetErrorString ? p->nccl.GetErrorString(rc) : "error"); return PGO_ERR_COMM; }
-    return PGO_OK;
+    if (!p->comm) return p->local_ids ? no_comm(p) : PGO_OK;
+    ++p->st_allreduces; p->st_bytes_allreduce += (double)n * sizeof(double);
+    return p->comm->allreduce(buf, n, op, p->err);
 }
 
-// The send buffer of the exchange about to be packed (the in-process communicator double-buffers by collective parity and first waits for the peers' reads of that buffer)
-int exchange_send_buffer(pgo_problem* p, double** out) {
-    int rc;
-    if (p->local_group && (rc = local_pre(p)) != PGO_OK) return rc;
-    *out = p->d_xsend[p->local_group ? (p->lc_count & 1) : 0].p;
-    return PGO_OK;
-}
-// Neighbour exchange of `K` doubles per row: rows [plan.send_off[q], plan.send_off[q+1]) of `sendbuf` go to rank q, rows [recv_off[q], recv_off[q+1]) of `recvbuf` come from it.
-// RCCL: one group of ncclSend / ncclRecv pairs (point-to-point over the xGMI link of each pair).  In-process communicator: one kernel reading the peers' send buffers.
-// Caller-supplied collective: its exchange callback, or — without one — an all-reduce of a zero-padded buffer that holds every pair's segment (correct, world x the bytes).
-int neighbor_exchange(pgo_problem* p, const pgo_mg::ExchangePlan& X, int K, const double* sendbuf, double* recvbuf) {
-    const int W = p->world, r = p->rank;
+// Neighbour exchange of `K` doubles per row (pgo_comm.hpp: Comm::exchange): `pack` fills the send buffer the transport hands out, `unpack` reads the receive buffer
+template <class Pack, class Unpack>
+int neighbor_exchange(pgo_problem* p, const pgo_mg::ExchangePlan& X, int K, Pack pack, Unpack unpack) {
+    if (!p->comm) return no_comm(p);
+    const int slot = p->comm->send_slot(p->err);
+    if (slot < 0) return slot;
+    pack(p->d_xsend[slot].p);
     ++p->st_exchanges; p->st_bytes_neighbour += (double)X.n_send() * K * sizeof(double);
-    if (p->local_group) {
-        pgo_local::Group* G = p->local_group;
-        pgo_local::Group::Slot& me = G->slot[r];
-        const int par = (int)(p->lc_count & 1);
-        HIPCHK(p, hipEventRecord(me.ready[par], p->st));
-        me.ptr[par] = sendbuf; me.send_off[par] = X.send_off.data();
-        if (!G->barrier()) { p->err = "in-process communicator: a rank did not reach the exchange (failed, left, or out of step)"; return PGO_ERR_COMM; }
-        LocalPeers P{};
-        int np = 0;
-        for (int q = 0; q < W; ++q) {
-            const int64_t cnt = (X.recv_off[(size_t)q + 1] - X.recv_off[(size_t)q]) * K;
-            if (q == r || cnt == 0) continue;
-            const int64_t* so = G->slot[q].send_off[par];
-            if ((so[r + 1] - so[r]) * K != cnt) { G->abort(); p->err = "in-process communicator: the ranks' exchange plans disagree"; return PGO_ERR_COMM; }
-            HIPCHK(p, hipStreamWaitEvent(p->st, G->slot[q].ready[par], 0));
-            P.src[np] = G->slot[q].ptr[par] + so[r] * K; P.off[np] = X.recv_off[(size_t)q] * K; P.cnt[np] = cnt; ++np;
-        }
-        P.n = np;
-        if (np > 0) launch_local_copy(recvbuf, P, p->st);
-        HIPCHK(p, hipEventRecord(me.done[par], p->st));
-        ++p->lc_count;
-        return PGO_OK;
-    }
-    if (p->custom_allreduce && p->custom_exchange) {
-        p->x_off_send.resize((size_t)W + 1); p->x_off_recv.resize((size_t)W + 1);
-        for (int q = 0; q <= W; ++q) { p->x_off_send[(size_t)q] = X.send_off[(size_t)q] * K; p->x_off_recv[(size_t)q] = X.recv_off[(size_t)q] * K; }
-        const int rc = p->custom_exchange(p->custom_ctx, sendbuf, p->x_off_send.data(), recvbuf, p->x_off_recv.data(), (void*)p->st);
-        if (rc != 0) { p->err = "custom exchange callback failed"; return PGO_ERR_COMM; }
-        return PGO_OK;
-    }
-    // PGO_EXCHANGE_VIA_ALLREDUCE=1 (read once; a production switch, not a debug hook): RCCL's point-to-point path is bypassed as well — the safety net for a node where
-    // ncclSend / ncclRecv misbehave (this repo's send / receive path has never run between two physical GPUs)
-    static const bool via_allreduce = []() { const char* e = std::getenv("PGO_EXCHANGE_VIA_ALLREDUCE"); return e && e[0] == '1' && e[1] == 0; }();
-    if (p->custom_allreduce || (p->comm && via_allreduce)) {
-        // emulation: [src][dst] segments in one buffer; this rank fills row `r`, the all-reduce fills the rest, column `r` is what it receives
-        std::vector<int64_t> off((size_t)W * W + 1, 0);
-        for (int i = 0; i < W * W; ++i) off[(size_t)i + 1] = off[(size_t)i] + X.pair_cnt[(size_t)i] * K;
-        const size_t total = (size_t)off[(size_t)W * W];
-        if (total == 0) return PGO_OK;
-        HIPCHK(p, p->d_tmp.ensure(total));
-        HIPCHK(p, hipMemsetAsync(p->d_tmp.p, 0, total * sizeof(double), p->st));
-        for (int q = 0; q < W; ++q) { const int64_t cnt = (X.send_off[(size_t)q + 1] - X.send_off[(size_t)q]) * K; if (cnt > 0) HIPCHK(p, hipMemcpyAsync(p->d_tmp.p + off[(size_t)r * W + q], sendbuf + X.send_off[(size_t)q] * K, (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, p->st)); }
-        int rca;
-        if ((rca = allreduce(p, p->d_tmp.p, total, 0)) != PGO_OK) return rca;
-        for (int q = 0; q < W; ++q) { const int64_t cnt = (X.recv_off[(size_t)q + 1] - X.recv_off[(size_t)q]) * K; if (cnt > 0) HIPCHK(p, hipMemcpyAsync(recvbuf + X.recv_off[(size_t)q] * K, p->d_tmp.p + off[(size_t)q * W + r], (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, p->st)); }
-        return PGO_OK;
-    }
-    if (!p->comm) return PGO_OK;
-    if (!p->nccl.Send || !p->nccl.Recv || !p->nccl.GroupStart || !p->nccl.GroupEnd) { p->err = "librccl lacks ncclSend / ncclRecv / ncclGroupStart / ncclGroupEnd"; return PGO_ERR_COMM; }
-    int rc = p->nccl.GroupStart();
-    for (int q = 0; q < W && rc == 0; ++q) {
-        if (q == r) continue;
-        const int64_t ns = (X.send_off[(size_t)q + 1] - X.send_off[(size_t)q]) * K, nr = (X.recv_off[(size_t)q + 1] - X.recv_off[(size_t)q]) * K;
-        if (ns > 0) rc = p->nccl.Send(sendbuf + X.send_off[(size_t)q] * K, (size_t)ns, /*ncclDouble*/ 8, q, p->comm, p->st);
-        if (rc == 0 && nr > 0) rc = p->nccl.Recv(recvbuf + X.recv_off[(size_t)q] * K, (size_t)nr, 8, q, p->comm, p->st);
-    }
-    const int rc_end = p->nccl.GroupEnd();
-    if (rc == 0) rc = rc_end;
-    if (rc != 0) { p->err = std::string("ncclSend / ncclRecv: ") + (p->nccl.GetErrorString ? p->nccl.GetErrorString(rc) : "error"); return PGO_ERR_COMM; }
+    size_t reduced = 0;      // (an exchange emulated by an all-reduce counts as one as well)
+    const int rc = p->comm->exchange({X.send_off.data(), X.recv_off.data(), X.pair_cnt.data()}, K, p->d_xsend[slot].p, p->d_xrecv.p, p->err, reduced);
+    if (reduced) { ++p->st_allreduces; p->st_bytes_allreduce += (double)reduced * sizeof(double); }
+    if (rc != PGO_OK) return rc;
+    unpack(p->d_xrecv.p);
     return PGO_OK;
 }
 
@@ -1439,33 +1312,18 @@ int neighbor_exchange(pgo_problem* p, const pgo_mg::ExchangePlan& X, int K, cons
 int exchange_rows(pgo_problem* p, double* a1, int k1, double* a2, int k2, const int32_t* stop = nullptr) {
     if (!p->local_ids) return PGO_OK;
     const pgo_mg::FinePlan& F = p->fine_plan;
-    const int K = k1 + k2;
-    int rc;
-    double* sb = nullptr;
-    if ((rc = exchange_send_buffer(p, &sb)) != PGO_OK) return rc;
-    launch_gather_rows(sb, a1, k1, a2, k2, F.x.n_send(), p->d_fp_send.p, stop, p->st);
-    if ((rc = neighbor_exchange(p, F.x, K, sb, p->d_xrecv.p)) != PGO_OK) return rc;
-    launch_sum_rows(p->d_xrecv.p, a1, k1, a2, k2, (int64_t)F.sh_loc.size(), p->d_fp_shloc.p, p->d_fp_sumptr.p, p->d_fp_sumsrc.p, stop, p->st);
-    return PGO_OK;
+    return neighbor_exchange(p, F.x, k1 + k2, [&](double* sb) { launch_gather_rows(sb, a1, k1, a2, k2, F.x.n_send(), p->d_fp_send.p, stop, p->st); },
+                             [&](const double* rb) { launch_sum_rows(rb, a1, k1, a2, k2, (int64_t)F.sh_loc.size(), p->d_fp_shloc.p, p->d_fp_sumptr.p, p->d_fp_sumsrc.p, stop, p->st); });
 }
 // ... and of the multigrid's level vectors: the rows of one or two vectors of level `l + 1` this rank owns and a peer reads go to that peer, the rows it reads come in
 int exchange_level(pgo_problem* p, int l, double* v1, double* v2, const int32_t* stop, const double* dinv) {
     if (!p->local_ids || (size_t)l >= p->lvl_plan.size() || !p->lvl_plan[(size_t)l].plan) return PGO_OK;
     const pgo_problem::LevelPlanDev& L = p->lvl_plan[(size_t)l];
-    int rc;
-    double* sb = nullptr;
-    if ((rc = exchange_send_buffer(p, &sb)) != PGO_OK) return rc;
-    if (dinv) {      // x = v1, r = v2: only r travels, x = Dinv r is formed on receipt (pointwise; every rank holds the level's Dinv)
-        launch_gather_rows(sb, v2, 6, nullptr, 0, L.plan->n_send(), L.send_idx, stop, p->st);
-        if ((rc = neighbor_exchange(p, *L.plan, 6, sb, p->d_xrecv.p)) != PGO_OK) return rc;
-        launch_scatter_rows_dinv(p->d_xrecv.p, v2, v1, dinv, L.plan->n_recv(), L.recv_idx, stop, p->st);
-        return PGO_OK;
-    }
-    const int K = v2 ? 12 : 6;
-    launch_gather_rows(sb, v1, 6, v2, v2 ? 6 : 0, L.plan->n_send(), L.send_idx, stop, p->st);
-    if ((rc = neighbor_exchange(p, *L.plan, K, sb, p->d_xrecv.p)) != PGO_OK) return rc;
-    launch_scatter_rows(p->d_xrecv.p, v1, 6, v2, v2 ? 6 : 0, L.plan->n_recv(), L.recv_idx, stop, p->st);
-    return PGO_OK;
+    if (dinv)      // x = v1, r = v2: only r travels, x = Dinv r is formed on receipt (pointwise; every rank holds the level's Dinv)
+        return neighbor_exchange(p, *L.plan, 6, [&](double* sb) { launch_gather_rows(sb, v2, 6, nullptr, 0, L.plan->n_send(), L.send_idx, stop, p->st); },
+                                 [&](const double* rb) { launch_scatter_rows_dinv(rb, v2, v1, dinv, L.plan->n_recv(), L.recv_idx, stop, p->st); });
+    return neighbor_exchange(p, *L.plan, v2 ? 12 : 6, [&](double* sb) { launch_gather_rows(sb, v1, 6, v2, v2 ? 6 : 0, L.plan->n_send(), L.send_idx, stop, p->st); },
+                             [&](const double* rb) { launch_scatter_rows(rb, v1, 6, v2, v2 ? 6 : 0, L.plan->n_recv(), L.recv_idx, stop, p->st); });
 }
 // ... and of the multigrid's SET-UP (distributed set-up, round 6): 6x6 blocks listed by slot (K doubles each: 36, or 18 for an fp32 block).  Copy: every block has one producer.
 // Sum: the parts of a block formed on several ranks are added, in ascending rank order, on every rank that needs it (pgo_mg_host.hpp: BlockPlan).  A plan with nothing to send
@@ -1473,23 +1331,13 @@ int exchange_level(pgo_problem* p, int l, double* v1, double* v2, const int32_t*
 static bool plan_is_empty(const pgo_mg::ExchangePlan& X) { for (int64_t c : X.pair_cnt) if (c) return false; return true; }
 int exchange_blocks_copy(pgo_problem* p, const pgo_mg::ExchangePlan& X, const int32_t* send_idx, const int32_t* recv_idx, double* arr, int K) {
     if (plan_is_empty(X)) return PGO_OK;
-    int rc;
-    double* sb = nullptr;
-    if ((rc = exchange_send_buffer(p, &sb)) != PGO_OK) return rc;
-    launch_gather_rows(sb, arr, K, nullptr, 0, X.n_send(), send_idx, nullptr, p->st);
-    if ((rc = neighbor_exchange(p, X, K, sb, p->d_xrecv.p)) != PGO_OK) return rc;
-    launch_scatter_rows(p->d_xrecv.p, arr, K, nullptr, 0, X.n_recv(), recv_idx, nullptr, p->st);
-    return PGO_OK;
+    return neighbor_exchange(p, X, K, [&](double* sb) { launch_gather_rows(sb, arr, K, nullptr, 0, X.n_send(), send_idx, nullptr, p->st); },
+                             [&](const double* rb) { launch_scatter_rows(rb, arr, K, nullptr, 0, X.n_recv(), recv_idx, nullptr, p->st); });
 }
 int exchange_blocks_sum(pgo_problem* p, const pgo_mg::BlockPlan& B, const pgo_problem::SetupPlanDev& D, double* arr) {
     if (plan_is_empty(B.x)) return PGO_OK;
-    int rc;
-    double* sb = nullptr;
-    if ((rc = exchange_send_buffer(p, &sb)) != PGO_OK) return rc;
-    launch_gather_rows(sb, arr, 36, nullptr, 0, B.x.n_send(), D.val_send, nullptr, p->st);
-    if ((rc = neighbor_exchange(p, B.x, 36, sb, p->d_xrecv.p)) != PGO_OK) return rc;
-    launch_sum_rows(p->d_xrecv.p, arr, 36, nullptr, 0, (int64_t)B.dst.size(), D.val_dst, D.val_sum_ptr, D.val_sum_src, nullptr, p->st);
-    return PGO_OK;
+    return neighbor_exchange(p, B.x, 36, [&](double* sb) { launch_gather_rows(sb, arr, 36, nullptr, 0, B.x.n_send(), D.val_send, nullptr, p->st); },
+                             [&](const double* rb) { launch_sum_rows(rb, arr, 36, nullptr, 0, (int64_t)B.dst.size(), D.val_dst, D.val_sum_ptr, D.val_sum_src, nullptr, p->st); });
 }
 // all-reduce of a host vector (graph build: rare, sizes up to a few tens of MB)
 int host_allreduce(pgo_problem* p, std::vector<double>& v, int op) {
@@ -1612,7 +1460,7 @@ bool mg_exchange_at(pgo_problem* p, int point, int lv, int* plan, double** v1, d
     auto dist = [&](int level) { return level >= 1 && level < nl && (size_t)(level - 1) < p->mg_dist.size() && p->mg_dist[(size_t)level - 1] != 0; };
     auto expl = [&](int level) { return level >= 1 && level < nl && p->mg_levels[level - 1].smoothed && p->mg_levels[level - 1].rt_valf != nullptr; };
     *v1 = nullptr; *v2 = nullptr; *plan = -1; *dinv = nullptr;
-    if (p->world <= 1 || p->lvl_plan.empty()) return false;
+    if (p->world() <= 1 || p->lvl_plan.empty()) return false;
     if (point == 0) {
         if (lv == nl) { if (nl == 1 || dist(nl - 1)) { *plan = nl - 1; *v1 = p->K.rc; return true; } return false; }
         MgLevelDev& A = p->mg_levels[lv - 1];
@@ -1781,10 +1629,8 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
         return PGO_OK;
     };
     // hipGraph: capture one chunk (iterations 2 .. 2+every-1: no `first` kernel, even start) once per graph build and preconditioner, and replay it
-    // Several ranks: a chunk holding RCCL's all-reduce can be captured as well (RCCL supports stream capture); not with a caller-supplied collective (a host callback).
-    // Opt-in (PGO_RCCL_GRAPH=1): it could only be tried with a 1-rank communicator on the 1-GPU development boxes.
-    static const bool rccl_graph = []() { const char* e = std::getenv("PGO_RCCL_GRAPH"); return e && e[0] == '1'; }();
-    const bool want_graph = o.cg_use_graph && !p->cg_graph_failed && (!p->local_ids || (p->comm != nullptr && p->custom_allreduce == nullptr && rccl_graph));
+    // Several ranks: only where the transport's collectives can be captured (pgo_comm.hip: RCCL, opt-in; not a caller-supplied collective, a host callback)
+    const bool want_graph = o.cg_use_graph && !p->cg_graph_failed && (!p->local_ids || (p->comm && p->comm->graph_capturable()));
     // Capture + instantiation cost about a millisecond: a PCG pays it only once it has run `graph_after` iterations eagerly (a graph that is rebuilt for every
     // solve — the reference's sessions: one new loop edge, one solve — and converges in a few hundred iterations never does; eager launches keep up with
     // 5-8 us kernels: measured 18.5 vs 19.4 ms at 300 keyframes, 64.0 vs 64.6 ms at 3000)
@@ -2632,6 +2478,19 @@ int add_edges(pgo_problem* p, HostClass& H, int64_t n, const int32_t* c1, const 
     return PGO_OK;
 }
 
+// Every pgo_comm_init*: one transport per handle; a new one changes the keyframes this handle works on (the union over ranks), so what was built for the old graph goes
+template <class Make>
+int attach_comm(pgo_problem* p, Make make) {
+    if (p->comm) { p->err = "a communicator is attached: call pgo_comm_destroy first"; return PGO_ERR_INVALID_ARG; }
+    int rc;
+    std::unique_ptr<pgo_comm::Comm> c;
+    if ((rc = set_device(p)) != PGO_OK || (rc = make(c)) != PGO_OK) return rc;
+    mg_job_cancel(p); mg_init_drop(p);
+    p->comm = std::move(c);
+    p->graph_dirty = true;
+    return PGO_OK;
+}
+
 }  // namespace
 
 // ================================================================================================
@@ -2745,7 +2604,10 @@ int pgo_destroy(pgo_problem* p) {
     mg_job_cancel(p);
     mg_init_drop(p);
     (void)hipSetDevice(p->device);
-    if (p->comm && p->nccl.CommDestroy) p->nccl.CommDestroy(p->comm);
+    // (the in-process group's peers may be gone: the group is aborted, not waited for.  Known limit: the send buffers below are freed once this handle's stream has drained —
+    // on one GPU hipFree waits for the peers' kernels as well, across GPUs a peer's copy kernel of the last exchange could still be reading them)
+    if (p->comm) p->comm->abandon();
+    p->comm.reset();
     (void)hipStreamSynchronize(p->st);
     for (auto& cc : p->cg_chunk) if (cc.exec) (void)hipGraphExecDestroy(cc.exec);
     if (p->poll) (void)hipHostFree(p->poll);
@@ -3082,103 +2944,25 @@ int pgo_apply_normal_operator(pgo_problem* p, const double* x, double* y) {
 }
 
 // ---- multi-GPU ----
-static int load_rccl(Rccl& r, std::string& err) {
-    if (r.h) return PGO_OK;
-    const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    for (const char* n : names) { r.h = dlopen(n, RTLD_NOW | RTLD_GLOBAL); if (r.h) break; }
-    if (!r.h) { err = std::string("dlopen(librccl): ") + dlerror(); return PGO_ERR_COMM; }
-    r.GetUniqueId = (int (*)(void*))dlsym(r.h, "ncclGetUniqueId");
-    r.CommInitRank = (int (*)(void**, int, Rccl::Uid, int))dlsym(r.h, "ncclCommInitRank");
-    r.AllReduce = (int (*)(const void*, void*, size_t, int, int, void*, hipStream_t))dlsym(r.h, "ncclAllReduce");
-    r.CommDestroy = (int (*)(void*))dlsym(r.h, "ncclCommDestroy");
-    r.Send = (int (*)(const void*, size_t, int, int, void*, hipStream_t))dlsym(r.h, "ncclSend");
-    r.Recv = (int (*)(void*, size_t, int, int, void*, hipStream_t))dlsym(r.h, "ncclRecv");
-    r.GroupStart = (int (*)())dlsym(r.h, "ncclGroupStart");
-    r.GroupEnd = (int (*)())dlsym(r.h, "ncclGroupEnd");
-    r.GetErrorString = (const char* (*)(int))dlsym(r.h, "ncclGetErrorString");
-    if (!r.GetUniqueId || !r.CommInitRank || !r.AllReduce || !r.CommDestroy) { err = "librccl: missing symbols"; return PGO_ERR_COMM; }
-    return PGO_OK;
-}
-static Rccl g_rccl_for_id;
-
-int pgo_comm_get_unique_id(uint8_t id[PGO_COMM_ID_BYTES]) {
-    if (!id) return PGO_ERR_INVALID_ARG;
-    std::string err;
-    if (load_rccl(g_rccl_for_id, err) != PGO_OK) return PGO_ERR_COMM;
-    Rccl::Uid u;
-    if (g_rccl_for_id.GetUniqueId(&u) != 0) return PGO_ERR_COMM;
-    std::memcpy(id, u.b, PGO_COMM_ID_BYTES);
-    return PGO_OK;
-}
 int pgo_comm_init(pgo_problem* p, int32_t rank, int32_t world, const uint8_t id[PGO_COMM_ID_BYTES]) {
     if (!p || !id || world < 1 || rank < 0 || rank >= world) return PGO_ERR_INVALID_ARG;
-    int rc;
-    if ((rc = set_device(p)) != PGO_OK) return rc;
-    if ((rc = load_rccl(p->nccl, p->err)) != PGO_OK) return rc;
-    Rccl::Uid u;
-    std::memcpy(u.b, id, PGO_COMM_ID_BYTES);
-    void* comm = nullptr;
-    const int nrc = p->nccl.CommInitRank(&comm, world, u, rank);
-    if (nrc != 0) { p->err = std::string("ncclCommInitRank: ") + (p->nccl.GetErrorString ? p->nccl.GetErrorString(nrc) : "error"); return PGO_ERR_COMM; }
-    mg_job_cancel(p); mg_init_drop(p);
-    p->comm = comm; p->rank = rank; p->world = world;
-    p->graph_dirty = true;   // keyframe participation is the union over ranks
-    return PGO_OK;
+    return attach_comm(p, [&](std::unique_ptr<pgo_comm::Comm>& c) { return pgo_comm::make_rccl_comm(id, rank, world, p->st, c, p->err); });
 }
 int pgo_comm_init_custom(pgo_problem* p, int32_t rank, int32_t world, pgo_allreduce_fn fn, void* ctx) {
     if (!p || !fn || world < 1 || rank < 0 || rank >= world) return PGO_ERR_INVALID_ARG;
-    mg_job_cancel(p); mg_init_drop(p);
-    p->custom_allreduce = fn; p->custom_ctx = ctx; p->rank = rank; p->world = world;
-    p->graph_dirty = true;
-    return PGO_OK;
+    return attach_comm(p, [&](std::unique_ptr<pgo_comm::Comm>& c) { c = pgo_comm::make_custom_comm(fn, ctx, rank, world, p->st); return PGO_OK; });
 }
 int pgo_comm_set_exchange(pgo_problem* p, pgo_exchange_fn fn) {
-    if (!p || !p->custom_allreduce) return PGO_ERR_INVALID_ARG;      // (belongs to a communicator set up by pgo_comm_init_custom)
-    p->custom_exchange = fn;
-    return PGO_OK;
-}
-int pgo_local_group_create(int32_t world, void** group) {
-    if (!group || world < 1 || world > pgo_local::MAX_RANKS) return PGO_ERR_INVALID_ARG;
-    pgo_local::Group* G = new (std::nothrow) pgo_local::Group();
-    if (!G) return PGO_ERR_OUT_OF_MEMORY;
-    G->world = world;
-    *group = G;
-    return PGO_OK;
-}
-int pgo_local_group_abort(void* group) {
-    if (!group) return PGO_ERR_INVALID_ARG;
-    static_cast<pgo_local::Group*>(group)->abort();
-    return PGO_OK;
-}
-int pgo_local_group_destroy(void* group) {
-    if (!group) return PGO_ERR_INVALID_ARG;
-    delete static_cast<pgo_local::Group*>(group);
-    return PGO_OK;
+    return p && p->comm && p->comm->set_exchange(fn) ? PGO_OK : PGO_ERR_INVALID_ARG;      // (belongs to a communicator set up by pgo_comm_init_custom)
 }
 int pgo_comm_init_local(pgo_problem* p, int32_t rank, int32_t world, void* group) {
-    pgo_local::Group* G = static_cast<pgo_local::Group*>(group);
-    if (!p || !G || world != G->world || rank < 0 || rank >= world) return PGO_ERR_INVALID_ARG;
-    int rc;
-    if ((rc = set_device(p)) != PGO_OK) return rc;
-    pgo_local::Group::Slot& me = G->slot[rank];
-    if (me.joined) { p->err = "in-process communicator: the rank is taken"; return PGO_ERR_INVALID_ARG; }
-    for (int k = 0; k < 2; ++k) {
-        HIPCHK(p, hipEventCreateWithFlags(&me.ready[k], hipEventDisableTiming));
-        HIPCHK(p, hipEventCreateWithFlags(&me.done[k], hipEventDisableTiming));
-    }
-    me.device = p->device; me.joined = true;
-    mg_job_cancel(p); mg_init_drop(p);
-    p->local_group = G; p->lc_count = 0; p->rank = rank; p->world = world;
-    p->graph_dirty = true;
-    // ranks on other GPUs of this process: their buffers are read over xGMI (peer access); every rank has joined once all have passed this barrier
-    if (!G->barrier()) { p->err = "in-process communicator: not all ranks joined"; return PGO_ERR_COMM; }
-    for (int q = 0; q < world; ++q) if (q != rank && G->slot[q].device != p->device) { const hipError_t e = hipDeviceEnablePeerAccess(G->slot[q].device, 0); if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { (void)hipGetLastError(); p->err = "in-process communicator: no peer access between the ranks' GPUs"; G->abort(); return PGO_ERR_COMM; } (void)hipGetLastError(); }
-    return PGO_OK;
+    if (!p || !group || rank < 0 || rank >= world) return PGO_ERR_INVALID_ARG;
+    return attach_comm(p, [&](std::unique_ptr<pgo_comm::Comm>& c) { return pgo_comm::make_local_comm(group, rank, world, p->device, p->st, c, p->err); });
 }
 int pgo_get_sharding_stats(pgo_problem* p, pgo_sharding_stats* out) {
     if (!p || !out) return PGO_ERR_INVALID_ARG;
     std::memset(out, 0, sizeof(*out));
-    out->world = p->world; out->rank = p->rank;
+    out->world = p->world(); out->rank = p->rank();
     if (!p->local_ids || p->graph_dirty) return PGO_OK;
     out->keyframes_local = p->N;
     for (double w : p->h_own) if (w != 0.0) ++out->keyframes_owned;
@@ -3263,24 +3047,8 @@ int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8) {
 }
 int pgo_comm_destroy(pgo_problem* p) {
     if (!p) return PGO_ERR_INVALID_ARG;
-    p->custom_allreduce = nullptr; p->custom_ctx = nullptr; p->custom_exchange = nullptr;
-    if (p->local_group) {      // every rank's stream has drained before any event or staging buffer goes (a peer's kernel may still be reading them)
-        pgo_local::Group* G = p->local_group;
-        (void)hipStreamSynchronize(p->st);
-        (void)G->barrier();
-        pgo_local::Group::Slot& me = G->slot[p->rank];
-        for (int k = 0; k < 2; ++k) {
-            if (me.ready[k]) (void)hipEventDestroy(me.ready[k]);
-            if (me.done[k]) (void)hipEventDestroy(me.done[k]);
-            if (me.stage[k]) (void)hipFree(me.stage[k]);
-            me.ready[k] = me.done[k] = nullptr; me.stage[k] = nullptr; me.stage_cap[k] = 0; me.ptr[k] = nullptr; me.send_off[k] = nullptr;
-        }
-        me.joined = false;
-        p->local_group = nullptr;
-    }
-    if (p->comm && p->nccl.CommDestroy) { (void)hipStreamSynchronize(p->st); p->nccl.CommDestroy(p->comm); }
+    p->comm.reset();
     mg_job_cancel(p); mg_init_drop(p);
-    p->comm = nullptr; p->rank = 0; p->world = 1;
     p->graph_dirty = true;
     return PGO_OK;
 }
@@ -3372,10 +3140,10 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
             launch_cg_init_scalars(p->C, g, g, 0.0, p->st);
         }
     }
-    // in-process ranks share the GPU(s) of one process: the timed launches of the ranks take turns (every rank's figure is what its GPU would need on its own)
-    const int turns = (p->local_group && (which == 7 || which == 8)) ? p->world : 1;
+    // several ranks: the timed launches take turns (every rank's figure is what its GPU would need on its own); only the in-process ranks, which share the GPU(s), wait for each other
+    const int turns = (p->comm && (which == 7 || which == 8)) ? p->world() : 1;
     for (int turn = 0; turn < turns; ++turn) {
-    if (turns > 1) { HIPCHK(p, hipStreamSynchronize(p->st)); if (!p->local_group->barrier()) { p->err = "in-process communicator: a rank left during pgo_time_kernel"; return PGO_ERR_COMM; } if (turn != p->rank) continue; }
+    if (turns > 1) { HIPCHK(p, hipStreamSynchronize(p->st)); if (!p->comm->barrier()) { p->err = "in-process communicator: a rank left during pgo_time_kernel"; return PGO_ERR_COMM; } if (turn != p->rank()) continue; }
     if (which == 5 && single_reduction(p)) {      // (its head needs the u.w partials of a matvec on the CURRENT u: launched back to back it sees stale ones, breaks down and returns early)
         p->err = "pgo_time_kernel(5): the single-reduction update cannot be timed without its matvec; time the iteration (2) and the matvec (4) and subtract"; return PGO_ERR_STATE;
     }
@@ -3475,7 +3243,7 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
         if (rep >= 1) { float msb = 0; HIPCHK(p, hipEventElapsedTime(&msb, e0, e1)); if (best_ms < 0.0 || (double)msb < best_ms) best_ms = (double)msb; }
     }
     }
-    if (turns > 1 && !p->local_group->barrier()) { p->err = "in-process communicator: a rank left during pgo_time_kernel"; return PGO_ERR_COMM; }
+    if (turns > 1 && !p->comm->barrier()) { p->err = "in-process communicator: a rank left during pgo_time_kernel"; return PGO_ERR_COMM; }
     if (which == 8) { p->mg_active = false; if ((rc = build_mg(p)) != PGO_OK) return rc; }      // (several ranks: the timed kernels ran without their exchanges — the operators are formed again, properly)
     *avg_ms = best_ms / launches;
     if (algorithmic_bytes) *algorithmic_bytes = bytes;
