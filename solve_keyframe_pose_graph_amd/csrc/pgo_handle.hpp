@@ -1,0 +1,270 @@
+// pgo_handle.hpp — the problem handle (struct pgo_problem) and what the two host translation units share: pgo_solver.hip (graph build, LM controller, PCG, C-ABI)
+// and pgo_multigrid.hip (the multigrid preconditioner's host lifecycle: hierarchy build, install, regroup, operators of each LM system).  Internal: not installed.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdlib>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "pgo.h"
+#include "pgo_internal.hpp"
+#include "pgo_comm.hpp"
+#include "pgo_mg_host.hpp"
+
+// (what the two translation units share stays inside libpgo: only the C-ABI of pgo.h is exported)
+#pragma GCC visibility push(hidden)
+namespace pgo {
+
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// Debug hooks.  None of them is honoured unless the process ALSO sets PGO_ENABLE_DEBUG_HOOKS=1 (read once per process): a PGO_DEBUG_* variable that leaks into a production
+// environment on its own does nothing.  The test suite sets the master switch in tests/conftest.py.
+inline bool debug_hooks_enabled() { static const bool on = []() { const char* e = std::getenv("PGO_ENABLE_DEBUG_HOOKS"); return e && e[0] == '1' && e[1] == 0; }(); return on; }
+// PGO_DEBUG_POISON=1 (read once per process): every new device allocation is filled with 0xFF bytes — a NaN in every double / float, -1 in every index —
+// so that a kernel reading memory nobody wrote fails the same way on every box instead of depending on what the allocation held before (tests/test_gpu_determinism.py runs
+// its solves under it and compares the results bit for bit with an unpoisoned run).
+inline bool debug_poison() { static const bool on = []() { const char* e = std::getenv("PGO_DEBUG_POISON"); return debug_hooks_enabled() && e && e[0] == '1' && e[1] == 0; }(); return on; }
+// PGO_DEBUG_BREAK_COARSE=1 (read at every operator build so that a test can switch it inside one process): the dense coarse inverse of the two-level method /
+// of the multigrid's coarsest level is applied with the wrong sign — a preconditioner that is not positive definite, i.e. a forced PCG breakdown.
+inline bool debug_break_coarse() { if (!debug_hooks_enabled()) return false; const char* e = std::getenv("PGO_DEBUG_BREAK_COARSE"); return e && e[0] == '1' && e[1] == 0; }
+
+// a device buffer that owns its memory: grown by ensure(), freed when it goes (the handle's buffers when the handle is deleted, a function's scratch at scope exit)
+template <class T>
+struct DBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DBuf() = default;
+    DBuf(const DBuf&) = delete;
+    DBuf& operator=(const DBuf&) = delete;
+    ~DBuf() { if (p) (void)hipFree(p); }
+    hipError_t ensure(size_t n) {
+        if (n <= cap) return hipSuccess;
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        const size_t want = n + n / 8 + 64;
+        hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
+        if (e == hipSuccess) cap = want;
+        if (e == hipSuccess && debug_poison()) { e = hipMemset(p, 0xFF, want * sizeof(T)); if (e == hipSuccess) e = hipDeviceSynchronize(); }
+        return e;
+    }
+};
+
+// a pair of timing events destroyed on EVERY exit of the function that holds it (the HIPCHK early returns included)
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t create() { hipError_t e = hipEventCreate(&e0); if (e == hipSuccess) e = hipEventCreate(&e1); return e; }
+    ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
+struct HostClass {
+    std::vector<int32_t> c1, c2, sw;
+    std::vector<double> meas;   // 8 per edge: q_obs(4) t_obs(3) w
+    int64_t size() const { return (int64_t)c1.size(); }
+};
+
+// ---- the multigrid's state on the handle (pgo_multigrid.hip)
+struct MgPrepared;                                        // host half of a hierarchy build (pgo_multigrid.hip)
+struct MgPreparedFree { void operator()(MgPrepared* Q) const; };
+using MgImage = std::unique_ptr<MgPrepared, MgPreparedFree>;
+
+// several ranks: a level's exchange (index lists in the int32 pool, segment bounds on the host), the distributed set-up's block exchanges of a level
+struct LevelPlanDev { const int32_t* send_idx = nullptr; const int32_t* recv_idx = nullptr; const pgo_mg::ExchangePlan* plan = nullptr; };
+struct SetupPlanDev { const int32_t* val_send = nullptr; const int32_t* val_dst = nullptr; const int32_t* val_sum_ptr = nullptr; const int32_t* val_sum_src = nullptr;
+                      const int32_t* ps_send = nullptr; const int32_t* ps_recv = nullptr; const int32_t* rv_send = nullptr; const int32_t* rv_recv = nullptr; };
+// this rank's rows of a level and the block ranges they span (one GPU, and levels every rank runs completely: everything)
+struct OwnRange { int64_t row0 = 0, row1 = 0, blk0 = 0, blk1 = 0, ps0 = 0, ps1 = 0, w0 = 0, w1 = 0, rT0 = 0, rT1 = 0; };
+
+// The one host build that may be in flight: a fresh graph's hierarchy (started at the top of build_graph, installed where it is first needed — build_mg, the end of the solve,
+// or the next solve_begin; until then `built` is true, "this graph has a hierarchy", and the level descriptors are empty) or a regroup (started after the accepted step that
+// moved the switches, installed where multigrid operators are next built).  Where either is installed depends on the solve's own history, never on timing.
+struct MgJob {
+    enum Kind { none, fresh, regroup };
+    Kind kind = none;
+    std::thread thread;
+    MgImage out;                          // what the worker fills
+    int rc = 0;                           // ... and its return code
+    MgImage old;                          // the image installed last: freed by the next worker or with the handle, off the solve's critical path (regroup_install)
+};
+
+struct MgState {
+    DBuf<double> f64; DBuf<int32_t> i32; DBuf<int64_t> i64;      // the hierarchy's arrays live in three pooled buffers
+    MgDev M{}; MgLevelDev levels[MG_MAX_LEVELS];
+    bool fine = false; MgLevelDev fineF{}, fineT{};      // smoothed keyframe transition (opt.mg_smoothed_fine): the keyframe level's set-up view and transfer view
+    int fine_auto = -1;                    // mg_smoothed_fine < 0: the decision of this graph build (-1 not taken yet, 0 / 1), written by the hierarchy's worker before it is joined
+    bool built = false, active = false;
+    pgo_mg::BuildCache cache;              // what the hierarchy builder keeps for a regroup of the same graph
+    std::vector<double> sw_built;          // [Es] s^2 of every switchable edge the current hierarchy was built with
+    int regroups = 0;                      // regroups of this solve
+    uint64_t geometry_epoch = 0;
+    MgJob job;
+    // several ranks: the level exchanges, per sparse level whether its kernels run on the owner's rows only
+    std::vector<LevelPlanDev> lvl_plan;
+    std::vector<pgo_mg::ExchangePlan> plans;      // the installed hierarchy's level plans (their segment bounds are read at every exchange)
+    std::vector<uint8_t> dist;
+    // distributed set-up (round 6): levels [0, first_whole) form the numbers of their own rows only, level first_whole is gathered, the rest is set up by every rank;
+    // 0: the set-up is replicated (one GPU; level 1 not distributed; pgo_options.mg_dist_setup = 0)
+    pgo_mg::SetupPlans setup; int first_whole = 0;
+    int32_t fw_row0 = 0, fw_row1 = 0; int64_t fw_blk0 = 0, fw_blk1 = 0;      // this rank's rows / blocks of level first_whole (it forms them, then all ranks gather the level)
+    std::vector<SetupPlanDev> su_plan;
+    std::vector<OwnRange> own;             // what the rank's cycle kernels read of every level (pgo_mg_level_norms)
+    int levels_distributed = 0; int64_t rows_total = 0, rows_own = 0, blocks_total = 0, blocks_own = 0;      // sharding counters
+    bool fresh_pending() const { return job.kind == MgJob::fresh; }
+};
+
+}  // namespace pgo
+#pragma GCC visibility pop
+
+using namespace pgo;
+
+struct pgo_problem {
+    pgo_options opt;
+    int device = 0;
+    hipStream_t st = nullptr;
+    std::string err;
+
+    HostClass rel, swe;
+    std::vector<PriorDev> priors;
+    std::vector<int32_t> constant_nodes;
+    bool graph_dirty = true, priors_dirty = true;
+
+    // device graph.  N = keyframes this handle works on: all of the caller's (one GPU), or — multi-GPU — only those touched by the
+    // rank's own residual blocks, renumbered densely in ascending global order ("rank-local subgraph"); N_global = the caller's count.
+    int64_t N = 0, S = 0, N_global = 0;
+    bool local_ids = false;
+    std::vector<int32_t> l2g, g2l;            // local -> global, global -> local (-1: not touched by this rank)
+    std::vector<uint8_t> h_touched_any;       // [N_global] some rank holds a residual block on the keyframe
+    std::vector<double> h_own;                // [N] 1.0 where this rank is the keyframe's owner (lowest rank touching it)
+    std::vector<double> h_init_q, h_init_t;   // multi-GPU: the caller's state at solve_begin (keyframes no rank touches are returned as given)
+    std::vector<uint64_t> h_touch_mask;       // [N_global] bit r: rank r holds a residual block on the keyframe (one all-reduce at graph build)
+    std::vector<int32_t> h_owner;             // [N_global] the rank that owns the keyframe: the one holding most of its residual blocks (a second all-reduce), -1: nobody touches it
+    pgo_mg::FinePlan fine_plan;               // the keyframes' neighbour exchange: who shares which keyframes with this rank, and the order their parts are summed in
+    DBuf<int32_t> d_l2g, d_fp_send, d_fp_shloc, d_fp_sumptr, d_fp_sumsrc;
+    DBuf<double> d_own, d_xsend[2], d_xrecv, d_xscal;   // owner weights; send buffers (by collective parity), receive buffer, the iteration's two scalars
+    int64_t n_sh_mine = 0, n_sh_global = 0;
+    // exchange accounting (pgo_get_sharding_stats)
+    int64_t st_exchanges = 0, st_allreduces = 0, st_pcg_iterations = 0; double st_bytes_neighbour = 0.0, st_bytes_allreduce = 0.0;
+    DBuf<int32_t> d_rc1, d_rc2, d_sc1, d_sc2, d_sidx, d_bsr_col;
+    DBuf<double> d_rmeas, d_smeas;
+    DBuf<int4> d_rwin, d_swin;
+    DBuf<PriorDev> d_prior;
+    DBuf<int64_t> d_inc_rowptr, d_inc, d_bsr_rowptr;
+    DBuf<uint8_t> d_node_free;
+    DBuf<double> d_Jr, d_Js, d_Jp;
+    DBuf<double> d_Hd_g;             // Hd [N][36] followed by g [N][6]  (contiguous: one all-reduce)
+    DBuf<double> d_Hoff, d_c, d_hss, d_gs;
+    DBuf<double> d_scale_p, d_scale_s, d_diag_p, d_diag_s, d_a_inv;
+    DBuf<double> d_val, d_Dtot_b;   // Dtot [N][36] followed by b [N][6]
+    DBuf<float> d_Lf;
+    DBuf<double> d_cgvec;            // x r r2 z p p2 q  (7 x [N][6])
+    DBuf<double> d_part;             // partial-sum scratch: several arrays of n_part
+    DBuf<double> d_cgpart;           // part_pq [MAX] + part_rz [2][MAX] + scal[4]
+    DBuf<int32_t> d_flags;           // cg flags [4] + invert fail [1]
+    DBuf<double> d_scal;             // S_N doubles
+    DBuf<double> d_pose[2], d_swv[2], d_delta_s, d_io;   // state ping-pong, staging for quat/t
+    DBuf<double> d_tmp;
+    DBuf<double> d_vio;              // raw VIO poses [n_vio][16] (graph construction, K0)
+    DBuf<int32_t> d_vio_idx; DBuf<double> d_vio_meas;   // K0's edge endpoints and measurements of one call
+    // two-level preconditioner (CoarseDev)
+    DBuf<double> d_ccen, d_cd, d_cAc, d_crc, d_cscr;
+    DBuf<float> d_cAcf;              // the dense inverse rounded to fp32
+    DBuf<int64_t> d_cblk_ptr, d_ccontrib;
+    DBuf<int32_t> d_cblk_ab, d_cagg_free, d_cinfo;
+    CoarseDev K{};
+    bool coarse_built = false, coarse_active = false;
+    int coarse_mode = 0;             // per solve: 0 not yet compared with plain block-Jacobi, 1 keep, 2 dropped (it did not pay on this graph)
+    int coarse_retests = 0; bool coarse_skip_all = false; double coarse_drop_radius = 0.0;   // dropped at a small radius: one more comparison once the radius reaches coarse_min_radius
+    int coarse_backoff = 0, coarse_skip = 0;   // a handle that keeps dropping it (incremental triggers on the same kind of graph) retests ever more rarely
+    int coarse_keep_streak = 0;      // consecutive solves that kept it: the comparison is then repeated only every 4th solve
+    uint64_t coarse_geometry_epoch = 0, lin_epoch = 0;   // lin_epoch counts linearisations (the centroids follow the poses)
+    MgState mg;                            // the aggregation multigrid (pgo_multigrid.hip)
+    uint64_t hoff_epoch = 0;               // linearisation whose J1^T J2 blocks L.Hoff holds (matrix-free solver: formed on demand for the multigrid's level-1 product)
+    int64_t n_vio = 0;
+    // matrix-free operator
+    DBuf<uint32_t> d_einc;
+    DBuf<uint32_t> d_einc_slot;
+    DBuf<ushort4> d_node_rng;
+    DBuf<int64_t> d_tile_inc0;
+    DBuf<int32_t> d_einc_other, d_tile_node0, d_tile_sw0, d_node_prior;
+    DBuf<double2> d_rec;
+    DBuf<double> d_lam;
+    MfDev F{};
+    bool built_mf = false;
+    int64_t mf_pair_lanes = 0, mf_rel_side_lanes = 0, mf_sw_lanes = 0;   // lanes of the matrix-free operator by kind (pgo_time_kernel's bytes)
+    int cur = 0;
+    int64_t n_part = MAX_PARTIALS;
+    std::vector<uint8_t> h_node_free, h_sw_used;
+    int64_t nnzb = 0;
+
+    GraphDev G{};
+    LinDev L{};
+    ScaleDev Sc{};
+    CgDev C{};
+
+    // LM state
+    bool in_solve = false, scale_ready = false, terminated = false, have_prev_step = false;
+    double radius = 0, decrease_factor = 2, x_cost = 0, x_norm = 0, gmax = 0;
+    bool reuse_diagonal = false;
+    int iteration = 0, invalid = 0;
+    double t_begin = 0, t_device0 = 0;
+    pgo_summary sum;
+
+    // the multi-rank transport (pgo_comm.hpp); none on one GPU
+    std::unique_ptr<pgo_comm::Comm> comm;
+    int rank() const { return comm ? comm->rank() : 0; }
+    int world() const { return comm ? comm->world() : 1; }
+
+    // pipelined convergence polling: pinned host copies of {flags[4], scal[4]} for two chunks in flight
+    struct Poll { int32_t flags[4]; double scal[4]; };
+    Poll* poll = nullptr; hipEvent_t poll_ev[2] = {nullptr, nullptr};      // poll[2]: snapshot at the start of a PCG phase (base point of the convergence-rate estimate)
+
+    // hipGraph of one PCG chunk (launch-bound inner loop); valid for (graph build epoch, tolerance, chunk length, solver)
+    // one captured chunk per preconditioner (0 block-Jacobi, 1 two-level, 2 multigrid): the hybrid policy changes between them inside a solve
+    struct CapturedChunk { hipGraphExec_t exec = nullptr; int len = 0; uint64_t epoch = 0; double scale = 0.0; bool sr = false; };   // scale: mg_correction_scale is a by-value kernel argument of the captured cycle
+    CapturedChunk cg_chunk[3];
+    hipGraphExec_t cg_graph = nullptr;   // the one in use (not owned)
+    uint64_t build_epoch = 1; bool cg_graph_failed = false;
+    double cg_predicted = 0.0;      // block-Jacobi-equivalent iterations predicted for the current LM system (build_system); 0: none
+    double cg_prev_equiv = 0.0, cg_prev_radius = 0.0;   // block-Jacobi-equivalent PCG iterations and radius of the last fully solved LM system of this solve
+    int mg_switch_at = 400;              // in-flight switch point of the current LM system (build_system)
+    int cg_extra = 0;                    // PCG iterations of the current LM step spent before a change of preconditioner
+    bool mg_failed = false;              // the multigrid operators of the current system could not be built
+    double last_rho = 1.0;               // relative decrease of the last accepted step of this solve
+    bool mg_start_deferred = false;      // the current system is predicted hard, but its multigrid operators are built only once the step has survived the first early-rejection pause
+};
+
+
+#define HIPCHK(p, expr) PGO_HIPCHK((p)->err, expr)
+
+#pragma GCC visibility push(hidden)
+namespace pgo {
+
+// ---- pgo_solver.hip: the collectives (no-ops without a communicator) and what a graph without a hierarchy preconditions with
+int allreduce(pgo_problem* p, double* buf, size_t n, int op /*0 sum, 2 max*/);
+int host_allreduce(pgo_problem* p, std::vector<double>& v, int op);
+int exchange_level(pgo_problem* p, int l, double* v1, double* v2, const int32_t* stop, const double* dinv);
+int exchange_blocks_copy(pgo_problem* p, const pgo_mg::ExchangePlan& X, const int32_t* send_idx, const int32_t* recv_idx, double* arr, int K);
+int exchange_blocks_sum(pgo_problem* p, const pgo_mg::BlockPlan& B, const SetupPlanDev& D, double* arr);
+int ensure_exchange_buffers(pgo_problem* p);
+int build_two_level_aggregates(pgo_problem* p);
+
+// ---- pgo_multigrid.hip
+bool wants_multigrid(const pgo_problem* p);
+void mg_drop_pending(pgo_problem* p);
+bool mg_start_fresh(pgo_problem* p, const double* sw_now);
+int build_multigrid(pgo_problem* p, const double* sw_now);
+int mg_fresh_install(pgo_problem* p);
+int regroup_if_moved(pgo_problem* p, const double* sv, bool in_solve);
+int regroup_start(pgo_problem* p);
+int build_mg(pgo_problem* p);
+int mg_operators(pgo_problem* p, int32_t* fail, bool hoff_valid, bool kernels_only, double t_build0);
+bool mg_exchange_at(pgo_problem* p, int point, int lv, int* plan, double** v1, double** v2, const double** dinv);
+int mg_apply_ranks(pgo_problem* p, bool inside_iteration);
+double mg_cs(const pgo_problem* p);
+double mg_scale(const pgo_problem* p);
+const MgLevelDev* mg_fine_view(const pgo_problem* p);
+
+}  // namespace pgo
+#pragma GCC visibility pop

@@ -303,7 +303,7 @@ void launch_mg_assemble_fine(const GraphDev& G, const LinDev& L, const ScaleDev&
                              double prolong_scale, bool hoff_valid, const double* pose8 = nullptr /* filtered form (F.dlump): the keyframes' positions of the current linearisation */);      // level 1 = Ps_0^T A Ps_0 (smoothed keyframe transition), then launch_mg_assemble_rest
 void launch_mg_assemble_rest(const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, double omega, int32_t* fail, hipStream_t st, double prolong_scale = 0.0 /* c = w_p / w of the smoothed transitions */,
                              int first_level = 0 /* levels[first_level].val is complete already: its inverses and everything above */);
-// ... and the pieces it is made of, each on the level's set-up share (MgLevelDev::su_*): several ranks run them with block exchanges in between (pgo_solver.hip: build_mg_ranks)
+// ... and the pieces it is made of, each on the level's set-up share (MgLevelDev::su_*): several ranks run them with block exchanges in between (pgo_multigrid.hip: build_mg_ranks)
 void launch_mg_level_inverses(const MgLevelDev& A, double omega, int32_t* fail, hipStream_t st);       // Dinv = omega D^-1 and the fp32 copy of the blocks
 void launch_mg_level_power(const MgLevelDev& A, double omega, hipStream_t st);                        // lambda_max(D^-1 A) estimate of a whole level -> A.xf[0]
 // ... of a distributed level, step by step (the caller exchanges the iterate's halo before every step and all-reduces the sums): start vector on the own rows of A.x (A.xt zeroed),

@@ -753,7 +753,7 @@ __global__ __launch_bounds__(256) void mg_rescale_dinv_kernel(MgLevelDev A, cons
     if (i < (int64_t)A.su_row1 * 36) A.Dinv[i] *= f;
 }
 // The whole level (one GPU, and levels every rank sets up completely).  A distributed level runs the same eight steps on the owners' rows with the halo of the iterate exchanged
-// before every step and the two norms all-reduced (pgo_solver.hip: build_mg_ranks, through the pieces below) — the same estimate up to the order of the sums.  (First tried: every
+// before every step and the two norms all-reduced (pgo_multigrid.hip: build_mg_ranks, through the pieces below) — the same estimate up to the order of the sums.  (First tried: every
 // rank on its own diagonal part of D^-1 A, the estimates maximised — a lower bound as well, no exchanges; scripts/gpu_ranks_soak.py case 36 — 6 010 keyframes on 3 ranks by index
 // ranges, two smoothed transitions — then missed a rescaling the whole-level estimate triggers and the PCG broke down on a preconditioner that was not positive definite.)
 void launch_mg_level_power(const MgLevelDev& A, double omega, hipStream_t st) {

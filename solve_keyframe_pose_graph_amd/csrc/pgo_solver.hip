@@ -8,38 +8,18 @@
 // linear solve is a device PCG instead of SPARSE_NORMAL_CHOLESKY.  There is NO CPU fallback: without a HIP
 // device pgo_create fails.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
-#include <thread>
 #include <vector>
 
-#include "pgo.h"
-#include "pgo_internal.hpp"
-#include "pgo_comm.hpp"
-#include "pgo_mg_host.hpp"
-
-using namespace pgo;
+#include "pgo_handle.hpp"
 
 namespace {
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// Debug hooks.  None of them is honoured unless the process ALSO sets PGO_ENABLE_DEBUG_HOOKS=1 (read once per process): a PGO_DEBUG_* variable that leaks into a production
-// environment on its own does nothing.  The test suite sets the master switch in tests/conftest.py.
-bool debug_hooks_enabled() { static const bool on = []() { const char* e = std::getenv("PGO_ENABLE_DEBUG_HOOKS"); return e && e[0] == '1' && e[1] == 0; }(); return on; }
-// PGO_DEBUG_POISON=1 (read once per process): every new device allocation is filled with 0xFF bytes — a NaN in every double / float, -1 in every index —
-// so that a kernel reading memory nobody wrote fails the same way on every box instead of depending on what the allocation held before (tests/test_gpu_determinism.py runs
-// its solves under it and compares the results bit for bit with an unpoisoned run).
-bool debug_poison() { static const bool on = []() { const char* e = std::getenv("PGO_DEBUG_POISON"); return debug_hooks_enabled() && e && e[0] == '1' && e[1] == 0; }(); return on; }
-
-// PGO_DEBUG_BREAK_COARSE=1 (read at every operator build so that a test can switch it inside one process): the dense coarse inverse of the two-level method /
-// of the multigrid's coarsest level is applied with the wrong sign — a preconditioner that is not positive definite, i.e. a forced PCG breakdown.
-bool debug_break_coarse() { if (!debug_hooks_enabled()) return false; const char* e = std::getenv("PGO_DEBUG_BREAK_COARSE"); return e && e[0] == '1' && e[1] == 0; }
 // PGO_DEBUG_GRAPH_AFTER=<n> (read once): the PCG captures its chunk as a hipGraph after n eager iterations instead of 192; values that are not an even number in [2, 10^6] are ignored
 int debug_graph_after() {
     static const int v = []() {
@@ -51,226 +31,8 @@ int debug_graph_after() {
     return v;
 }
 
-template <class T>
-struct DBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        const size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        if (e == hipSuccess && debug_poison()) { e = hipMemset(p, 0xFF, want * sizeof(T)); if (e == hipSuccess) e = hipDeviceSynchronize(); }
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-// a pair of timing events destroyed on EVERY exit of the function that holds it (the HIPCHK early returns included)
-struct EventPair {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t create() { hipError_t e = hipEventCreate(&e0); if (e == hipSuccess) e = hipEventCreate(&e1); return e; }
-    ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-
-// function-local device scratch (freed at scope exit; DBuf members of pgo_problem are released by pgo_destroy)
-template <class T>
-struct ScopedBuf : DBuf<T> { ~ScopedBuf() { this->release(); } };
-
-struct HostClass {
-    std::vector<int32_t> c1, c2, sw;
-    std::vector<double> meas;   // 8 per edge: q_obs(4) t_obs(3) w
-    int64_t size() const { return (int64_t)c1.size(); }
-};
-
 // scalar slots
 enum { S_COST = 0, S_PRIOR_COST = 1, S_MODEL = 2, S_SW_STEP2 = 3, S_SW_XNORM2 = 4, S_GMAX = 5, S_STEP2 = 6, S_XNORM2 = 7, S_N = 8 };
-
-// Host half of a multigrid build (pgo_mg_host.hpp's hierarchy + the pooled index arrays and offsets of its device image): no HIP call, no collective in here when the handle is a
-// single rank's — that half can therefore run on a worker thread while the stream works on other LM steps (regroup, below); mg_install() uploads it.
-struct MgPrepared {
-    bool ok = false;
-    pgo_mg::Hierarchy H;
-    std::vector<int32_t> agg0_l, mem0_ptr_l, mem0_l;      // several ranks: the keyframe-indexed arrays in the handle's local numbering
-    std::vector<double> inv_cnt;
-    std::vector<int32_t> pi32; std::vector<int64_t> pi64; size_t nf64 = 0;
-    struct Off { size_t col, parent, agg_ptr, tile, tile_rows, rowptr, g_ptr, g_ent, val, Dinv, pos, d, r, x, xt, xf, valf, ps_rowptr, ps_col, w_rowptr, w_col, psT_ptr, psT_ent, ps_val, w_val, t, u, y, zero, row_of, tr_of, ps_row, w_row,
-                        rt_rows, rT_rows, rT_col, rT_of_w, ps_of_w, rt_valf, r_valf; int rT_tiles, rT_seg_shift; };
-    std::vector<Off> off;
-    size_t o_agg0 = 0, o_mem0_ptr = 0, o_mem0 = 0, o_blk_tab = 0, o_d0 = 0, o_inv = 0;
-    bool have_tab = false;
-    // smoothed keyframe transition: the keyframe level F (pgo_mg_host.hpp) — its own block pattern and contribution ids, Ps / W structure, Ps by level-1 row for the restriction
-    bool fine = false;
-    struct FineOff { size_t rowptr, col, ent, ps_rowptr, ps_col, w_rowptr, w_col, psT_ptr, psT_ent, ps_row, w_row, rT_of_ps, rT_col, rT_rows, val, Dinv, ps_val, w_val, rt_valf, r_valf, lump; int rT_tiles, rT_seg_shift; bool filtered; } fo{};
-    // several ranks: who sends which rows of the level vectors to whom (plans[l]: level l+1; the last: the dense level's residual), and this rank's share of every level
-    std::vector<pgo_mg::ExchangePlan> plans;
-    std::vector<size_t> o_plan_send, o_plan_recv;      // offsets of the plans' index lists in the int32 pool
-    struct Share { int32_t tile0 = 0, tiles_own = 0, rT_row0 = 0, rT_row1 = 0; bool distributed = false; };
-    std::vector<Share> share;
-    int32_t a0 = 0, a1 = 0;                            // the rank's own level-1 aggregates
-    // several ranks, distributed set-up: the block exchanges of every distributed level (pgo_mg_host.hpp: SetupPlans) and where their index lists sit in the int32 pool
-    pgo_mg::SetupPlans setup;
-    struct SetupOff { size_t val_send = 0, val_dst = 0, val_sum_ptr = 0, val_sum_src = 0, ps_send = 0, ps_recv = 0, rv_send = 0, rv_recv = 0, prod = 0; };
-    std::vector<SetupOff> o_setup;
-    std::vector<int32_t> g0_slots; size_t o_g0 = 0;      // distributed set-up: the level-1 blocks this rank contributes to
-    std::vector<double> sw_built;          // [Es] s^2 of every switchable edge this hierarchy was matched with
-    double moved = 0.0, of_edges = 0.0, host_ms = 0.0;
-};
-
-}  // namespace
-
-struct pgo_problem {
-    pgo_options opt;
-    int device = 0;
-    hipStream_t st = nullptr;
-    std::string err;
-
-    HostClass rel, swe;
-    std::vector<PriorDev> priors;
-    std::vector<int32_t> constant_nodes;
-    bool graph_dirty = true, priors_dirty = true;
-
-    // device graph.  N = keyframes this handle works on: all of the caller's (one GPU), or — multi-GPU — only those touched by the
-    // rank's own residual blocks, renumbered densely in ascending global order ("rank-local subgraph"); N_global = the caller's count.
-    int64_t N = 0, S = 0, N_global = 0;
-    bool local_ids = false;
-    std::vector<int32_t> l2g, g2l;            // local -> global, global -> local (-1: not touched by this rank)
-    std::vector<uint8_t> h_touched_any;       // [N_global] some rank holds a residual block on the keyframe
-    std::vector<double> h_own;                // [N] 1.0 where this rank is the keyframe's owner (lowest rank touching it)
-    std::vector<double> h_init_q, h_init_t;   // multi-GPU: the caller's state at solve_begin (keyframes no rank touches are returned as given)
-    std::vector<uint64_t> h_touch_mask;       // [N_global] bit r: rank r holds a residual block on the keyframe (one all-reduce at graph build)
-    std::vector<int32_t> h_owner;             // [N_global] the rank that owns the keyframe: the one holding most of its residual blocks (a second all-reduce), -1: nobody touches it
-    pgo_mg::FinePlan fine_plan;               // the keyframes' neighbour exchange: who shares which keyframes with this rank, and the order their parts are summed in
-    DBuf<int32_t> d_l2g, d_fp_send, d_fp_shloc, d_fp_sumptr, d_fp_sumsrc;
-    DBuf<double> d_own, d_xsend[2], d_xrecv, d_xscal;   // owner weights; send buffers (by collective parity), receive buffer, the iteration's two scalars
-    int64_t n_sh_mine = 0, n_sh_global = 0;
-    // multigrid level exchanges (installed with the hierarchy)
-    struct LevelPlanDev { const int32_t* send_idx = nullptr; const int32_t* recv_idx = nullptr; const pgo_mg::ExchangePlan* plan = nullptr; };
-    std::vector<LevelPlanDev> lvl_plan;
-    std::vector<pgo_mg::ExchangePlan> mg_plans;   // several ranks: the installed hierarchy's level plans (their segment bounds are read at every exchange)
-    std::vector<uint8_t> mg_dist;             // per sparse level: its kernels run on the owner's rows only
-    // distributed set-up (round 6): levels [0, mg_first_whole) form the numbers of their own rows only, level mg_first_whole is gathered, the rest is set up by every rank;
-    // 0: the set-up is replicated (one GPU; level 1 not distributed; pgo_options.mg_dist_setup = 0)
-    pgo_mg::SetupPlans mg_setup; int mg_first_whole = 0;
-    int32_t mg_fw_row0 = 0, mg_fw_row1 = 0; int64_t mg_fw_blk0 = 0, mg_fw_blk1 = 0;      // this rank's rows / blocks of level mg_first_whole (it forms them, then all ranks gather the level)
-    struct SetupPlanDev { const int32_t* val_send = nullptr; const int32_t* val_dst = nullptr; const int32_t* val_sum_ptr = nullptr; const int32_t* val_sum_src = nullptr;
-                          const int32_t* ps_send = nullptr; const int32_t* ps_recv = nullptr; const int32_t* rv_send = nullptr; const int32_t* rv_recv = nullptr; };
-    std::vector<SetupPlanDev> su_plan;
-    struct OwnRange { int64_t row0 = 0, row1 = 0, blk0 = 0, blk1 = 0, ps0 = 0, ps1 = 0, w0 = 0, w1 = 0, rT0 = 0, rT1 = 0; };      // this rank's rows of every level and the block ranges they span (one GPU, and levels every rank runs completely: everything)
-    std::vector<OwnRange> mg_own;
-    int mg_levels_distributed = 0; int64_t mg_rows_total = 0, mg_rows_own = 0, mg_blocks_total = 0, mg_blocks_own = 0;
-    // exchange accounting (pgo_get_sharding_stats)
-    int64_t st_exchanges = 0, st_allreduces = 0, st_pcg_iterations = 0; double st_bytes_neighbour = 0.0, st_bytes_allreduce = 0.0;
-    DBuf<int32_t> d_rc1, d_rc2, d_sc1, d_sc2, d_sidx, d_bsr_col;
-    DBuf<double> d_rmeas, d_smeas;
-    DBuf<int4> d_rwin, d_swin;
-    DBuf<PriorDev> d_prior;
-    DBuf<int64_t> d_inc_rowptr, d_inc, d_bsr_rowptr;
-    DBuf<uint8_t> d_node_free;
-    DBuf<double> d_Jr, d_Js, d_Jp;
-    DBuf<double> d_Hd_g;             // Hd [N][36] followed by g [N][6]  (contiguous: one all-reduce)
-    DBuf<double> d_Hoff, d_c, d_hss, d_gs;
-    DBuf<double> d_scale_p, d_scale_s, d_diag_p, d_diag_s, d_a_inv;
-    DBuf<double> d_val, d_Dtot_b;   // Dtot [N][36] followed by b [N][6]
-    DBuf<float> d_Lf;
-    DBuf<double> d_cgvec;            // x r r2 z p p2 q  (7 x [N][6])
-    DBuf<double> d_part;             // partial-sum scratch: several arrays of n_part
-    DBuf<double> d_cgpart;           // part_pq [MAX] + part_rz [2][MAX] + scal[4]
-    DBuf<int32_t> d_flags;           // cg flags [4] + invert fail [1]
-    DBuf<double> d_scal;             // S_N doubles
-    DBuf<double> d_pose[2], d_swv[2], d_delta_s, d_io;   // state ping-pong, staging for quat/t
-    DBuf<double> d_tmp;
-    DBuf<double> d_vio;              // raw VIO poses [n_vio][16] (graph construction, K0)
-    DBuf<int32_t> d_vio_idx; DBuf<double> d_vio_meas;   // K0's edge endpoints and measurements of one call
-    // two-level preconditioner (CoarseDev)
-    DBuf<double> d_ccen, d_cd, d_cAc, d_crc, d_cscr;
-    DBuf<float> d_cAcf;              // the dense inverse rounded to fp32
-    DBuf<int64_t> d_cblk_ptr, d_ccontrib;
-    DBuf<int32_t> d_cblk_ab, d_cagg_free, d_cinfo;
-    CoarseDev K{};
-    bool coarse_built = false, coarse_active = false;
-    int coarse_mode = 0;             // per solve: 0 not yet compared with plain block-Jacobi, 1 keep, 2 dropped (it did not pay on this graph)
-    int coarse_retests = 0; bool coarse_skip_all = false; double coarse_drop_radius = 0.0;   // dropped at a small radius: one more comparison once the radius reaches coarse_min_radius
-    int coarse_backoff = 0, coarse_skip = 0;   // a handle that keeps dropping it (incremental triggers on the same kind of graph) retests ever more rarely
-    int coarse_keep_streak = 0;      // consecutive solves that kept it: the comparison is then repeated only every 4th solve
-    uint64_t coarse_geometry_epoch = 0, lin_epoch = 0;   // lin_epoch counts linearisations (the centroids follow the poses)
-    // aggregation multigrid (MgDev): hierarchy arrays live in three pooled buffers
-    DBuf<double> d_mg_f64; DBuf<int32_t> d_mg_i32; DBuf<int64_t> d_mg_i64;
-    MgDev M{}; MgLevelDev mg_levels[MG_MAX_LEVELS];
-    int mg_fine_auto = -1;                 // mg_smoothed_fine < 0: the decision of this graph build (-1 not taken yet, 0 / 1), written by the hierarchy's worker before it is joined
-    bool mg_fine = false; MgLevelDev mg_fineF{}, mg_fineT{};      // smoothed keyframe transition (opt.mg_smoothed_fine): the keyframe level's set-up view and transfer view
-    bool mg_built = false, mg_active = false;
-    pgo_mg::BuildCache mg_cache;           // what the hierarchy builder keeps for a regroup of the same graph
-    std::vector<double> mg_sw_built;       // [Es] s^2 of every switchable edge the current hierarchy was built with
-    int mg_regroups = 0;                   // regroups of this solve
-    // a regroup in flight: the host half of the rebuild runs on a worker thread from the LM iteration that found the switches moved (after an accepted step) and is
-    // installed where multigrid operators are next built — both points depend on the solve's own history only, never on timing
-    std::thread mg_job; std::unique_ptr<MgPrepared> mg_job_out, mg_job_old; bool mg_job_running = false;
-    int rc_job = 0;
-    // the hierarchy of a freshly built graph (one GPU): its host half is started on a worker thread at the top of build_graph and INSTALLED where it is first needed —
-    // build_mg (the first LM system that wants multigrid operators), the end of the solve, or the next solve_begin; until then mg_built is true ("this graph has a
-    // hierarchy") and the level descriptors are empty.  When it is needed is a property of the solve, how long the wait is not: results do not depend on timing.
-    std::thread mg_init_thread; std::unique_ptr<MgPrepared> mg_init_out; bool mg_init_pending = false; int rc_mg_init = 0;
-    uint64_t mg_geometry_epoch = 0;
-    uint64_t hoff_epoch = 0;               // linearisation whose J1^T J2 blocks L.Hoff holds (matrix-free solver: formed on demand for the multigrid's level-1 product)
-    int64_t n_vio = 0;
-    // matrix-free operator
-    DBuf<uint32_t> d_einc;
-    DBuf<uint32_t> d_einc_slot;
-    DBuf<ushort4> d_node_rng;
-    DBuf<int64_t> d_tile_inc0;
-    DBuf<int32_t> d_einc_other, d_tile_node0, d_tile_sw0, d_node_prior;
-    DBuf<double2> d_rec;
-    DBuf<double> d_lam;
-    MfDev F{};
-    bool built_mf = false;
-    int64_t mf_pair_lanes = 0, mf_rel_side_lanes = 0, mf_sw_lanes = 0;   // lanes of the matrix-free operator by kind (pgo_time_kernel's bytes)
-    int cur = 0;
-    int64_t n_part = MAX_PARTIALS;
-    std::vector<uint8_t> h_node_free, h_sw_used;
-    int64_t nnzb = 0;
-
-    GraphDev G{};
-    LinDev L{};
-    ScaleDev Sc{};
-    CgDev C{};
-
-    // LM state
-    bool in_solve = false, scale_ready = false, terminated = false, have_prev_step = false;
-    double radius = 0, decrease_factor = 2, x_cost = 0, x_norm = 0, gmax = 0;
-    bool reuse_diagonal = false;
-    int iteration = 0, invalid = 0;
-    double t_begin = 0, t_device0 = 0;
-    pgo_summary sum;
-
-    // the multi-rank transport (pgo_comm.hpp); none on one GPU
-    std::unique_ptr<pgo_comm::Comm> comm;
-    int rank() const { return comm ? comm->rank() : 0; }
-    int world() const { return comm ? comm->world() : 1; }
-
-    // pipelined convergence polling: pinned host copies of {flags[4], scal[4]} for two chunks in flight
-    struct Poll { int32_t flags[4]; double scal[4]; };
-    Poll* poll = nullptr; hipEvent_t poll_ev[2] = {nullptr, nullptr};      // poll[2]: snapshot at the start of a PCG phase (base point of the convergence-rate estimate)
-
-    // hipGraph of one PCG chunk (launch-bound inner loop); valid for (graph build epoch, tolerance, chunk length, solver)
-    // one captured chunk per preconditioner (0 block-Jacobi, 1 two-level, 2 multigrid): the hybrid policy changes between them inside a solve
-    struct CapturedChunk { hipGraphExec_t exec = nullptr; int len = 0; uint64_t epoch = 0; double scale = 0.0; bool sr = false; };   // scale: mg_correction_scale is a by-value kernel argument of the captured cycle
-    CapturedChunk cg_chunk[3];
-    hipGraphExec_t cg_graph = nullptr;   // the one in use (not owned)
-    uint64_t build_epoch = 1; bool cg_graph_failed = false;
-    double cg_predicted = 0.0;      // block-Jacobi-equivalent iterations predicted for the current LM system (build_system); 0: none
-    double cg_prev_equiv = 0.0, cg_prev_radius = 0.0;   // block-Jacobi-equivalent PCG iterations and radius of the last fully solved LM system of this solve
-    int mg_switch_at = 400;              // in-flight switch point of the current LM system (build_system)
-    int cg_extra = 0;                    // PCG iterations of the current LM step spent before a change of preconditioner
-    bool mg_failed = false;              // the multigrid operators of the current system could not be built
-    double last_rho = 1.0;               // relative decrease of the last accepted step of this solve
-    bool mg_start_deferred = false;      // the current system is predicted hard, but its multigrid operators are built only once the step has survived the first early-rejection pause
-};
-
-namespace {
-
-#define HIPCHK(p, expr) PGO_HIPCHK((p)->err, expr)
 
 int set_device(pgo_problem* p) { HIPCHK(p, hipSetDevice(p->device)); return PGO_OK; }
 
@@ -322,576 +84,29 @@ int upload_class(pgo_problem* p, const HostClass& H, bool is_sw, DBuf<int32_t>& 
     return PGO_OK;
 }
 
-int allreduce(pgo_problem* p, double* buf, size_t n, int op);
-int host_allreduce(pgo_problem* p, std::vector<double>& v, int op);
+}  // namespace
 
-// The aggregation multigrid's hierarchy for the graph of this handle and the given switch values (host array over the caller's switches, or null): host-side structure
-// (pgo_mg_host.hpp), pooled device arrays, level descriptors.  Called by build_graph, and again inside a solve when the switch values have moved far from the ones the
-// hierarchy was built with (regroup): the levels above level 1 are matched along the couplings that are alive NOW.  p->mg_cache keeps what does not depend on the switches.
-// host half: hierarchy + pooled index arrays.  Reads the handle's edge lists, options and mg_cache only (single rank: no HIP, no collective -> may run on a worker thread)
-int mg_prepare_impl(pgo_problem* p, const double* sw_now, MgPrepared& Q);
-// (runs on worker threads as well: nothing may escape — the C-ABI never throws, and an exception leaving a std::thread is std::terminate)
-int mg_prepare(pgo_problem* p, const double* sw_now, MgPrepared& Q) {
-    try { return mg_prepare_impl(p, sw_now, Q); }
-    catch (const std::bad_alloc&) { Q.ok = false; return PGO_ERR_OUT_OF_MEMORY; }
-    catch (...) { Q.ok = false; return PGO_ERR_OUT_OF_MEMORY; }
-}
-int mg_prepare_impl(pgo_problem* p, const double* sw_now, MgPrepared& Q) {
-    const int64_t N = p->N, Ng = p->N_global, S = p->S;
-    const int64_t Er = p->rel.size(), Es = p->swe.size();
-    int rc;
-    const double t0 = now_s();
-    pgo_mg::Hierarchy& H = Q.H;
-    pgo_mg::timing() = p->opt.verbosity > 1;
-    const int dense_max = std::max(1, std::min(p->opt.mg_dense_max_nodes, 512));
-    // smoothed prolongators (denser coarse operators, two more row products per cycle on each such level) pay while the coarse levels are latency-bound: measured
-    // C4 (200k keyframes) 3.56 -> 2.37 s, C5 (1M keyframes, level 1 = 125k nodes: bandwidth-bound) 8.5 -> 11.1 s.  -1 = by size; with them aggregates of 4 above level 1, else of 8
-    const double loop_discount = std::max(0.0, p->opt.mg_loop_discount);
-    const int n_smoothed = p->opt.mg_smoothed_levels < 0 ? (Ng <= 500000 ? 1 : 0) : std::min(p->opt.mg_smoothed_levels, MG_MAX_LEVELS);
-    const int passes0 = std::max(1, std::min(p->opt.mg_first_passes, 3)), passes = p->opt.mg_passes <= 0 ? (n_smoothed > 0 ? 2 : 3) : std::min(p->opt.mg_passes, 3);
-    std::vector<double> sw_w;
-    if (sw_now && S > 0) { sw_w.resize((size_t)Es); for (int64_t e = 0; e < Es; ++e) { const double sv = sw_now[p->swe.sw[e]]; sw_w[e] = sv * sv; } }
-    Q.sw_built.assign((size_t)Es, 1.0);
-    if (!sw_w.empty()) Q.sw_built = sw_w;
-    bool ok;
-    std::vector<int32_t>& agg0_l = Q.agg0_l; std::vector<int32_t>& mem0_ptr_l = Q.mem0_ptr_l; std::vector<int32_t>& mem0_l = Q.mem0_l;
-    std::vector<double>& inv_cnt = Q.inv_cnt;
-    std::vector<int64_t> fine_rowptr, fine_ent; std::vector<int32_t> fine_col;
-    // smoothed keyframe transition (one GPU): 1 = on, 0 = off, < 0 = BY THE DENSITY OF THE LEVELS IT MAKES (round 6).  It halves the multigrid iterations everywhere and pays
-    // while its denser levels are still latency-sized: over the eight graph types measured in round 5 the sparse levels of the smoothed hierarchy hold 43 000 - 375 000 blocks where
-    // it wins (+9 ... +52 %) and 714 000 - 3.9 M where it loses (-19 ... -43 %).  So the hierarchy is built WITH it (graphs beyond 80 000 keyframes are not tried: C3's 100 000 give
-    // 734 000 blocks), its blocks are counted, and above SMOOTHED_FINE_MAX_BLOCKS it is built again without (level-0 matching and level-1 structure come from the cache; all of
-    // this runs on the worker thread beside build_graph).  Decided once per graph build — a regroup keeps the decision.
-    // The limit: round 5's eight graph types are separated by anything between 375 000 and 714 000; round 6's soak of 36 random graphs of 5 000 - 80 000 keyframes
-    // (scripts/gpu_mid_soak.py, profiles/r06_mid_soak.txt) found the zone in between mixed — 300 000 blocks -28 % (10 000 keyframes, f = 1..5 + yaw, plain loops), 351 000 +4.5 %,
-    // 371 000 -24 %, 375 000 +18 % — and nothing below 280 000 that loses: a missed gain costs less than a regression, so the limit sits under the mixed zone.
-    constexpr int64_t SMOOTHED_FINE_MAX_BLOCKS = 280000, SMOOTHED_FINE_TRY_MAX_KEYFRAMES = 80000;
-    bool want_fine = !p->local_ids && (p->opt.mg_smoothed_fine > 0 || (p->opt.mg_smoothed_fine < 0 && (p->mg_fine_auto == 1 || (p->mg_fine_auto < 0 && Ng <= SMOOTHED_FINE_TRY_MAX_KEYFRAMES))));
-    const bool fine_on_trial = want_fine && p->opt.mg_smoothed_fine < 0 && p->mg_fine_auto < 0;
-    auto fine_pattern = [&]() {
-        // the keyframe level's block pattern: row i = block (i, i), then one block per incident edge (relative-pose edges first, each class in edge order), and what each block IS for
-        // fine_block_value (kind 0: the keyframe's reduced diagonal block; 1 / 2: a relative-pose edge seen from its first / second keyframe; 3 / 4: a switchable edge)
-        fine_rowptr.assign((size_t)N + 1, 0);
-        for (int64_t e = 0; e < Er; ++e) { fine_rowptr[(size_t)p->rel.c1[e] + 1]++; fine_rowptr[(size_t)p->rel.c2[e] + 1]++; }
-        for (int64_t e = 0; e < Es; ++e) { fine_rowptr[(size_t)p->swe.c1[e] + 1]++; fine_rowptr[(size_t)p->swe.c2[e] + 1]++; }
-        for (int64_t n = 0; n < N; ++n) fine_rowptr[(size_t)n + 1] += fine_rowptr[n] + 1;
-        fine_col.resize((size_t)fine_rowptr[N]); fine_ent.resize((size_t)fine_rowptr[N]);
-        std::vector<int64_t> fillb((size_t)N);
-        for (int64_t n = 0; n < N; ++n) { fine_col[(size_t)fine_rowptr[n]] = (int32_t)n; fine_ent[(size_t)fine_rowptr[n]] = (n << 3) | 0; fillb[n] = fine_rowptr[n] + 1; }
-        auto add = [&](int64_t e, int32_t a, int32_t b, int kind) {
-            fine_col[(size_t)fillb[a]] = b; fine_ent[(size_t)fillb[a]++] = (e << 3) | kind;
-            fine_col[(size_t)fillb[b]] = a; fine_ent[(size_t)fillb[b]++] = (e << 3) | (kind + 1);
-        };
-        for (int64_t e = 0; e < Er; ++e) add(e, p->rel.c1[e], p->rel.c2[e], 1);
-        for (int64_t e = 0; e < Es; ++e) add(e, p->swe.c1[e], p->swe.c2[e], 3);
-    };
-    if (want_fine) fine_pattern();
-    // filtered smoothed keyframe transition: the blocks that enter the prolongator — the keyframe's own block and its relative-pose (odometry) edges; switchable loop closures do not
-    std::vector<uint8_t> fine_keep;
-    const bool filtered = want_fine && p->opt.mg_fine_filter != 0 && Es > 0;
-    if (filtered) { fine_keep.resize(fine_ent.size()); for (size_t k = 0; k < fine_ent.size(); ++k) fine_keep[k] = (fine_ent[k] & 7) <= 2 ? 1 : 0; }
-    if (!p->local_ids) {
-        ok = pgo_mg::build_hierarchy(N, p->h_node_free, p->rel.c1, p->rel.c2, p->rel.meas.data() + 7, 8, p->swe.c1, p->swe.c2, sw_w.empty() ? nullptr : sw_w.data(), passes0, passes, dense_max, MG_TILE_ROWS,
-                                     MG_MAX_LEVELS, H, false, MG_BLOCK0, nullptr, n_smoothed, loop_discount, &p->mg_cache, want_fine ? &fine_rowptr : nullptr, want_fine ? &fine_col : nullptr,
-                                     nullptr, filtered ? &fine_keep : nullptr);
-        if (fine_on_trial) {
-            int64_t blocks = 0;
-            if (ok) for (size_t l = 0; l + 1 < H.L.size(); ++l) blocks += (int64_t)H.L[l].col.size();
-            const bool keep = ok && blocks <= SMOOTHED_FINE_MAX_BLOCKS;
-            if (p->opt.verbosity > 0) std::fprintf(stderr, "[pgo] multigrid: smoothed keyframe transition on trial: its sparse levels hold %lld blocks (limit %lld) -> %s\n", (long long)blocks, (long long)SMOOTHED_FINE_MAX_BLOCKS, keep ? "kept" : "not used");
-            p->mg_fine_auto = keep ? 1 : 0;
-            if (!keep) {
-                want_fine = false;
-                ok = pgo_mg::build_hierarchy(N, p->h_node_free, p->rel.c1, p->rel.c2, p->rel.meas.data() + 7, 8, p->swe.c1, p->swe.c2, sw_w.empty() ? nullptr : sw_w.data(), passes0, passes, dense_max, MG_TILE_ROWS,
-                                             MG_MAX_LEVELS, H, false, MG_BLOCK0, nullptr, n_smoothed, loop_discount, &p->mg_cache, nullptr, nullptr);
-            }
-        }
-    } else {
-        // Several ranks: every rank gathers the endpoints and weights of ALL edges (one all-reduce of a zero-padded buffer: 24 B per edge, once per graph build)
-        // and builds the same hierarchy from the global graph; its own edges and owned keyframes are what it contributes to level 1 (pgo_mg_host.hpp).
-        std::vector<double> cnt((size_t)2 * p->world(), 0.0);
-        cnt[(size_t)2 * p->rank()] = (double)Er; cnt[(size_t)2 * p->rank() + 1] = (double)Es;
-        if ((rc = host_allreduce(p, cnt, 0)) != PGO_OK) return rc;
-        int64_t ErT = 0, EsT = 0, my_r = 0, my_s = 0;
-        for (int r = 0; r < p->world(); ++r) { if (r == p->rank()) { my_r = ErT; my_s = EsT; } ErT += (int64_t)(cnt[(size_t)2 * r] + 0.5); EsT += (int64_t)(cnt[(size_t)2 * r + 1] + 0.5); }
-        std::vector<double> buf((size_t)3 * (ErT + EsT), 0.0);
-        double* b_rc1 = buf.data(); double* b_rc2 = b_rc1 + ErT; double* b_rw = b_rc2 + ErT; double* b_sc1 = b_rw + ErT; double* b_sc2 = b_sc1 + EsT; double* b_sw = b_sc2 + EsT;
-        for (int64_t e = 0; e < Er; ++e) { b_rc1[my_r + e] = p->rel.c1[e]; b_rc2[my_r + e] = p->rel.c2[e]; b_rw[my_r + e] = p->rel.meas[(size_t)8 * e + 7]; }
-        for (int64_t e = 0; e < Es; ++e) { b_sc1[my_s + e] = p->swe.c1[e]; b_sc2[my_s + e] = p->swe.c2[e]; b_sw[my_s + e] = sw_w.empty() ? 1.0 : sw_w[e]; }
-        if ((rc = host_allreduce(p, buf, 0)) != PGO_OK) return rc;
-        std::vector<int32_t> grc1((size_t)ErT), grc2((size_t)ErT), gsc1((size_t)EsT), gsc2((size_t)EsT);
-        std::vector<double> grw(b_rw, b_rw + ErT), gsw(b_sw, b_sw + EsT);
-        for (int64_t e = 0; e < ErT; ++e) { grc1[e] = (int32_t)(b_rc1[e] + 0.5); grc2[e] = (int32_t)(b_rc2[e] + 0.5); }
-        for (int64_t e = 0; e < EsT; ++e) { gsc1[e] = (int32_t)(b_sc1[e] + 0.5); gsc2[e] = (int32_t)(b_sc2[e] + 0.5); }
-        std::vector<uint8_t> gfree((size_t)Ng);
-        for (int64_t g = 0; g < Ng; ++g) gfree[g] = p->h_touched_any[g];
-        for (int32_t c : p->constant_nodes) if (c >= 0 && c < Ng) gfree[c] = 0;
-        const pgo_mg::LocalContrib local{&p->l2g, &p->h_own, &p->rel.c1, &p->rel.c2, &p->swe.c1, &p->swe.c2};
-        // distributed cycle: aggregates never mix owners, every level is numbered owner-major (pgo_mg_host.hpp: Owners)
-        pgo_mg::Owners OW; OW.touch_mask = &p->h_touch_mask; OW.owner = &p->h_owner; OW.world = p->world(); OW.dist_min_rows = p->opt.mg_dist_min_rows > 0 ? p->opt.mg_dist_min_rows : 8192;
-        ok = pgo_mg::build_hierarchy(Ng, gfree, grc1, grc2, grw.data(), 1, gsc1, gsc2, (sw_now && S > 0) ? gsw.data() : nullptr, passes0, passes, dense_max, MG_TILE_ROWS, MG_MAX_LEVELS, H, false, 0, &local, n_smoothed, loop_discount, &p->mg_cache,
-                                     nullptr, nullptr, p->world() > 1 ? &OW : nullptr);
-        if (ok && p->world() > 1) {
-            // the cycle's plans, and beside them on a thread of its own — the two read the finished hierarchy and write their own results — the set-up's (the set-up distributed
-            // like the cycle: who contributes to / needs which blocks; the gathered edge lists are rank by rank)
-            const bool want_setup = p->opt.mg_dist_setup != 0;
-            std::vector<int64_t> rel_off((size_t)p->world() + 1, 0), sw_off((size_t)p->world() + 1, 0);
-            for (int r = 0; r < p->world(); ++r) { rel_off[(size_t)r + 1] = rel_off[(size_t)r] + (int64_t)(cnt[(size_t)2 * r] + 0.5); sw_off[(size_t)r + 1] = sw_off[(size_t)r] + (int64_t)(cnt[(size_t)2 * r + 1] + 0.5); }
-            const bool tm = pgo_mg::timing();
-            std::atomic<bool> worker_failed{false};      // (declared before the thread and its joiner: destroyed after them)
-            std::thread worker;
-            struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join_worker{worker};
-            bool started = false;
-            if (want_setup && pgo_mg::host_threads() > 1) {
-                try {
-                    worker = std::thread([&]() { try { pgo_mg::timing() = tm; pgo_mg::build_setup_plans(H, p->rank(), p->world(), grc1, grc2, rel_off, gsc1, gsc2, sw_off, Q.setup); } catch (...) { worker_failed.store(true); } });
-                    started = true;
-                } catch (...) {}
-            }
-            pgo_mg::build_level_plans(H, OW, p->rank(), Q.plans);
-            if (started) { worker.join(); if (worker_failed.load()) throw std::bad_alloc(); }
-            else if (want_setup) pgo_mg::build_setup_plans(H, p->rank(), p->world(), grc1, grc2, rel_off, gsc1, gsc2, sw_off, Q.setup);
-        }
-        if (ok) {
-            const int32_t n1g = (int32_t)H.mem0_ptr.size() - 1;
-            inv_cnt.resize((size_t)n1g);
-            for (int32_t a = 0; a < n1g; ++a) inv_cnt[a] = 1.0 / (double)std::max(1, H.mem0_ptr[a + 1] - H.mem0_ptr[a]);
-            agg0_l.resize((size_t)N); mem0_ptr_l.assign((size_t)n1g + 1, 0);
-            for (int64_t l = 0; l < N; ++l) { agg0_l[l] = p->h_node_free[l] ? H.agg0[p->l2g[l]] : -1; if (agg0_l[l] >= 0) mem0_ptr_l[(size_t)agg0_l[l] + 1]++; }
-            for (int32_t a = 0; a < n1g; ++a) mem0_ptr_l[(size_t)a + 1] += mem0_ptr_l[a];
-            mem0_l.resize((size_t)mem0_ptr_l[n1g]);
-            std::vector<int32_t> fillm(mem0_ptr_l.begin(), mem0_ptr_l.end() - 1);
-            for (int64_t l = 0; l < N; ++l) if (agg0_l[l] >= 0) mem0_l[(size_t)fillm[agg0_l[l]]++] = (int32_t)l;
-        }
-    }
-    Q.ok = ok;
-    if (!ok) return PGO_OK;
-    const std::vector<int32_t>& A0 = p->local_ids ? agg0_l : H.agg0;
-    const std::vector<int32_t>& M0P = p->local_ids ? mem0_ptr_l : H.mem0_ptr;
-    const std::vector<int32_t>& M0 = p->local_ids ? mem0_l : H.mem0;
-    const int nl = (int)H.L.size();
-    // this rank's share of every sparse level (one GPU, and levels every rank runs completely: all of it)
-    const bool dist = H.world > 1;
-    Q.share.assign((size_t)nl, MgPrepared::Share{});
-    for (int l = 0; l + 1 < nl; ++l) {
-        const pgo_mg::HostLevel& A = H.L[(size_t)l];
-        MgPrepared::Share& sh = Q.share[(size_t)l];
-        const int32_t tiles = A.tile_agg0.empty() ? 0 : (int32_t)A.tile_agg0.size() - 1;
-        sh.distributed = dist && A.distributed;
-        if (sh.distributed) { sh.tile0 = A.tile_ptr[(size_t)p->rank()]; sh.tiles_own = A.tile_ptr[(size_t)p->rank() + 1] - sh.tile0; sh.rT_row0 = H.L[(size_t)l + 1].own_ptr[(size_t)p->rank()]; sh.rT_row1 = H.L[(size_t)l + 1].own_ptr[(size_t)p->rank() + 1]; }
-        else { sh.tile0 = 0; sh.tiles_own = tiles; sh.rT_row0 = 0; sh.rT_row1 = H.L[(size_t)l + 1].n; }
-    }
-    Q.a0 = dist ? H.L[0].own_ptr[(size_t)p->rank()] : 0; Q.a1 = dist ? H.L[0].own_ptr[(size_t)p->rank() + 1] : H.L[0].n;
-    // pooled arrays: (offset, count) per array; doubles rounded up to even counts (16-B loads)
-    std::vector<int32_t>& pi32 = Q.pi32; std::vector<int64_t>& pi64 = Q.pi64;
-    {   // one allocation per pool (the arrays are appended one by one: without the reservation the 10-MB pools are reallocated and copied a dozen times)
-        size_t n32 = A0.size() + M0P.size() + M0.size() + (size_t)((N + MG_BLOCK0 - 1) / MG_BLOCK0) * MG_BLOCK0 * 4 + 64, n64 = 0;
-        for (const pgo_mg::HostLevel& A : H.L) {
-            const size_t tiles = A.tile_agg0.empty() ? 0 : A.tile_agg0.size() - 1;
-            n32 += 3 * A.col.size() + A.parent.size() + A.agg_ptr.size() + tiles * (4 + 2 * (size_t)MG_TILE_ROWS) + A.ps_rowptr.size() + 2 * A.ps_col.size() + A.w_rowptr.size() + 5 * A.w_col.size() + (A.smoothed ? tiles * 2 * (size_t)MG_TILE_ROWS + ((size_t)A.rT_rowptr.size() / 4 + 2) * 2 * (size_t)MG_TILE_ROWS : 0) + 16;
-            n64 += A.rowptr.size() + A.g_ptr.size() + A.g_ent.size() + A.psT_ptr.size() + A.psT_ent.size();
-        }
-        if (H.fine_smoothed) {
-            const pgo_mg::HostLevel& F = H.F;
-            n32 += F.col.size() + F.ps_rowptr.size() + 4 * F.ps_col.size() + F.w_rowptr.size() + 2 * F.w_col.size() + ((size_t)H.L[0].n / 4 + 2) * 2 * (size_t)MG_TILE_ROWS + 16;
-            n64 += F.rowptr.size() + F.col.size() + F.psT_ptr.size() + F.psT_ent.size();
-        }
-        pi32.reserve(n32); pi64.reserve(n64);
-    }
-    auto put32 = [&](const std::vector<int32_t>& v) { const size_t o = pi32.size(); pi32.insert(pi32.end(), v.begin(), v.end()); return o; };
-    auto put64 = [&](const std::vector<int64_t>& v) { const size_t o = pi64.size(); pi64.insert(pi64.end(), v.begin(), v.end()); return o; };
-    size_t& nf64 = Q.nf64;
-    auto take = [&](size_t cnt) { const size_t o = nf64; nf64 += (cnt + 1) & ~(size_t)1; return o; };
-    Q.off.assign((size_t)nl, MgPrepared::Off{});
-    Q.o_agg0 = put32(A0); Q.o_mem0_ptr = put32(M0P); Q.o_mem0 = put32(M0);
-    // slot table of the restriction inside the vector update: per run of MG_BLOCK0 keyframes its aggregates {id, 8 members as run-local bytes}
-    bool have_tab = !p->local_ids && !H.fine_smoothed;      // (smoothed keyframe transition: restriction and prolongation need neighbouring runs — kernels of their own)
-    if (have_tab) {
-        const int64_t runs = (N + MG_BLOCK0 - 1) / MG_BLOCK0;
-        std::vector<int32_t> tab((size_t)runs * MG_BLOCK0 * 4);
-        for (size_t k = 0; k < tab.size(); k += 4) { tab[k] = -1; tab[k + 1] = -1; tab[k + 2] = -1; tab[k + 3] = 0; }
-        std::vector<int> fill((size_t)runs, 0);
-        const int32_t n1h = (int32_t)H.mem0_ptr.size() - 1;
-        for (int32_t a = 0; a < n1h && have_tab; ++a) {
-            const int32_t m0 = H.mem0_ptr[a], m1 = H.mem0_ptr[a + 1];
-            if (m1 <= m0) continue;
-            const int64_t run = H.mem0[m0] / MG_BLOCK0;
-            if (m1 - m0 > 8 || fill[run] >= MG_BLOCK0) { have_tab = false; break; }
-            uint32_t w[2] = {0xffffffffu, 0xffffffffu};
-            for (int32_t m = m0; m < m1; ++m) {
-                if (H.mem0[m] / MG_BLOCK0 != run) { have_tab = false; break; }
-                const int j = m - m0;
-                w[j >> 2] = (w[j >> 2] & ~(0xffu << (8 * (j & 3)))) | ((uint32_t)(H.mem0[m] - run * MG_BLOCK0) << (8 * (j & 3)));
-            }
-            int32_t* e = &tab[((size_t)run * MG_BLOCK0 + fill[run]++) * 4];
-            e[0] = a; e[1] = (int32_t)w[0]; e[2] = (int32_t)w[1];
-        }
-        if (have_tab) { while (pi32.size() % 4) pi32.push_back(0); Q.o_blk_tab = put32(tab); }
-    }
-    Q.have_tab = have_tab;
-    Q.o_d0 = take((size_t)N * 3);
-    const size_t n1_all = (size_t)H.L[0].n;
-    Q.o_inv = p->local_ids ? take(n1_all) : 0;
-    for (int l = 0; l < nl; ++l) {
-        const pgo_mg::HostLevel& A = H.L[l];
-        MgPrepared::Off& o = Q.off[l];
-        o.col = put32(A.col); o.parent = put32(A.parent); o.agg_ptr = put32(A.agg_ptr);
-        {   // block -> row, block -> slot of the transposed block (rows hold the diagonal block first, the others by ascending column)
-            std::vector<int32_t> row_of(A.col.size()), tr_of(A.col.size());
-            pgo_mg::parallel_ranges(A.n, pgo_mg::host_threads(), [&](int, int32_t lo, int32_t hi) {      // (rows are independent; level 2 of C3 holds 193 000 blocks)
-                for (int32_t i = lo; i < hi; ++i)
-                    for (int64_t k = A.rowptr[i]; k < A.rowptr[(size_t)i + 1]; ++k) {
-                        row_of[(size_t)k] = i;
-                        const int32_t j = A.col[(size_t)k];
-                        int64_t t = k;
-                        if (j != i) {
-                            const int32_t* b = A.col.data() + A.rowptr[j] + 1; const int32_t* e = A.col.data() + A.rowptr[(size_t)j + 1];
-                            const int32_t* f = std::lower_bound(b, e, i);
-                            if (f != e && *f == i) t = f - A.col.data();
-                        }
-                        tr_of[(size_t)k] = (int32_t)t;
-                    }
-            });
-            o.row_of = put32(row_of); o.tr_of = put32(tr_of);
-        }
-        {   // per tile {a0, a1, i0, i1}, 16-B aligned
-            std::vector<int32_t> info;
-            for (size_t tt = 0; tt + 1 < A.tile_agg0.size(); ++tt) { const int32_t a0 = A.tile_agg0[tt], a1 = A.tile_agg0[tt + 1]; info.insert(info.end(), {a0, a1, A.agg_ptr[a0], A.agg_ptr[a1]}); }
-            while (pi32.size() % 4) pi32.push_back(0);
-            o.tile = put32(info);
-            std::vector<int32_t> rows;      // [tile][MG_TILE_ROWS] {first block, end block} of each row of the tile
-            for (size_t tt = 0; tt + 1 < A.tile_agg0.size(); ++tt) {
-                const int32_t i0 = A.agg_ptr[A.tile_agg0[tt]], i1 = A.agg_ptr[A.tile_agg0[tt + 1]];
-                for (int li = 0; li < MG_TILE_ROWS; ++li) { const int32_t r = i0 + li; rows.push_back(r < i1 ? (int32_t)A.rowptr[r] : 0); rows.push_back(r < i1 ? (int32_t)A.rowptr[r + 1] : 0); }
-            }
-            o.tile_rows = put32(rows);
-        }
-        o.rowptr = put64(A.rowptr); o.g_ptr = put64(A.g_ptr); o.g_ent = put64(A.g_ent);
-        o.val = take(A.col.size() * 36); o.Dinv = take((size_t)A.n * 36); o.pos = take((size_t)A.n * 3); o.d = take((size_t)A.n * 3);
-        o.r = take((size_t)A.n * 6); o.x = take((size_t)A.n * 6); o.xt = take((size_t)A.n * 6); o.xf = take((size_t)A.n * 6);
-        o.valf = take((A.col.size() * 36 + 1) / 2);      // fp32 copy of the blocks, carved out of the fp64 pool
-        if (A.smoothed) {
-            o.ps_rowptr = put32(A.ps_rowptr); o.ps_col = put32(A.ps_col); o.w_rowptr = put32(A.w_rowptr); o.w_col = put32(A.w_col);
-            o.psT_ptr = put64(A.psT_ptr); o.psT_ent = put64(A.psT_ent);
-            {
-                std::vector<int32_t> ps_row(A.ps_col.size()), w_row(A.w_col.size());
-                for (int32_t i = 0; i < A.n; ++i) {
-                    for (int32_t k = A.ps_rowptr[i]; k < A.ps_rowptr[(size_t)i + 1]; ++k) ps_row[(size_t)k] = i;
-                    for (int32_t k = A.w_rowptr[i]; k < A.w_rowptr[(size_t)i + 1]; ++k) w_row[(size_t)k] = i;
-                }
-                o.ps_row = put32(ps_row); o.w_row = put32(w_row);
-            }
-            o.ps_val = take(A.ps_col.size() * 36); o.w_val = take(A.w_col.size() * 36);
-            o.t = take((size_t)A.n * 6); o.u = take((size_t)A.n * 6); o.y = take((size_t)A.n * 6); o.zero = take((size_t)A.n * 6);
-            {   // explicit transfer operator: index arrays, per-tile block ranges of R^T (this level's tiles) and of R (tiles of consecutive coarse rows), fp32 block arrays
-                o.rT_col = put32(A.rT_col); o.rT_of_w = put32(A.rT_of_w); o.ps_of_w = put32(A.ps_of_w);
-                std::vector<int32_t> rows;
-                for (size_t tt = 0; tt + 1 < A.tile_agg0.size(); ++tt) {
-                    const int32_t i0 = A.agg_ptr[A.tile_agg0[tt]], i1 = A.agg_ptr[A.tile_agg0[tt + 1]];
-                    for (int li = 0; li < MG_TILE_ROWS; ++li) { const int32_t r = i0 + li; rows.push_back(r < i1 ? A.w_rowptr[r] : 0); rows.push_back(r < i1 ? A.w_rowptr[(size_t)r + 1] : 0); }
-                }
-                while (pi32.size() % 2) pi32.push_back(0);
-                o.rt_rows = put32(rows);
-                o.rT_seg_shift = A.rT_seg >= 8 ? 3 : A.rT_seg >= 4 ? 2 : A.rT_seg >= 2 ? 1 : 0;
-                const int rpt = MG_TILE_ROWS >> o.rT_seg_shift;
-                const int32_t nb0 = Q.share[(size_t)l].rT_row0, nb = Q.share[(size_t)l].rT_row1;      // (several ranks: the restriction's tiles cover the rank's own coarse rows)
-                o.rT_tiles = (nb - nb0 + rpt - 1) / rpt;
-                rows.clear();
-                for (int tt = 0; tt < o.rT_tiles; ++tt)
-                    for (int li = 0; li < MG_TILE_ROWS; ++li) { const int32_t r = nb0 + tt * rpt + li; const bool in = li < rpt && r < nb; rows.push_back(in ? A.rT_rowptr[r] : 0); rows.push_back(in ? A.rT_rowptr[(size_t)r + 1] : 0); }
-                o.rT_rows = put32(rows);
-                o.rt_valf = take((A.w_col.size() * 36 + 1) / 2); o.r_valf = take((A.w_col.size() * 36 + 1) / 2);
-            }
-        }
-    }
-    Q.o_plan_send.assign(Q.plans.size(), 0); Q.o_plan_recv.assign(Q.plans.size(), 0);
-    for (size_t l = 0; l < Q.plans.size(); ++l) { Q.o_plan_send[l] = put32(Q.plans[l].send_idx); Q.o_plan_recv[l] = put32(Q.plans[l].recv_idx); }
-    Q.g0_slots.clear(); Q.o_g0 = 0;
-    if (Q.setup.first_whole > 0) {
-        const pgo_mg::HostLevel& L1 = H.L[0];
-        for (size_t k = 0; k + 1 < L1.g_ptr.size(); ++k) if (L1.g_ptr[k + 1] > L1.g_ptr[k]) Q.g0_slots.push_back((int32_t)k);
-        Q.o_g0 = put32(Q.g0_slots);
-    }
-    Q.o_setup.assign(Q.setup.val.size(), MgPrepared::SetupOff{});
-    for (size_t l = 0; l < Q.setup.val.size(); ++l) {
-        MgPrepared::SetupOff& so = Q.o_setup[l];
-        const pgo_mg::BlockPlan& B = Q.setup.val[l];
-        so.val_send = put32(B.x.send_idx); so.val_dst = put32(B.dst); so.val_sum_ptr = put32(B.sum_ptr); so.val_sum_src = put32(B.sum_src);
-        if (l < Q.setup.ps.size()) {
-            so.ps_send = put32(Q.setup.ps[l].send_idx); so.ps_recv = put32(Q.setup.ps[l].recv_idx); so.rv_send = put32(Q.setup.rv[l].send_idx); so.rv_recv = put32(Q.setup.rv[l].recv_idx);
-            so.prod = put32(Q.setup.prod[l]);
-        }
-    }
-    Q.fine = H.fine_smoothed;
-    if (Q.fine) {
-        const pgo_mg::HostLevel& F = H.F;
-        MgPrepared::FineOff& o = Q.fo;
-        const int32_t n1 = H.L[0].n;
-        o.rowptr = put64(F.rowptr); o.ent = put64(fine_ent); o.col = put32(F.col);
-        o.ps_rowptr = put32(F.ps_rowptr); o.ps_col = put32(F.ps_col); o.w_rowptr = put32(F.w_rowptr); o.w_col = put32(F.w_col);
-        o.psT_ptr = put64(F.psT_ptr); o.psT_ent = put64(F.psT_ent);
-        std::vector<int32_t> ps_row(F.ps_col.size()), w_row(F.w_col.size());
-        for (int32_t i = 0; i < F.n; ++i) {
-            for (int32_t k = F.ps_rowptr[i]; k < F.ps_rowptr[(size_t)i + 1]; ++k) ps_row[(size_t)k] = i;
-            for (int32_t k = F.w_rowptr[i]; k < F.w_rowptr[(size_t)i + 1]; ++k) w_row[(size_t)k] = i;
-        }
-        o.ps_row = put32(ps_row); o.w_row = put32(w_row);
-        // Ps by level-1 row (the restriction r_1 = Ps_0^T r runs as the restriction half of mg_sdown_kernel): position e of psT_ent = slot of the transposed block
-        std::vector<int32_t> rT_of_ps(F.ps_col.size()), rT_col(F.ps_col.size());
-        for (size_t e = 0; e < F.psT_ent.size(); ++e) { rT_of_ps[(size_t)(F.psT_ent[e] & 0xffffffffll)] = (int32_t)e; rT_col[e] = (int32_t)(F.psT_ent[e] >> 32); }
-        o.rT_of_ps = put32(rT_of_ps); o.rT_col = put32(rT_col);
-        const double mean_row = (double)F.ps_col.size() / (double)std::max(1, n1);
-        int seg = 1;
-        while (seg < 8 && mean_row > 5.0 * seg) seg *= 2;
-        o.rT_seg_shift = seg >= 8 ? 3 : seg >= 4 ? 2 : seg >= 2 ? 1 : 0;
-        const int rpt = MG_TILE_ROWS >> o.rT_seg_shift;
-        o.rT_tiles = (n1 + rpt - 1) / rpt;
-        std::vector<int32_t> rows;
-        rows.reserve((size_t)o.rT_tiles * MG_TILE_ROWS * 2);
-        for (int tt = 0; tt < o.rT_tiles; ++tt)
-            for (int li = 0; li < MG_TILE_ROWS; ++li) { const int32_t r = tt * rpt + li; const bool in = li < rpt && r < n1; rows.push_back(in ? (int32_t)F.psT_ptr[r] : 0); rows.push_back(in ? (int32_t)F.psT_ptr[(size_t)r + 1] : 0); }
-        while (pi32.size() % 2) pi32.push_back(0);
-        o.rT_rows = put32(rows);
-        o.val = take(F.col.size() * 36); o.Dinv = take((size_t)F.n * 36); o.ps_val = take(F.ps_col.size() * 36); o.w_val = take(F.w_col.size() * 36);
-        o.rt_valf = take((F.ps_col.size() * 36 + 1) / 2); o.r_valf = take((F.ps_col.size() * 36 + 1) / 2);
-        o.filtered = filtered && want_fine;
-        o.lump = o.filtered ? take((size_t)F.n * 36) : 0;
-    }
-    Q.host_ms = (now_s() - t0) * 1e3;
-    if (p->opt.verbosity > 1) std::fprintf(stderr, "[pgo] hierarchy (host): pooled arrays + descriptors      (total %.2f ms, %u hardware threads reported)\n", Q.host_ms, std::thread::hardware_concurrency());
-    return PGO_OK;
-}
+namespace pgo {
 
 // several ranks: send / receive buffers for the largest exchange of the handle — 42 doubles per row of the keyframes' plan (diagonal block + gradient), 12 per row of a
 // level plan (x and r of a level travel together).  Two send buffers: the in-process communicator double-buffers by collective parity.
 int ensure_exchange_buffers(pgo_problem* p) {
     if (!p->local_ids) return PGO_OK;
     size_t ns = (size_t)p->fine_plan.x.n_send() * 42, nr = (size_t)p->fine_plan.x.n_recv() * 42;
-    for (const pgo_problem::LevelPlanDev& L : p->lvl_plan) if (L.plan) { ns = std::max(ns, (size_t)L.plan->n_send() * 12); nr = std::max(nr, (size_t)L.plan->n_recv() * 12); }
-    if (p->mg_first_whole > 0) {      // distributed set-up: 36 doubles per block of the levels, of Ps and per row of Dinv (the level plans), 18 per fp32 block of R
-        for (int l = 0; l < p->mg_first_whole && (size_t)l < p->lvl_plan.size(); ++l) if (p->lvl_plan[(size_t)l].plan) { ns = std::max(ns, (size_t)p->lvl_plan[(size_t)l].plan->n_send() * 36); nr = std::max(nr, (size_t)p->lvl_plan[(size_t)l].plan->n_recv() * 36); }
-        for (const pgo_mg::BlockPlan& B : p->mg_setup.val) { ns = std::max(ns, (size_t)B.x.n_send() * 36); nr = std::max(nr, (size_t)B.x.n_recv() * 36); }
-        for (const pgo_mg::ExchangePlan& X : p->mg_setup.ps) { ns = std::max(ns, (size_t)X.n_send() * 36); nr = std::max(nr, (size_t)X.n_recv() * 36); }
-        for (const pgo_mg::ExchangePlan& X : p->mg_setup.rv) { ns = std::max(ns, (size_t)X.n_send() * 18); nr = std::max(nr, (size_t)X.n_recv() * 18); }
+    for (const LevelPlanDev& L : p->mg.lvl_plan) if (L.plan) { ns = std::max(ns, (size_t)L.plan->n_send() * 12); nr = std::max(nr, (size_t)L.plan->n_recv() * 12); }
+    if (p->mg.first_whole > 0) {      // distributed set-up: 36 doubles per block of the levels, of Ps and per row of Dinv (the level plans), 18 per fp32 block of R
+        for (int l = 0; l < p->mg.first_whole && (size_t)l < p->mg.lvl_plan.size(); ++l) if (p->mg.lvl_plan[(size_t)l].plan) { ns = std::max(ns, (size_t)p->mg.lvl_plan[(size_t)l].plan->n_send() * 36); nr = std::max(nr, (size_t)p->mg.lvl_plan[(size_t)l].plan->n_recv() * 36); }
+        for (const pgo_mg::BlockPlan& B : p->mg.setup.val) { ns = std::max(ns, (size_t)B.x.n_send() * 36); nr = std::max(nr, (size_t)B.x.n_recv() * 36); }
+        for (const pgo_mg::ExchangePlan& X : p->mg.setup.ps) { ns = std::max(ns, (size_t)X.n_send() * 36); nr = std::max(nr, (size_t)X.n_recv() * 36); }
+        for (const pgo_mg::ExchangePlan& X : p->mg.setup.rv) { ns = std::max(ns, (size_t)X.n_send() * 18); nr = std::max(nr, (size_t)X.n_recv() * 18); }
     }
     HIPCHK(p, p->d_xsend[0].ensure(ns + 64)); HIPCHK(p, p->d_xsend[1].ensure(ns + 64)); HIPCHK(p, p->d_xrecv.ensure(nr + 64)); HIPCHK(p, p->d_xscal.ensure(16));
     return PGO_OK;
 }
 
-// device half: pools (re)allocated, index arrays uploaded, level descriptors filled.  The stream must not be running multigrid kernels of the previous hierarchy.
-int mg_install(pgo_problem* p, MgPrepared& Q) {
-    const int64_t N = p->N;
-    p->coarse_built = false; p->coarse_active = false; p->K = CoarseDev{};
-    p->mg_built = false; p->mg_active = false; p->M = MgDev{}; p->mg_geometry_epoch = 0; p->lvl_plan.clear(); p->su_plan.clear(); p->mg_first_whole = 0; p->mg_own.clear();
-    if (!Q.ok) { if (p->opt.verbosity > 0) std::fprintf(stderr, "[pgo] multigrid: the graph does not coarsen (isolated keyframes?) -> off\n"); return PGO_OK; }
-    const pgo_mg::Hierarchy& H = Q.H;
-    const int nl = (int)H.L.size();
-    const std::vector<int32_t>& pi32 = Q.pi32; const std::vector<int64_t>& pi64 = Q.pi64; const size_t nf64 = Q.nf64;
-    const int n_top = H.L[nl - 1].n;
-    const int nc = (6 * n_top + 63) / 64 * 64;
-    HIPCHK(p, p->d_mg_i32.ensure(std::max<size_t>(pi32.size(), 1))); HIPCHK(p, p->d_mg_i64.ensure(std::max<size_t>(pi64.size(), 1))); HIPCHK(p, p->d_mg_f64.ensure(std::max<size_t>(nf64, 2)));
-    HIPCHK(p, p->d_cAc.ensure((size_t)nc * nc)); HIPCHK(p, p->d_cAcf.ensure((size_t)nc * nc)); HIPCHK(p, p->d_crc.ensure((size_t)nc * 2)); HIPCHK(p, p->d_cscr.ensure((size_t)nc * 64 + 4096)); HIPCHK(p, p->d_cinfo.ensure(4));
-    HIPCHK(p, hipMemcpyAsync(p->d_mg_i32.p, pi32.data(), pi32.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
-    HIPCHK(p, hipMemcpyAsync(p->d_mg_i64.p, pi64.data(), pi64.size() * sizeof(int64_t), hipMemcpyHostToDevice, p->st));
-    HIPCHK(p, hipMemsetAsync(p->d_mg_f64.p, 0, nf64 * sizeof(double), p->st));
-    HIPCHK(p, hipMemsetAsync(p->d_crc.p, 0, (size_t)nc * 2 * sizeof(double), p->st));
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    const int32_t* b32 = p->d_mg_i32.p; const int64_t* b64 = p->d_mg_i64.p; double* bf = p->d_mg_f64.p;
-    p->M = MgDev{nl, H.L[0].n, b32 + Q.o_agg0, b32 + Q.o_mem0_ptr, b32 + Q.o_mem0, bf + Q.o_d0, Q.have_tab ? reinterpret_cast<const int4*>(b32 + Q.o_blk_tab) : nullptr, nullptr, Q.a0, Q.a1,
-                 Q.setup.first_whole > 0 ? b32 + Q.o_g0 : nullptr, Q.setup.first_whole > 0 ? (int32_t)Q.g0_slots.size() : 0, 0};
-    if (p->local_ids) {
-        HIPCHK(p, hipMemcpyAsync(bf + Q.o_inv, Q.inv_cnt.data(), Q.inv_cnt.size() * sizeof(double), hipMemcpyHostToDevice, p->st));
-        HIPCHK(p, hipStreamSynchronize(p->st));
-        p->M.inv_cnt = bf + Q.o_inv;
-    }
-    p->mg_levels_distributed = 0; p->mg_rows_total = p->mg_rows_own = p->mg_blocks_total = p->mg_blocks_own = 0;
-    p->mg_dist.assign((size_t)nl, 0);
-    for (int l = 0; l + 1 < nl; ++l) p->mg_dist[(size_t)l] = Q.share[(size_t)l].distributed ? 1 : 0;
-    for (int l = 0; l < nl; ++l) {
-        const pgo_mg::HostLevel& A = H.L[l];
-        const MgPrepared::Off& o = Q.off[l];
-        MgLevelDev& D = p->mg_levels[l];
-        D = MgLevelDev{};
-        D.n = A.n; D.n_next = l + 1 < nl ? H.L[l + 1].n : 0; D.tiles = A.tile_agg0.empty() ? 0 : (int32_t)A.tile_agg0.size() - 1; D.nnzb = (int64_t)A.col.size();
-        D.rowptr = b64 + o.rowptr; D.col = b32 + o.col; D.val = bf + o.val; D.g_ptr = b64 + o.g_ptr; D.g_ent = b64 + o.g_ent;
-        D.Dinv = bf + o.Dinv; D.pos = bf + o.pos; D.d = bf + o.d; D.parent = b32 + o.parent; D.agg_ptr = b32 + o.agg_ptr; D.tile_info = reinterpret_cast<const int4*>(b32 + o.tile); D.tile_rows = reinterpret_cast<const int2*>(b32 + o.tile_rows);
-        D.r = bf + o.r; D.x = bf + o.x; D.xt = bf + o.xt; D.xf = bf + o.xf; D.valf = reinterpret_cast<float*>(bf + o.valf);
-        D.row_of = b32 + o.row_of; D.tr_of = b32 + o.tr_of;
-        D.seg_shift = A.seg >= 8 ? 3 : A.seg >= 4 ? 2 : A.seg >= 2 ? 1 : 0;
-        D.pad3_ = l;      // (the level's index: read by the timeline variant build only)
-        {   // what the rank's cycle kernels read of the level (pgo_mg_level_norms: the same ranges whichever way the set-up ran)
-            pgo_problem::OwnRange R;
-            const bool mine = l + 1 < nl && Q.share[(size_t)l].distributed;
-            const int32_t r0 = mine ? A.own_ptr[(size_t)p->rank()] : 0, r1 = mine ? A.own_ptr[(size_t)p->rank() + 1] : A.n;
-            R.row0 = r0; R.row1 = r1; R.blk0 = A.rowptr[(size_t)r0]; R.blk1 = A.rowptr[(size_t)r1];
-            if (A.smoothed) {
-                R.ps0 = A.ps_rowptr[(size_t)r0]; R.ps1 = A.ps_rowptr[(size_t)r1]; R.w0 = A.w_rowptr[(size_t)r0]; R.w1 = A.w_rowptr[(size_t)r1];
-                R.rT0 = A.rT_rowptr[(size_t)Q.share[(size_t)l].rT_row0]; R.rT1 = A.rT_rowptr[(size_t)Q.share[(size_t)l].rT_row1];
-            }
-            p->mg_own.push_back(R);
-        }
-        {   // the set-up's share of the level: a distributed level under the distributed set-up forms its own rows, every other one all of them
-            const bool part = l < Q.setup.first_whole;
-            const int32_t r0 = part ? A.own_ptr[(size_t)p->rank()] : 0, r1 = part ? A.own_ptr[(size_t)p->rank() + 1] : A.n;
-            D.su_row0 = r0; D.su_row1 = r1; D.su_blk0 = A.rowptr[(size_t)r0]; D.su_blk1 = A.rowptr[(size_t)r1];
-            D.su_ps0 = A.smoothed ? A.ps_rowptr[(size_t)r0] : 0; D.su_ps1 = A.smoothed ? A.ps_rowptr[(size_t)r1] : 0;
-            D.su_w0 = A.smoothed ? A.w_rowptr[(size_t)r0] : 0; D.su_w1 = A.smoothed ? A.w_rowptr[(size_t)r1] : 0;
-            D.su_prod = nullptr; D.n_su_prod = 0;
-            if (part && A.smoothed) { D.su_prod = b32 + Q.o_setup[(size_t)l].prod; D.n_su_prod = (int32_t)Q.setup.prod[(size_t)l].size(); }
-        }
-        {   // the cycle's share of the level (several ranks: the owner's rows; else all of it)
-            const MgPrepared::Share& sh = Q.share[(size_t)l];
-            D.tile0 = sh.tile0; D.tiles_own = l + 1 < nl ? sh.tiles_own : 0; D.rT_row0 = sh.rT_row0; D.rT_row1 = l + 1 < nl ? sh.rT_row1 : 0;
-            if (l + 1 < nl) {
-                if (sh.distributed) ++p->mg_levels_distributed;
-                const int64_t blocks = (int64_t)A.col.size() + (A.smoothed ? 2 * (int64_t)A.w_col.size() : 0);
-                int64_t own_rows = A.n, own_blocks = blocks;
-                if (sh.distributed) {
-                    const int32_t r0 = A.own_ptr[(size_t)p->rank()], r1 = A.own_ptr[(size_t)p->rank() + 1];
-                    own_rows = r1 - r0;
-                    own_blocks = A.rowptr[(size_t)r1] - A.rowptr[(size_t)r0];
-                    if (A.smoothed) own_blocks += (int64_t)(A.w_rowptr[(size_t)r1] - A.w_rowptr[(size_t)r0]) + (int64_t)(A.rT_rowptr[(size_t)sh.rT_row1] - A.rT_rowptr[(size_t)sh.rT_row0]);
-                }
-                p->mg_rows_total += A.n; p->mg_rows_own += own_rows; p->mg_blocks_total += blocks; p->mg_blocks_own += own_blocks;
-            }
-        }
-        if (A.smoothed) {
-            D.smoothed = 1; D.n_ps = (int32_t)A.ps_col.size(); D.n_w = (int32_t)A.w_col.size();
-            D.ps_rowptr = b32 + o.ps_rowptr; D.ps_col = b32 + o.ps_col; D.w_rowptr = b32 + o.w_rowptr; D.w_col = b32 + o.w_col; D.psT_ptr = b64 + o.psT_ptr; D.psT_ent = b64 + o.psT_ent;
-            D.ps_row = b32 + o.ps_row; D.w_row = b32 + o.w_row;
-            D.ps_val = bf + o.ps_val; D.w_val = bf + o.w_val; D.t = bf + o.t; D.u = bf + o.u; D.y = bf + o.y; D.zero = bf + o.zero;
-            if (p->opt.mg_explicit_transfer != 0 || p->local_ids) {      // (several ranks: always the explicit form — the implicit one would need two more exchanges per level)
-                D.rt_valf = reinterpret_cast<float*>(bf + o.rt_valf); D.r_valf = reinterpret_cast<float*>(bf + o.r_valf);
-                D.rt_rows = reinterpret_cast<const int2*>(b32 + o.rt_rows); D.rT_rows = reinterpret_cast<const int2*>(b32 + o.rT_rows);
-                D.rT_col = b32 + o.rT_col; D.rT_of_w = b32 + o.rT_of_w; D.ps_of_w = b32 + o.ps_of_w;
-                D.rT_tiles = o.rT_tiles; D.rT_seg_shift = o.rT_seg_shift;
-            }
-        }
-    }
-    p->mg_fine = Q.fine; p->mg_fineF = MgLevelDev{}; p->mg_fineT = MgLevelDev{};
-    if (Q.fine) {
-        const pgo_mg::HostLevel& Fh = H.F;
-        const MgPrepared::FineOff& o = Q.fo;
-        MgLevelDev& F = p->mg_fineF;
-        F.n = Fh.n; F.n_next = H.L[0].n; F.tiles = 0; F.nnzb = (int64_t)Fh.col.size();
-        F.tile0 = 0; F.tiles_own = 0; F.rT_row0 = 0; F.rT_row1 = H.L[0].n;      // (one GPU: the restriction covers every level-1 row)
-        F.su_row0 = 0; F.su_row1 = Fh.n; F.su_blk0 = 0; F.su_blk1 = (int64_t)Fh.col.size(); F.su_ps0 = 0; F.su_ps1 = (int32_t)Fh.ps_col.size(); F.su_w0 = 0; F.su_w1 = (int32_t)Fh.w_col.size(); F.su_prod = nullptr; F.n_su_prod = 0;
-        F.dlump = o.filtered ? bf + o.lump : nullptr;
-        F.rowptr = b64 + o.rowptr; F.col = b32 + o.col; F.val = bf + o.val; F.g_ent = b64 + o.ent; F.Dinv = bf + o.Dinv;
-        F.d = p->M.d0; F.parent = p->M.agg0;
-        F.smoothed = 1; F.n_ps = (int32_t)Fh.ps_col.size(); F.n_w = (int32_t)Fh.w_col.size();
-        F.ps_rowptr = b32 + o.ps_rowptr; F.ps_col = b32 + o.ps_col; F.w_rowptr = b32 + o.w_rowptr; F.w_col = b32 + o.w_col; F.psT_ptr = b64 + o.psT_ptr; F.psT_ent = b64 + o.psT_ent;
-        F.ps_row = b32 + o.ps_row; F.w_row = b32 + o.w_row; F.ps_val = bf + o.ps_val; F.w_val = bf + o.w_val;
-        // the transfer view: the explicit operator's fields describe Ps itself (its own pattern by keyframe row; by level-1 row for the restriction)
-        MgLevelDev& T = p->mg_fineT;
-        T = F;
-        T.rt_valf = reinterpret_cast<float*>(bf + o.rt_valf); T.r_valf = reinterpret_cast<float*>(bf + o.r_valf);
-        T.rT_of_w = b32 + o.rT_of_ps; T.rT_col = b32 + o.rT_col; T.rT_rows = reinterpret_cast<const int2*>(b32 + o.rT_rows);
-        T.rT_tiles = o.rT_tiles; T.rT_seg_shift = o.rT_seg_shift;
-    }
-    // the dense coarsest level shares the buffers of the two-level preconditioner, which the multigrid replaces on this graph
-    p->K.n_agg = n_top; p->K.nc = nc; p->K.Ac = p->d_cAc.p; p->K.Acf = p->d_cAcf.p; p->K.rc = p->d_crc.p; p->K.yc = p->d_crc.p + nc;
-    p->mg_built = true;
-    p->mg_sw_built.swap(Q.sw_built);
-    if (p->opt.verbosity > 0) {
-        std::fprintf(stderr, "[pgo] multigrid: %lld keyframes", (long long)N);
-        for (int l = 0; l < nl; ++l) {
-            int64_t longest = 0;
-            for (int32_t i = 0; i < H.L[l].n; ++i) longest = std::max<int64_t>(longest, H.L[l].rowptr[(size_t)i + 1] - H.L[l].rowptr[(size_t)i]);
-            std::fprintf(stderr, " -> %d (%lld blocks, longest row %lld%s)", H.L[l].n, (long long)H.L[l].col.size(), (long long)longest, H.L[l].smoothed ? ", smoothed prolongator above" : "");
-        }
-        std::fprintf(stderr, ", coarsest dense %d (host %.1f ms)\n", nc, Q.host_ms);
-    }
-    // several ranks: the level exchanges' index lists live in the int32 pool; the segment bounds stay on the host (p->mg_plans)
-    p->mg_plans.swap(Q.plans);
-    p->lvl_plan.assign(p->mg_plans.size(), pgo_problem::LevelPlanDev{});
-    for (size_t l = 0; l < p->mg_plans.size(); ++l) p->lvl_plan[l] = pgo_problem::LevelPlanDev{b32 + Q.o_plan_send[l], b32 + Q.o_plan_recv[l], &p->mg_plans[l]};
-    p->mg_first_whole = Q.setup.first_whole;
-    if (p->mg_first_whole > 0) {
-        const pgo_mg::HostLevel& W = H.L[(size_t)p->mg_first_whole];
-        p->mg_fw_row0 = W.own_ptr[(size_t)p->rank()]; p->mg_fw_row1 = W.own_ptr[(size_t)p->rank() + 1];
-        p->mg_fw_blk0 = W.rowptr[(size_t)p->mg_fw_row0]; p->mg_fw_blk1 = W.rowptr[(size_t)p->mg_fw_row1];
-    }
-    p->mg_setup = std::move(Q.setup);
-    p->su_plan.assign(Q.o_setup.size(), pgo_problem::SetupPlanDev{});
-    for (size_t l = 0; l < Q.o_setup.size(); ++l) {
-        const MgPrepared::SetupOff& so = Q.o_setup[l];
-        p->su_plan[l] = pgo_problem::SetupPlanDev{b32 + so.val_send, b32 + so.val_dst, b32 + so.val_sum_ptr, b32 + so.val_sum_src, b32 + so.ps_send, b32 + so.ps_recv, b32 + so.rv_send, b32 + so.rv_recv};
-    }
-    int rcx;
-    if ((rcx = ensure_exchange_buffers(p)) != PGO_OK) return rcx;
-    return PGO_OK;
-}
-
-// a regroup in flight is waited for and dropped (its result belongs to a solve state that is gone, or the graph is about to change)
-void mg_job_cancel(pgo_problem* p) {
-    if (p->mg_job.joinable()) p->mg_job.join();
-    p->mg_job_running = false; p->mg_job_out.reset();
-}
-
-// the pending hierarchy of a fresh graph build is not wanted any more (the graph is about to change, the handle to go): the worker is waited for, its result dropped, and the
-// graph marked for a rebuild (mg_built was an announcement, not a fact)
-void mg_init_drop(pgo_problem* p) {
-    if (p->mg_init_thread.joinable()) p->mg_init_thread.join();
-    if (p->mg_init_pending) { p->mg_init_pending = false; p->mg_init_out.reset(); p->mg_built = false; p->graph_dirty = true; }
-}
-int build_multigrid(pgo_problem* p, const double* sw_now, MgPrepared* ready);
-int build_two_level_aggregates(pgo_problem* p);
-// ... or it is needed now: waited for and installed
-int mg_init_finish(pgo_problem* p) {
-    if (!p->mg_init_pending) return PGO_OK;
-    const double t0 = now_s();
-    if (p->mg_init_thread.joinable()) p->mg_init_thread.join();
-    p->mg_init_pending = false;
-    std::unique_ptr<MgPrepared> Q = std::move(p->mg_init_out);
-    if (p->rc_mg_init != PGO_OK || !Q) {      // the worker failed: the handle keeps working with what a graph without a hierarchy gets (build_graph's synchronous path does the same)
-        p->mg_built = false;
-        const int rc_worker = p->rc_mg_init != PGO_OK ? p->rc_mg_init : PGO_ERR_STATE;
-        HIPCHK(p, hipStreamSynchronize(p->st));
-        const int rc2 = build_two_level_aggregates(p);
-        ++p->build_epoch;
-        return rc2 != PGO_OK ? rc2 : rc_worker;
-    }
-    const double waited = (now_s() - t0) * 1e3;
-    int rc;
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    if ((rc = build_multigrid(p, nullptr, Q.get())) != PGO_OK) return rc;
-    // a hierarchy that does not coarsen: the graph falls back to the two-level method — exactly what build_graph's synchronous path (several ranks) gives the same graph
-    if (!p->mg_built && (rc = build_two_level_aggregates(p)) != PGO_OK) return rc;
-    ++p->build_epoch;
-    if (p->opt.verbosity > 1) std::fprintf(stderr, "[pgo] multigrid: hierarchy of the new graph installed at its first use: host half %.2f ms on a worker thread, waited %.2f ms, installed in %.2f ms%s\n",
-                                           Q->host_ms, waited, (now_s() - t0) * 1e3 - waited, p->mg_built ? "" : " — it does not coarsen: the two-level method on this graph");
-    p->mg_job_old = std::move(Q);      // (freed off the solve's critical path: regroup_install's note on munmap and the GPU's address space)
-    return PGO_OK;
-}
-
-// The aggregation multigrid's hierarchy for the graph of this handle and the given switch values (host array over the caller's switches, or null): host-side structure
-// (pgo_mg_host.hpp), pooled device arrays, level descriptors.  Called by build_graph, and again when the switch values have moved far from the ones the hierarchy was
-// built with (regroup): the levels above level 1 are matched along the couplings that are alive NOW.  p->mg_cache keeps what does not depend on the switches.
-// the caller's keyframe and switch counts decide (the same answer on every rank): graphs with switchable loop closures — all of the reference's — take the multigrid from
-// mg_min_keyframes_switchable on, graphs without from mg_min_keyframes; mg_min_keyframes = 0 turns it off altogether
-bool wants_multigrid(const pgo_problem* p) {
-    int64_t mg_from = p->opt.mg_min_keyframes;
-    if (mg_from > 0 && p->S > 0 && p->opt.mg_min_keyframes_switchable > 0) mg_from = std::min<int64_t>(mg_from, p->opt.mg_min_keyframes_switchable);
-    return mg_from > 0 && p->N_global >= mg_from;
-}
-// `ready`: the host half prepared beforehand (build_graph runs it on a worker thread beside its own host work and uploads)
-int build_multigrid(pgo_problem* p, const double* sw_now, MgPrepared* ready) {
-    int rc;
-    mg_job_cancel(p);
-    p->coarse_built = false; p->coarse_active = false; p->K = CoarseDev{};
-    p->mg_built = false; p->mg_active = false; p->M = MgDev{}; p->mg_geometry_epoch = 0; p->lvl_plan.clear(); p->su_plan.clear(); p->mg_first_whole = 0; p->mg_own.clear();
-    if (wants_multigrid(p)) {
-        MgPrepared Q;
-        if (!ready && (rc = mg_prepare(p, sw_now, Q)) != PGO_OK) return rc;
-        if ((rc = mg_install(p, ready ? *ready : Q)) != PGO_OK) return rc;
-    }
-    if (p->local_ids && !p->mg_built) { p->lvl_plan.clear(); if ((rc = ensure_exchange_buffers(p)) != PGO_OK) return rc; }
-    return PGO_OK;
-}
 
 // The two-level method's aggregates (consecutive keyframes) and the contribution lists of its dense coarse operator, for the graph as built: what a graph WITHOUT a multigrid
-// hierarchy preconditions with.  Called by build_graph, and by mg_init_finish when the hierarchy a worker thread prepared turns out not to coarsen (the synchronous path —
+// hierarchy preconditions with.  Called by build_graph, and by mg_fresh_install when the hierarchy a worker thread prepared turns out not to coarsen (the synchronous path —
 // several ranks — decides that inside build_graph; one GPU only learns it where the hierarchy is first needed: both end up with the same preconditioner).
 int build_two_level_aggregates(pgo_problem* p) {
     const int64_t N = p->N, Er = p->rel.size(), Es = p->swe.size();
@@ -949,9 +164,12 @@ int build_two_level_aggregates(pgo_problem* p) {
     return PGO_OK;
 }
 
+}  // namespace pgo
+
+namespace {
+
 int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
-    mg_job_cancel(p);      // (a regroup's worker reads the host arrays rebuilt below)
-    mg_init_drop(p);
+    mg_drop_pending(p);      // (a worker reads the host arrays rebuilt below)
     double t_phase = now_s();
     auto phase = [&](const char* what) { if (p->opt.verbosity > 1) { const double t = now_s(); std::fprintf(stderr, "[pgo] build_graph: %-34s %7.2f ms\n", what, (t - t_phase) * 1e3); t_phase = t; } };
     // ---- validate against the array sizes the caller solves with
@@ -1023,7 +241,7 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
                 return PGO_OK;
             };
             if ((rc2 = up(p->d_fp_send, F.x.send_idx)) != PGO_OK || (rc2 = up(p->d_fp_shloc, F.sh_loc)) != PGO_OK || (rc2 = up(p->d_fp_sumptr, F.sum_ptr)) != PGO_OK || (rc2 = up(p->d_fp_sumsrc, F.sum_src)) != PGO_OK) return rc2;
-            p->lvl_plan.clear();
+            p->mg.lvl_plan.clear();
             if ((rc2 = ensure_exchange_buffers(p)) != PGO_OK) return rc2;
         }
         HIPCHK(p, hipStreamSynchronize(p->st));
@@ -1051,18 +269,8 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
     // One GPU: the HOST half of the multigrid hierarchy (pgo_mg_host.hpp: ~0.1 s for C3, single-threaded sorts and matchings) needs the edge lists and the free flags
     // only, so it runs on a worker thread beside the rest of this function — incident-list upload, matrix-free tile packing, buffer allocation — and is installed where
     // build_multigrid used to compute it.  Nothing here depends on timing: the result is the same hierarchy.  (Several ranks: its host half holds collectives.)
-    struct Guard { pgo_problem* p; bool committed = false; ~Guard() { if (!committed) mg_init_drop(p); } } mg_guard{p};     // an early return below waits for the worker and drops its result
-    p->mg_cache.valid = false; p->mg_fine_auto = -1;
-    bool mg_async = false;
-    if (!p->local_ids && wants_multigrid(p)) {
-        p->mg_init_out.reset(new MgPrepared());
-        p->rc_mg_init = PGO_OK; p->mg_init_pending = true; mg_async = true;
-        MgPrepared* Qp = p->mg_init_out.get();
-        std::vector<double> sw_copy;      // the caller's switch array is only guaranteed to live as long as this call
-        if (sw_now && S > 0) sw_copy.assign(sw_now, sw_now + S);
-        try { p->mg_init_thread = std::thread([p, sw_copy, Qp]() { p->rc_mg_init = mg_prepare(p, sw_copy.empty() ? nullptr : sw_copy.data(), *Qp); }); }
-        catch (...) { p->rc_mg_init = mg_prepare(p, sw_now, *Qp); }
-    }
+    struct Guard { pgo_problem* p; bool committed = false; ~Guard() { if (!committed) mg_drop_pending(p); } } mg_guard{p};     // an early return below waits for the worker and drops its result
+    mg_start_fresh(p, sw_now);
     if ((rc = upload_class(p, p->rel, false, p->d_rc1, p->d_rc2, p->d_sidx /*unused*/, p->d_rmeas, p->d_rwin, G.rel)) != PGO_OK) return rc;
     if ((rc = upload_class(p, p->swe, true, p->d_sc1, p->d_sc2, p->d_sidx, p->d_smeas, p->d_swin, G.sw)) != PGO_OK) return rc;
     const int64_t Er = G.rel.E, Es = G.sw.E, Eg = (int64_t)p->priors.size();
@@ -1263,17 +471,11 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
     // ---- aggregation multigrid for large graphs: hierarchy of graph-following rigid aggregates (pgo_mg_host.hpp), built by build_multigrid() below — which a solve
     // may call again with the current switch values (regroup)
     phase("work buffers");
-    if (mg_async) {
-        // not waited for here: installed where it is first needed (mg_init_finish).  What build_multigrid would have reset:
-        mg_job_cancel(p);
-        p->coarse_built = false; p->coarse_active = false; p->K = CoarseDev{};
-        p->mg_active = false; p->M = MgDev{}; p->mg_geometry_epoch = 0; p->mg_sw_built.clear();
-        p->mg_built = true;      // announced; mg_init_finish corrects it should the graph not coarsen
-    } else if ((rc = build_multigrid(p, sw_now, nullptr)) != PGO_OK) return rc;
+    if ((rc = build_multigrid(p, sw_now)) != PGO_OK) return rc;      // (one GPU: only announced, the hierarchy is on the worker)
     phase("multigrid hierarchy");
-    if (p->mg_built && p->built_mf) { HIPCHK(p, p->d_Hoff.ensure((size_t)(p->G.rel.Epad + p->G.sw.Epad) * 36)); p->L.Hoff = p->d_Hoff.p; }      // the multigrid's level-1 product reads J1^T J2 per edge
+    if (p->mg.built && p->built_mf) { HIPCHK(p, p->d_Hoff.ensure((size_t)(p->G.rel.Epad + p->G.sw.Epad) * 36)); p->L.Hoff = p->d_Hoff.p; }      // the multigrid's level-1 product reads J1^T J2 per edge
     p->hoff_epoch = 0;
-    if (!p->mg_built && (rc = build_two_level_aggregates(p)) != PGO_OK) return rc;      // (a graph that got the multigrid never uses the two-level method: its dense operator would be built and uploaded for nothing)
+    if (!p->mg.built && (rc = build_two_level_aggregates(p)) != PGO_OK) return rc;      // (a graph that got the multigrid never uses the two-level method: its dense operator would be built and uploaded for nothing)
     phase("two-level aggregates");
     mg_guard.committed = true;
     p->graph_dirty = false; p->priors_dirty = false;
@@ -1281,9 +483,13 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
     return PGO_OK;
 }
 
+}  // namespace
+
+namespace pgo {
+
 // ---- collectives (no-ops without a communicator; a 1-rank communicator still issues every call) ----
 // a graph built for several ranks whose communicator has gone since (pgo_comm_destroy inside a solve): its collectives fail
-int no_comm(pgo_problem* p) { p->err = "no communicator: the graph was built for several ranks (pgo_comm_destroy inside a solve?)"; return PGO_ERR_STATE; }
+static int no_comm(pgo_problem* p) { p->err = "no communicator: the graph was built for several ranks (pgo_comm_destroy inside a solve?)"; return PGO_ERR_STATE; }
 int allreduce(pgo_problem* p, double* buf, size_t n, int op /*0 sum, 2 max*/) {
     if (!p->comm) return p->local_ids ? no_comm(p) : PGO_OK;
     ++p->st_allreduces; p->st_bytes_allreduce += (double)n * sizeof(double);
@@ -1292,7 +498,7 @@ int allreduce(pgo_problem* p, double* buf, size_t n, int op /*0 sum, 2 max*/) {
 
 // Neighbour exchange of `K` doubles per row (pgo_comm.hpp: Comm::exchange): `pack` fills the send buffer the transport hands out, `unpack` reads the receive buffer
 template <class Pack, class Unpack>
-int neighbor_exchange(pgo_problem* p, const pgo_mg::ExchangePlan& X, int K, Pack pack, Unpack unpack) {
+static int neighbor_exchange(pgo_problem* p, const pgo_mg::ExchangePlan& X, int K, Pack pack, Unpack unpack) {
     if (!p->comm) return no_comm(p);
     const int slot = p->comm->send_slot(p->err);
     if (slot < 0) return slot;
@@ -1309,7 +515,7 @@ int neighbor_exchange(pgo_problem* p, const pgo_mg::ExchangePlan& X, int K, Pack
 // Multi-GPU exchange of the keyframes' rows: sums, over the ranks sharing them, the rows of one or two keyframe-indexed device arrays (k1 + k2 doubles per keyframe).  Every rank
 // sends its partial rows of the keyframes it shares with a peer to that peer and adds what it receives in ascending rank order (pgo_mg_host.hpp: build_fine_plan): all ranks
 // end up with the same bits.  Keyframes touched by a single rank never travel.  `stop` (device flag): a stopped PCG sends zeros and keeps its rows.
-int exchange_rows(pgo_problem* p, double* a1, int k1, double* a2, int k2, const int32_t* stop = nullptr) {
+static int exchange_rows(pgo_problem* p, double* a1, int k1, double* a2, int k2, const int32_t* stop = nullptr) {
     if (!p->local_ids) return PGO_OK;
     const pgo_mg::FinePlan& F = p->fine_plan;
     return neighbor_exchange(p, F.x, k1 + k2, [&](double* sb) { launch_gather_rows(sb, a1, k1, a2, k2, F.x.n_send(), p->d_fp_send.p, stop, p->st); },
@@ -1317,8 +523,8 @@ int exchange_rows(pgo_problem* p, double* a1, int k1, double* a2, int k2, const 
 }
 // ... and of the multigrid's level vectors: the rows of one or two vectors of level `l + 1` this rank owns and a peer reads go to that peer, the rows it reads come in
 int exchange_level(pgo_problem* p, int l, double* v1, double* v2, const int32_t* stop, const double* dinv) {
-    if (!p->local_ids || (size_t)l >= p->lvl_plan.size() || !p->lvl_plan[(size_t)l].plan) return PGO_OK;
-    const pgo_problem::LevelPlanDev& L = p->lvl_plan[(size_t)l];
+    if (!p->local_ids || (size_t)l >= p->mg.lvl_plan.size() || !p->mg.lvl_plan[(size_t)l].plan) return PGO_OK;
+    const LevelPlanDev& L = p->mg.lvl_plan[(size_t)l];
     if (dinv)      // x = v1, r = v2: only r travels, x = Dinv r is formed on receipt (pointwise; every rank holds the level's Dinv)
         return neighbor_exchange(p, *L.plan, 6, [&](double* sb) { launch_gather_rows(sb, v2, 6, nullptr, 0, L.plan->n_send(), L.send_idx, stop, p->st); },
                                  [&](const double* rb) { launch_scatter_rows_dinv(rb, v2, v1, dinv, L.plan->n_recv(), L.recv_idx, stop, p->st); });
@@ -1334,7 +540,7 @@ int exchange_blocks_copy(pgo_problem* p, const pgo_mg::ExchangePlan& X, const in
     return neighbor_exchange(p, X, K, [&](double* sb) { launch_gather_rows(sb, arr, K, nullptr, 0, X.n_send(), send_idx, nullptr, p->st); },
                              [&](const double* rb) { launch_scatter_rows(rb, arr, K, nullptr, 0, X.n_recv(), recv_idx, nullptr, p->st); });
 }
-int exchange_blocks_sum(pgo_problem* p, const pgo_mg::BlockPlan& B, const pgo_problem::SetupPlanDev& D, double* arr) {
+int exchange_blocks_sum(pgo_problem* p, const pgo_mg::BlockPlan& B, const SetupPlanDev& D, double* arr) {
     if (plan_is_empty(B.x)) return PGO_OK;
     return neighbor_exchange(p, B.x, 36, [&](double* sb) { launch_gather_rows(sb, arr, 36, nullptr, 0, B.x.n_send(), D.val_send, nullptr, p->st); },
                              [&](const double* rb) { launch_sum_rows(rb, arr, 36, nullptr, 0, (int64_t)B.dst.size(), D.val_dst, D.val_sum_ptr, D.val_sum_src, nullptr, p->st); });
@@ -1350,6 +556,10 @@ int host_allreduce(pgo_problem* p, std::vector<double>& v, int op) {
     HIPCHK(p, hipStreamSynchronize(p->st));
     return PGO_OK;
 }
+
+}  // namespace pgo
+
+namespace {
 
 // keyframe-indexed device array of this handle (k doubles per keyframe) -> the caller's array over ALL keyframes, complete on every rank
 // (multi-GPU: each keyframe is contributed by its owner; keyframes no rank touches come back as zeros)
@@ -1433,65 +643,9 @@ int linearize(pgo_problem* p, double* cost_out) {
     return PGO_OK;
 }
 
-static int build_mg(pgo_problem* p);
-static int regroup_if_moved(pgo_problem* p, const double* sv, bool in_solve);
-static int regroup_start(pgo_problem* p);
-// c = w_p / w of the smoothed prolongators (Dinv holds w D^-1)
-double mg_cs(const pgo_problem* p) {
-    const double om = p->opt.mg_omega > 0.0 && p->opt.mg_omega <= 1.0 ? p->opt.mg_omega : 0.9;
-    const double wp = p->opt.mg_prolongation_damping > 0.0 && p->opt.mg_prolongation_damping < 0.85 ? p->opt.mg_prolongation_damping : 0.6;
-    return wp / om;
-}
-static const MgLevelDev* mg_fine_view(const pgo_problem* p) { return p->mg_fine ? &p->mg_fineT : nullptr; }      // smoothed keyframe transition: what launch_mg_apply restricts and prolongs with
-double mg_scale(const pgo_problem* p) { return p->opt.mg_correction_scale >= 1.0 && p->opt.mg_correction_scale <= 4.0 ? p->opt.mg_correction_scale : 1.0; }
 
 struct CgResult { int iterations; bool breakdown; double rel_residual; bool converged; };
 
-// Several ranks: which exchange the multigrid cycle needs at one of launch_mg_apply's hook points (pgo_internal.hpp: MgExchangeHook) — the plan (index of the level whose vectors
-// travel) and the one or two vectors; false: none.  Level `lv` (1-based) is "distributed" when its kernels run on the owner's rows only; otherwise every rank runs all its rows.
-//   point 0, down-sweep of lv (lv = n_levels: the dense solve):  a distributed level reads x (with an explicit transfer operator also r) on the halo of its rows; a level every
-//            rank runs completely needs r and x complete — a gather — when what produced them ran on owned rows only (the level below is distributed, or lv = 1: the restriction
-//            from the keyframes covers the rank's own aggregates)
-//   point 1, up-sweep of a distributed lv:  plain transition: xt of lv on the halo, unless the level above wrote all of it (a level every rank runs completely, or the dense
-//            solve, prolongs into every child it holds a valid x for: own rows + halo); explicit operator: xf of lv + 1 on the columns of R^T, when that level is distributed
-//   point 2, prolongation to the keyframes:  xf of level 1 at the aggregates of every keyframe the rank touches, when level 1 is distributed
-bool mg_exchange_at(pgo_problem* p, int point, int lv, int* plan, double** v1, double** v2, const double** dinv /* non-null result: only r (*v2) travels, x (*v1) = Dinv r is formed on receipt */) {
-    const int nl = p->M.n_levels;
-    auto dist = [&](int level) { return level >= 1 && level < nl && (size_t)(level - 1) < p->mg_dist.size() && p->mg_dist[(size_t)level - 1] != 0; };
-    auto expl = [&](int level) { return level >= 1 && level < nl && p->mg_levels[level - 1].smoothed && p->mg_levels[level - 1].rt_valf != nullptr; };
-    *v1 = nullptr; *v2 = nullptr; *plan = -1; *dinv = nullptr;
-    if (p->world() <= 1 || p->lvl_plan.empty()) return false;
-    if (point == 0) {
-        if (lv == nl) { if (nl == 1 || dist(nl - 1)) { *plan = nl - 1; *v1 = p->K.rc; return true; } return false; }
-        MgLevelDev& A = p->mg_levels[lv - 1];
-        if (dist(lv)) { *plan = lv - 1; *v1 = A.x; if (expl(lv)) { *v2 = A.r; *dinv = A.Dinv; } return true; }
-        if (lv == 1 || dist(lv - 1)) { *plan = lv - 1; *v1 = A.x; *v2 = A.r; *dinv = A.Dinv; return true; }
-        return false;
-    }
-    if (point == 1) {
-        if (!dist(lv)) return false;
-        if (expl(lv)) { if (dist(lv + 1)) { *plan = lv; *v1 = p->mg_levels[lv].xf; return true; } return false; }
-        if (dist(lv + 1)) { *plan = lv - 1; *v1 = p->mg_levels[lv - 1].xt; return true; }
-        return false;
-    }
-    if (point == 2) { if (nl >= 2 && dist(1)) { *plan = nl; *v1 = p->mg_levels[0].xf; return true; } return false; }      // (the prolongation's own plan: a subset of level 1's halo)
-    return false;
-}
-struct MgHookCtx { pgo_problem* p; const int32_t* stop; };
-int mg_exchange_hook(void* ctx, int point, int level) {
-    MgHookCtx* c = static_cast<MgHookCtx*>(ctx);
-    int plan; double* v1; double* v2; const double* dinv;
-    if (!mg_exchange_at(c->p, point, level, &plan, &v1, &v2, &dinv)) return PGO_OK;
-    return exchange_level(c->p, plan, v1, v2, c->stop, dinv);
-}
-// z += s P V(P^T r) on several ranks: the cycle's kernels on this rank's share of every level, the exchanges their reads need in between
-int mg_apply_ranks(pgo_problem* p, bool inside_iteration) {
-    MgHookCtx hc{p, inside_iteration ? p->C.flags : nullptr};
-    MgExchangeHook hook{&hc, mg_exchange_hook};
-    int hrc = PGO_OK;
-    launch_mg_apply(p->G, p->C, p->M, p->mg_levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), inside_iteration, p->st, false, mg_cs(p), nullptr, &hook, &hrc);
-    return hrc;
-}
 
 
 // One GPU, matrix-free matvec, tolerance not below 1e-11: the PCG runs in its single-reduction (Chronopoulos-Gear) form — matvec w = A u with the partials of u.w, then ONE
@@ -1500,7 +654,7 @@ int mg_apply_ranks(pgo_problem* p, bool inside_iteration) {
 // same gates (tolerance >= 1e-11, <= 150 000 keyframes); only its unfused form — aggregates too large for the update kernel's groups — stays classic.
 bool single_reduction(const pgo_problem* p) {
     // (the two-level method: only its fused three-kernel iteration has a single-reduction form; its unfused form — aggregates too large for the update kernel's groups — stays classic)
-    const bool two_level = p->coarse_active && !p->mg_active;
+    const bool two_level = p->coarse_active && !p->mg.active;
     // ... and only where the iteration is latency-bound: the form trades one partial-sum head (~4.5 us) for 96 more bytes per keyframe and iteration, which costs more than the
     // head from ~130 000 keyframes on — measured +1.4 % on C3 (100k) and +2...+7 % on 12k-60k-keyframe graphs, but -1.2 % on C4 (200k) and -1.7 % on C5 (1M)
     // (profiles/r05_single_reduction_graph_types.txt, r05_option_ab_c4_c5.txt)
@@ -1528,16 +682,16 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
     const bool multi = p->local_ids;
     // two-level preconditioner in three kernels per iteration (prolongation inside the matvec, restriction inside the update, r.(P y) from the dense solve):
     // the update kernel's r.z partials take `fused_parts` slots, the solve's C.extra_rz slots behind them
-    const bool fused_coarse = !multi && p->coarse_active && !p->mg_active && p->built_mf && coarse_group_keyframes(p->K) > 0;
+    const bool fused_coarse = !multi && p->coarse_active && !p->mg.active && p->built_mf && coarse_group_keyframes(p->K) > 0;
     const int fused_parts = fused_coarse ? coarse_update_grid(p->G, p->K) : 0;
     if (fused_coarse) p->C.extra_rz = coarse_solve_grid(p->K);
-    else if (!p->mg_active) p->C.extra_rz = 0;
+    else if (!p->mg.active) p->C.extra_rz = 0;
     // several ranks, PCG start: r = b (- A x), u = M^-1 r, p = s = 0; part_rz <- owner-weighted partials of gamma_0 (summed over ranks with the first iteration's scalars),
     // part_pq <- partials of b.D^-1 b, summed over ranks here once: the reference norm of the stopping test.  With the multigrid: the distributed cycle (mg_apply_ranks).
     auto start_multi = [&](int warm_i) -> int {
         int rcs;
         const int g = launch_cg_init_vectors(p->G, p->C, warm_i, p->st);
-        if (p->mg_active && (rcs = mg_apply_ranks(p, false)) != PGO_OK) return rcs;      // z += P0 V(P0^T r): the restriction covers the rank's own aggregates (all their keyframes are local)
+        if (p->mg.active && (rcs = mg_apply_ranks(p, false)) != PGO_OK) return rcs;      // z += P0 V(P0^T r): the restriction covers the rank's own aggregates (all their keyframes are local)
         double* bb = p->C.scal + 12;
         launch_reduce(p->C.part_pq, g, 0, bb, p->st);
         if ((rcs = allreduce(p, bb, 1, 0)) != PGO_OK) return rcs;
@@ -1545,11 +699,11 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
         return PGO_OK;
     };
     if (resume_from < 0) {
-        if (!multi && (p->coarse_active || p->mg_active)) {
+        if (!multi && (p->coarse_active || p->mg.active)) {
             // z = D^-1 r + P Ac^-1 P^T r (or the multigrid cycle): the coarse term is added to z and to the r.z partials before the scalars are formed
             int g = launch_cg_init_vectors(p->G, p->C, warm ? 1 : 0, p->st);
             const int g_bb = g;      // the slots of part_pq that hold the partials of b.D^-1 b
-            if (p->mg_active) launch_mg_apply(p->G, p->C, p->M, p->mg_levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
+            if (p->mg.active) launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
             else launch_coarse_apply(p->G, p->C, p->K, p->C.r, p->C.z, p->C.part_rz, false, p->st);
             if (fused_coarse) {    // z is complete here: the slots the fused kernels will use beyond the start-up kernels' stay zero for this parity
                 HIPCHK(p, hipMemsetAsync(p->C.part_rz + g, 0, (size_t)(fused_parts + p->C.extra_rz - g) * sizeof(double), p->st));
@@ -1569,9 +723,9 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
         // per iteration with the coarse space in its unfused form -> 12 iterations, three in the fused form -> 24
         if (p->coarse_active && !multi) e = std::min(e, fused_coarse ? 24 : 12);
         int n_sm = 0;
-        for (int l = 0; l < p->M.n_levels; ++l) n_sm += (p->mg_levels[l].smoothed && !p->mg_levels[l].rt_valf) ? 1 : 0;      // two more kernels per cycle for every level whose smoothed prolongator is applied implicitly (none with the explicit transfer operator)
-        if (p->mg_active && multi) e = std::min(e, std::max(2, (72 / (6 * p->M.n_levels + 12)) & ~1));      // (every exchange is a pack kernel, the transfer and an unpack kernel)
-        if (p->mg_active && !multi) e = std::max(2, (72 / (2 * p->M.n_levels + 3 + 2 * n_sm)) & ~1);   // at most 2 n_levels + 1 cycle kernels + matvec + update per iteration (one less with the restriction inside the update)
+        for (int l = 0; l < p->mg.M.n_levels; ++l) n_sm += (p->mg.levels[l].smoothed && !p->mg.levels[l].rt_valf) ? 1 : 0;      // two more kernels per cycle for every level whose smoothed prolongator is applied implicitly (none with the explicit transfer operator)
+        if (p->mg.active && multi) e = std::min(e, std::max(2, (72 / (6 * p->mg.M.n_levels + 12)) & ~1));      // (every exchange is a pack kernel, the transfer and an unpack kernel)
+        if (p->mg.active && !multi) e = std::max(2, (72 / (2 * p->mg.M.n_levels + 3 + 2 * n_sm)) & ~1);   // at most 2 n_levels + 1 cycle kernels + matvec + update per iteration (one less with the restriction inside the update)
         return e;
     };
     every = chunk_length();
@@ -1588,10 +742,10 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
         if (sr) {      // matvec (no head: it only asks whether the PCG has stopped), update with the iteration's one reduction point, [the multigrid cycle]
             launch_mf_apply_dot_live(p->G, p->F, p->Sc, p->C, p->st);
             const int n_pq = mf_grid_size(p->F), first = kk == 0 ? 1 : 0;      // (first: also when a PCG that stopped before its first update is resumed — p = s = 0 still)
-            const bool mg_restrict_fused = p->mg_active && p->M.blk_tab != nullptr;
-            if (mg_restrict_fused) launch_cg_update_mg_sr(p->G, p->C, p->M, p->mg_levels, p->K, kk, first, n_pq, p->st);
+            const bool mg_restrict_fused = p->mg.active && p->mg.M.blk_tab != nullptr;
+            if (mg_restrict_fused) launch_cg_update_mg_sr(p->G, p->C, p->mg.M, p->mg.levels, p->K, kk, first, n_pq, p->st);
             else launch_cg_update_sr(p->G, p->C, kk, first, n_pq, p->st);
-            if (p->mg_active) launch_mg_apply(p->G, p->C, p->M, p->mg_levels, p->K, p->C.r, p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, mg_scale(p), true, p->st, mg_restrict_fused, mg_cs(p), mg_fine_view(p));
+            if (p->mg.active) launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, mg_scale(p), true, p->st, mg_restrict_fused, mg_cs(p), mg_fine_view(p));
             return PGO_OK;
         }
         if (multi) {
@@ -1607,7 +761,7 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
             if ((r2 = allreduce(p, p->d_xscal.p, 2, 0)) != PGO_OK) return r2;
             launch_cgcg_update(p->G, p->C, kk, kk == 0 ? 1 : 0, p->st, nullptr, nullptr, p->d_xscal.p);   // (first: also when a PCG that stopped before its first update is resumed: p = s = 0 still)
             ++p->st_pcg_iterations;
-            if (p->mg_active && (r2 = mg_apply_ranks(p, true)) != PGO_OK) return r2;      // u = D^-1 r + P0 V(P0^T r)
+            if (p->mg.active && (r2 = mg_apply_ranks(p, true)) != PGO_OK) return r2;      // u = D^-1 r + P0 V(P0^T r)
             return PGO_OK;
         }
         if (fused_coarse) {
@@ -1619,11 +773,11 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
         int n_pq = cg_grid_size(p->G);
         if (p->built_mf) { launch_mf_spmv(p->G, p->F, p->Sc, p->C, kk, tol2, p->st); n_pq = mf_grid_size(p->F); }
         else launch_cg_spmv(p->G, p->C, kk, tol2, p->st);
-        const bool mg_restrict_fused = p->mg_active && p->M.blk_tab != nullptr;      // the vector update also restricts the new residual to level 1
-        if (mg_restrict_fused) launch_cg_update_mg(p->G, p->C, p->M, p->mg_levels, p->K, kk, n_pq, p->st);
+        const bool mg_restrict_fused = p->mg.active && p->mg.M.blk_tab != nullptr;      // the vector update also restricts the new residual to level 1
+        if (mg_restrict_fused) launch_cg_update_mg(p->G, p->C, p->mg.M, p->mg.levels, p->K, kk, n_pq, p->st);
         else launch_cg_update(p->G, p->C, kk, n_pq, p->st);
         // the new residual is in the OTHER r buffer, its r.z partials in the other parity's slots
-        if (p->mg_active) launch_mg_apply(p->G, p->C, p->M, p->mg_levels, p->K, (kk & 1) ? p->C.r : p->C.r2, p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, mg_scale(p), true, p->st, mg_restrict_fused, mg_cs(p), mg_fine_view(p));
+        if (p->mg.active) launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, (kk & 1) ? p->C.r : p->C.r2, p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, mg_scale(p), true, p->st, mg_restrict_fused, mg_cs(p), mg_fine_view(p));
         else if (p->coarse_active)
             launch_coarse_apply(p->G, p->C, p->K, (kk & 1) ? p->C.r : p->C.r2, p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, true, p->st);
         return PGO_OK;
@@ -1636,7 +790,7 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
     // 5-8 us kernels: measured 18.5 vs 19.4 ms at 300 keyframes, 64.0 vs 64.6 ms at 3000)
     const int graph_after = debug_graph_after();
     auto ensure_graph = [&](bool may_capture) {
-        const int mode = p->mg_active ? 2 : p->coarse_active ? 1 : 0;
+        const int mode = p->mg.active ? 2 : p->coarse_active ? 1 : 0;
         pgo_problem::CapturedChunk& cc = p->cg_chunk[mode];
         if (!want_graph || p->cg_graph_failed || (cc.exec != nullptr && cc.epoch == p->build_epoch && cc.len == every && cc.scale == mg_scale(p) && cc.sr == sr)) { p->cg_graph = want_graph && !p->cg_graph_failed ? cc.exec : nullptr; return; }
         if (!may_capture) { p->cg_graph = nullptr; return; }
@@ -1700,7 +854,7 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
     auto switch_to_mg = [&](int so_far) -> int {
         int rcs;
         if ((rcs = build_mg(p)) != PGO_OK) return rcs;
-        if (!p->mg_active) { p->mg_failed = true; return PGO_OK; }
+        if (!p->mg.active) { p->mg_failed = true; return PGO_OK; }
         p->cg_extra += so_far;
         if (p->built_mf) launch_mf_apply(p->G, p->F, p->Sc, p->C, p->C.x, p->C.q, p->st);
         else launch_apply_operator(p->G, p->C, p->C.x, p->C.q, p->st);
@@ -1709,7 +863,7 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
             if ((rcs = start_multi(1)) != PGO_OK) return rcs;
         } else {
             const int g = launch_cg_init_vectors(p->G, p->C, 1, p->st);
-            launch_mg_apply(p->G, p->C, p->M, p->mg_levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
+            launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
             launch_cg_init_scalars(p->C, g, g, tol2, p->st);
         }
         k = 0; n_chunks = 0; waited = -1;
@@ -1719,7 +873,7 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
         return PGO_OK;
     };
     // a system predicted hard whose step has survived the first early-rejection pause (lm_step): the multigrid takes over from the iterate the pause left
-    if (switch_now && resume_from >= 0 && p->mg_built && !p->mg_active && !p->mg_failed && (rc = switch_to_mg(resume_from)) != PGO_OK) return rc;
+    if (switch_now && resume_from >= 0 && p->mg.built && !p->mg.active && !p->mg_failed && (rc = switch_to_mg(resume_from)) != PGO_OK) return rc;
     eg_next = every;
     if (end_game && (resume_from >= 0 || k == 0)) eg_snapshot();
     while (k < o.cg_max_iterations && !done) {
@@ -1755,7 +909,7 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
             // recognised as hard: the polled r.z values give its convergence rate, and a system that would need >= the start threshold in total at that rate (and at
             // least twice what it has done) switches now.  Depends on the solve's own data alone; several ranks: r.z and the reference norm are all-reduced values, every
             // rank sees the same bits and takes the same branch.
-            if (!done && p->mg_built && !p->mg_active && !p->mg_failed && !p->mg_start_deferred && o.mg_switch_iterations > 0 && k < p->mg_switch_at) {
+            if (!done && p->mg.built && !p->mg.active && !p->mg_failed && !p->mg_start_deferred && o.mg_switch_iterations > 0 && k < p->mg_switch_at) {
                 const int kk = p->poll[check & 1].flags[2];
                 const double rz = p->poll[check & 1].scal[1], bb = p->poll[check & 1].scal[0];
                 if (rz > 0.0 && bb > 0.0) {
@@ -1773,7 +927,7 @@ int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume
         // Hybrid preconditioning: most LM systems (small trust regions, steps about to be rejected) are solved by block-Jacobi in a few
         // hundred cheap iterations; one that is not done after mg_switch_iterations is a hard one, and from there the multigrid (4x fewer
         // iterations or better at ~3x the price) takes over: operators built now, PCG restarted from the current iterate.
-        if (!done && p->mg_built && !p->mg_active && !p->mg_failed && k >= p->mg_switch_at && k < o.cg_max_iterations) {     // (several ranks: every quantity tested here is the same on all of them)
+        if (!done && p->mg.built && !p->mg.active && !p->mg_failed && k >= p->mg_switch_at && k < o.cg_max_iterations) {     // (several ranks: every quantity tested here is the same on all of them)
             HIPCHK(p, hipMemcpyAsync(hflags, p->C.flags, sizeof(hflags), hipMemcpyDeviceToHost, p->st));
             HIPCHK(p, hipStreamSynchronize(p->st));
             if (hflags[0]) { done = true; (void)enqueue_poll(n_chunks & 1); ++n_chunks; break; }
@@ -1840,223 +994,6 @@ static int build_coarse(pgo_problem* p) {
     return PGO_OK;
 }
 
-// Multigrid operators of the system just built: Galerkin products level by level, block-Jacobi inverses, dense inverse of the coarsest level.
-// A block that is not numerically positive definite leaves the multigrid off for this LM iteration (plain block-Jacobi).
-// Regroup: the hierarchy was built from the switch values of its time (0.99 everywhere at the first solve of a graph).  A few LM steps later the solver has
-// switched the outliers off, and aggregates of the levels above level 1 that such a loop closure held together are no rigid pieces any more: measured on C3, the
-// late systems need 305 / 367 / 454 multigrid iterations with the hierarchy of the start against 156 / 187 / 249 with one built from the final switch values.  So when
-// multigrid operators are about to be built and the switch values have moved far from the hierarchy's (switchable edges that moved by > 0.5 in s^2 make up more than mg_regroup_fraction of ALL
-// edges), the levels above level 1 are matched again along the couplings alive NOW (the keyframes' level-1 aggregates, matched along relative-pose edges only, and the
-// level-1 structure are cached: pgo_mg::BuildCache) — at most twice per solve.  Several ranks: the count is all-reduced, every rank regroups at the same LM step.
-// how many switchable edges have moved by > 0.5 in s^2 since the hierarchy was matched, against ALL residual blocks (what counts is how much of the coupling structure
-// changed: C4 has 2 % loop closures — no regroup pays there); summed over the ranks
-static int regroup_count(pgo_problem* p, const double* sv, std::vector<double>& cnt, double moved_by = 0.5) {
-    const int64_t Es = p->swe.size();
-    cnt.assign(2, 0.0);
-    for (int64_t e = 0; e < Es; ++e) { const double w = sv[p->swe.sw[e]] * sv[p->swe.sw[e]]; if (std::fabs(w - p->mg_sw_built[e]) > moved_by) cnt[0] += 1.0; }
-    cnt[1] = (double)(Es + p->rel.size());
-    return p->local_ids ? host_allreduce(p, cnt, 0) : PGO_OK;
-}
-// A regroup is TRANSACTIONAL: the hierarchy in place is replaced only by one that coarsened; when the matching along the current couplings stalls (build_hierarchy
-// gives up above 0.85 nodes per node, or runs out of levels) the installed hierarchy stays — with the new switch record, so that the same failing attempt is not
-// repeated at every later check — instead of the handle silently falling back to plain block-Jacobi for the rest of its life.
-static int regroup_commit(pgo_problem* p, MgPrepared& Q) {
-    if (!Q.ok) {
-        if (p->opt.verbosity > 0) std::fprintf(stderr, "[pgo] multigrid: the regrouped hierarchy does not coarsen -> the one in place stays\n");
-        p->mg_sw_built.swap(Q.sw_built);
-        return PGO_OK;
-    }
-    int rc;
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    if ((rc = mg_install(p, Q)) != PGO_OK) return rc;
-    ++p->build_epoch;      // captured PCG chunks hold pointers into the old pools
-    return PGO_OK;
-}
-static int regroup_if_moved(pgo_problem* p, const double* sv /* host: the caller's switch array */, bool in_solve) {
-    std::vector<double> cnt;
-    int rc;
-    if ((rc = regroup_count(p, sv, cnt, in_solve ? 0.5 : 0.0)) != PGO_OK) return rc;
-    // inside a solve: once the moved edges are a sizeable part of the coupling structure.  At the START of a solve: whenever ANY switch differs from the record — the
-    // hierarchy a solve starts with is then a function of the graph and of the solve's own start values alone, whatever earlier solves of the handle left behind
-    // (pgo.h: "no per-handle history"; tests/test_gpu_determinism.py solves from state A after a solve that regrouped and compares with a fresh handle, bit for bit).
-    if (in_solve ? !(cnt[0] > p->opt.mg_regroup_fraction * cnt[1]) : !(cnt[0] > 0.0)) return PGO_OK;
-    const double t0 = now_s();
-    mg_job_cancel(p);
-    MgPrepared Q;
-    if ((rc = mg_prepare(p, sv, Q)) != PGO_OK) return rc;
-    if ((rc = regroup_commit(p, Q)) != PGO_OK) return rc;
-    if (in_solve) ++p->mg_regroups;
-    if (p->opt.verbosity > 0) std::fprintf(stderr, "[pgo] multigrid: regrouped %s (%.0f switchable edges of %.0f edges moved), %.1f ms\n", in_solve ? "inside the solve" : "for the new start", cnt[0], cnt[1], (now_s() - t0) * 1e3);
-    return PGO_OK;
-}
-static bool regroup_allowed(const pgo_problem* p) {
-    // (not during the first three LM iterations: the switches of outliers — and of inliers far from the odometry guess, which recover — are still falling then: measured on C3,
-    // 17 % of the switchable edges have moved after the first step, and a regroup there is paid twice)
-    return p->opt.mg_regroup_fraction > 0.0 && p->mg_built && p->S > 0 && p->mg_regroups < 2 && p->iteration >= 3 && (int64_t)p->mg_sw_built.size() == p->swe.size();
-}
-// several ranks: the regroup happens where multigrid operators are about to be built, synchronously (its host half holds collectives) — every rank at the same LM step
-static int maybe_regroup(pgo_problem* p) {
-    if (!regroup_allowed(p) || p->iteration <= 3) return PGO_OK;
-    std::vector<double> sv((size_t)p->S);
-    HIPCHK(p, hipMemcpyAsync(sv.data(), p->d_swv[p->cur].p, sv.size() * sizeof(double), hipMemcpyDeviceToHost, p->st));
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    return regroup_if_moved(p, sv.data(), true);
-}
-// One GPU: the HOST half of a regroup (≈25 ms for C3: matching of the upper levels, structures of the smoothed transition, pooled arrays) starts on a worker thread right
-// after the accepted step that moved the switches far enough, and is installed where multigrid operators are next built (regroup_install) — on C3 that is a dozen cheap
-// block-Jacobi LM steps later, so the solve never waits for it.  Which step starts it and which step installs it depend on the solve's own history only.
-static int regroup_start(pgo_problem* p) {
-    if (p->local_ids || p->mg_job_running || !regroup_allowed(p)) return PGO_OK;
-    std::vector<double> sv((size_t)p->S);
-    HIPCHK(p, hipMemcpyAsync(sv.data(), p->d_swv[p->cur].p, sv.size() * sizeof(double), hipMemcpyDeviceToHost, p->st));
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    std::vector<double> cnt;
-    int rc;
-    if ((rc = regroup_count(p, sv.data(), cnt)) != PGO_OK) return rc;
-    if (!(cnt[0] > p->opt.mg_regroup_fraction * cnt[1])) return PGO_OK;
-    ++p->mg_regroups;
-    p->mg_job_out.reset(new MgPrepared());
-    p->mg_job_out->moved = cnt[0]; p->mg_job_out->of_edges = cnt[1];
-    p->mg_job_running = true; p->rc_job = PGO_OK;
-    MgPrepared* Q = p->mg_job_out.get();
-    MgPrepared* old_image = p->mg_job_old.release();
-    try {
-        p->mg_job = std::thread([p, Q, old_image, sv]() { delete old_image; p->rc_job = mg_prepare(p, sv.data(), *Q); });
-    } catch (...) {      // no thread to be had (the C-ABI never throws): the same work on this one
-        delete old_image;
-        p->rc_job = mg_prepare(p, sv.data(), *Q);
-    }
-    return PGO_OK;
-}
-static int regroup_install(pgo_problem* p) {
-    if (!p->mg_job_running) return PGO_OK;
-    const double t0 = now_s();
-    if (p->mg_job.joinable()) p->mg_job.join();
-    p->mg_job_running = false;
-    std::unique_ptr<MgPrepared> Q = std::move(p->mg_job_out);
-    if (p->rc_job != PGO_OK || !Q) return p->rc_job;
-    const double waited = (now_s() - t0) * 1e3;
-    int rc;
-    if ((rc = regroup_commit(p, *Q)) != PGO_OK) return rc;
-    // The host image is NOT freed here: it was allocated by the worker thread (an mmap-backed malloc arena), and returning ~100 MB of it to the system from this thread
-    // costs 5 ms of munmap plus a ~10 ms stall of the next kernels (measured: MMU-notifier invalidations reach the GPU's address space).  It is kept until the next
-    // regroup's worker (or pgo_destroy) drops it, off the solve's critical path.
-    p->mg_job_old = std::move(Q);
-    MgPrepared* Qk = p->mg_job_old.get();
-    if (p->opt.verbosity > 0) std::fprintf(stderr, "[pgo] multigrid: regrouped inside the solve (%.0f switchable edges of %.0f edges moved): host half %.1f ms on a worker thread, waited %.1f ms, installed in %.1f ms\n",
-                                           Qk->moved, Qk->of_edges, Qk->host_ms, waited, (now_s() - t0) * 1e3 - waited);
-    return PGO_OK;
-}
-
-// Several ranks, distributed set-up (round 6): the operators of the current LM system with every DISTRIBUTED level formed by its rows' owners.
-//   level 1:  every rank's part of the Galerkin product from its own edges and owned keyframes (as before), then — instead of the all-reduce of ALL of level 1's blocks — the
-//             parts of the blocks two ranks share go to the ranks that need them (BlockPlan: summed in ascending rank order)
-//   level l distributed:  block-Jacobi inverses, the fp32 copy, the smoother's safety estimate (the whole level's eight power steps on the owners' rows: the iterate's halo before
-//             every step, one 3-double all-reduce of the norms and the failure flag — a failed block counts for all ranks); a smoothed transition above it: Dinv of the halo rows (the cycle forms x = Dinv r on receipt), Ps on its own rows, the rows of Ps its rows of W = A Ps
-//             multiply from their owners, W and R^T = Ps - Dinv W on its own rows, the blocks of R whose coarse row is another rank's to that rank, its rows' part of Ps^T W to
-//             the needers; a plain transition: P^T A P on its own rows (children are the parent's rank's), the blocks above the diagonal also to the column's owner
-//   the first level every rank runs completely:  formed like that by its rows' owners, gathered by all; from there on every rank forms the same small levels and the dense inverse
-// Nothing here is replicated that grows with the graph: under weak scaling a rank's set-up stays its share + the small top.
-static int build_mg_ranks(pgo_problem* p, double omega, int32_t* fail, bool hoff_valid, bool kernels_only = false /* pgo_time_kernel(8): this rank's kernels without the exchanges (the numbers are then meaningless) */) {
-    const int fw = p->mg_first_whole;
-    int rc;
-    launch_mg_galerkin0(p->G, p->L, p->Sc, p->C, p->M, p->mg_levels, p->st, hoff_valid);
-    if (!kernels_only && (rc = exchange_blocks_sum(p, p->mg_setup.val[0], p->su_plan[0], p->mg_levels[0].val)) != PGO_OK) return rc;
-    for (int l = 0; l < fw; ++l) {
-        MgLevelDev& A = p->mg_levels[l];
-        MgLevelDev& B = p->mg_levels[l + 1];
-        launch_mg_level_inverses(A, omega, fail, p->st);
-        {   // the smoother's safety estimate: the whole level's power method, the iterate's halo exchanged before every step, the norms (and the failure flag) summed over the ranks
-            launch_mg_power_init(A, p->st);
-            double* v = A.x; double* w = A.xt;
-            for (int it = 0; it < 8; ++it) {
-                if (!kernels_only && (rc = exchange_level(p, l, v, nullptr, nullptr, nullptr)) != PGO_OK) return rc;
-                launch_mg_power_step(A, v, w, omega, p->st);
-                std::swap(v, w);
-            }
-            launch_mg_power_sums(A, w, v, fail, p->d_xscal.p + 8, p->st);      // (v: 8 steps, w: 7 steps)
-            if (!kernels_only && (rc = allreduce(p, p->d_xscal.p + 8, 3, 0)) != PGO_OK) return rc;
-            launch_mg_power_finish(p->d_xscal.p + 8, fail, A.xf, p->st);
-            launch_mg_level_rescale(A, A.xf, omega, p->st);
-        }
-        if (A.smoothed) {
-            const pgo_problem::LevelPlanDev& LP = p->lvl_plan[(size_t)l];
-            if (!kernels_only && LP.plan && (rc = exchange_blocks_copy(p, *LP.plan, LP.send_idx, LP.recv_idx, A.Dinv, 36)) != PGO_OK) return rc;
-            launch_mg_transition_ps(A, mg_cs(p), p->st);
-            if (!kernels_only && (rc = exchange_blocks_copy(p, p->mg_setup.ps[(size_t)l], p->su_plan[(size_t)l].ps_send, p->su_plan[(size_t)l].ps_recv, A.ps_val, 36)) != PGO_OK) return rc;
-            launch_mg_transition_w(A, p->st);
-            if (!kernels_only && (rc = exchange_blocks_copy(p, p->mg_setup.rv[(size_t)l], p->su_plan[(size_t)l].rv_send, p->su_plan[(size_t)l].rv_recv, reinterpret_cast<double*>(A.r_valf), 18)) != PGO_OK) return rc;
-            launch_mg_transition_product(A, B, p->st);
-        } else if (l + 1 == fw) {      // the first level every rank runs completely: its own rows here, the rest by the gather below
-            MgLevelDev Bo = B;
-            Bo.su_row0 = p->mg_fw_row0; Bo.su_row1 = p->mg_fw_row1; Bo.su_blk0 = p->mg_fw_blk0; Bo.su_blk1 = p->mg_fw_blk1;
-            launch_mg_level_galerkin(A, Bo, p->st);
-        } else launch_mg_level_galerkin(A, B, p->st);
-        if (!kernels_only && (rc = exchange_blocks_sum(p, p->mg_setup.val[(size_t)l + 1], p->su_plan[(size_t)l + 1], B.val)) != PGO_OK) return rc;
-    }
-    launch_mg_assemble_rest(p->M, p->mg_levels, p->K, omega, fail, p->st, mg_cs(p), fw);
-    return PGO_OK;
-}
-
-static int build_mg(pgo_problem* p) {
-    p->mg_active = false;
-    if (!p->mg_built) return PGO_OK;
-    { int rci; if ((rci = mg_init_finish(p)) != PGO_OK) return rci; }      // the hierarchy of a fresh graph build is installed where it is first needed
-    if (!p->mg_built) return PGO_OK;
-    const double t_build0 = now_s();
-    { int rcr; if ((rcr = p->local_ids ? maybe_regroup(p) : regroup_install(p)) != PGO_OK) return rcr; }
-    if (!p->mg_built) return PGO_OK;
-    if (p->opt.verbosity > 1) std::fprintf(stderr, "[pgo] multigrid: build_mg past the regroup at %.2f ms\n", (now_s() - t_build0) * 1e3);
-    int rcm;
-    if (p->mg_geometry_epoch != p->lin_epoch) {              // the aggregates' centroids follow the poses of the current linearisation
-        if (p->local_ids) {     // a level-1 node's keyframes live on several ranks: owner-weighted position sums, one all-reduce, then as on one GPU
-            launch_mg_geometry0_sum(p->G, p->M, p->mg_levels, p->d_pose[p->cur].p, p->st);
-            if ((rcm = allreduce(p, p->mg_levels[0].pos, (size_t)p->M.n1 * 3, 0)) != PGO_OK) return rcm;
-            launch_mg_geometry_finish(p->G, p->M, p->mg_levels, p->d_pose[p->cur].p, p->st);
-        } else launch_mg_geometry(p->G, p->M, p->mg_levels, p->d_pose[p->cur].p, p->st);
-        p->mg_geometry_epoch = p->lin_epoch;
-    }
-    int32_t* fail = p->d_cinfo.p;
-    HIPCHK(p, hipMemsetAsync(fail, 0, sizeof(int32_t), p->st));
-    const double omega = p->opt.mg_omega > 0.0 && p->opt.mg_omega <= 1.0 ? p->opt.mg_omega : 0.9;
-    // level 1's Galerkin product reads J1^T J2 of every edge: the block-CSR solver has them from K2; under the matrix-free solver they are formed here, once per linearisation
-    // that builds multigrid operators (an edge-parallel pass whose Jacobian loads coalesce, ~60 us on C3 — the wavefront-per-block product gathering K1's Jacobians itself,
-    // twelve strided loads per lane and contribution, took 0.9 ms)
-    bool hoff_valid = !p->built_mf;
-    if (p->built_mf && p->d_Hoff.cap >= (size_t)(p->G.rel.Epad + p->G.sw.Epad) * 36) {
-        if (p->hoff_epoch != p->lin_epoch) { p->L.Hoff = p->d_Hoff.p; launch_k2_offdiag(p->G, p->L, p->st); p->hoff_epoch = p->lin_epoch; }
-        hoff_valid = true;
-    }
-    if (p->local_ids && p->mg_first_whole > 0) {
-        if ((rcm = build_mg_ranks(p, omega, fail, hoff_valid)) != PGO_OK) return rcm;
-    } else if (p->local_ids) {  // level 1 = the sum of the ranks' Galerkin products (each edge lives on one rank, each diagonal block is its owner's); the levels above are replicated
-        launch_mg_galerkin0(p->G, p->L, p->Sc, p->C, p->M, p->mg_levels, p->st, hoff_valid);
-        if ((rcm = allreduce(p, p->mg_levels[0].val, (size_t)p->mg_levels[0].nnzb * 36, 0)) != PGO_OK) return rcm;
-        launch_mg_assemble_rest(p->M, p->mg_levels, p->K, omega, fail, p->st, mg_cs(p));
-    } else if (p->opt.verbosity > 1) {
-        HIPCHK(p, hipStreamSynchronize(p->st)); std::fprintf(stderr, "[pgo] multigrid: geometry done at %.2f ms\n", (now_s() - t_build0) * 1e3);
-        launch_mg_galerkin0(p->G, p->L, p->Sc, p->C, p->M, p->mg_levels, p->st, hoff_valid);
-        HIPCHK(p, hipStreamSynchronize(p->st)); std::fprintf(stderr, "[pgo] multigrid: galerkin0 done at %.2f ms\n", (now_s() - t_build0) * 1e3);
-        launch_mg_assemble_rest(p->M, p->mg_levels, p->K, omega, fail, p->st, mg_cs(p));
-    } else if (p->mg_fine) {      // smoothed keyframe transition: level 1 = Ps_0^T A Ps_0 from the keyframe level's own blocks
-        launch_mg_assemble_fine(p->G, p->L, p->Sc, p->C, p->mg_fineF, p->mg_fineT, p->mg_levels[0], omega, fail, p->st, mg_cs(p), hoff_valid, p->d_pose[p->cur].p);
-        launch_mg_assemble_rest(p->M, p->mg_levels, p->K, omega, fail, p->st, mg_cs(p));
-    } else launch_mg_assemble(p->G, p->L, p->Sc, p->C, p->M, p->mg_levels, p->K, omega, fail, p->st, mg_cs(p), hoff_valid);
-    if (p->opt.verbosity > 1) { HIPCHK(p, hipStreamSynchronize(p->st)); std::fprintf(stderr, "[pgo] multigrid: level operators done at %.2f ms\n", (now_s() - t_build0) * 1e3); }
-    launch_coarse_invert(p->K, p->d_cscr.p, fail, p->st);
-    if (debug_break_coarse()) launch_coarse_negate(p->K, p->st);
-    int32_t h = 1;
-    HIPCHK(p, hipMemcpyAsync(&h, fail, sizeof(h), hipMemcpyDeviceToHost, p->st));
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    p->mg_active = h == 0;
-    // level 1's up-sweep kernel also prolongs to the keyframes; its workgroups (at most MAX_PARTIALS, each taking every gridDim-th tile) put their r.z partials behind the update kernel's
-    // (measured: 1 114 tiles on 1 024 workgroups — C4 — lose 3 % to the ragged second trip against the separate prolongation kernel; 3 907 tiles — C5 — gain 3.5 %)
-    const int t1 = p->mg_levels[0].tiles;
-    p->C.extra_rz = (p->mg_active && !p->local_ids && !p->mg_fine && p->M.n_levels >= 2 && (t1 <= MAX_PARTIALS || t1 >= 2 * MAX_PARTIALS)) ? std::min<int>(t1, MAX_PARTIALS) : 0;
-    if (p->opt.verbosity > 0 && h != 0) std::fprintf(stderr, "[pgo] multigrid: a coarse block is not positive definite at radius %.1e -> off for this iteration\n", p->radius);
-    if (p->opt.verbosity > 1) std::fprintf(stderr, "[pgo] multigrid: operators of LM iteration %d built in %.2f ms\n", p->iteration, (now_s() - t_build0) * 1e3);
-    return PGO_OK;
-}
 
 int build_system(pgo_problem* p, bool* ok) {
     int rc;
@@ -2073,10 +1010,10 @@ int build_system(pgo_problem* p, bool* ok) {
         fail = f[0] != 0.0;
     }
     *ok = fail == 0;
-    p->mg_active = false; p->mg_failed = false; p->C.extra_rz = 0; p->mg_start_deferred = false;
+    p->mg.active = false; p->mg_failed = false; p->C.extra_rz = 0; p->mg_start_deferred = false;
     // block-Jacobi-equivalent iterations this system is expected to need: those of the last fully solved system of this solve x sqrt(radius ratio); 0 = no prediction
     p->cg_predicted = (p->cg_prev_radius > 0.0 && p->radius > 0.0) ? p->cg_prev_equiv * std::sqrt(p->radius / p->cg_prev_radius) : 0.0;
-    if (*ok && p->mg_built) {
+    if (*ok && p->mg.built) {
         // Which preconditioner the PCG of this LM system starts with.  Block-Jacobi iterations grow like sqrt(radius) from one accepted step
         // to the next, so the previous step of this solve predicts this one (a multigrid iteration counts as 4 block-Jacobi ones: it costs
         // ~2.5x and saves 4x or more on hard systems):  predicted >= 1.75 x mg_switch_iterations -> multigrid (from the first iteration, or after the prelude below);
@@ -2132,13 +1069,13 @@ int solve_begin(pgo_problem* p, const double* quat, const double* t, const doubl
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
     p->t_begin = now_s();
-    mg_job_cancel(p);
+    if (p->mg.job.kind == MgJob::regroup) mg_drop_pending(p);
     const bool rebuild = p->graph_dirty || p->priors_dirty || N != p->N_global || S != p->S;
     if (rebuild) { if ((rc = build_graph(p, N, S, sw)) != PGO_OK) return rc; }
-    else if ((rc = mg_init_finish(p)) != PGO_OK) return rc;      // (an unchanged graph whose hierarchy no solve has needed yet: installed, then compared with this solve's start values)
-    if (!rebuild && p->opt.mg_regroup_fraction > 0.0 && p->mg_built && S > 0 && sw && (int64_t)p->mg_sw_built.size() == p->swe.size()) {
+    else if ((rc = mg_fresh_install(p)) != PGO_OK) return rc;      // (an unchanged graph whose hierarchy no solve has needed yet: installed, then compared with this solve's start values)
+    if (!rebuild && p->opt.mg_regroup_fraction > 0.0 && p->mg.built && S > 0 && sw && (int64_t)p->mg.sw_built.size() == p->swe.size()) {
         // the hierarchy of an unchanged graph was built (or regrouped inside the last solve) for other switch values than this solve starts from: the levels above level 1
-        // are rebuilt for the start values whenever ANY switch differs from the record (regroup_if_moved, moved_by = 0) — a synchronous mg_prepare + mg_install, tens of
+        // are rebuilt for the start values whenever ANY switch differs from the record (regroup_if_moved, moved_by = 0) — a synchronous rebuild and install, tens of
         // milliseconds on C3 — so that repeated solves from the same state stay bitwise identical whatever the handle solved before.  What this costs in practice: a session's
         // next trigger has a NEW graph (one more loop edge: full rebuild anyway); only a re-solve of an unchanged graph from other switch values pays it.  (The matching
         // depends on the switch values continuously — coupling strengths order the heavy-edge matching — so "nearly the same switches" is not a safe reason to keep a hierarchy.)
@@ -2164,7 +1101,7 @@ int solve_begin(pgo_problem* p, const double* quat, const double* t, const doubl
     p->in_solve = true; p->terminated = false; p->scale_ready = false; p->have_prev_step = false;
     p->st_exchanges = p->st_allreduces = p->st_pcg_iterations = 0; p->st_bytes_neighbour = p->st_bytes_allreduce = 0.0;
     p->coarse_retests = 0; p->coarse_drop_radius = 0.0;
-    p->cg_prev_equiv = 0.0; p->cg_prev_radius = 0.0; p->mg_regroups = 0; p->last_rho = 1.0;
+    p->cg_prev_equiv = 0.0; p->cg_prev_radius = 0.0; p->mg.regroups = 0; p->last_rho = 1.0;
     if (p->coarse_skip > 0) { p->coarse_mode = 2; p->coarse_skip_all = true; --p->coarse_skip; }
     else { p->coarse_mode = (p->coarse_keep_streak % 4 != 0) ? 1 : 0; p->coarse_skip_all = false; }
     p->radius = p->opt.initial_trust_region_radius; p->decrease_factor = 2.0; p->reuse_diagonal = false; p->iteration = 0; p->invalid = 0;
@@ -2262,7 +1199,7 @@ int lm_step(pgo_problem* p, int ignore_termination, int* done) {
                                       sn > o.parameter_tolerance * (p->x_norm + o.parameter_tolerance) && std::fabs(dc) > o.function_tolerance * p->x_cost;
             if (clear_reject) evaluated = true;
             else {
-                const bool to_mg = p->mg_start_deferred && !p->mg_active;
+                const bool to_mg = p->mg_start_deferred && !p->mg.active;
                 p->mg_start_deferred = false;
                 if ((rc = run_pcg(p, &cg, false, sidx + 1 < n_stages ? stages[sidx + 1].tol : o.cg_rel_tolerance, cg.iterations, to_mg)) != PGO_OK) return rc;
             }
@@ -2299,11 +1236,11 @@ int lm_step(pgo_problem* p, int ignore_termination, int* done) {
         // dense coarse inverse is applied rounded to fp32: at large trust-region radii the coarse operator's condition number exceeds what fp32 resolves, and the rounded
         // inverse need not be positive definite) is not the system's fault: the same system is solved again by plain block-Jacobi before the step may count as invalid.
         // Ceres' exact factorisation never turns a solvable step into an invalid one (reference src/PoseGraphSLAM.cpp:1903).
-        precond_used = p->mg_active ? PGO_PRECOND_MULTIGRID : (p->coarse_active ? PGO_PRECOND_TWO_LEVEL : PGO_PRECOND_BLOCK_JACOBI);
-        if (cg.breakdown && (p->mg_active || p->coarse_active) && !evaluated) {
+        precond_used = p->mg.active ? PGO_PRECOND_MULTIGRID : (p->coarse_active ? PGO_PRECOND_TWO_LEVEL : PGO_PRECOND_BLOCK_JACOBI);
+        if (cg.breakdown && (p->mg.active || p->coarse_active) && !evaluated) {
             if (o.verbosity > 0) std::fprintf(stderr, "[pgo] %s: PCG breakdown at radius %.1e after %d iterations (preconditioner not positive definite) -> block-Jacobi for this system\n",
-                                              p->mg_active ? "multigrid" : "two-level method", p->radius, cg.iterations);
-            if (p->mg_active) { p->mg_active = false; p->mg_failed = true; }
+                                              p->mg.active ? "multigrid" : "two-level method", p->radius, cg.iterations);
+            if (p->mg.active) { p->mg.active = false; p->mg_failed = true; }
             p->coarse_active = false;      // (this system only: build_coarse decides again for the next one)
             p->C.extra_rz = 0;
             p->cg_extra += cg.iterations;
@@ -2318,17 +1255,17 @@ int lm_step(pgo_problem* p, int ignore_termination, int* done) {
         if (cg.breakdown) { ok = false; why_invalid = PGO_STEP_INVALID_BREAKDOWN; }
         // block-Jacobi-equivalent work of this system, for the next system's choice of preconditioner (build_system)
         if (!evaluated && !cg.breakdown) {
-            const double equiv = p->mg_levels[0].smoothed ? 8.0 : 4.0;     // block-Jacobi iterations one multigrid iteration stands for on a hard system
-            p->cg_prev_equiv = (double)p->cg_extra + (p->mg_active ? equiv : 1.0) * (double)cg.iterations; p->cg_prev_radius = p->radius;
+            const double equiv = p->mg.levels[0].smoothed ? 8.0 : 4.0;     // block-Jacobi iterations one multigrid iteration stands for on a hard system
+            p->cg_prev_equiv = (double)p->cg_extra + (p->mg.active ? equiv : 1.0) * (double)cg.iterations; p->cg_prev_radius = p->radius;
         }
     }
     it.cg_iterations = cg.iterations + p->cg_extra; it.cg_residual = cg.rel_residual;
     const double t_solved = now_s();
     it.seconds_system = t_built - t0; it.seconds_pcg = t_solved - t_built;
-    it.cg_iterations_multigrid = p->mg_active ? cg.iterations : 0; it.single_reduction = ok && single_reduction(p) ? 1 : 0;
-    if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d PCG: %d iterations%s after %d with block-Jacobi; system + preconditioner %.3f ms, PCG %.3f ms\n", p->iteration, cg.iterations, p->mg_active ? " with the multigrid" : "", p->cg_extra, (t_built - t0) * 1e3, (t_solved - t_built) * 1e3);
+    it.cg_iterations_multigrid = p->mg.active ? cg.iterations : 0; it.single_reduction = ok && single_reduction(p) ? 1 : 0;
+    if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d PCG: %d iterations%s after %d with block-Jacobi; system + preconditioner %.3f ms, PCG %.3f ms\n", p->iteration, cg.iterations, p->mg.active ? " with the multigrid" : "", p->cg_extra, (t_built - t0) * 1e3, (t_solved - t_built) * 1e3);
     p->sum.cg_iterations += cg.iterations + p->cg_extra;
-    if (p->mg_active) p->sum.cg_iterations_multigrid += cg.iterations;     // iterations before an in-flight switch (cg_extra) ran with block-Jacobi
+    if (p->mg.active) p->sum.cg_iterations_multigrid += cg.iterations;     // iterations before an in-flight switch (cg_extra) ran with block-Jacobi
     if (ok) {
         if (!evaluated && (rc = evaluate_candidate()) != PGO_OK) return rc;
         it.seconds_evaluate = now_s() - t_solved;
@@ -2455,8 +1392,8 @@ int solve_end(pgo_problem* p, double* quat, double* t, double* sw, pgo_summary* 
     // of graph) skip it, 1, 3, 7, 15 solves at a time, before comparing again; one win resets the back-off
     if (p->coarse_mode == 2 && !p->coarse_skip_all) { p->coarse_backoff = std::min(2 * p->coarse_backoff + 1, 15); p->coarse_skip = p->coarse_backoff; }
     if (p->coarse_mode == 1) ++p->coarse_keep_streak; else if (p->coarse_mode == 2 && !p->coarse_skip_all) p->coarse_keep_streak = 0;
-    mg_job_cancel(p);      // a regroup nobody needed any more: dropped (the hierarchy in place keeps its own switch record)
-    if ((rc = mg_init_finish(p)) != PGO_OK) return rc;      // a fresh graph's hierarchy that this solve never needed: installed now, for the handle's next solves
+    if (p->mg.job.kind == MgJob::regroup) mg_drop_pending(p);      // a regroup nobody needed any more: dropped (the hierarchy in place keeps its own switch record)
+    if ((rc = mg_fresh_install(p)) != PGO_OK) return rc;      // a fresh graph's hierarchy that this solve never needed: installed now, for the handle's next solves
     p->sum.seconds_total = now_s() - p->t_begin;
     if (out) *out = p->sum;
     p->in_solve = false;
@@ -2466,8 +1403,7 @@ int solve_end(pgo_problem* p, double* quat, double* t, double* sw, pgo_summary* 
 int add_edges(pgo_problem* p, HostClass& H, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, const int32_t* sw) {
     if (n < 0 || (n > 0 && (!c1 || !c2 || !T))) { p->err = "null edge array"; return PGO_ERR_INVALID_ARG; }
     for (int64_t k = 0; k < n; ++k) if (c1[k] < 0 || c2[k] < 0 || c1[k] == c2[k] || (sw && sw[k] < 0)) { p->err = "negative index or self edge"; return PGO_ERR_INVALID_ARG; }
-    mg_job_cancel(p);      // (the worker reads the edge lists)
-    mg_init_drop(p);
+    mg_drop_pending(p);      // (the worker reads the edge lists)
     const size_t base = H.c1.size();
     H.c1.insert(H.c1.end(), c1, c1 + n);
     H.c2.insert(H.c2.end(), c2, c2 + n);
@@ -2485,7 +1421,7 @@ int attach_comm(pgo_problem* p, Make make) {
     int rc;
     std::unique_ptr<pgo_comm::Comm> c;
     if ((rc = set_device(p)) != PGO_OK || (rc = make(c)) != PGO_OK) return rc;
-    mg_job_cancel(p); mg_init_drop(p);
+    mg_drop_pending(p);
     p->comm = std::move(c);
     p->graph_dirty = true;
     return PGO_OK;
@@ -2601,10 +1537,9 @@ int pgo_create(pgo_problem** out, const pgo_options* opts) {
 
 int pgo_destroy(pgo_problem* p) {
     if (!p) return PGO_ERR_INVALID_ARG;
-    mg_job_cancel(p);
-    mg_init_drop(p);
+    mg_drop_pending(p);
     (void)hipSetDevice(p->device);
-    // (the in-process group's peers may be gone: the group is aborted, not waited for.  Known limit: the send buffers below are freed once this handle's stream has drained —
+    // (the in-process group's peers may be gone: the group is aborted, not waited for.  Known limit: the send buffers are freed with the handle, once its stream has drained —
     // on one GPU hipFree waits for the peers' kernels as well, across GPUs a peer's copy kernel of the last exchange could still be reading them)
     if (p->comm) p->comm->abandon();
     p->comm.reset();
@@ -2612,19 +1547,6 @@ int pgo_destroy(pgo_problem* p) {
     for (auto& cc : p->cg_chunk) if (cc.exec) (void)hipGraphExecDestroy(cc.exec);
     if (p->poll) (void)hipHostFree(p->poll);
     for (int i = 0; i < 2; ++i) if (p->poll_ev[i]) (void)hipEventDestroy(p->poll_ev[i]);
-    p->d_rc1.release(); p->d_rc2.release(); p->d_sc1.release(); p->d_sc2.release(); p->d_sidx.release(); p->d_bsr_col.release();
-    p->d_rmeas.release(); p->d_smeas.release(); p->d_rwin.release(); p->d_swin.release(); p->d_prior.release();
-    p->d_inc_rowptr.release(); p->d_inc.release(); p->d_bsr_rowptr.release(); p->d_node_free.release();
-    p->d_Jr.release(); p->d_Js.release(); p->d_Jp.release(); p->d_Hd_g.release(); p->d_Hoff.release(); p->d_c.release(); p->d_hss.release(); p->d_gs.release();
-    p->d_scale_p.release(); p->d_scale_s.release(); p->d_diag_p.release(); p->d_diag_s.release(); p->d_a_inv.release();
-    p->d_val.release(); p->d_Lf.release(); p->d_Dtot_b.release(); p->d_cgvec.release(); p->d_part.release(); p->d_cgpart.release();
-    p->d_flags.release(); p->d_scal.release(); p->d_pose[0].release(); p->d_pose[1].release(); p->d_swv[0].release(); p->d_swv[1].release();
-    p->d_delta_s.release(); p->d_io.release(); p->d_tmp.release(); p->d_vio.release(); p->d_vio_idx.release(); p->d_vio_meas.release();
-    p->d_mg_f64.release(); p->d_mg_i32.release(); p->d_mg_i64.release();
-    p->d_ccen.release(); p->d_cd.release(); p->d_cAc.release(); p->d_crc.release(); p->d_cblk_ptr.release(); p->d_ccontrib.release(); p->d_cblk_ab.release(); p->d_cagg_free.release(); p->d_cinfo.release(); p->d_cscr.release(); p->d_cAcf.release();
-    p->d_l2g.release(); p->d_fp_send.release(); p->d_fp_shloc.release(); p->d_fp_sumptr.release(); p->d_fp_sumsrc.release(); p->d_own.release(); p->d_xsend[0].release(); p->d_xsend[1].release(); p->d_xrecv.release(); p->d_xscal.release();
-    p->d_einc.release(); p->d_einc_slot.release(); p->d_node_rng.release(); p->d_tile_inc0.release(); p->d_einc_other.release();
-    p->d_tile_node0.release(); p->d_tile_sw0.release(); p->d_node_prior.release(); p->d_rec.release(); p->d_lam.release();
     (void)hipStreamDestroy(p->st);
     delete p;
     return PGO_OK;
@@ -2633,8 +1555,7 @@ int pgo_destroy(pgo_problem* p) {
 int pgo_set_options(pgo_problem* p, const pgo_options* o) {
     if (!p || !o) return PGO_ERR_INVALID_ARG;
     const int dev = p->opt.device_id;
-    mg_job_cancel(p);
-    mg_init_drop(p);
+    mg_drop_pending(p);
     if (o->linear_solver != p->opt.linear_solver) p->graph_dirty = true;
     // the preconditioner hierarchies are part of the device graph build
     if (o->mg_min_keyframes != p->opt.mg_min_keyframes || o->mg_min_keyframes_switchable != p->opt.mg_min_keyframes_switchable || o->mg_first_passes != p->opt.mg_first_passes || o->mg_passes != p->opt.mg_passes ||
@@ -2651,8 +1572,7 @@ int pgo_reserve(pgo_problem* p, int64_t n_nodes, int64_t n_edges) {
     if ((size_t)n_edges <= p->rel.c1.capacity() && (size_t)n_edges <= p->rel.c2.capacity() && (size_t)n_edges * 8 <= p->rel.meas.capacity()) return PGO_OK;      // nothing moves
     // the edge arrays are about to be reallocated: the hierarchy workers (a fresh graph's, a regroup's) read them — same rule as every other mutating entry point
     if (p->in_solve) { p->err = "pgo_reserve inside a solve (between pgo_solve_begin and pgo_solve_end)"; return PGO_ERR_STATE; }
-    mg_job_cancel(p);
-    mg_init_drop(p);
+    mg_drop_pending(p);
     p->rel.c1.reserve(n_edges); p->rel.c2.reserve(n_edges); p->rel.meas.reserve((size_t)n_edges * 8);
     return PGO_OK;
 }
@@ -2679,8 +1599,7 @@ int pgo_set_node_regularizers(pgo_problem* p, int64_t n, const int32_t* node, co
         eigen_matrix_to_quat(P.Rf, P.qf);
         P.w = weight[k]; P.node = node[k]; P.pad_ = 0;
     }
-    mg_job_cancel(p);
-    mg_init_drop(p);
+    mg_drop_pending(p);
     p->priors.swap(v);
     p->priors_dirty = true;
     return PGO_OK;
@@ -2688,8 +1607,7 @@ int pgo_set_node_regularizers(pgo_problem* p, int64_t n, const int32_t* node, co
 int pgo_set_nodes_constant(pgo_problem* p, int64_t n, const int32_t* node) {
     if (!p || n < 0 || (n > 0 && !node)) return PGO_ERR_INVALID_ARG;
     for (int64_t k = 0; k < n; ++k) if (node[k] < 0) return PGO_ERR_INVALID_ARG;
-    mg_job_cancel(p);      // (the worker reads h_node_free / constant_nodes)
-    mg_init_drop(p);
+    mg_drop_pending(p);      // (the worker reads h_node_free / constant_nodes)
     p->constant_nodes.insert(p->constant_nodes.end(), node, node + n);
     p->graph_dirty = true;
     return PGO_OK;
@@ -2702,7 +1620,7 @@ int pgo_set_vio_poses(pgo_problem* p, int64_t first, int64_t n, const double* w_
     HIPCHK(p, hipSetDevice(p->device));
     const int64_t need = first + n;
     if ((size_t)need * 16 > p->d_vio.cap) {       // grow geometrically, keep the old poses
-        ScopedBuf<double> bigger;
+        DBuf<double> bigger;
         HIPCHK(p, bigger.ensure((size_t)std::max<int64_t>(need + need / 2, 1024) * 16));
         if (p->n_vio > 0) HIPCHK(p, hipMemcpyAsync(bigger.p, p->d_vio.p, (size_t)p->n_vio * 16 * sizeof(double), hipMemcpyDeviceToDevice, p->st));
         HIPCHK(p, hipStreamSynchronize(p->st));
@@ -2719,8 +1637,7 @@ int pgo_add_odometry_edges_from_vio(pgo_problem* p, const int32_t* set_id, int64
     if (!p || u_begin < 0 || u_end < u_begin || f_max < 1) return PGO_ERR_INVALID_ARG;
     if (u_end > p->n_vio) { p->err = "odometry edges requested beyond the resident VIO poses"; return PGO_ERR_INVALID_ARG; }
     if (p->in_solve) { p->err = "graph construction inside a solve"; return PGO_ERR_STATE; }
-    mg_job_cancel(p);      // (a regroup's worker left behind by a failed solve reads the edge lists)
-    mg_init_drop(p);
+    mg_drop_pending(p);      // (a regroup's worker left behind by a failed solve reads the edge lists)
     std::vector<int32_t> c1, c2;
     c1.reserve((size_t)(u_end - u_begin) * f_max); c2.reserve(c1.capacity());
     for (int64_t u = u_begin; u < u_end; ++u)
@@ -2765,8 +1682,8 @@ int pgo_initial_guess_from_vio(pgo_problem* p, int64_t n_left, const double* lef
     }
     if (!any) return PGO_OK;
     HIPCHK(p, hipSetDevice(p->device));
-    ScopedBuf<double> d_left, d_q, d_t;
-    ScopedBuf<int32_t> d_sel;
+    DBuf<double> d_left, d_q, d_t;
+    DBuf<int32_t> d_sel;
     HIPCHK(p, d_left.ensure((size_t)n_left * 16)); HIPCHK(p, d_q.ensure((size_t)cnt * 4)); HIPCHK(p, d_t.ensure((size_t)cnt * 3)); HIPCHK(p, d_sel.ensure((size_t)cnt));
     HIPCHK(p, hipMemcpyAsync(d_left.p, left, (size_t)n_left * 16 * sizeof(double), hipMemcpyHostToDevice, p->st));
     HIPCHK(p, hipMemcpyAsync(d_sel.p, left_of_node, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
@@ -2797,8 +1714,7 @@ int pgo_solve_begin(pgo_problem* p, const double* q, const double* t, const doub
 }
 // a failed step or write-back: no regroup worker outlives it (it reads host arrays the caller may change next), and a stream capture a failing launch left open is ended
 static void after_failure(pgo_problem* p) {
-    mg_job_cancel(p);
-    mg_init_drop(p);
+    mg_drop_pending(p);
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (p->st && hipStreamIsCapturing(p->st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(p->st, &g); if (g) (void)hipGraphDestroy(g); p->cg_graph_failed = true; }
     (void)hipGetLastError();
@@ -2911,7 +1827,7 @@ int pgo_manifold_plus(pgo_problem* p, int64_t n, const double* quat, const doubl
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
     const bool with_t = t != nullptr && t_out != nullptr;
-    ScopedBuf<double> d;
+    DBuf<double> d;
     HIPCHK(p, d.ensure((size_t)n * 20));
     double* dq = d.p; double* dd = dq + 4 * n; double* dqo = dd + 6 * n; double* dt = dqo + 4 * n; double* dto = dt + 3 * n;
     HIPCHK(p, hipMemcpyAsync(dq, quat, (size_t)n * 4 * sizeof(double), hipMemcpyHostToDevice, p->st));
@@ -2972,37 +1888,37 @@ int pgo_get_sharding_stats(pgo_problem* p, pgo_sharding_stats* out) {
     const double fine = (double)p->fine_plan.x.n_send() * 48.0 + 16.0;
     out->bytes_sent_per_bj_iteration = fine; out->exchanges_per_bj_iteration = 1;
     out->bytes_round5_per_bj_iteration = (6.0 * (double)p->n_sh_global + 2.0) * 8.0;
-    if (p->mg_built && !p->mg_init_pending && p->M.n_levels >= 1) {
-        const int nl = p->M.n_levels;
-        out->mg_levels = nl; out->mg_levels_distributed = p->mg_levels_distributed;
-        out->mg_rows_total = p->mg_rows_total; out->mg_rows_own = p->mg_rows_own; out->mg_blocks_total = p->mg_blocks_total; out->mg_blocks_own = p->mg_blocks_own;
+    if (p->mg.built && !p->mg.fresh_pending() && p->mg.M.n_levels >= 1) {
+        const int nl = p->mg.M.n_levels;
+        out->mg_levels = nl; out->mg_levels_distributed = p->mg.levels_distributed;
+        out->mg_rows_total = p->mg.rows_total; out->mg_rows_own = p->mg.rows_own; out->mg_blocks_total = p->mg.blocks_total; out->mg_blocks_own = p->mg.blocks_own;
         double bytes = fine; int nx = 1;
-        auto count = [&](int point, int lv) { int plan; double* v1; double* v2; const double* dinv; if (mg_exchange_at(p, point, lv, &plan, &v1, &v2, &dinv) && p->lvl_plan[(size_t)plan].plan) { bytes += (double)p->lvl_plan[(size_t)plan].plan->n_send() * (v2 && !dinv ? 96.0 : 48.0); ++nx; } };
+        auto count = [&](int point, int lv) { int plan; double* v1; double* v2; const double* dinv; if (mg_exchange_at(p, point, lv, &plan, &v1, &v2, &dinv) && p->mg.lvl_plan[(size_t)plan].plan) { bytes += (double)p->mg.lvl_plan[(size_t)plan].plan->n_send() * (v2 && !dinv ? 96.0 : 48.0); ++nx; } };
         for (int l = 1; l <= nl; ++l) count(0, l);
         for (int l = nl - 1; l >= 1; --l) count(1, l);
         count(2, 1);
         out->bytes_sent_per_mg_iteration = bytes; out->exchanges_per_mg_iteration = nx;
-        out->bytes_round5_per_mg_iteration = (6.0 * (double)p->n_sh_global + 2.0 + 6.0 * (double)p->M.n1) * 8.0;
+        out->bytes_round5_per_mg_iteration = (6.0 * (double)p->n_sh_global + 2.0 + 6.0 * (double)p->mg.M.n1) * 8.0;
         // the set-up: blocks formed per LM system (level matrices; Ps, W and R^T of smoothed transitions), by all and by this rank; what its exchanges send
-        const int fw = p->mg_first_whole;
+        const int fw = p->mg.first_whole;
         for (int l = 0; l + 1 < nl; ++l) {
-            const MgLevelDev& A = p->mg_levels[l];
+            const MgLevelDev& A = p->mg.levels[l];
             const int64_t all = A.nnzb + (A.smoothed ? (int64_t)A.n_ps + 2 * (int64_t)A.n_w : 0);
             const int64_t own = l < fw ? (A.su_blk1 - A.su_blk0) + (A.smoothed ? (int64_t)(A.su_ps1 - A.su_ps0) + 2 * (int64_t)(A.su_w1 - A.su_w0) : 0) : all;
             out->mg_setup_blocks_total += all; out->mg_setup_blocks_own += own;
         }
-        out->bytes_allreduce_replicated_setup = (double)p->mg_levels[0].nnzb * 288.0;
+        out->bytes_allreduce_replicated_setup = (double)p->mg.levels[0].nnzb * 288.0;
         out->mg_setup_levels_own_rows = fw; out->mg_setup_exchanges = 1;
         if (fw > 0) {
             double sb = 0.0; int nx = 0;
             auto add = [&](const pgo_mg::ExchangePlan& X, double bytes_per_row) { if (!plan_is_empty(X)) { sb += (double)X.n_send() * bytes_per_row; ++nx; } };
-            for (const pgo_mg::BlockPlan& B : p->mg_setup.val) add(B.x, 288.0);
+            for (const pgo_mg::BlockPlan& B : p->mg.setup.val) add(B.x, 288.0);
             for (int l = 0; l < fw; ++l) {
                 nx += 9; sb += 24.0;      // the level's power method: eight halo exchanges of the iterate + the 3-double all-reduce
-                if ((size_t)l < p->lvl_plan.size() && p->lvl_plan[(size_t)l].plan) sb += 8.0 * (double)p->lvl_plan[(size_t)l].plan->n_send() * 48.0;
-                if (!p->mg_levels[l].smoothed) continue;
-                if ((size_t)l < p->lvl_plan.size() && p->lvl_plan[(size_t)l].plan) add(*p->lvl_plan[(size_t)l].plan, 288.0);
-                add(p->mg_setup.ps[(size_t)l], 288.0); add(p->mg_setup.rv[(size_t)l], 144.0);
+                if ((size_t)l < p->mg.lvl_plan.size() && p->mg.lvl_plan[(size_t)l].plan) sb += 8.0 * (double)p->mg.lvl_plan[(size_t)l].plan->n_send() * 48.0;
+                if (!p->mg.levels[l].smoothed) continue;
+                if ((size_t)l < p->mg.lvl_plan.size() && p->mg.lvl_plan[(size_t)l].plan) add(*p->mg.lvl_plan[(size_t)l].plan, 288.0);
+                add(p->mg.setup.ps[(size_t)l], 288.0); add(p->mg.setup.rv[(size_t)l], 144.0);
             }
             out->bytes_sent_per_mg_setup = sb; out->mg_setup_exchanges = nx;
         }
@@ -3013,11 +1929,11 @@ int pgo_get_sharding_stats(pgo_problem* p, pgo_sharding_stats* out) {
 int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8) {
     if (!p || !out8) return PGO_ERR_INVALID_ARG;
     for (int k = 0; k < 8; ++k) out8[k] = 0.0;
-    if (!p->mg_built || p->mg_init_pending || level < 1 || level > p->M.n_levels || (size_t)(level - 1) >= p->mg_own.size()) { p->err = "pgo_mg_level_norms: no such level (is a hierarchy installed?)"; return PGO_ERR_INVALID_ARG; }
+    if (!p->mg.built || p->mg.fresh_pending() || level < 1 || level > p->mg.M.n_levels || (size_t)(level - 1) >= p->mg.own.size()) { p->err = "pgo_mg_level_norms: no such level (is a hierarchy installed?)"; return PGO_ERR_INVALID_ARG; }
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
-    const MgLevelDev& A = p->mg_levels[level - 1];
-    const pgo_problem::OwnRange& R = p->mg_own[(size_t)level - 1];
+    const MgLevelDev& A = p->mg.levels[level - 1];
+    const OwnRange& R = p->mg.own[(size_t)level - 1];
     HIPCHK(p, hipStreamSynchronize(p->st));
     auto sq64 = [&](const double* dev, int64_t first, int64_t count, double* out) -> int {
         if (!dev || count <= 0) return PGO_OK;
@@ -3033,7 +1949,7 @@ int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8) {
         long double s = 0.0L; for (float v : h) s += (long double)v * v;
         *out = (double)s; return PGO_OK;
     };
-    const bool sparse = level < p->M.n_levels;
+    const bool sparse = level < p->mg.M.n_levels;
     if ((rc = sq64(A.val, R.blk0 * 36, (R.blk1 - R.blk0) * 36, out8 + 0)) != PGO_OK) return rc;
     if (sparse) {
         if ((rc = sq32(A.valf, R.blk0 * 36, (R.blk1 - R.blk0) * 36, out8 + 1)) != PGO_OK) return rc;
@@ -3048,7 +1964,7 @@ int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8) {
 int pgo_comm_destroy(pgo_problem* p) {
     if (!p) return PGO_ERR_INVALID_ARG;
     p->comm.reset();
-    mg_job_cancel(p); mg_init_drop(p);
+    mg_drop_pending(p);
     p->graph_dirty = true;
     return PGO_OK;
 }
@@ -3126,17 +2042,17 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
     const GraphDev& G = p->G;
     double bytes = 0, best_ms = -1.0;
     if (which == 6 || which == 7 || which == 8) {   // one multigrid-preconditioned PCG iteration (6) / its level kernels alone (7) / the kernels of the multigrid's set-up (8), on the current LM system
-        if (!p->mg_built || !p->built_mf || (p->local_ids && which == 6)) { p->err = "pgo_time_kernel: this graph has no multigrid hierarchy (mg_min_keyframes) / several ranks: only the level kernels (7) can be timed"; return PGO_ERR_STATE; }
+        if (!p->mg.built || !p->built_mf || (p->local_ids && which == 6)) { p->err = "pgo_time_kernel: this graph has no multigrid hierarchy (mg_min_keyframes) / several ranks: only the level kernels (7) can be timed"; return PGO_ERR_STATE; }
         const pgo_options& o = p->opt;
         if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, o.min_lm_diagonal, o.max_lm_diagonal, p->st);
         bool ok = true;
         if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
-        if (!p->mg_active && (rc = build_mg(p)) != PGO_OK) return rc;
-        if (!p->mg_active) { p->err = "pgo_time_kernel: the multigrid operators of this system are not positive definite"; return PGO_ERR_NUMERIC; }
+        if (!p->mg.active && (rc = build_mg(p)) != PGO_OK) return rc;
+        if (!p->mg.active) { p->err = "pgo_time_kernel: the multigrid operators of this system are not positive definite"; return PGO_ERR_NUMERIC; }
         const int g = launch_cg_init_vectors(p->G, p->C, 0, p->st);
         if (p->local_ids) { if ((rc = mg_apply_ranks(p, false)) != PGO_OK) return rc; launch_cg_set_tolerance(p->C, 0.0, p->st); }      // (one full distributed cycle: every level vector holds finite numbers)
         else {
-            launch_mg_apply(p->G, p->C, p->M, p->mg_levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
+            launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
             launch_cg_init_scalars(p->C, g, g, 0.0, p->st);
         }
     }
@@ -3152,7 +2068,7 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
         if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, o.min_lm_diagonal, o.max_lm_diagonal, p->st);
         bool ok = true;
         if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
-        p->mg_active = false; p->coarse_active = false; p->C.extra_rz = 0;   // the timed iteration is the plain block-Jacobi one: no partial-sum slots of a multigrid / two-level solve
+        p->mg.active = false; p->coarse_active = false; p->C.extra_rz = 0;   // the timed iteration is the plain block-Jacobi one: no partial-sum slots of a multigrid / two-level solve
         launch_cg_init(p->G, p->C, 0, 0.0, p->st);
     }
     const double N = (double)G.N, E = (double)(G.rel.E + G.sw.E), Es = (double)G.sw.E;
@@ -3192,31 +2108,31 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
                 case 3: launch_k1(G, p->d_pose[nxt].p, p->d_swv[nxt].p, false, part(p, 5), &np, p->st); bytes = k1_algorithmic_bytes(G, false); break;
                 case 6: case 7: {
                           const int kk = rep == 0 ? 0 : i + 1;
-                          const bool fused = p->M.blk_tab != nullptr;
+                          const bool fused = p->mg.M.blk_tab != nullptr;
                           const bool sr = single_reduction(p);
                           if (which == 6 && sr) {
                               launch_mf_apply_dot_live(G, p->F, p->Sc, p->C, p->st);
-                              if (fused) launch_cg_update_mg_sr(G, p->C, p->M, p->mg_levels, p->K, kk, kk == 0 ? 1 : 0, mf_grid_size(p->F), p->st);
+                              if (fused) launch_cg_update_mg_sr(G, p->C, p->mg.M, p->mg.levels, p->K, kk, kk == 0 ? 1 : 0, mf_grid_size(p->F), p->st);
                               else launch_cg_update_sr(G, p->C, kk, kk == 0 ? 1 : 0, mf_grid_size(p->F), p->st);
                           } else if (which == 6) {
                               launch_mf_spmv(G, p->F, p->Sc, p->C, kk, 0.0, p->st);
-                              if (fused) launch_cg_update_mg(G, p->C, p->M, p->mg_levels, p->K, kk, mf_grid_size(p->F), p->st);
+                              if (fused) launch_cg_update_mg(G, p->C, p->mg.M, p->mg.levels, p->K, kk, mf_grid_size(p->F), p->st);
                               else launch_cg_update(G, p->C, kk, mf_grid_size(p->F), p->st);
                           }
                           if (p->local_ids) {      // several ranks: this rank's share of the cycle's kernels, no exchanges (what its GPU computes per cycle)
-                              launch_mg_apply(G, p->C, p->M, p->mg_levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), nullptr);
-                              bytes = (double)p->mg_blocks_own * 148.0 + (double)p->mg_rows_own * (288.0 + 24.0 + 8.0 * 48.0 + 16.0) + (double)p->K.nc * (double)p->K.nc * 4.0 + (double)p->K.nc * 16.0;
+                              launch_mg_apply(G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), nullptr);
+                              bytes = (double)p->mg.blocks_own * 148.0 + (double)p->mg.rows_own * (288.0 + 24.0 + 8.0 * 48.0 + 16.0) + (double)p->K.nc * (double)p->K.nc * 4.0 + (double)p->K.nc * 16.0;
                               break;
                           }
-                          launch_mg_apply(G, p->C, p->M, p->mg_levels, p->K, sr ? p->C.r : ((kk & 1) ? p->C.r : p->C.r2), p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, mg_scale(p), true, p->st, which == 6 && fused, mg_cs(p), mg_fine_view(p));
+                          launch_mg_apply(G, p->C, p->mg.M, p->mg.levels, p->K, sr ? p->C.r : ((kk & 1) ? p->C.r : p->C.r2), p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, mg_scale(p), true, p->st, which == 6 && fused, mg_cs(p), mg_fine_view(p));
                           // Bytes of this design, each array once per kernel that streams it.  Fine level as in case 2 (+ the restriction's per-keyframe offsets and slot table,
                           // the prolongation's read-modify-write of z, offsets and aggregate index); every sparse coarse level: its fp32 blocks and column indices twice
                           // (down- and up-sweep), Dinv, positions/offsets and its four vectors; the dense level: the fp32 inverse once.
                           const double lanes_rel = (double)(p->mf_pair_lanes + p->mf_rel_side_lanes), lanes_sw = (double)p->mf_sw_lanes;
                           const double fine = lanes_rel * (128.0 + 12.0) + lanes_sw * (128.0 + 12.0 + 8.0) + N * ((sr ? 2.0 : 4.0) * 48.0 + 48.0 + 13.0) + N * ((sr ? 11.0 : 7.0) * 48.0 + 96.0);
                           double cyc = N * (24.0 + 16.0 / 8.0 * 8.0) /* d0 + slot table (restriction) */ + N * (2.0 * 48.0 + 24.0 + 4.0 + 4.0) /* z read + write, d0, agg0, member list (prolongation) */;
-                          for (int l = 0; l + 1 < p->M.n_levels; ++l) {
-                              const MgLevelDev& A = p->mg_levels[l];
+                          for (int l = 0; l + 1 < p->mg.M.n_levels; ++l) {
+                              const MgLevelDev& A = p->mg.levels[l];
                               if (A.smoothed && A.rt_valf)      // explicit transfer operator: the level's own blocks once (smoothing step), R and R^T once each, Dinv once, r / x / y / xf and the level above's r, x
                                   cyc += (double)A.nnzb * (144.0 + 4.0) + 2.0 * (double)A.n_w * (144.0 + 4.0) + (double)A.n * (288.0 + 24.0 + 8.0 * 48.0 + 16.0) + (double)A.n_next * (288.0 + 2.0 * 48.0 + 8.0);
                               else
@@ -3226,13 +2142,8 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
                           bytes = which == 6 ? fine + cyc : cyc;
                           break; }
                 case 8: {     // this rank's kernels of one multigrid set-up (operators of an LM system incl. the dense inverse), without the exchanges between them
-                          const double omega = p->opt.mg_omega > 0.0 && p->opt.mg_omega <= 1.0 ? p->opt.mg_omega : 0.9;
                           const bool hoff_valid = !p->built_mf || p->hoff_epoch == p->lin_epoch;
-                          int32_t* fail = p->d_cinfo.p;
-                          if (p->local_ids && p->mg_first_whole > 0) { if ((rc = build_mg_ranks(p, omega, fail, hoff_valid, true)) != PGO_OK) return rc; }
-                          else if (p->mg_fine) { launch_mg_assemble_fine(p->G, p->L, p->Sc, p->C, p->mg_fineF, p->mg_fineT, p->mg_levels[0], omega, fail, p->st, mg_cs(p), hoff_valid, p->d_pose[p->cur].p); launch_mg_assemble_rest(p->M, p->mg_levels, p->K, omega, fail, p->st, mg_cs(p)); }
-                          else launch_mg_assemble(p->G, p->L, p->Sc, p->C, p->M, p->mg_levels, p->K, omega, fail, p->st, mg_cs(p), hoff_valid);
-                          launch_coarse_invert(p->K, p->d_cscr.p, fail, p->st);
+                          if ((rc = mg_operators(p, p->d_cinfo.p, hoff_valid, true, -1.0)) != PGO_OK) return rc;
                           bytes = 0.0;
                           break; }
                 default: return PGO_ERR_INVALID_ARG;
@@ -3244,7 +2155,7 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
     }
     }
     if (turns > 1 && !p->comm->barrier()) { p->err = "in-process communicator: a rank left during pgo_time_kernel"; return PGO_ERR_COMM; }
-    if (which == 8) { p->mg_active = false; if ((rc = build_mg(p)) != PGO_OK) return rc; }      // (several ranks: the timed kernels ran without their exchanges — the operators are formed again, properly)
+    if (which == 8) { p->mg.active = false; if ((rc = build_mg(p)) != PGO_OK) return rc; }      // (several ranks: the timed kernels ran without their exchanges — the operators are formed again, properly)
     *avg_ms = best_ms / launches;
     if (algorithmic_bytes) *algorithmic_bytes = bytes;
     return PGO_OK;
@@ -3260,7 +2171,7 @@ int pgo_time_vio_odometry_kernel(pgo_problem* p, int32_t f_max, int32_t launches
     for (int64_t u = 0; u < p->n_vio; ++u) for (int f = 1; f <= f_max; ++f) if (u - f >= 0) c.push_back((int32_t)u);
     const int64_t n = (int64_t)c.size();
     for (int64_t u = 0; u < p->n_vio; ++u) for (int f = 1; f <= f_max; ++f) if (u - f >= 0) c.push_back((int32_t)(u - f));
-    ScopedBuf<int32_t> d_c; ScopedBuf<double> d_meas;
+    DBuf<int32_t> d_c; DBuf<double> d_meas;
     HIPCHK(p, d_c.ensure((size_t)2 * n)); HIPCHK(p, d_meas.ensure((size_t)8 * n));
     HIPCHK(p, hipMemcpyAsync(d_c.p, c.data(), (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
     EventPair ev;
@@ -3288,7 +2199,7 @@ int pgo_dense_spd_inverse(pgo_problem* p, int32_t n, const double* a, double* a_
         if (i < n) std::memcpy(&h[(size_t)i * nc], a + (size_t)i * n, (size_t)n * sizeof(double));
         else h[(size_t)i * nc + i] = 1.0;
     }
-    ScopedBuf<double> d_a, d_scr; ScopedBuf<int32_t> d_fail;
+    DBuf<double> d_a, d_scr; DBuf<int32_t> d_fail;
     HIPCHK(p, d_a.ensure((size_t)nc * nc)); HIPCHK(p, d_scr.ensure((size_t)nc * 64 + 4096)); HIPCHK(p, d_fail.ensure(1));
     CoarseDev K{}; K.nc = nc; K.Ac = d_a.p;
     EventPair ev;
@@ -3319,7 +2230,7 @@ int pgo_device_synchronize(pgo_problem* p) {
     if (!p) return PGO_ERR_INVALID_ARG;
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
-    if ((rc = mg_init_finish(p)) != PGO_OK) return rc;      // "everything this handle has in flight": the hierarchy worker of a fresh graph build too
+    if ((rc = mg_fresh_install(p)) != PGO_OK) return rc;      // "everything this handle has in flight": the hierarchy worker of a fresh graph build too
     HIPCHK(p, hipStreamSynchronize(p->st));
     return PGO_OK;
 }

@@ -156,7 +156,7 @@ def test_a_graph_whose_hierarchy_does_not_coarsen_falls_back_to_the_two_level_me
     """One 9 600-keyframe trajectory whose every 8th link is a SWITCHABLE closure instead of an odometry edge: level 1 groups keyframes along odometry edges only (1 200
     aggregates of 8), and above level 1 a SINGLE switchable closure between two aggregates counts for nothing (mg_loop_discount) — the matching stalls, the hierarchy cannot be
     built, although the graph is large enough for the multigrid (mg_min_keyframes_switchable) and, being one long chain, hard for plain block-Jacobi.  One GPU prepares the
-    hierarchy on a worker thread and only learns this where it is first needed (mg_init_finish): from there on the handle must work with the two-level method — what the same
+    hierarchy on a worker thread and only learns this where it is first needed (mg_fresh_install): from there on the handle must work with the two-level method — what the same
     graph gets when the multigrid is switched off — not with plain block-Jacobi for the rest of its life (round-4 advisor finding).  Checked: steps preconditioned by the
     two-level method appear in the log (never the multigrid), and the trajectory is the oracle's (banded exact Cholesky)."""
     rng = np.random.default_rng(12)

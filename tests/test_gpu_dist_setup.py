@@ -1,4 +1,4 @@
-"""GPU: the multigrid's DISTRIBUTED SET-UP (pgo_options.mg_dist_setup = 1, pgo_solver.hip: build_mg_ranks) against the replicated one (= 0: level 1's blocks all-reduced, every
+"""GPU: the multigrid's DISTRIBUTED SET-UP (pgo_options.mg_dist_setup = 1, pgo_multigrid.hip: build_mg_ranks) against the replicated one (= 0: level 1's blocks all-reduced, every
 level above formed by every rank) with in-process ranks on one GPU.  After ONE LM iteration from the same state with the multigrid from the first PCG iteration — one set-up on
 identical inputs — what every rank's cycle kernels read of every level (its rows' fp64 blocks, their fp32 copy, block-Jacobi inverses, R^T, R, the dense inverse:
 pgo_mg_level_norms) agrees to the order of the sums; full solves take the same decisions with the same costs.  (Host side of the same thing, replayed on the CPU:

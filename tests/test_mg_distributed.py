@@ -317,7 +317,7 @@ def exchange_sum(world, plans, arrays):
 
 @pytest.mark.parametrize("world,policy,smoothed,dist_min", [(2, "chain", 1, 64), (4, "spatial", 1, 64), (3, "spatial", 0, 64), (4, "spatial", 2, 32), (8, "spatial", 0, 16), (3, "spatial", 1, 100000)])
 def test_distributed_setup_replayed_with_scalar_blocks(shim, world, policy, smoothed, dist_min):
-    """The distributed SET-UP (pgo_solver.hip: build_mg_ranks) replayed with numpy, every 6x6 block a scalar: each rank holds arrays that are NaN wherever it has not formed or
+    """The distributed SET-UP (pgo_multigrid.hip: build_mg_ranks) replayed with numpy, every 6x6 block a scalar: each rank holds arrays that are NaN wherever it has not formed or
     received a number, forms what libpgo's kernels form on its own rows — level 1 from its own edges and owned keyframes, Dinv, Ps, W, R, the Galerkin products — from exactly the
     entries those kernels read, and exchanges blocks by the plans of pgo_mg_host.hpp: build_setup_plans.  Every entry its cycle kernels read must then equal the single-process
     result: its rows' blocks (and the transposed upper blocks of other owners: the fp32 copy is symmetrised), Dinv on its rows and their halo, R^T on its rows, R on its coarse
