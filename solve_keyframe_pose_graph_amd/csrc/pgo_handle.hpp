@@ -1,10 +1,12 @@
-// pgo_handle.hpp — the problem handle (struct pgo_problem) and what the two host translation units share: pgo_solver.hip (graph build, LM controller, PCG, C-ABI)
-// and pgo_multigrid.hip (the multigrid preconditioner's host lifecycle: hierarchy build, install, regroup, operators of each LM system).  Internal: not installed.
+// pgo_handle.hpp — the problem handle (struct pgo_problem) and what the host translation units share: pgo_solver.hip (graph build, LM controller, C-ABI),
+// pgo_pcg.hip (the two-level method, the preconditioner of each LM system, the PCG driver) and pgo_multigrid.hip (the multigrid preconditioner's host lifecycle:
+// hierarchy build, install, regroup, operators of each LM system).  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <thread>
@@ -15,7 +17,7 @@
 #include "pgo_comm.hpp"
 #include "pgo_mg_host.hpp"
 
-// (what the two translation units share stays inside libpgo: only the C-ABI of pgo.h is exported)
+// (what the translation units share stays inside libpgo: only the C-ABI of pgo.h is exported)
 #pragma GCC visibility push(hidden)
 namespace pgo {
 
@@ -31,6 +33,17 @@ inline bool debug_poison() { static const bool on = []() { const char* e = std::
 // PGO_DEBUG_BREAK_COARSE=1 (read at every operator build so that a test can switch it inside one process): the dense coarse inverse of the two-level method /
 // of the multigrid's coarsest level is applied with the wrong sign — a preconditioner that is not positive definite, i.e. a forced PCG breakdown.
 inline bool debug_break_coarse() { if (!debug_hooks_enabled()) return false; const char* e = std::getenv("PGO_DEBUG_BREAK_COARSE"); return e && e[0] == '1' && e[1] == 0; }
+
+// PGO_DEBUG_GRAPH_AFTER=<n> (read once): the PCG captures its chunk as a hipGraph after n eager iterations instead of 192; values that are not an even number in [2, 10^6] are ignored
+inline int debug_graph_after() {
+    static const int v = []() {
+        const char* e = std::getenv("PGO_DEBUG_GRAPH_AFTER");
+        if (!debug_hooks_enabled() || !e) return 192;
+        char* end = nullptr; const long n = std::strtol(e, &end, 10);
+        return (end && *end == 0 && n >= 2 && n <= 1000000 && (n & 1) == 0) ? (int)n : 192;
+    }();
+    return v;
+}
 
 // a device buffer that owns its memory: grown by ensure(), freed when it goes (the handle's buffers when the handle is deleted, a function's scratch at scope exit)
 template <class T>
@@ -114,6 +127,66 @@ struct MgState {
     bool fresh_pending() const { return job.kind == MgJob::fresh; }
 };
 
+// ---- the two-level preconditioner's state on the handle (pgo_pcg.hip).  The multigrid's dense coarsest level borrows K and its buffers (pgo_multigrid.hip).
+struct CoarseState {
+    DBuf<double> d_ccen, d_cd, d_cAc, d_crc, d_cscr;
+    DBuf<float> d_cAcf;              // the dense inverse rounded to fp32
+    DBuf<int64_t> d_cblk_ptr, d_ccontrib;
+    DBuf<int32_t> d_cblk_ab, d_cagg_free, d_cinfo;
+    CoarseDev K{};
+    bool built = false, active = false;
+    int mode = 0;                    // per solve: 0 not yet compared with plain block-Jacobi, 1 keep, 2 dropped (it did not pay on this graph)
+    int retests = 0; bool skip_all = false; double drop_radius = 0.0;   // dropped at a small radius: one more comparison once the radius reaches coarse_min_radius
+    int backoff = 0, skip = 0;       // a handle that keeps dropping it (incremental triggers on the same kind of graph) retests ever more rarely
+    int keep_streak = 0;             // consecutive solves that kept it: the comparison is then repeated only every 4th solve
+    uint64_t geometry_epoch = 0;     // the linearisation (lin_epoch) the aggregates' centroids were computed at
+};
+
+// the handle's stream.  It goes with the handle, after the PCG's captured graphs and pinned poll buffer (pgo_problem declares it just before PcgState) and before the
+// device buffers: the order in which the handle's resources have always been released
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream&) = delete;
+    OwnedStream& operator=(const OwnedStream&) = delete;
+    ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+
+// ---- the PCG driver's state on the handle (pgo_pcg.hip)
+struct PcgState {
+    // pipelined convergence polling: pinned host copies of {flags[4], scal[4]} for two chunks in flight
+    struct Poll { int32_t flags[4]; double scal[4]; };
+    Poll* poll = nullptr; hipEvent_t poll_ev[2] = {nullptr, nullptr};      // poll[2]: snapshot at the start of a PCG phase (base point of the convergence-rate estimate)
+    // hipGraph of one PCG chunk (launch-bound inner loop); valid for (graph build epoch, tolerance, chunk length, solver)
+    // one captured chunk per preconditioner (0 block-Jacobi, 1 two-level, 2 multigrid): the hybrid policy changes between them inside a solve
+    struct CapturedChunk { hipGraphExec_t exec = nullptr; int len = 0; uint64_t epoch = 0; double scale = 0.0; bool sr = false; };   // scale: mg_correction_scale is a by-value kernel argument of the captured cycle
+    CapturedChunk cg_chunk[3];
+    hipGraphExec_t cg_graph = nullptr;   // the one in use (not owned)
+    uint64_t build_epoch = 1; bool cg_graph_failed = false;
+    double cg_predicted = 0.0;      // block-Jacobi-equivalent iterations predicted for the current LM system (build_system); 0: none
+    double cg_prev_equiv = 0.0, cg_prev_radius = 0.0;   // block-Jacobi-equivalent PCG iterations and radius of the last fully solved LM system of this solve
+    int mg_switch_at = 400;              // in-flight switch point of the current LM system (build_system)
+    int cg_extra = 0;                    // PCG iterations of the current LM step spent before a change of preconditioner
+    bool mg_failed = false;              // the multigrid operators of the current system could not be built
+    bool mg_start_deferred = false;      // the current system is predicted hard, but its multigrid operators are built only once the step has survived the first early-rejection pause
+    PcgState() = default;
+    PcgState(const PcgState&) = delete;
+    PcgState& operator=(const PcgState&) = delete;
+    hipError_t create() {      // pgo_create: the pinned poll buffer and its events
+        hipError_t e = hipHostMalloc((void**)&poll, 3 * sizeof(Poll), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&poll_ev[0], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&poll_ev[1], hipEventDisableTiming);
+        if (e == hipSuccess) std::memset(poll, 0, 3 * sizeof(Poll));
+        return e;
+    }
+    ~PcgState() {
+        for (CapturedChunk& cc : cg_chunk) if (cc.exec) (void)hipGraphExecDestroy(cc.exec);
+        if (poll) (void)hipHostFree(poll);
+        for (hipEvent_t e : poll_ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
 }  // namespace pgo
 #pragma GCC visibility pop
 
@@ -122,7 +195,6 @@ using namespace pgo;
 struct pgo_problem {
     pgo_options opt;
     int device = 0;
-    hipStream_t st = nullptr;
     std::string err;
 
     HostClass rel, swe;
@@ -167,18 +239,8 @@ struct pgo_problem {
     DBuf<double> d_tmp;
     DBuf<double> d_vio;              // raw VIO poses [n_vio][16] (graph construction, K0)
     DBuf<int32_t> d_vio_idx; DBuf<double> d_vio_meas;   // K0's edge endpoints and measurements of one call
-    // two-level preconditioner (CoarseDev)
-    DBuf<double> d_ccen, d_cd, d_cAc, d_crc, d_cscr;
-    DBuf<float> d_cAcf;              // the dense inverse rounded to fp32
-    DBuf<int64_t> d_cblk_ptr, d_ccontrib;
-    DBuf<int32_t> d_cblk_ab, d_cagg_free, d_cinfo;
-    CoarseDev K{};
-    bool coarse_built = false, coarse_active = false;
-    int coarse_mode = 0;             // per solve: 0 not yet compared with plain block-Jacobi, 1 keep, 2 dropped (it did not pay on this graph)
-    int coarse_retests = 0; bool coarse_skip_all = false; double coarse_drop_radius = 0.0;   // dropped at a small radius: one more comparison once the radius reaches coarse_min_radius
-    int coarse_backoff = 0, coarse_skip = 0;   // a handle that keeps dropping it (incremental triggers on the same kind of graph) retests ever more rarely
-    int coarse_keep_streak = 0;      // consecutive solves that kept it: the comparison is then repeated only every 4th solve
-    uint64_t coarse_geometry_epoch = 0, lin_epoch = 0;   // lin_epoch counts linearisations (the centroids follow the poses)
+    CoarseState coarse;                    // the two-level preconditioner (pgo_pcg.hip)
+    uint64_t lin_epoch = 0;                // counts linearisations (the two-level method's centroids follow the poses)
     MgState mg;                            // the aggregation multigrid (pgo_multigrid.hip)
     uint64_t hoff_epoch = 0;               // linearisation whose J1^T J2 blocks L.Hoff holds (matrix-free solver: formed on demand for the multigrid's level-1 product)
     int64_t n_vio = 0;
@@ -216,23 +278,9 @@ struct pgo_problem {
     int rank() const { return comm ? comm->rank() : 0; }
     int world() const { return comm ? comm->world() : 1; }
 
-    // pipelined convergence polling: pinned host copies of {flags[4], scal[4]} for two chunks in flight
-    struct Poll { int32_t flags[4]; double scal[4]; };
-    Poll* poll = nullptr; hipEvent_t poll_ev[2] = {nullptr, nullptr};      // poll[2]: snapshot at the start of a PCG phase (base point of the convergence-rate estimate)
-
-    // hipGraph of one PCG chunk (launch-bound inner loop); valid for (graph build epoch, tolerance, chunk length, solver)
-    // one captured chunk per preconditioner (0 block-Jacobi, 1 two-level, 2 multigrid): the hybrid policy changes between them inside a solve
-    struct CapturedChunk { hipGraphExec_t exec = nullptr; int len = 0; uint64_t epoch = 0; double scale = 0.0; bool sr = false; };   // scale: mg_correction_scale is a by-value kernel argument of the captured cycle
-    CapturedChunk cg_chunk[3];
-    hipGraphExec_t cg_graph = nullptr;   // the one in use (not owned)
-    uint64_t build_epoch = 1; bool cg_graph_failed = false;
-    double cg_predicted = 0.0;      // block-Jacobi-equivalent iterations predicted for the current LM system (build_system); 0: none
-    double cg_prev_equiv = 0.0, cg_prev_radius = 0.0;   // block-Jacobi-equivalent PCG iterations and radius of the last fully solved LM system of this solve
-    int mg_switch_at = 400;              // in-flight switch point of the current LM system (build_system)
-    int cg_extra = 0;                    // PCG iterations of the current LM step spent before a change of preconditioner
-    bool mg_failed = false;              // the multigrid operators of the current system could not be built
+    OwnedStream st;                      // (declared here: released after pcg, before everything above)
+    PcgState pcg;                        // the PCG driver (pgo_pcg.hip)
     double last_rho = 1.0;               // relative decrease of the last accepted step of this solve
-    bool mg_start_deferred = false;      // the current system is predicted hard, but its multigrid operators are built only once the step has survived the first early-rejection pause
 };
 
 
@@ -244,11 +292,41 @@ namespace pgo {
 // ---- pgo_solver.hip: the collectives (no-ops without a communicator) and what a graph without a hierarchy preconditions with
 int allreduce(pgo_problem* p, double* buf, size_t n, int op /*0 sum, 2 max*/);
 int host_allreduce(pgo_problem* p, std::vector<double>& v, int op);
+int exchange_rows(pgo_problem* p, double* a1, int k1, double* a2, int k2, const int32_t* stop = nullptr);
 int exchange_level(pgo_problem* p, int l, double* v1, double* v2, const int32_t* stop, const double* dinv);
 int exchange_blocks_copy(pgo_problem* p, const pgo_mg::ExchangePlan& X, const int32_t* send_idx, const int32_t* recv_idx, double* arr, int K);
 int exchange_blocks_sum(pgo_problem* p, const pgo_mg::BlockPlan& B, const SetupPlanDev& D, double* arr);
 int ensure_exchange_buffers(pgo_problem* p);
+
+// ---- pgo_pcg.hip: the two-level method, the preconditioner of each LM system, the PCG driver
 int build_two_level_aggregates(pgo_problem* p);
+void two_level_solve_begin(pgo_problem* p);
+void two_level_solve_end(pgo_problem* p);
+int build_system(pgo_problem* p, bool* ok);
+bool single_reduction(const pgo_problem* p);
+// The form of a PCG iteration: its recurrence, and what follows the vector update.  Chosen once per PCG phase (choose_form), again where the in-flight switch installs the multigrid.
+struct PcgForm {
+    enum Rec { ranks, sr, sr_coarse, classic_mf, classic_csr, classic_coarse };   // several ranks (Chronopoulos-Gear), single-reduction [+ fused two-level], classic [+ fused two-level]
+    enum Post { none, mg_cycle, mg_restricted, two_level };                        // the multigrid cycle (restriction inside the update or not), the unfused two-level correction
+    Rec rec; Post post;
+    int fused_parts;                     // the fused two-level method: the update kernel's r.z partial slots (the dense solve's C.extra_rz follow them)
+    bool single_red() const { return rec == sr || rec == sr_coarse; }
+    bool fused_coarse() const { return rec == sr_coarse || rec == classic_coarse; }
+    bool mg() const { return post == mg_cycle || post == mg_restricted; }
+    int precond() const { return mg() ? 2 : (fused_coarse() || post == two_level) ? 1 : 0; }      // 0 block-Jacobi, 1 two-level, 2 multigrid
+};
+PcgForm choose_form(const pgo_problem* p, bool this_rank_only = false);      // this_rank_only: the rank's own iteration, without exchanges (pgo_time_kernel)
+void pcg_matvec(pgo_problem* p, const PcgForm& f, int k, double tol2);
+int pcg_update(pgo_problem* p, const PcgForm& f, int k);
+int pcg_precond(pgo_problem* p, const PcgForm& f, int k);
+int pcg_iteration(pgo_problem* p, const PcgForm& f, int k, double tol2);
+int pcg_start(pgo_problem* p, const PcgForm& f, bool warm, double tol2);
+struct CgResult { int iterations; bool breakdown; double rel_residual; bool converged; };
+// one PCG phase: up to tol (relative); resume >= 0 continues the stopped PCG at that iteration index (device state x, r, z, p and the partial sums are those of `resume`
+// completed iterations); warm: start from the previous solution; switch_now: the multigrid takes over from the iterate a pause left; max_iterations 0: opt.cg_max_iterations
+struct PcgPhase { double tol; int resume = -1; bool warm = false; bool switch_now = false; int max_iterations = 0; };
+int run_pcg(pgo_problem* p, CgResult* res, const PcgPhase& ph);
+int finish_system(pgo_problem* p, CgResult* cg, bool evaluated, int* precond_used);
 
 // ---- pgo_multigrid.hip
 bool wants_multigrid(const pgo_problem* p);

@@ -419,7 +419,7 @@ int mg_prepare_impl(pgo_problem* p, const double* sw_now, MgPrepared& Q) {
 // what a new hierarchy replaces: the installed one, and the two-level method (the multigrid replaces it on the graphs that have one)
 void mg_reset(pgo_problem* p) {
     MgState& m = p->mg;
-    p->coarse_built = false; p->coarse_active = false; p->K = CoarseDev{};
+    p->coarse.built = false; p->coarse.active = false; p->coarse.K = CoarseDev{};
     m.built = false; m.active = false; m.M = MgDev{}; m.geometry_epoch = 0; m.lvl_plan.clear(); m.su_plan.clear(); m.first_whole = 0; m.own.clear();
 }
 
@@ -434,11 +434,11 @@ int mg_install(pgo_problem* p, MgPrepared& Q) {
     const int n_top = H.L[nl - 1].n;
     const int nc = (6 * n_top + 63) / 64 * 64;
     HIPCHK(p, m.i32.ensure(std::max<size_t>(Q.pi32.size(), 1))); HIPCHK(p, m.i64.ensure(std::max<size_t>(Q.pi64.size(), 1))); HIPCHK(p, m.f64.ensure(std::max<size_t>(Q.nf64, 2)));
-    HIPCHK(p, p->d_cAc.ensure((size_t)nc * nc)); HIPCHK(p, p->d_cAcf.ensure((size_t)nc * nc)); HIPCHK(p, p->d_crc.ensure((size_t)nc * 2)); HIPCHK(p, p->d_cscr.ensure((size_t)nc * 64 + 4096)); HIPCHK(p, p->d_cinfo.ensure(4));
+    HIPCHK(p, p->coarse.d_cAc.ensure((size_t)nc * nc)); HIPCHK(p, p->coarse.d_cAcf.ensure((size_t)nc * nc)); HIPCHK(p, p->coarse.d_crc.ensure((size_t)nc * 2)); HIPCHK(p, p->coarse.d_cscr.ensure((size_t)nc * 64 + 4096)); HIPCHK(p, p->coarse.d_cinfo.ensure(4));
     HIPCHK(p, hipMemcpyAsync(m.i32.p, Q.pi32.data(), Q.pi32.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
     HIPCHK(p, hipMemcpyAsync(m.i64.p, Q.pi64.data(), Q.pi64.size() * sizeof(int64_t), hipMemcpyHostToDevice, p->st));
     HIPCHK(p, hipMemsetAsync(m.f64.p, 0, Q.nf64 * sizeof(double), p->st));
-    HIPCHK(p, hipMemsetAsync(p->d_crc.p, 0, (size_t)nc * 2 * sizeof(double), p->st));
+    HIPCHK(p, hipMemsetAsync(p->coarse.d_crc.p, 0, (size_t)nc * 2 * sizeof(double), p->st));
     char* const base[3] = {reinterpret_cast<char*>(m.i32.p), reinterpret_cast<char*>(m.i64.p), reinterpret_cast<char*>(m.f64.p)};
     const size_t elem[3] = {sizeof(int32_t), sizeof(int64_t), sizeof(double)};
     for (const MgPrepared::Reloc& r : Q.reloc) { void* at = base[r.pool] + r.off * elem[r.pool]; std::memcpy(r.field, &at, sizeof(at)); }
@@ -450,7 +450,7 @@ int mg_install(pgo_problem* p, MgPrepared& Q) {
     m.dist.swap(Q.dist); m.own.swap(Q.own);
     m.levels_distributed = Q.levels_distributed; m.rows_total = Q.rows_total; m.rows_own = Q.rows_own; m.blocks_total = Q.blocks_total; m.blocks_own = Q.blocks_own;
     // the dense coarsest level shares the buffers of the two-level preconditioner, which the multigrid replaces on this graph
-    p->K.n_agg = n_top; p->K.nc = nc; p->K.Ac = p->d_cAc.p; p->K.Acf = p->d_cAcf.p; p->K.rc = p->d_crc.p; p->K.yc = p->d_crc.p + nc;
+    p->coarse.K.n_agg = n_top; p->coarse.K.nc = nc; p->coarse.K.Ac = p->coarse.d_cAc.p; p->coarse.K.Acf = p->coarse.d_cAcf.p; p->coarse.K.rc = p->coarse.d_crc.p; p->coarse.K.yc = p->coarse.d_crc.p + nc;
     m.built = true;
     m.sw_built.swap(Q.sw_built);
     if (p->opt.verbosity > 0) {
@@ -549,7 +549,7 @@ int mg_fresh_install(pgo_problem* p) {
         const int rc_worker = p->mg.job.rc != PGO_OK ? p->mg.job.rc : PGO_ERR_STATE;
         HIPCHK(p, hipStreamSynchronize(p->st));
         const int rc2 = build_two_level_aggregates(p);
-        ++p->build_epoch;
+        ++p->pcg.build_epoch;
         return rc2 != PGO_OK ? rc2 : rc_worker;
     }
     const double waited = (now_s() - t0) * 1e3;
@@ -558,7 +558,7 @@ int mg_fresh_install(pgo_problem* p) {
     if ((rc = mg_install(p, *Q)) != PGO_OK) return rc;
     // a hierarchy that does not coarsen: the graph falls back to the two-level method — exactly what build_graph's synchronous path (several ranks) gives the same graph
     if (!p->mg.built && (rc = build_two_level_aggregates(p)) != PGO_OK) return rc;
-    ++p->build_epoch;
+    ++p->pcg.build_epoch;
     if (p->opt.verbosity > 1) std::fprintf(stderr, "[pgo] multigrid: hierarchy of the new graph installed at its first use: host half %.2f ms on a worker thread, waited %.2f ms, installed in %.2f ms%s\n",
                                            Q->host_ms, waited, (now_s() - t0) * 1e3 - waited, p->mg.built ? "" : " — it does not coarsen: the two-level method on this graph");
     p->mg.job.old = std::move(Q);
@@ -589,7 +589,7 @@ bool mg_exchange_at(pgo_problem* p, int point, int lv, int* plan, double** v1, d
     *v1 = nullptr; *v2 = nullptr; *plan = -1; *dinv = nullptr;
     if (p->world() <= 1 || p->mg.lvl_plan.empty()) return false;
     if (point == 0) {
-        if (lv == nl) { if (nl == 1 || dist(nl - 1)) { *plan = nl - 1; *v1 = p->K.rc; return true; } return false; }
+        if (lv == nl) { if (nl == 1 || dist(nl - 1)) { *plan = nl - 1; *v1 = p->coarse.K.rc; return true; } return false; }
         MgLevelDev& A = p->mg.levels[lv - 1];
         if (dist(lv)) { *plan = lv - 1; *v1 = A.x; if (expl(lv)) { *v2 = A.r; *dinv = A.Dinv; } return true; }
         if (lv == 1 || dist(lv - 1)) { *plan = lv - 1; *v1 = A.x; *v2 = A.r; *dinv = A.Dinv; return true; }
@@ -616,7 +616,7 @@ int mg_apply_ranks(pgo_problem* p, bool inside_iteration) {
     MgHookCtx hc{p, inside_iteration ? p->C.flags : nullptr};
     MgExchangeHook hook{&hc, mg_exchange_hook};
     int hrc = PGO_OK;
-    launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), inside_iteration, p->st, false, mg_cs(p), nullptr, &hook, &hrc);
+    launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->coarse.K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), inside_iteration, p->st, false, mg_cs(p), nullptr, &hook, &hrc);
     return hrc;
 }
 
@@ -649,7 +649,7 @@ static int regroup_commit(pgo_problem* p, MgPrepared& Q) {
     int rc;
     HIPCHK(p, hipStreamSynchronize(p->st));
     if ((rc = mg_install(p, Q)) != PGO_OK) return rc;
-    ++p->build_epoch;      // captured PCG chunks hold pointers into the old pools
+    ++p->pcg.build_epoch;      // captured PCG chunks hold pointers into the old pools
     return PGO_OK;
 }
 int regroup_if_moved(pgo_problem* p, const double* sv /* host: the caller's switch array */, bool in_solve) {
@@ -782,9 +782,9 @@ int mg_operators(pgo_problem* p, int32_t* fail, bool hoff_valid, bool kernels_on
         if (p->local_ids && m.first_whole > 0) { if ((rc = build_mg_ranks(p, omega, fail, kernels_only)) != PGO_OK) return rc; }
         else if (p->local_ids && !kernels_only && (rc = allreduce(p, m.levels[0].val, (size_t)m.levels[0].nnzb * 36, 0)) != PGO_OK) return rc;
     }
-    launch_mg_assemble_rest(m.M, m.levels, p->K, omega, fail, p->st, mg_cs(p), m.first_whole);
+    launch_mg_assemble_rest(m.M, m.levels, p->coarse.K, omega, fail, p->st, mg_cs(p), m.first_whole);
     if ((rc = stage("level operators")) != PGO_OK) return rc;
-    launch_coarse_invert(p->K, p->d_cscr.p, fail, p->st);
+    launch_coarse_invert(p->coarse.K, p->coarse.d_cscr.p, fail, p->st);
     return PGO_OK;
 }
 
@@ -808,7 +808,7 @@ int build_mg(pgo_problem* p) {
         } else launch_mg_geometry(p->G, m.M, m.levels, p->d_pose[p->cur].p, p->st);
         m.geometry_epoch = p->lin_epoch;
     }
-    int32_t* fail = p->d_cinfo.p;
+    int32_t* fail = p->coarse.d_cinfo.p;
     HIPCHK(p, hipMemsetAsync(fail, 0, sizeof(int32_t), p->st));
     // level 1's Galerkin product reads J1^T J2 of every edge: the block-CSR solver has them from K2; under the matrix-free solver they are formed here, once per linearisation
     // that builds multigrid operators (an edge-parallel pass whose Jacobian loads coalesce, ~60 us on C3 — the wavefront-per-block product gathering K1's Jacobians itself,
@@ -819,7 +819,7 @@ int build_mg(pgo_problem* p) {
         hoff_valid = true;
     }
     if ((rc = mg_operators(p, fail, hoff_valid, false, t_build0)) != PGO_OK) return rc;
-    if (debug_break_coarse()) launch_coarse_negate(p->K, p->st);
+    if (debug_break_coarse()) launch_coarse_negate(p->coarse.K, p->st);
     int32_t h = 1;
     HIPCHK(p, hipMemcpyAsync(&h, fail, sizeof(h), hipMemcpyDeviceToHost, p->st));
     HIPCHK(p, hipStreamSynchronize(p->st));

@@ -1,5 +1,5 @@
 // pgo_solver.hip — host side of libpgo: persistent problem, device graph construction, the Ceres-compatible
-// Levenberg-Marquardt trust-region controller, PCG driver, optional RCCL edge sharding, and the C-ABI (include/pgo.h).
+// Levenberg-Marquardt trust-region controller (its PCG: pgo_pcg.hip), optional RCCL edge sharding, and the C-ABI (include/pgo.h).
 //
 // What it replaces in the reference: the `ceres::Problem` bookkeeping calls of
 // PoseGraphSLAM::reinit_ceres_problem_onnewloopedge_optimize6DOF (src/PoseGraphSLAM.cpp:1340-1367,1550-1556,
@@ -19,17 +19,6 @@
 #include "pgo_handle.hpp"
 
 namespace {
-
-// PGO_DEBUG_GRAPH_AFTER=<n> (read once): the PCG captures its chunk as a hipGraph after n eager iterations instead of 192; values that are not an even number in [2, 10^6] are ignored
-int debug_graph_after() {
-    static const int v = []() {
-        const char* e = std::getenv("PGO_DEBUG_GRAPH_AFTER");
-        if (!debug_hooks_enabled() || !e) return 192;
-        char* end = nullptr; const long n = std::strtol(e, &end, 10);
-        return (end && *end == 0 && n >= 2 && n <= 1000000 && (n & 1) == 0) ? (int)n : 192;
-    }();
-    return v;
-}
 
 // scalar slots
 enum { S_COST = 0, S_PRIOR_COST = 1, S_MODEL = 2, S_SW_STEP2 = 3, S_SW_XNORM2 = 4, S_GMAX = 5, S_STEP2 = 6, S_XNORM2 = 7, S_N = 8 };
@@ -101,66 +90,6 @@ int ensure_exchange_buffers(pgo_problem* p) {
         for (const pgo_mg::ExchangePlan& X : p->mg.setup.rv) { ns = std::max(ns, (size_t)X.n_send() * 18); nr = std::max(nr, (size_t)X.n_recv() * 18); }
     }
     HIPCHK(p, p->d_xsend[0].ensure(ns + 64)); HIPCHK(p, p->d_xsend[1].ensure(ns + 64)); HIPCHK(p, p->d_xrecv.ensure(nr + 64)); HIPCHK(p, p->d_xscal.ensure(16));
-    return PGO_OK;
-}
-
-
-// The two-level method's aggregates (consecutive keyframes) and the contribution lists of its dense coarse operator, for the graph as built: what a graph WITHOUT a multigrid
-// hierarchy preconditions with.  Called by build_graph, and by mg_fresh_install when the hierarchy a worker thread prepared turns out not to coarsen (the synchronous path —
-// several ranks — decides that inside build_graph; one GPU only learns it where the hierarchy is first needed: both end up with the same preconditioner).
-int build_two_level_aggregates(pgo_problem* p) {
-    const int64_t N = p->N, Er = p->rel.size(), Es = p->swe.size();
-    const int32_t* g2l = p->local_ids ? p->g2l.data() : nullptr;
-    auto L = [g2l](int32_t g) -> int32_t { return g2l ? g2l[g] : g; };
-    int n_agg = p->opt.coarse_aggregates;
-    // a graph with no more keyframes than `half` (256 by default) gets one aggregate per keyframe: the coarse operator IS the reduced system and the "preconditioner"
-    // its dense inverse (a direct solve; the PCG around it only refines); larger graphs: at least 8 keyframes per aggregate, but not fewer than `half` aggregates — the
-    // dense inverse (cubic in the aggregates) is what small graphs pay for (scripts/gpu_small_graphs.py) — and at most coarse_aggregates (768: measured on
-    // chain-like session graphs of 6 000 - 23 000 keyframes, scripts/gpu_session_aggregates.py: 768 beats 512 by 3 - 45 %, 1024 and 1536 lose to the cubic inverse)
-    const int half = std::min(n_agg / 2, 256);
-    if (N <= half) n_agg = (int)N;
-    else n_agg = (int)std::min<int64_t>(n_agg, std::max<int64_t>(N / 8, half));
-    if (n_agg >= 2 && !p->local_ids && (N + n_agg - 1) / n_agg <= 1024) {    // aggregates of thousands of keyframes are never used (build_coarse)
-        const int m = (int)((N + n_agg - 1) / n_agg);
-        n_agg = (int)((N + m - 1) / m);
-        std::vector<int32_t> agg_free((size_t)n_agg, 0);
-        for (int64_t n = 0; n < N; ++n) if (p->h_node_free[n]) agg_free[n / m]++;
-        // (block key, entry) pairs; key = a * n_agg + b with a <= b
-        std::vector<std::pair<int64_t, int64_t>> ent;
-        ent.reserve((size_t)N + 2 * (size_t)(Er + Es));
-        for (int64_t n = 0; n < N; ++n) if (p->h_node_free[n]) ent.push_back({(int64_t)(n / m) * n_agg + n / m, (n << 3) | 0});
-        auto edge = [&](int64_t e, int32_t c1, int32_t c2, int kind_fwd) {
-            if (!p->h_node_free[c1] || !p->h_node_free[c2]) return;       // rows and columns of fixed keyframes are not part of the system
-            const int64_t a = c1 / m, b = c2 / m;
-            if (a < b) ent.push_back({a * n_agg + b, (e << 3) | kind_fwd});
-            else if (a > b) ent.push_back({b * n_agg + a, (e << 3) | (kind_fwd + 1)});
-            else { ent.push_back({a * n_agg + a, (e << 3) | kind_fwd}); ent.push_back({a * n_agg + a, (e << 3) | (kind_fwd + 1)}); }
-        };
-        for (int64_t e = 0; e < Er; ++e) edge(e, L(p->rel.c1[e]), L(p->rel.c2[e]), 1);
-        for (int64_t e = 0; e < Es; ++e) edge(e, L(p->swe.c1[e]), L(p->swe.c2[e]), 3);
-        for (int a = 0; a < n_agg; ++a) if (agg_free[a] == 0) ent.push_back({(int64_t)a * n_agg + a, -1});   // identity block: listed, no contribution
-        std::stable_sort(ent.begin(), ent.end(), [](const std::pair<int64_t, int64_t>& x, const std::pair<int64_t, int64_t>& y) { return x.first < y.first; });
-        std::vector<int64_t> blk_ptr, contrib;
-        std::vector<int32_t> blk_ab;
-        int64_t prev = -1;
-        for (const auto& kv : ent) {
-            if (kv.first != prev) { blk_ptr.push_back((int64_t)contrib.size()); blk_ab.push_back((int32_t)(kv.first / n_agg)); blk_ab.push_back((int32_t)(kv.first % n_agg)); prev = kv.first; }
-            if (kv.second >= 0) contrib.push_back(kv.second);
-        }
-        blk_ptr.push_back((int64_t)contrib.size());
-        const int n_blk = (int)blk_ab.size() / 2;
-        const int nc = (6 * n_agg + 63) / 64 * 64;      // padded with a decoupled identity block (the dense kernels work on 64-wide tiles)
-        HIPCHK(p, p->d_ccen.ensure((size_t)n_agg * 3)); HIPCHK(p, p->d_cd.ensure((size_t)N * 3)); HIPCHK(p, p->d_cAc.ensure((size_t)nc * nc)); HIPCHK(p, p->d_cAcf.ensure((size_t)nc * nc));
-        HIPCHK(p, p->d_crc.ensure((size_t)nc * 2)); HIPCHK(p, p->d_cscr.ensure((size_t)nc * 64 + 4096)); HIPCHK(p, hipMemsetAsync(p->d_crc.p, 0, (size_t)nc * 2 * sizeof(double), p->st)); HIPCHK(p, p->d_cblk_ptr.ensure(blk_ptr.size())); HIPCHK(p, p->d_ccontrib.ensure(std::max<size_t>(contrib.size(), 1)));
-        HIPCHK(p, p->d_cblk_ab.ensure(blk_ab.size())); HIPCHK(p, p->d_cagg_free.ensure(n_agg)); HIPCHK(p, p->d_cinfo.ensure(4));
-        HIPCHK(p, hipMemcpyAsync(p->d_cblk_ptr.p, blk_ptr.data(), blk_ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, p->st));
-        if (!contrib.empty()) HIPCHK(p, hipMemcpyAsync(p->d_ccontrib.p, contrib.data(), contrib.size() * sizeof(int64_t), hipMemcpyHostToDevice, p->st));
-        HIPCHK(p, hipMemcpyAsync(p->d_cblk_ab.p, blk_ab.data(), blk_ab.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
-        HIPCHK(p, hipMemcpyAsync(p->d_cagg_free.p, agg_free.data(), n_agg * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
-        HIPCHK(p, hipStreamSynchronize(p->st));
-        p->K = CoarseDev{n_agg, nc, m, n_blk, p->d_ccen.p, p->d_cd.p, p->d_cAc.p, p->d_crc.p, p->d_crc.p + nc, p->d_cblk_ptr.p, p->d_cblk_ab.p, p->d_ccontrib.p, p->d_cagg_free.p, p->d_cAcf.p};
-        p->coarse_built = true;
-    }
     return PGO_OK;
 }
 
@@ -479,7 +408,7 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
     phase("two-level aggregates");
     mg_guard.committed = true;
     p->graph_dirty = false; p->priors_dirty = false;
-    ++p->build_epoch;   // invalidates the captured PCG graph (kernel arguments hold device pointers / sizes)
+    ++p->pcg.build_epoch;   // invalidates the captured PCG graph (kernel arguments hold device pointers / sizes)
     return PGO_OK;
 }
 
@@ -515,7 +444,7 @@ static int neighbor_exchange(pgo_problem* p, const pgo_mg::ExchangePlan& X, int 
 // Multi-GPU exchange of the keyframes' rows: sums, over the ranks sharing them, the rows of one or two keyframe-indexed device arrays (k1 + k2 doubles per keyframe).  Every rank
 // sends its partial rows of the keyframes it shares with a peer to that peer and adds what it receives in ascending rank order (pgo_mg_host.hpp: build_fine_plan): all ranks
 // end up with the same bits.  Keyframes touched by a single rank never travel.  `stop` (device flag): a stopped PCG sends zeros and keeps its rows.
-static int exchange_rows(pgo_problem* p, double* a1, int k1, double* a2, int k2, const int32_t* stop = nullptr) {
+int exchange_rows(pgo_problem* p, double* a1, int k1, double* a2, int k2, const int32_t* stop) {
     if (!p->local_ids) return PGO_OK;
     const pgo_mg::FinePlan& F = p->fine_plan;
     return neighbor_exchange(p, F.x, k1 + k2, [&](double* sb) { launch_gather_rows(sb, a1, k1, a2, k2, F.x.n_send(), p->d_fp_send.p, stop, p->st); },
@@ -643,409 +572,6 @@ int linearize(pgo_problem* p, double* cost_out) {
     return PGO_OK;
 }
 
-
-struct CgResult { int iterations; bool breakdown; double rel_residual; bool converged; };
-
-
-
-// One GPU, matrix-free matvec, tolerance not below 1e-11: the PCG runs in its single-reduction (Chronopoulos-Gear) form — matvec w = A u with the partials of u.w, then ONE
-// vector kernel whose head re-reduces u.w and r.u together (pgo_kernels.hip: sr_head).  Decided by the options alone, so every phase of a paused PCG runs the same form.
-// The two-level method: its FUSED three-kernel iteration has a single-reduction form of its own (launch_mf_apply_dot_live_coarse + launch_cg_update_restrict_sr) and runs it under the
-// same gates (tolerance >= 1e-11, <= 150 000 keyframes); only its unfused form — aggregates too large for the update kernel's groups — stays classic.
-bool single_reduction(const pgo_problem* p) {
-    // (the two-level method: only its fused three-kernel iteration has a single-reduction form; its unfused form — aggregates too large for the update kernel's groups — stays classic)
-    const bool two_level = p->coarse_active && !p->mg.active;
-    // ... and only where the iteration is latency-bound: the form trades one partial-sum head (~4.5 us) for 96 more bytes per keyframe and iteration, which costs more than the
-    // head from ~130 000 keyframes on — measured +1.4 % on C3 (100k) and +2...+7 % on 12k-60k-keyframe graphs, but -1.2 % on C4 (200k) and -1.7 % on C5 (1M)
-    // (profiles/r05_single_reduction_graph_types.txt, r05_option_ab_c4_c5.txt)
-    constexpr int64_t SINGLE_REDUCTION_MAX_KEYFRAMES = 150000;
-    return p->opt.cg_single_reduction != 0 && !p->local_ids && p->built_mf && p->opt.cg_rel_tolerance >= 1e-11 && p->N_global <= SINGLE_REDUCTION_MAX_KEYFRAMES &&
-           (!two_level || coarse_group_keyframes(p->K) > 0);
-}
-
-// rel_tol: relative tolerance of this phase.  resume_from >= 0: continue the stopped PCG at that iteration index with the new tolerance
-// (device state x, r, z, p and the partial sums are those of `resume_from` completed iterations).
-int run_pcg(pgo_problem* p, CgResult* res, bool warm, double rel_tol, int resume_from, bool switch_now = false) {
-    const pgo_options& o = p->opt;
-    int rc0;
-    const double tol2 = rel_tol * rel_tol;
-    if (resume_from >= 0) {
-        launch_cg_set_tolerance(p->C, tol2, p->st);
-    } else if (warm) {
-        // after a rejected step the system keeps H and only the damping grows: start from the previous solution (q = A x first)
-        if (p->built_mf) launch_mf_apply(p->G, p->F, p->Sc, p->C, p->C.x, p->C.q, p->st);
-        else launch_apply_operator(p->G, p->C, p->C.x, p->C.q, p->st);
-        if ((rc0 = exchange_rows(p, p->C.q, 6, nullptr, 0)) != PGO_OK) return rc0;
-    }
-    // Multi-GPU: the PCG runs in Chronopoulos-Gear form (pgo_kernels.hip): both dot products of an iteration — gamma = r.u (owner-weighted partials of the previous update) and
-    // delta = u.A u (rank-local partials) — are known right after the matvec: ONE 2-double all-reduce per iteration, beside the neighbour exchange of the shared rows of w = A u.
-    const bool multi = p->local_ids;
-    // two-level preconditioner in three kernels per iteration (prolongation inside the matvec, restriction inside the update, r.(P y) from the dense solve):
-    // the update kernel's r.z partials take `fused_parts` slots, the solve's C.extra_rz slots behind them
-    const bool fused_coarse = !multi && p->coarse_active && !p->mg.active && p->built_mf && coarse_group_keyframes(p->K) > 0;
-    const int fused_parts = fused_coarse ? coarse_update_grid(p->G, p->K) : 0;
-    if (fused_coarse) p->C.extra_rz = coarse_solve_grid(p->K);
-    else if (!p->mg.active) p->C.extra_rz = 0;
-    // several ranks, PCG start: r = b (- A x), u = M^-1 r, p = s = 0; part_rz <- owner-weighted partials of gamma_0 (summed over ranks with the first iteration's scalars),
-    // part_pq <- partials of b.D^-1 b, summed over ranks here once: the reference norm of the stopping test.  With the multigrid: the distributed cycle (mg_apply_ranks).
-    auto start_multi = [&](int warm_i) -> int {
-        int rcs;
-        const int g = launch_cg_init_vectors(p->G, p->C, warm_i, p->st);
-        if (p->mg.active && (rcs = mg_apply_ranks(p, false)) != PGO_OK) return rcs;      // z += P0 V(P0^T r): the restriction covers the rank's own aggregates (all their keyframes are local)
-        double* bb = p->C.scal + 12;
-        launch_reduce(p->C.part_pq, g, 0, bb, p->st);
-        if ((rcs = allreduce(p, bb, 1, 0)) != PGO_OK) return rcs;
-        launch_cgcg_scalars_init(p->C, bb, tol2, p->st);
-        return PGO_OK;
-    };
-    if (resume_from < 0) {
-        if (!multi && (p->coarse_active || p->mg.active)) {
-            // z = D^-1 r + P Ac^-1 P^T r (or the multigrid cycle): the coarse term is added to z and to the r.z partials before the scalars are formed
-            int g = launch_cg_init_vectors(p->G, p->C, warm ? 1 : 0, p->st);
-            const int g_bb = g;      // the slots of part_pq that hold the partials of b.D^-1 b
-            if (p->mg.active) launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
-            else launch_coarse_apply(p->G, p->C, p->K, p->C.r, p->C.z, p->C.part_rz, false, p->st);
-            if (fused_coarse) {    // z is complete here: the slots the fused kernels will use beyond the start-up kernels' stay zero for this parity
-                HIPCHK(p, hipMemsetAsync(p->C.part_rz + g, 0, (size_t)(fused_parts + p->C.extra_rz - g) * sizeof(double), p->st));
-                g = fused_parts;
-            }
-            launch_cg_init_scalars(p->C, g, g_bb, tol2, p->st);
-        } else if (!multi) launch_cg_init(p->G, p->C, warm ? 1 : 0, tol2, p->st);
-        else if ((rc0 = start_multi(warm ? 1 : 0)) != PGO_OK) return rc0;
-    }
-    int k = resume_from >= 0 ? resume_from : 0;
-    int32_t hflags[3] = {0, 0, 0};
-    double hscal[3] = {0, 0, 0};
-    int every = 2;
-    auto chunk_length = [&]() {
-        int e = std::max(2, o.cg_check_every) & ~1;   // even: the r/p ping-pong parity repeats from chunk to chunk
-        // captured chunks stay at <= 72 kernel nodes (rocprofv3 7.2 crashes while a graph of 120 nodes is captured under --kernel-trace; 80 are fine): five kernels
-        // per iteration with the coarse space in its unfused form -> 12 iterations, three in the fused form -> 24
-        if (p->coarse_active && !multi) e = std::min(e, fused_coarse ? 24 : 12);
-        int n_sm = 0;
-        for (int l = 0; l < p->mg.M.n_levels; ++l) n_sm += (p->mg.levels[l].smoothed && !p->mg.levels[l].rt_valf) ? 1 : 0;      // two more kernels per cycle for every level whose smoothed prolongator is applied implicitly (none with the explicit transfer operator)
-        if (p->mg.active && multi) e = std::min(e, std::max(2, (72 / (6 * p->mg.M.n_levels + 12)) & ~1));      // (every exchange is a pack kernel, the transfer and an unpack kernel)
-        if (p->mg.active && !multi) e = std::max(2, (72 / (2 * p->mg.M.n_levels + 3 + 2 * n_sm)) & ~1);   // at most 2 n_levels + 1 cycle kernels + matvec + update per iteration (one less with the restriction inside the update)
-        return e;
-    };
-    every = chunk_length();
-    int rc;
-    const bool sr = single_reduction(p);
-    auto one_iteration = [&](int kk) -> int {
-        if (sr && fused_coarse) {      // two-level method: w = A (z_bj + P y), update + restriction with the one reduction point, dense solve (y, coarse part of r.u)
-            const int pending = kk > 0 ? 1 : 0;      // (iteration 0: the PCG start has left the complete u in C.z)
-            launch_mf_apply_dot_live_coarse(p->G, p->F, p->Sc, p->C, p->K, pending, p->st);
-            launch_cg_update_restrict_sr(p->G, p->C, p->K, kk, kk == 0 ? 1 : 0, pending, mf_grid_size(p->F), p->st);
-            launch_coarse_solve_dot(p->K, p->C.flags, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE + fused_parts, p->st);
-            return PGO_OK;
-        }
-        if (sr) {      // matvec (no head: it only asks whether the PCG has stopped), update with the iteration's one reduction point, [the multigrid cycle]
-            launch_mf_apply_dot_live(p->G, p->F, p->Sc, p->C, p->st);
-            const int n_pq = mf_grid_size(p->F), first = kk == 0 ? 1 : 0;      // (first: also when a PCG that stopped before its first update is resumed — p = s = 0 still)
-            const bool mg_restrict_fused = p->mg.active && p->mg.M.blk_tab != nullptr;
-            if (mg_restrict_fused) launch_cg_update_mg_sr(p->G, p->C, p->mg.M, p->mg.levels, p->K, kk, first, n_pq, p->st);
-            else launch_cg_update_sr(p->G, p->C, kk, first, n_pq, p->st);
-            if (p->mg.active) launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, mg_scale(p), true, p->st, mg_restrict_fused, mg_cs(p), mg_fine_view(p));
-            return PGO_OK;
-        }
-        if (multi) {
-            const int g = cg_grid_size(p->G);
-            int g_pq = g;
-            if (p->built_mf) { launch_mf_apply_dot(p->G, p->F, p->Sc, p->C, p->C.z, p->C.q, p->st); g_pq = mf_grid_size(p->F); }   // w = A_r u and the partials of u.w in one kernel
-            else { launch_apply_operator(p->G, p->C, p->C.z, p->C.q, p->st); launch_cgcg_dots(p->G, p->C, p->st); }
-            // The iteration's exchanges: the partial rows of w of the keyframes this rank shares go to the ranks sharing them (one group of sends / receives), the parts are
-            // summed in ascending rank order; [delta, gamma] by ONE all-reduce of two doubles.  Then the update; with the multigrid the distributed cycle.
-            int r2;
-            launch_cg_reduce2_live(p->C, p->C.part_pq, g_pq, p->C.part_rz, g, p->d_xscal.p, p->st);
-            if ((r2 = exchange_rows(p, p->C.q, 6, nullptr, 0, p->C.flags)) != PGO_OK) return r2;
-            if ((r2 = allreduce(p, p->d_xscal.p, 2, 0)) != PGO_OK) return r2;
-            launch_cgcg_update(p->G, p->C, kk, kk == 0 ? 1 : 0, p->st, nullptr, nullptr, p->d_xscal.p);   // (first: also when a PCG that stopped before its first update is resumed: p = s = 0 still)
-            ++p->st_pcg_iterations;
-            if (p->mg.active && (r2 = mg_apply_ranks(p, true)) != PGO_OK) return r2;      // u = D^-1 r + P0 V(P0^T r)
-            return PGO_OK;
-        }
-        if (fused_coarse) {
-            launch_mf_spmv_coarse(p->G, p->F, p->Sc, p->C, p->K, kk, tol2, fused_parts, kk > 0 ? 1 : 0, p->st);
-            launch_cg_update_restrict(p->G, p->C, p->K, kk, mf_grid_size(p->F), p->st);
-            launch_coarse_solve_dot(p->K, p->C.flags, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE + fused_parts, p->st);
-            return PGO_OK;
-        }
-        int n_pq = cg_grid_size(p->G);
-        if (p->built_mf) { launch_mf_spmv(p->G, p->F, p->Sc, p->C, kk, tol2, p->st); n_pq = mf_grid_size(p->F); }
-        else launch_cg_spmv(p->G, p->C, kk, tol2, p->st);
-        const bool mg_restrict_fused = p->mg.active && p->mg.M.blk_tab != nullptr;      // the vector update also restricts the new residual to level 1
-        if (mg_restrict_fused) launch_cg_update_mg(p->G, p->C, p->mg.M, p->mg.levels, p->K, kk, n_pq, p->st);
-        else launch_cg_update(p->G, p->C, kk, n_pq, p->st);
-        // the new residual is in the OTHER r buffer, its r.z partials in the other parity's slots
-        if (p->mg.active) launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, (kk & 1) ? p->C.r : p->C.r2, p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, mg_scale(p), true, p->st, mg_restrict_fused, mg_cs(p), mg_fine_view(p));
-        else if (p->coarse_active)
-            launch_coarse_apply(p->G, p->C, p->K, (kk & 1) ? p->C.r : p->C.r2, p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, true, p->st);
-        return PGO_OK;
-    };
-    // hipGraph: capture one chunk (iterations 2 .. 2+every-1: no `first` kernel, even start) once per graph build and preconditioner, and replay it
-    // Several ranks: only where the transport's collectives can be captured (pgo_comm.hip: RCCL, opt-in; not a caller-supplied collective, a host callback)
-    const bool want_graph = o.cg_use_graph && !p->cg_graph_failed && (!p->local_ids || (p->comm && p->comm->graph_capturable()));
-    // Capture + instantiation cost about a millisecond: a PCG pays it only once it has run `graph_after` iterations eagerly (a graph that is rebuilt for every
-    // solve — the reference's sessions: one new loop edge, one solve — and converges in a few hundred iterations never does; eager launches keep up with
-    // 5-8 us kernels: measured 18.5 vs 19.4 ms at 300 keyframes, 64.0 vs 64.6 ms at 3000)
-    const int graph_after = debug_graph_after();
-    auto ensure_graph = [&](bool may_capture) {
-        const int mode = p->mg.active ? 2 : p->coarse_active ? 1 : 0;
-        pgo_problem::CapturedChunk& cc = p->cg_chunk[mode];
-        if (!want_graph || p->cg_graph_failed || (cc.exec != nullptr && cc.epoch == p->build_epoch && cc.len == every && cc.scale == mg_scale(p) && cc.sr == sr)) { p->cg_graph = want_graph && !p->cg_graph_failed ? cc.exec : nullptr; return; }
-        if (!may_capture) { p->cg_graph = nullptr; return; }
-        if (cc.exec) { (void)hipGraphExecDestroy(cc.exec); cc.exec = nullptr; }
-        hipGraph_t gr = nullptr;
-        bool ok = hipStreamBeginCapture(p->st, hipStreamCaptureModeThreadLocal) == hipSuccess;
-        if (ok) {
-            for (int j = 0; j < every; ++j) (void)one_iteration(2 + j);
-            ok = hipStreamEndCapture(p->st, &gr) == hipSuccess && gr != nullptr;
-        }
-        const double t_inst = now_s();
-        if (ok) ok = hipGraphInstantiate(&cc.exec, gr, nullptr, nullptr, 0) == hipSuccess;
-        if (o.verbosity > 1) std::fprintf(stderr, "[pgo] PCG chunk of %d iterations (preconditioner %d) captured, instantiated in %.2f ms\n", every, mode, (now_s() - t_inst) * 1e3);
-        if (gr) (void)hipGraphDestroy(gr);
-        if (!ok) { cc.exec = nullptr; p->cg_graph_failed = true; (void)hipGetLastError(); }
-        else { cc.epoch = p->build_epoch; cc.len = every; cc.scale = mg_scale(p); cc.sr = sr; }
-        p->cg_graph = cc.exec;
-    };
-    ensure_graph(k >= graph_after);
-    // Chunks of `every` iterations; the convergence flag of chunk j is read (pinned memory + event) only AFTER chunk j+1 has been
-    // enqueued, so the GPU never drains while the host polls.  A chunk enqueued after convergence is a string of early-exit kernels.
-    int n_chunks = 0, waited = -1;
-    int ex_k0 = -1; double ex_rz0 = 0.0;      // first polled (iteration, r.z) of this run: base of the convergence-rate estimate
-    bool done = false;
-    // END GAME (round 5, one GPU).  A chunk enqueued past convergence is a string of early-exit kernels (~2 us each: 100-150 us per stopped PCG with a chunk in flight, more
-    // than a tenth of a session-sized PCG).  The polled r.z values give the convergence rate; once the predicted remaining iterations fall below two chunks the host stops
-    // running ahead: it enqueues what the prediction asks for (+15 % + 4 iterations: an early-exit iteration costs a quarter of a host round trip), eagerly, and polls at once.
-    // Chunk lengths depend on the device's own r.z values alone — the PCG's iterates do not depend on how its iterations are cut into chunks.
-    const bool end_game = o.cg_end_game != 0 && !multi;
-    bool eg_tight = false, eg_have = false; int eg_next = every; int eg_k = 0; double eg_rz = 0.0;
-    auto eg_snapshot = [&]() { if (end_game) launch_cg_poll(p->C, p->poll[2].flags, p->poll[2].scal, p->st); eg_have = false; };      // (read only after a later poll's event: stream order)
-    auto eg_update = [&](int slot) {      // a completed poll: new rate estimate from the last two points, length of the next chunk
-        if (!end_game) return;
-        const int kk = p->poll[slot].flags[2];
-        const double rz = p->poll[slot].scal[1], bb = p->poll[slot].scal[0];
-        if (!eg_have) { eg_k = p->poll[2].flags[2]; eg_rz = p->poll[2].scal[1]; eg_have = true; }
-        eg_tight = false; eg_next = every;
-        if (rz > 0.0 && bb > 0.0 && eg_rz > 0.0 && kk > eg_k && rz < eg_rz) {
-            const double lr = std::log(rz / eg_rz) / (double)(kk - eg_k);
-            const double need = std::log(tol2 * bb / rz);
-            const double left = need < 0.0 ? need / lr - (double)(k - kk) : 0.0;      // iterations still to run beyond what is already enqueued
-            if (left < 2.0 * (double)every) {
-                eg_tight = true;
-                const int want = (int)std::ceil(std::max(left, 0.0) * 1.15 + 4.0);
-                eg_next = std::max(2, std::min(every, (want + 1) & ~1));
-            }
-        }
-        if (kk > eg_k) { eg_k = kk; eg_rz = rz; }
-    };
-    auto enqueue_poll = [&](int slot) -> int {
-#ifdef PGO_POLL_BY_COPY
-        HIPCHK(p, hipMemcpyAsync(p->poll[slot].flags, p->C.flags, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, p->st));
-        HIPCHK(p, hipMemcpyAsync(p->poll[slot].scal, p->C.scal, 3 * sizeof(double), hipMemcpyDeviceToHost, p->st));
-#else
-        launch_cg_poll(p->C, p->poll[slot].flags, p->poll[slot].scal, p->st);
-#endif
-        HIPCHK(p, hipEventRecord(p->poll_ev[slot], p->st));
-        return PGO_OK;
-    };
-    // block-Jacobi -> multigrid inside one system: operators built now, PCG restarted from the current iterate (`so_far` iterations are booked as cg_extra)
-    auto switch_to_mg = [&](int so_far) -> int {
-        int rcs;
-        if ((rcs = build_mg(p)) != PGO_OK) return rcs;
-        if (!p->mg.active) { p->mg_failed = true; return PGO_OK; }
-        p->cg_extra += so_far;
-        if (p->built_mf) launch_mf_apply(p->G, p->F, p->Sc, p->C, p->C.x, p->C.q, p->st);
-        else launch_apply_operator(p->G, p->C, p->C.x, p->C.q, p->st);
-        if (multi) {
-            if ((rcs = exchange_rows(p, p->C.q, 6, nullptr, 0)) != PGO_OK) return rcs;
-            if ((rcs = start_multi(1)) != PGO_OK) return rcs;
-        } else {
-            const int g = launch_cg_init_vectors(p->G, p->C, 1, p->st);
-            launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
-            launch_cg_init_scalars(p->C, g, g, tol2, p->st);
-        }
-        k = 0; n_chunks = 0; waited = -1;
-        every = chunk_length();
-        eg_tight = false; eg_next = every; eg_have = false; eg_snapshot();
-        ensure_graph(true);      // a system that needed the switch is a long one
-        return PGO_OK;
-    };
-    // a system predicted hard whose step has survived the first early-rejection pause (lm_step): the multigrid takes over from the iterate the pause left
-    if (switch_now && resume_from >= 0 && p->mg.built && !p->mg.active && !p->mg_failed && (rc = switch_to_mg(resume_from)) != PGO_OK) return rc;
-    eg_next = every;
-    if (end_game && (resume_from >= 0 || k == 0)) eg_snapshot();
-    while (k < o.cg_max_iterations && !done) {
-        if (eg_tight && n_chunks > 0 && waited < n_chunks - 1) {      // end game: the chunk in flight is waited for before anything else is enqueued
-            HIPCHK(p, hipEventSynchronize(p->poll_ev[(n_chunks - 1) & 1]));
-            waited = n_chunks - 1;
-            if (p->poll[waited & 1].flags[0]) { done = true; break; }
-            eg_update(waited & 1);
-        }
-        // (a phase that only has to reach an early-rejection pause's loose tolerance is a matter of a few iterations: its first chunk is short, the rate estimate takes over from there)
-        const int first_short = end_game && n_chunks == 0 && rel_tol >= 5e-3 ? std::min(every, 8) : every;
-        const int chunk = std::min(eg_tight ? eg_next : first_short, o.cg_max_iterations - k);
-        if (want_graph && !p->cg_graph_failed && !p->cg_graph && k >= graph_after && (k & 1) == 0) ensure_graph(true);
-        if (k >= 2 && chunk == every && want_graph && p->cg_graph && (k & 1) == 0) {
-            HIPCHK(p, hipGraphLaunch(p->cg_graph, p->st));
-            k += every;
-        } else {
-            // iterations 0,1 run eagerly (iteration 0 has its own kernel arguments); an odd resume index takes one eager iteration to realign
-            const int n = k == 0 ? std::min(2, chunk) : ((k & 1) ? 1 : chunk);
-            const bool startup = k == 0 || (k & 1);
-            for (int j = 0; j < n; ++j, ++k) if ((rc = one_iteration(k)) != PGO_OK) return rc;
-            if (startup && k < o.cg_max_iterations) continue;     // no host poll after the start-up iterations
-        }
-        if ((rc = enqueue_poll(n_chunks & 1)) != PGO_OK) return rc;
-        // the first two chunks are polled immediately (short solves finish there); afterwards one chunk stays in flight
-        const int check = (n_chunks < 2 || eg_tight) ? n_chunks : n_chunks - 1;
-        if (check > waited) {
-            HIPCHK(p, hipEventSynchronize(p->poll_ev[check & 1]));
-            waited = check;
-            if (p->poll[check & 1].flags[0]) done = true;
-            else eg_update(check & 1);
-            // A system without a prediction (the first of a solve, the first after rejected steps) need not burn mg_switch_iterations block-Jacobi iterations to be
-            // recognised as hard: the polled r.z values give its convergence rate, and a system that would need >= the start threshold in total at that rate (and at
-            // least twice what it has done) switches now.  Depends on the solve's own data alone; several ranks: r.z and the reference norm are all-reduced values, every
-            // rank sees the same bits and takes the same branch.
-            if (!done && p->mg.built && !p->mg.active && !p->mg_failed && !p->mg_start_deferred && o.mg_switch_iterations > 0 && k < p->mg_switch_at) {
-                const int kk = p->poll[check & 1].flags[2];
-                const double rz = p->poll[check & 1].scal[1], bb = p->poll[check & 1].scal[0];
-                if (rz > 0.0 && bb > 0.0) {
-                    if (ex_k0 < 0) { if (kk >= 24) { ex_k0 = kk; ex_rz0 = rz; } }
-                    else if (kk >= 96 && kk > ex_k0) {
-                        const double lr = std::log(rz / ex_rz0) / (double)(kk - ex_k0);                        // log reduction per iteration (negative while converging)
-                        const double need = std::log(o.cg_rel_tolerance * o.cg_rel_tolerance * bb / rz);      // what is left down to the final tolerance (negative)
-                        const double total = lr < 0.0 ? (double)kk + need / lr : 1e30;
-                        if (total >= 1.75 * (double)o.mg_switch_iterations && total >= 2.0 * (double)kk) p->mg_switch_at = std::min(p->mg_switch_at, k);
-                    }
-                }
-            }
-        }
-        ++n_chunks;
-        // Hybrid preconditioning: most LM systems (small trust regions, steps about to be rejected) are solved by block-Jacobi in a few
-        // hundred cheap iterations; one that is not done after mg_switch_iterations is a hard one, and from there the multigrid (4x fewer
-        // iterations or better at ~3x the price) takes over: operators built now, PCG restarted from the current iterate.
-        if (!done && p->mg.built && !p->mg.active && !p->mg_failed && k >= p->mg_switch_at && k < o.cg_max_iterations) {     // (several ranks: every quantity tested here is the same on all of them)
-            HIPCHK(p, hipMemcpyAsync(hflags, p->C.flags, sizeof(hflags), hipMemcpyDeviceToHost, p->st));
-            HIPCHK(p, hipStreamSynchronize(p->st));
-            if (hflags[0]) { done = true; (void)enqueue_poll(n_chunks & 1); ++n_chunks; break; }
-            if ((rc = switch_to_mg(hflags[2])) != PGO_OK) return rc;
-        }
-    }
-    if (n_chunks > 0) {   // the state after the LAST enqueued chunk is the final one (kernels past convergence do nothing)
-        HIPCHK(p, hipEventSynchronize(p->poll_ev[(n_chunks - 1) & 1]));
-        std::memcpy(hflags, p->poll[(n_chunks - 1) & 1].flags, sizeof(hflags));
-        std::memcpy(hscal, p->poll[(n_chunks - 1) & 1].scal, sizeof(hscal));
-    } else {
-        HIPCHK(p, hipMemcpyAsync(hflags, p->C.flags, sizeof(hflags), hipMemcpyDeviceToHost, p->st));
-        HIPCHK(p, hipMemcpyAsync(hscal, p->C.scal, sizeof(hscal), hipMemcpyDeviceToHost, p->st));
-        HIPCHK(p, hipStreamSynchronize(p->st));
-    }
-    res->converged = hflags[0] != 0 && hflags[1] == 0;
-    if (!hflags[0] && !multi) {   // iteration cap reached: one more convergence test so that scal[1] holds the last r.z (x is already final)
-        launch_cg_set_tolerance(p->C, 1e300, p->st);
-        if (sr) { if ((rc = one_iteration(k)) != PGO_OK) return rc; }      // (its update's head finds r.u below the tolerance: scal[1] <- r.u, nothing else moves)
-        else if (fused_coarse) launch_mf_spmv_coarse(p->G, p->F, p->Sc, p->C, p->K, k, 1e300, fused_parts, k > 0 ? 1 : 0, p->st);
-        else if (p->built_mf) launch_mf_spmv(p->G, p->F, p->Sc, p->C, k, 1e300, p->st);
-        else launch_cg_spmv(p->G, p->C, k, 1e300, p->st);
-        HIPCHK(p, hipMemcpyAsync(hflags, p->C.flags, sizeof(hflags), hipMemcpyDeviceToHost, p->st));
-        HIPCHK(p, hipMemcpyAsync(hscal, p->C.scal, sizeof(hscal), hipMemcpyDeviceToHost, p->st));
-        HIPCHK(p, hipStreamSynchronize(p->st));
-    }
-    res->iterations = hflags[2];
-    res->breakdown = hflags[1] != 0;
-    res->rel_residual = hscal[0] > 0 ? std::sqrt(std::max(0.0, hscal[1]) / hscal[0]) : 0.0;
-    return PGO_OK;
-}
-
-// Coarse operator of the two-level preconditioner for the system just built: Ac = P^T A P (deterministic assembly) and its dense inverse
-// (blocked Gauss-Jordan kernels).  A coarse operator that is not numerically positive definite leaves the coarse space off for this iteration.
-static int build_coarse(pgo_problem* p) {
-    p->coarse_active = false;
-    const double t_coarse0 = now_s();
-    // Where it pays: always when the aggregates are small (the coarse space is then a sizeable fraction of the problem: graphs up to
-    // ~64 x coarse_aggregates keyframes), otherwise only at large trust regions, where the slow modes are the long wavelengths
-    // (measured: scripts/gpu_coarse_ab.py).
-    if (!p->coarse_built || p->opt.coarse_aggregates <= 0) return PGO_OK;
-    if (p->coarse_mode == 2) {
-        // dropped at a smaller trust region: the long wavelengths it removes dominate more and more as the radius grows, so it gets another
-        // comparison once the radius is 9x (two accepted steps) beyond the one it lost at — at most twice per solve
-        if (p->coarse_retests >= 2 || p->coarse_skip_all || !(p->radius >= 9.0 * p->coarse_drop_radius)) return PGO_OK;   // (eligibility by aggregate size / coarse_min_radius is checked below)
-        ++p->coarse_retests; p->coarse_mode = 0;
-    }
-    if (!(p->K.m <= 64 || (p->radius >= p->opt.coarse_min_radius && p->K.m <= 1024))) return PGO_OK;   // aggregates of thousands of keyframes are too coarse to help
-    if (p->coarse_geometry_epoch != p->lin_epoch) {          // the aggregates' centroids follow the poses of the current linearisation
-        launch_coarse_geometry(p->G, p->K, p->d_pose[p->cur].p, p->st);
-        p->coarse_geometry_epoch = p->lin_epoch;
-    }
-    launch_coarse_assemble(p->G, p->L, p->Sc, p->C, p->K, p->st);
-    int32_t* fail = p->d_cinfo.p;
-    HIPCHK(p, hipMemsetAsync(fail, 0, sizeof(int32_t), p->st));
-    launch_coarse_invert(p->K, p->d_cscr.p, fail, p->st);
-    if (debug_break_coarse()) launch_coarse_negate(p->K, p->st);
-    int32_t h = 1;
-    HIPCHK(p, hipMemcpyAsync(&h, fail, sizeof(h), hipMemcpyDeviceToHost, p->st));
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    p->coarse_active = h == 0;
-    if (p->opt.verbosity > 1) std::fprintf(stderr, "[pgo] coarse operator assembled and inverted in %.3f ms (since the start of build_coarse)\n", (now_s() - t_coarse0) * 1e3);
-    if (p->opt.verbosity > 0) std::fprintf(stderr, "[pgo] coarse space: %d aggregates of %d keyframes, %d blocks, radius %.1e: %s\n", p->K.n_agg, p->K.m, p->K.n_blk, p->radius, h == 0 ? "on" : "coarse operator not positive definite -> off");
-    return PGO_OK;
-}
-
-
-int build_system(pgo_problem* p, bool* ok) {
-    int rc;
-    HIPCHK(p, hipMemsetAsync(p->d_flags.p + 4, 0, sizeof(int32_t), p->st));
-    launch_build_rows(p->G, p->L, p->Sc, p->C, p->radius, 1 /*one GPU: this handle adds Hd, g and the damping; multi-GPU: the keyframe's owner (G.own)*/, p->built_mf ? p->d_lam.p : nullptr, p->st);
-    if ((rc = exchange_rows(p, p->C.Dtot, 36, p->C.b, 6)) != PGO_OK) return rc;   // reduced diagonal + rhs of shared keyframes
-    launch_invert_rows(p->G, p->C, p->d_flags.p + 4, p->st);
-    int32_t fail = 0;
-    HIPCHK(p, hipMemcpyAsync(&fail, p->d_flags.p + 4, sizeof(int32_t), hipMemcpyDeviceToHost, p->st));
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    if (p->local_ids) {      // a block that fails on one rank makes the step invalid on all of them (the ranks must take the same branch: collectives follow)
-        std::vector<double> f(1, fail ? 1.0 : 0.0);
-        if ((rc = host_allreduce(p, f, 2)) != PGO_OK) return rc;
-        fail = f[0] != 0.0;
-    }
-    *ok = fail == 0;
-    p->mg.active = false; p->mg_failed = false; p->C.extra_rz = 0; p->mg_start_deferred = false;
-    // block-Jacobi-equivalent iterations this system is expected to need: those of the last fully solved system of this solve x sqrt(radius ratio); 0 = no prediction
-    p->cg_predicted = (p->cg_prev_radius > 0.0 && p->radius > 0.0) ? p->cg_prev_equiv * std::sqrt(p->radius / p->cg_prev_radius) : 0.0;
-    if (*ok && p->mg.built) {
-        // Which preconditioner the PCG of this LM system starts with.  Block-Jacobi iterations grow like sqrt(radius) from one accepted step
-        // to the next, so the previous step of this solve predicts this one (a multigrid iteration counts as 4 block-Jacobi ones: it costs
-        // ~2.5x and saves 4x or more on hard systems):  predicted >= 1.75 x mg_switch_iterations -> multigrid (from the first iteration, or after the prelude below);
-        // predicted easier than that -> block-Jacobi, and the in-flight switch of run_pcg waits for twice the prediction (switching 400
-        // iterations into a system that needs 520 throws the work away); no prediction (first step, after a rejected one) -> block-Jacobi with
-        // the switch at mg_switch_iterations.  Depends on this solve's own history only.
-        double predicted = 0.0;
-        // (round 3, with the smoothed cycle: start factors 1.0 - 2.25, waiting factors 1.5 - 2.0 and switch points 200 - 600 all within +-2 % on C3 and C4)
-        // (with the deferred start and the regroup off the critical path, session 2 of round 3: start 1.0 - 2.25 x wait 1.5 / 2.0 on C3 0.311 - 0.333 s, C4 1.498 - 1.542 s; 1.75 / 2.0 is the best pair on both)
-        const double start_factor = 1.75, wait_factor = 2.0;
-        if (p->cg_prev_radius > 0.0 && p->radius > 0.0) predicted = p->cg_prev_equiv * std::sqrt(p->radius / p->cg_prev_radius);
-        p->mg_switch_at = p->opt.mg_switch_iterations;
-        if (predicted > 0.0 && predicted < start_factor * (double)p->opt.mg_switch_iterations) p->mg_switch_at = std::max(p->opt.mg_switch_iterations, (int)(wait_factor * predicted));
-        // A system predicted hard gets the multigrid from the first iteration — unless the step can still be rejected early: most steps that ARE rejected follow a long
-        // accepted one at a large radius, i.e. exactly the systems predicted hard, and block-Jacobi reaches the first pause (cg_early_tolerance, a few dozen iterations)
-        // for a fraction of what the operators cost (C3, step 4: 32 ms for a step thrown away at 21 iterations).  Then the build waits for the pause (lm_step).
-        const bool hard = p->opt.mg_switch_iterations <= 0 || predicted >= start_factor * (double)p->opt.mg_switch_iterations;
-        // ... and only where a rejection is in the air: the previous step was rejected (rejections come in streaks: the radius shrinks over several steps), or the last accepted
-        // step's relative decrease fell below 0.8 — the quadratic model is losing its grip (C3's and C4's first rejected steps follow rho = 0.67 and 0.62; the accepted hard steps
-        // of both follow rho >= 0.89, and a prelude there is 74 block-Jacobi iterations the multigrid would not have needed: 3 ms x 5 on C3, 5 ms x 12 on C4)
-        const bool rejection_likely = p->reuse_diagonal || p->last_rho < 0.8;
-        p->mg_start_deferred = hard && rejection_likely && p->opt.mg_switch_iterations > 0 && p->opt.cg_early_tolerance > p->opt.cg_rel_tolerance;
-        if (p->mg_start_deferred) {      // ... but not for long: a step that has not reached the pause within the prelude is a hard one that stays (late C3 systems need ~300 block-Jacobi iterations to 1e-2)
-            const int prelude = 72;      // three chunks (measured on C3 / C4, 20 steps: 48 -> 0.392 / 1.500 s — C3's rejected step 4 needs 53 —, 72 -> 0.322 / 1.515 s, 96 -> 0.324 / 1.524 s)
-            p->mg_switch_at = std::min(p->mg_switch_at, prelude);
-        }
-        if (hard && !p->mg_start_deferred && (rc = build_mg(p)) != PGO_OK) return rc;
-    }
-    else if (*ok && (rc = build_coarse(p)) != PGO_OK) return rc;
-    return PGO_OK;
-}
-
 const char* step_reason_text(int r) {
     static const char* const t[] = {"ok", "REJ(rho)", "REJ(pause)", "INVALID(factorization)", "INVALID(breakdown)", "INVALID(model)", "CONVERGED"};
     return r >= 0 && r < 7 ? t[r] : "?";
@@ -1100,10 +626,8 @@ int solve_begin(pgo_problem* p, const double* quat, const double* t, const doubl
     std::memset(&p->sum, 0, sizeof(p->sum));
     p->in_solve = true; p->terminated = false; p->scale_ready = false; p->have_prev_step = false;
     p->st_exchanges = p->st_allreduces = p->st_pcg_iterations = 0; p->st_bytes_neighbour = p->st_bytes_allreduce = 0.0;
-    p->coarse_retests = 0; p->coarse_drop_radius = 0.0;
-    p->cg_prev_equiv = 0.0; p->cg_prev_radius = 0.0; p->mg.regroups = 0; p->last_rho = 1.0;
-    if (p->coarse_skip > 0) { p->coarse_mode = 2; p->coarse_skip_all = true; --p->coarse_skip; }
-    else { p->coarse_mode = (p->coarse_keep_streak % 4 != 0) ? 1 : 0; p->coarse_skip_all = false; }
+    p->pcg.cg_prev_equiv = 0.0; p->pcg.cg_prev_radius = 0.0; p->mg.regroups = 0; p->last_rho = 1.0;
+    two_level_solve_begin(p);
     p->radius = p->opt.initial_trust_region_radius; p->decrease_factor = 2.0; p->reuse_diagonal = false; p->iteration = 0; p->invalid = 0;
     p->sum.termination_type = PGO_NO_CONVERGENCE;
     if ((rc = linearize(p, &p->x_cost)) != PGO_OK) return rc;
@@ -1141,7 +665,7 @@ int lm_step(pgo_problem* p, int ignore_termination, int* done) {
     int why_invalid = ok ? PGO_STEP_ACCEPTED : PGO_STEP_INVALID_FACTORIZATION;      // pgo_iteration.reason of an invalid step
     int precond_used = PGO_PRECOND_BLOCK_JACOBI;
     CgResult cg{0, false, 0.0, false};
-    p->cg_extra = 0;
+    p->pcg.cg_extra = 0;
     const int nxt = p->cur ^ 1;
     double h[S_N] = {0};
     // candidate point x (+) delta, its cost, the model cost change and the step norms -> h[]
@@ -1180,7 +704,7 @@ int lm_step(pgo_problem* p, int ignore_termination, int* done) {
         //     (profiles/r05_pause_rule.txt); a system without a prediction counts as mg_switch_iterations iterations;
         //   * none elsewhere.  The PCG's own iterates do not depend on where it pauses.
         const bool rejection_likely = p->reuse_diagonal || p->last_rho < 0.8;
-        const double predicted_its = p->cg_predicted > 0.0 ? p->cg_predicted : (double)(o.mg_switch_iterations > 0 ? o.mg_switch_iterations : 400);
+        const double predicted_its = p->pcg.cg_predicted > 0.0 ? p->pcg.cg_predicted : (double)(o.mg_switch_iterations > 0 ? o.mg_switch_iterations : 400);
         const bool expensive = predicted_its * (double)p->N_global >= 5.6e7;
         const bool armed = p->N_global >= CG_PAUSE_MIN_KEYFRAMES || p->sum.num_unsuccessful_steps > 0;
         const bool pauses = armed && (rejection_likely || p->opt.cg_pause_always != 0);
@@ -1188,7 +712,7 @@ int lm_step(pgo_problem* p, int ignore_termination, int* done) {
         if ((pauses || early_only) && o.cg_early_tolerance > o.cg_rel_tolerance) stages[n_stages++] = Stage{o.cg_early_tolerance, o.cg_early_reject_rho};
         if (pauses && o.cg_mid_tolerance > o.cg_rel_tolerance && (n_stages == 0 || o.cg_mid_tolerance < stages[0].tol)) stages[n_stages++] = Stage{o.cg_mid_tolerance, o.cg_mid_reject_rho};
         const bool warm = o.cg_warm_start != 0 && p->have_prev_step && p->reuse_diagonal;
-        if ((rc = run_pcg(p, &cg, warm, n_stages ? stages[0].tol : o.cg_rel_tolerance, -1)) != PGO_OK) return rc;
+        if ((rc = run_pcg(p, &cg, PcgPhase{n_stages ? stages[0].tol : o.cg_rel_tolerance, -1, warm})) != PGO_OK) return rc;
         for (int sidx = 0; sidx < n_stages && !cg.breakdown && !evaluated; ++sidx) {
             if ((rc = evaluate_candidate()) != PGO_OK) return rc;
             const double mc = -h[S_MODEL];
@@ -1199,72 +723,21 @@ int lm_step(pgo_problem* p, int ignore_termination, int* done) {
                                       sn > o.parameter_tolerance * (p->x_norm + o.parameter_tolerance) && std::fabs(dc) > o.function_tolerance * p->x_cost;
             if (clear_reject) evaluated = true;
             else {
-                const bool to_mg = p->mg_start_deferred && !p->mg.active;
-                p->mg_start_deferred = false;
-                if ((rc = run_pcg(p, &cg, false, sidx + 1 < n_stages ? stages[sidx + 1].tol : o.cg_rel_tolerance, cg.iterations, to_mg)) != PGO_OK) return rc;
+                const bool to_mg = p->pcg.mg_start_deferred && !p->mg.active;
+                p->pcg.mg_start_deferred = false;
+                if ((rc = run_pcg(p, &cg, PcgPhase{sidx + 1 < n_stages ? stages[sidx + 1].tol : o.cg_rel_tolerance, cg.iterations, false, to_mg})) != PGO_OK) return rc;
             }
         }
-        // The coarse space pays by a large factor or not at all (it can even cost iterations on chains that odometry weights cut into
-        // many loose pieces), so once per solve — at the first full-accuracy step that used it — plain block-Jacobi gets the SAME
-        // iteration budget on the same system: if it does not converge within it the coarse space stays for the rest of
-        // the solve, otherwise it is dropped.  The test costs at most as many iterations as the coarse run took.
-        if (p->coarse_active && p->coarse_mode == 0 && !evaluated && !cg.breakdown && cg.converged) {
-            HIPCHK(p, p->d_tmp.ensure((size_t)p->N * 6));
-            HIPCHK(p, hipMemcpyAsync(p->d_tmp.p, p->C.x, (size_t)p->N * 6 * sizeof(double), hipMemcpyDeviceToDevice, p->st));
-            const int saved_cap = p->opt.cg_max_iterations;
-            // an iteration with the coarse space costs 2.6-2.8x a plain one (three more kernels at the latency floor, measured from 200 to
-            // 20k keyframes): equal TIME budgets
-            p->opt.cg_max_iterations = std::max(3 * cg.iterations, 2 * (std::max(2, p->opt.cg_check_every) & ~1));
-            p->coarse_active = false;
-            CgResult plain{0, false, 0.0, false};
-            rc = run_pcg(p, &plain, false, o.cg_rel_tolerance, -1);
-            p->opt.cg_max_iterations = saved_cap;
-            if (rc != PGO_OK) return rc;
-            if (plain.converged && !plain.breakdown) {      // block-Jacobi alone is at least as fast here
-                // lost although it needed clearly fewer iterations: worth another comparison at a larger radius; lost without even that
-                // (the aggregates' rigid modes are not this graph's slow modes): no more comparisons in this solve
-                if ((double)plain.iterations < 1.2 * (double)cg.iterations) p->coarse_retests = 2;
-                p->coarse_mode = 2; cg.iterations += plain.iterations; p->coarse_drop_radius = p->radius;
-            }
-            else {
-                p->coarse_mode = 1; p->coarse_active = true; p->coarse_backoff = 0;
-                HIPCHK(p, hipMemcpyAsync(p->C.x, p->d_tmp.p, (size_t)p->N * 6 * sizeof(double), hipMemcpyDeviceToDevice, p->st));
-                cg.iterations += plain.iterations;
-            }
-        }
-        // A breakdown under the multigrid (its cycle was not positive definite on this system — a smoother at its stability limit) or under the two-level method (its
-        // dense coarse inverse is applied rounded to fp32: at large trust-region radii the coarse operator's condition number exceeds what fp32 resolves, and the rounded
-        // inverse need not be positive definite) is not the system's fault: the same system is solved again by plain block-Jacobi before the step may count as invalid.
-        // Ceres' exact factorisation never turns a solvable step into an invalid one (reference src/PoseGraphSLAM.cpp:1903).
-        precond_used = p->mg.active ? PGO_PRECOND_MULTIGRID : (p->coarse_active ? PGO_PRECOND_TWO_LEVEL : PGO_PRECOND_BLOCK_JACOBI);
-        if (cg.breakdown && (p->mg.active || p->coarse_active) && !evaluated) {
-            if (o.verbosity > 0) std::fprintf(stderr, "[pgo] %s: PCG breakdown at radius %.1e after %d iterations (preconditioner not positive definite) -> block-Jacobi for this system\n",
-                                              p->mg.active ? "multigrid" : "two-level method", p->radius, cg.iterations);
-            if (p->mg.active) { p->mg.active = false; p->mg_failed = true; }
-            p->coarse_active = false;      // (this system only: build_coarse decides again for the next one)
-            p->C.extra_rz = 0;
-            p->cg_extra += cg.iterations;
-            ++p->sum.pcg_retries;
-            precond_used = PGO_PRECOND_BLOCK_JACOBI | PGO_PRECOND_RETRIED;
-            // The iterate the broken-down PCG stopped at is a valid starting point (x_k with r_k = b - A x_k; a breakdown leaves x untouched): warm start.  Should that one
-            // break down as well (a NaN that reached x), the system is solved from zero.
-            if ((rc = run_pcg(p, &cg, true, o.cg_rel_tolerance, -1)) != PGO_OK) return rc;
-            if (cg.breakdown) { p->cg_extra += cg.iterations; if ((rc = run_pcg(p, &cg, false, o.cg_rel_tolerance, -1)) != PGO_OK) return rc; }
-        }
+        if ((rc = finish_system(p, &cg, evaluated, &precond_used)) != PGO_OK) return rc;
         p->have_prev_step = !cg.breakdown;
         if (cg.breakdown) { ok = false; why_invalid = PGO_STEP_INVALID_BREAKDOWN; }
-        // block-Jacobi-equivalent work of this system, for the next system's choice of preconditioner (build_system)
-        if (!evaluated && !cg.breakdown) {
-            const double equiv = p->mg.levels[0].smoothed ? 8.0 : 4.0;     // block-Jacobi iterations one multigrid iteration stands for on a hard system
-            p->cg_prev_equiv = (double)p->cg_extra + (p->mg.active ? equiv : 1.0) * (double)cg.iterations; p->cg_prev_radius = p->radius;
-        }
     }
-    it.cg_iterations = cg.iterations + p->cg_extra; it.cg_residual = cg.rel_residual;
+    it.cg_iterations = cg.iterations + p->pcg.cg_extra; it.cg_residual = cg.rel_residual;
     const double t_solved = now_s();
     it.seconds_system = t_built - t0; it.seconds_pcg = t_solved - t_built;
     it.cg_iterations_multigrid = p->mg.active ? cg.iterations : 0; it.single_reduction = ok && single_reduction(p) ? 1 : 0;
-    if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d PCG: %d iterations%s after %d with block-Jacobi; system + preconditioner %.3f ms, PCG %.3f ms\n", p->iteration, cg.iterations, p->mg.active ? " with the multigrid" : "", p->cg_extra, (t_built - t0) * 1e3, (t_solved - t_built) * 1e3);
-    p->sum.cg_iterations += cg.iterations + p->cg_extra;
+    if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d PCG: %d iterations%s after %d with block-Jacobi; system + preconditioner %.3f ms, PCG %.3f ms\n", p->iteration, cg.iterations, p->mg.active ? " with the multigrid" : "", p->pcg.cg_extra, (t_built - t0) * 1e3, (t_solved - t_built) * 1e3);
+    p->sum.cg_iterations += cg.iterations + p->pcg.cg_extra;
     if (p->mg.active) p->sum.cg_iterations_multigrid += cg.iterations;     // iterations before an in-flight switch (cg_extra) ran with block-Jacobi
     if (ok) {
         if (!evaluated && (rc = evaluate_candidate()) != PGO_OK) return rc;
@@ -1387,11 +860,7 @@ int solve_end(pgo_problem* p, double* quat, double* t, double* sw, pgo_summary* 
         std::memcpy(t, ht.data(), ht.size() * sizeof(double));
         if (sw && p->S > 0) std::memcpy(sw, hs.data(), hs.size() * sizeof(double));
     }
-    // (a solve that kept it: the next three solves of this handle use it without the comparison)
-    // a solve in which the coarse space lost every comparison: the following solves of this handle (incremental triggers on the same kind
-    // of graph) skip it, 1, 3, 7, 15 solves at a time, before comparing again; one win resets the back-off
-    if (p->coarse_mode == 2 && !p->coarse_skip_all) { p->coarse_backoff = std::min(2 * p->coarse_backoff + 1, 15); p->coarse_skip = p->coarse_backoff; }
-    if (p->coarse_mode == 1) ++p->coarse_keep_streak; else if (p->coarse_mode == 2 && !p->coarse_skip_all) p->coarse_keep_streak = 0;
+    two_level_solve_end(p);
     if (p->mg.job.kind == MgJob::regroup) mg_drop_pending(p);      // a regroup nobody needed any more: dropped (the hierarchy in place keeps its own switch record)
     if ((rc = mg_fresh_install(p)) != PGO_OK) return rc;      // a fresh graph's hierarchy that this solve never needed: installed now, for the handle's next solves
     p->sum.seconds_total = now_s() - p->t_begin;
@@ -1500,11 +969,9 @@ int pgo_create(pgo_problem** out, const pgo_options* opts) {
     if (dev < 0) { if (hipGetDevice(&dev) != hipSuccess) dev = 0; }
     if (dev >= count) { delete p; return PGO_ERR_NO_DEVICE; }
     p->device = dev;
-    if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking) != hipSuccess) { delete p; return PGO_ERR_NO_DEVICE; }
+    if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&p->st.s, hipStreamNonBlocking) != hipSuccess) { delete p; return PGO_ERR_NO_DEVICE; }
     std::memset(&p->sum, 0, sizeof(p->sum));
-    if (hipHostMalloc((void**)&p->poll, 3 * sizeof(pgo_problem::Poll), hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&p->poll_ev[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p->poll_ev[1], hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(p->st); delete p; return PGO_ERR_OUT_OF_MEMORY; }
-    std::memset(p->poll, 0, 3 * sizeof(pgo_problem::Poll));
+    if (p->pcg.create() != hipSuccess) { delete p; return PGO_ERR_OUT_OF_MEMORY; }
     // One-time costs of the process belong here, not in the first trigger: the first device allocation and the first kernel launch of the library (its code object goes to the
     // device).  Failures here are not errors (the solve reports its own).  (A captured + instantiated graph would also take the first hipGraphInstantiate of the process off the
     // first long PCG — 9.4 ms against 0.2 ms for later ones — but a capture in one thread makes a concurrent synchronous hipMemcpy of ANOTHER thread fail with
@@ -1544,11 +1011,7 @@ int pgo_destroy(pgo_problem* p) {
     if (p->comm) p->comm->abandon();
     p->comm.reset();
     (void)hipStreamSynchronize(p->st);
-    for (auto& cc : p->cg_chunk) if (cc.exec) (void)hipGraphExecDestroy(cc.exec);
-    if (p->poll) (void)hipHostFree(p->poll);
-    for (int i = 0; i < 2; ++i) if (p->poll_ev[i]) (void)hipEventDestroy(p->poll_ev[i]);
-    (void)hipStreamDestroy(p->st);
-    delete p;
+    delete p;      // (its members release the captured graphs, the pinned poll buffer and its events, then the stream, then the device buffers)
     return PGO_OK;
 }
 
@@ -1716,7 +1179,7 @@ int pgo_solve_begin(pgo_problem* p, const double* q, const double* t, const doub
 static void after_failure(pgo_problem* p) {
     mg_drop_pending(p);
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (p->st && hipStreamIsCapturing(p->st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(p->st, &g); if (g) (void)hipGraphDestroy(g); p->cg_graph_failed = true; }
+    if (p->st && hipStreamIsCapturing(p->st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(p->st, &g); if (g) (void)hipGraphDestroy(g); p->pcg.cg_graph_failed = true; }
     (void)hipGetLastError();
 }
 int pgo_lm_step(pgo_problem* p, int32_t ignore_termination, int32_t* done) {
@@ -1958,7 +1421,7 @@ int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8) {
             if ((rc = sq32(A.rt_valf, R.w0 * 36, (R.w1 - R.w0) * 36, out8 + 3)) != PGO_OK) return rc;
             if ((rc = sq32(A.r_valf, R.rT0 * 36, (R.rT1 - R.rT0) * 36, out8 + 4)) != PGO_OK) return rc;
         }
-    } else if ((rc = sq64(p->K.Ac, 0, (int64_t)p->K.nc * p->K.nc, out8 + 5)) != PGO_OK) return rc;      // the dense level: its inverse
+    } else if ((rc = sq64(p->coarse.K.Ac, 0, (int64_t)p->coarse.K.nc * p->coarse.K.nc, out8 + 5)) != PGO_OK) return rc;      // the dense level: its inverse
     return PGO_OK;
 }
 int pgo_comm_destroy(pgo_problem* p) {
@@ -2049,12 +1512,8 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
         if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
         if (!p->mg.active && (rc = build_mg(p)) != PGO_OK) return rc;
         if (!p->mg.active) { p->err = "pgo_time_kernel: the multigrid operators of this system are not positive definite"; return PGO_ERR_NUMERIC; }
-        const int g = launch_cg_init_vectors(p->G, p->C, 0, p->st);
-        if (p->local_ids) { if ((rc = mg_apply_ranks(p, false)) != PGO_OK) return rc; launch_cg_set_tolerance(p->C, 0.0, p->st); }      // (one full distributed cycle: every level vector holds finite numbers)
-        else {
-            launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
-            launch_cg_init_scalars(p->C, g, g, 0.0, p->st);
-        }
+        if (!p->local_ids) { if ((rc = pcg_start(p, choose_form(p), false, 0.0)) != PGO_OK) return rc; }      // (tolerance 0: never converges during the timed launches)
+        else { launch_cg_init_vectors(p->G, p->C, 0, p->st); if ((rc = mg_apply_ranks(p, false)) != PGO_OK) return rc; launch_cg_set_tolerance(p->C, 0.0, p->st); }      // (one full distributed cycle: every level vector holds finite numbers)
     }
     // several ranks: the timed launches take turns (every rank's figure is what its GPU would need on its own); only the in-process ranks, which share the GPU(s), wait for each other
     const int turns = (p->comm && (which == 7 || which == 8)) ? p->world() : 1;
@@ -2068,7 +1527,7 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
         if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, o.min_lm_diagonal, o.max_lm_diagonal, p->st);
         bool ok = true;
         if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
-        p->mg.active = false; p->coarse_active = false; p->C.extra_rz = 0;   // the timed iteration is the plain block-Jacobi one: no partial-sum slots of a multigrid / two-level solve
+        p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0;   // the timed iteration is the plain block-Jacobi one: no partial-sum slots of a multigrid / two-level solve
         launch_cg_init(p->G, p->C, 0, 0.0, p->st);
     }
     const double N = (double)G.N, E = (double)(G.rel.E + G.sw.E), Es = (double)G.sw.E;
@@ -2085,14 +1544,10 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
                 case 1: launch_k2(G, p->L, !p->built_mf, p->st, p->built_mf ? &p->F : nullptr); bytes = (624.0 * G.rel.E + 688.0 * Es) + 288.0 * E + 336.0 * N + 112.0 * Es; break;
                 case 2: case 4: case 5: {   // one PCG iteration (2), its matvec alone (4), its vector update alone (5)
                           const int kk = rep == 0 ? 0 : i + 1;
-                          const bool sr = single_reduction(p);      // the form the solver runs on this handle
-                          if (sr) {
-                              if (which != 5) launch_mf_apply_dot_live(G, p->F, p->Sc, p->C, p->st);
-                              if (which != 4) launch_cg_update_sr(G, p->C, kk, kk == 0 ? 1 : 0, mf_grid_size(p->F), p->st);
-                          } else {
-                              if (which != 5) { if (p->built_mf) launch_mf_spmv(G, p->F, p->Sc, p->C, kk, 0.0, p->st); else launch_cg_spmv(G, p->C, kk, 0.0, p->st); }
-                              if (which != 4) launch_cg_update(G, p->C, kk, p->built_mf ? mf_grid_size(p->F) : cg_grid_size(G), p->st);
-                          }
+                          const PcgForm f = choose_form(p, true);      // the form the solver runs on this handle (several ranks: the rank's own iteration, no exchanges)
+                          const bool sr = f.single_red();
+                          if (which != 5) pcg_matvec(p, f, kk, 0.0);
+                          if (which != 4 && (rc = pcg_update(p, f, kk)) != PGO_OK) return rc;
                           // Bytes this design moves per iteration, each array once.  Matrix-free matvec: per LANE (a relative-pose edge with both
                           // keyframes in one tile is one lane, every other edge side its own) the compact record (8 double2 planes; 11 for switchable
                           // sides) + 12 B of index data (+ a_inv for switchable sides); per keyframe z and p_prev read, p and q written (4 x 48),
@@ -2108,23 +1563,16 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
                 case 3: launch_k1(G, p->d_pose[nxt].p, p->d_swv[nxt].p, false, part(p, 5), &np, p->st); bytes = k1_algorithmic_bytes(G, false); break;
                 case 6: case 7: {
                           const int kk = rep == 0 ? 0 : i + 1;
-                          const bool fused = p->mg.M.blk_tab != nullptr;
-                          const bool sr = single_reduction(p);
-                          if (which == 6 && sr) {
-                              launch_mf_apply_dot_live(G, p->F, p->Sc, p->C, p->st);
-                              if (fused) launch_cg_update_mg_sr(G, p->C, p->mg.M, p->mg.levels, p->K, kk, kk == 0 ? 1 : 0, mf_grid_size(p->F), p->st);
-                              else launch_cg_update_sr(G, p->C, kk, kk == 0 ? 1 : 0, mf_grid_size(p->F), p->st);
-                          } else if (which == 6) {
-                              launch_mf_spmv(G, p->F, p->Sc, p->C, kk, 0.0, p->st);
-                              if (fused) launch_cg_update_mg(G, p->C, p->mg.M, p->mg.levels, p->K, kk, mf_grid_size(p->F), p->st);
-                              else launch_cg_update(G, p->C, kk, mf_grid_size(p->F), p->st);
-                          }
-                          if (p->local_ids) {      // several ranks: this rank's share of the cycle's kernels, no exchanges (what its GPU computes per cycle)
-                              launch_mg_apply(G, p->C, p->mg.M, p->mg.levels, p->K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), nullptr);
-                              bytes = (double)p->mg.blocks_own * 148.0 + (double)p->mg.rows_own * (288.0 + 24.0 + 8.0 * 48.0 + 16.0) + (double)p->K.nc * (double)p->K.nc * 4.0 + (double)p->K.nc * 16.0;
+                          if (p->local_ids) {      // several ranks (7 only): this rank's share of the cycle's kernels, no exchanges (what its GPU computes per cycle)
+                              launch_mg_apply(G, p->C, p->mg.M, p->mg.levels, p->coarse.K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), nullptr);
+                              bytes = (double)p->mg.blocks_own * 148.0 + (double)p->mg.rows_own * (288.0 + 24.0 + 8.0 * 48.0 + 16.0) + (double)p->coarse.K.nc * (double)p->coarse.K.nc * 4.0 + (double)p->coarse.K.nc * 16.0;
                               break;
                           }
-                          launch_mg_apply(G, p->C, p->mg.M, p->mg.levels, p->K, sr ? p->C.r : ((kk & 1) ? p->C.r : p->C.r2), p->C.z, p->C.part_rz + (size_t)((kk & 1) ^ 1) * RZ_STRIDE, mg_scale(p), true, p->st, which == 6 && fused, mg_cs(p), mg_fine_view(p));
+                          PcgForm f = choose_form(p);
+                          const bool sr = f.single_red();
+                          if (which == 6) { pcg_matvec(p, f, kk, 0.0); if ((rc = pcg_update(p, f, kk)) != PGO_OK) return rc; }
+                          else f.post = PcgForm::mg_cycle;      // (the cycle alone: the restriction is its own)
+                          if ((rc = pcg_precond(p, f, kk)) != PGO_OK) return rc;
                           // Bytes of this design, each array once per kernel that streams it.  Fine level as in case 2 (+ the restriction's per-keyframe offsets and slot table,
                           // the prolongation's read-modify-write of z, offsets and aggregate index); every sparse coarse level: its fp32 blocks and column indices twice
                           // (down- and up-sweep), Dinv, positions/offsets and its four vectors; the dense level: the fp32 inverse once.
@@ -2138,12 +1586,12 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
                               else
                               cyc += (A.smoothed ? 4.0 : 2.0) * (double)A.nnzb * (144.0 + 4.0) + (double)A.n * ((A.smoothed ? 4.0 : 2.0) * 288.0 /* Dinv: smoothing steps */ + 24.0 + (A.smoothed ? 18.0 : 10.0) * 48.0 + 16.0);
                           }
-                          cyc += (double)p->K.nc * (double)p->K.nc * 4.0 + (double)p->K.nc * 16.0;
+                          cyc += (double)p->coarse.K.nc * (double)p->coarse.K.nc * 4.0 + (double)p->coarse.K.nc * 16.0;
                           bytes = which == 6 ? fine + cyc : cyc;
                           break; }
                 case 8: {     // this rank's kernels of one multigrid set-up (operators of an LM system incl. the dense inverse), without the exchanges between them
                           const bool hoff_valid = !p->built_mf || p->hoff_epoch == p->lin_epoch;
-                          if ((rc = mg_operators(p, p->d_cinfo.p, hoff_valid, true, -1.0)) != PGO_OK) return rc;
+                          if ((rc = mg_operators(p, p->coarse.d_cinfo.p, hoff_valid, true, -1.0)) != PGO_OK) return rc;
                           bytes = 0.0;
                           break; }
                 default: return PGO_ERR_INVALID_ARG;
