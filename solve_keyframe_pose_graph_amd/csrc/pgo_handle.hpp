@@ -34,6 +34,25 @@ inline bool debug_poison() { static const bool on = []() { const char* e = std::
 // of the multigrid's coarsest level is applied with the wrong sign — a preconditioner that is not positive definite, i.e. a forced PCG breakdown.
 inline bool debug_break_coarse() { if (!debug_hooks_enabled()) return false; const char* e = std::getenv("PGO_DEBUG_BREAK_COARSE"); return e && e[0] == '1' && e[1] == 0; }
 
+// PGO_DEBUG_NO_SPLIT_UPDATE=1 (read once per process): the multigrid PCG keeps the unsplit vector update (cg_update_mg_kernel<true>) where it would split it
+// (tests/test_gpu_split_update.py compares the two bit for bit).
+inline bool debug_no_split_update() { static const bool on = []() { const char* e = std::getenv("PGO_DEBUG_NO_SPLIT_UPDATE"); return debug_hooks_enabled() && e && e[0] == '1' && e[1] == 0; }(); return on; }
+// PGO_DEBUG_SPLIT_HOSTS=<a>,<b> (read once; for scans): the eligible launches of the cycle (mg_rider_hosts' order) that carry the split update's two riders, a <= b
+// (a == b: one launch carries both); ignored unless both exist on the hierarchy at hand
+inline bool debug_split_hosts(int* a, int* b) {
+    static const int v = []() {
+        const char* e = std::getenv("PGO_DEBUG_SPLIT_HOSTS");
+        if (!debug_hooks_enabled() || !e) return -1;
+        char* end = nullptr; const long x = std::strtol(e, &end, 10);
+        if (!end || *end != ',' || x < 0 || x > 63) return -1;
+        const long y = std::strtol(end + 1, &end, 10);
+        return (end && *end == 0 && y >= x && y <= 63) ? (int)(x * 64 + y) : -1;
+    }();
+    if (v < 0) return false;
+    *a = v / 64; *b = v % 64;
+    return true;
+}
+
 // PGO_DEBUG_GRAPH_AFTER=<n> (read once): the PCG captures its chunk as a hipGraph after n eager iterations instead of 192; values that are not an even number in [2, 10^6] are ignored
 inline int debug_graph_after() {
     static const int v = []() {
@@ -310,6 +329,7 @@ struct PcgForm {
     enum Post { none, mg_cycle, mg_restricted, two_level };                        // the multigrid cycle (restriction inside the update or not), the unfused two-level correction
     Rec rec; Post post;
     int fused_parts;                     // the fused two-level method: the update kernel's r.z partial slots (the dense solve's C.extra_rz follow them)
+    UpdSplit split;                      // sr + mg_restricted: the launches of the cycle that carry the half of the update nothing waits for (off: the unsplit kernel)
     bool single_red() const { return rec == sr || rec == sr_coarse; }
     bool fused_coarse() const { return rec == sr_coarse || rec == classic_coarse; }
     bool mg() const { return post == mg_cycle || post == mg_restricted; }

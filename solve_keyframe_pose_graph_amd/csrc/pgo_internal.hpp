@@ -212,6 +212,19 @@ struct CgDev {
     double* scal;         // [0]=||b||^2_{M^-1} [1]=last r.z [2]=unused [3]=squared relative tolerance
     int32_t* flags;       // [0]=done [1]=breakdown [2]=iterations
 };
+// The split single-reduction update of the multigrid PCG (one GPU, restriction inside the update): cg_update_mg_crit_kernel does what the cycle waits for, the rest of the
+// update RIDES in two of the cycle's sparse-level launches, as `riders` extra workgroups behind the launch's own (cg_update's workgroup -> keyframe mapping and r.u slots):
+//   kind & 1  direction and solution  p = u + beta p, x += alpha p     (reads u in z: a launch BEFORE the one that carries kind & 2)
+//   kind & 2  block-Jacobi part       z = D^-1 r, partials of r.z      (a launch before the one that adds P_0 x_1 to z)
+// alpha and gamma are the head's (scal[9 + 2 parity], scal[8 + 2 parity]); beta = gamma / gamma_prev is formed again from the same two doubles.
+struct UpdRiderDev {
+    int32_t kind, riders, parity, first;      // kind 0: the launch carries nothing
+    int64_t N;
+    const double* scal; const double* r; const float* Lf;
+    double* z; double* p; double* x; double* part_rz;      // part_rz: the slots of the NEXT iteration's parity
+};
+// which two launches of the cycle carry the riders: ordinals among the cycle's eligible launches (mg_rider_hosts), -1: the unsplit kernel
+struct UpdSplit { int host_a = -1, host_b = -1; bool on() const { return host_a >= 0; } };
 
 // ---- launchers (pgo_kernels.hip).  All asynchronous on `st`. ----
 void launch_k1(const GraphDev& G, const double* pose8, const double* sw, bool want_jacobian, double* partials /*[MAX_PARTIALS]*/, int* n_partials, hipStream_t st);
@@ -326,10 +339,14 @@ struct MgExchangeHook { void* ctx; int (*fn)(void* ctx, int point, int level); }
 void launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, const double* r, double* z, double* part_rz, double scale, bool inside_iteration, hipStream_t st,
                      bool restricted = false /* r_1 (and x_1) already formed by launch_cg_update_mg */, double prolong_scale = 0.0 /* c of the smoothed transitions */,
                      const MgLevelDev* fine = nullptr /* smoothed keyframe transition: the keyframe level's transfer view (r_1 = Ps_0^T r and z += s Ps_0 x_1 by kernels of their own) */,
-                     const MgExchangeHook* hook = nullptr /* several ranks: called where the cycle needs rows of other ranks */, int* hook_rc = nullptr);
+                     const MgExchangeHook* hook = nullptr /* several ranks: called where the cycle needs rows of other ranks */, int* hook_rc = nullptr,
+                     const UpdSplit* split = nullptr /* after launch_cg_update_mg_crit: the launches that carry the rest of the update */, int parity = 0, int first = 0,
+                     int* n_hosts = nullptr /* out: the eligible launches this cycle made — mg_rider_hosts' count, or the two enumerations have drifted apart */);
+int mg_rider_hosts(const CgDev& C, const MgDev& M, const MgLevelDev* levels, int* tiles /*[2 MG_MAX_LEVELS]*/);      // launches of a restricted cycle that can carry riders (their own workgroups, launch order)
 // cg_update + r_1 = P_0^T r', x_1 = w D_1^-1 r_1 of the multigrid (M.blk_tab)
 void launch_cg_update_mg(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int n_pq_partials, hipStream_t st);
 void launch_cg_update_mg_sr(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int first, int n_pq_partials, hipStream_t st);      // single-reduction form (cg_update_kernel<true>) with the same restriction
+void launch_cg_update_mg_crit(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int first, int n_pq_partials, hipStream_t st);    // ... its critical half only (UpdRiderDev): launch_mg_apply(split) must follow
 
 double k1_algorithmic_bytes(const GraphDev& G, bool want_jacobian);
 

@@ -587,13 +587,81 @@ __global__ __launch_bounds__(CG_BLOCK) void mg_smooth_step_kernel(MgLevelDev A, 
     __shared__ double tb[CG_BLOCK];
     mg_smooth_step_tile(A, (int)blockIdx.x + A.tile0, in_r, in_x, out_w, add1, add2, out, cs, stop, xch, tb);
 }
+// ---- riders: the half of the split single-reduction update that nothing waits for until the level-1 up-sweep (UpdRiderDev, pgo_internal.hpp) ----
+// Rider workgroup `rb` of `U.riders` takes the keyframes workgroup rb of cg_update_mg_kernel takes.  The expressions are those of cg_update_mg_body, statement by statement.
+__device__ __forceinline__ void upd_rider_direction(const UpdRiderDev& U, int rb) {
+    const double alpha = U.scal[9 + 2 * U.parity], gamma = U.scal[8 + 2 * U.parity];
+    double beta = 0.0;
+    if (!U.first) { const double gamma_prev = U.scal[8 + 2 * (U.parity ^ 1)]; beta = gamma / gamma_prev; }
+    const double2* __restrict__ zv = reinterpret_cast<const double2*>(U.z);
+    double2* __restrict__ pout = reinterpret_cast<double2*>(U.p);
+    double2* __restrict__ xv = reinterpret_cast<double2*>(U.x);
+    const int64_t pairs = U.N * 3;
+    for (int64_t i = (int64_t)rb * CG_BLOCK + threadIdx.x; i < pairs; i += (int64_t)U.riders * CG_BLOCK) {
+        const double2 u0 = zv[i];
+        double2 p0 = pout[i], x0 = xv[i];
+        p0.x = u0.x + beta * p0.x; p0.y = u0.y + beta * p0.y;
+        x0.x += alpha * p0.x; x0.y += alpha * p0.y;
+        pout[i] = p0; xv[i] = x0;
+    }
+}
+// lds: 2 CG_BLOCK doubles (the trip's residual) + CG_BLOCK / 3 x LF_STRIDE floats (its block-Jacobi factors), 16-B aligned: 9 KB of the host kernel's buffers; red: CG_BLOCK / 64 doubles
+__device__ __forceinline__ void upd_rider_jacobi(const UpdRiderDev& U, int rb, double* lds, double* red) {
+    constexpr int KF = CG_BLOCK / 3;
+    double2* rnew = reinterpret_cast<double2*>(lds);
+    float* lfs = reinterpret_cast<float*>(lds + 2 * CG_BLOCK);
+    const double2* __restrict__ rin = reinterpret_cast<const double2*>(U.r);
+    double2* __restrict__ zv = reinterpret_cast<double2*>(U.z);
+    const int t = threadIdx.x;
+    const int64_t pairs = U.N * 3;
+    const int64_t stride = (int64_t)U.riders * CG_BLOCK;
+    const int64_t trips = (pairs + stride - 1) / stride;
+    double acc = 0.0;
+    for (int64_t it = 0; it < trips; ++it) {
+        const int64_t base = (it * U.riders + rb) * CG_BLOCK;
+        const int64_t i = base + t;
+        const bool live = i < pairs;
+        double2 rr = make_double2(0.0, 0.0);
+        float4 lf0 = make_float4(0.f, 0.f, 0.f, 0.f), lf1 = lf0;
+        if (live) rr = rin[i];
+        const int64_t first_node = base / 3;
+        const float4* lp = reinterpret_cast<const float4*>(U.Lf + (size_t)first_node * LF_STRIDE);
+        if (first_node + t / 6 < U.N) lf0 = lp[t];
+        if (first_node + (t + CG_BLOCK) / 6 < U.N) lf1 = lp[t + CG_BLOCK];
+        reinterpret_cast<float4*>(lfs)[t] = lf0; reinterpret_cast<float4*>(lfs)[t + CG_BLOCK] = lf1;
+        rnew[t] = rr;
+        __syncthreads();
+        if (live) {
+            const int j = t % 3;
+            const double* r6 = reinterpret_cast<const double*>(rnew + (t - j));
+            const double2 z = lf_apply_pair(lfs + (t / 3) * LF_STRIDE, r6, j);
+            zv[i] = z;
+            acc += rr.x * z.x + rr.y * z.y;
+        }
+        if (it + 1 < trips) __syncthreads();      // the LDS buffers are rewritten by the next trip
+    }
+    const double s = block_sum(acc, red);
+    if (threadIdx.x == 0) U.part_rz[rb] = s;
+    static_assert(KF * LF_STRIDE / 4 == 2 * CG_BLOCK, "two 16-B loads per lane stage a trip's factors");
+}
+// the workgroups of a level launch behind its own `own` tiles; true: this workgroup was a rider (it has nothing else to do)
+__device__ __forceinline__ bool upd_riders(const UpdRiderDev& U, int own, const int32_t* __restrict__ stop, double* lds, double* red) {
+    if (U.kind == 0 || (int)blockIdx.x < own) return false;
+    const int rb = (int)blockIdx.x - own;
+    if ((stop && *stop) || rb >= U.riders) return true;
+    if (U.kind & 1) upd_rider_direction(U, rb);
+    if (U.kind & 2) upd_rider_jacobi(U, rb, lds, red);      // (both in one launch: a lane writes the z entries it has read itself)
+    return true;
+}
 // Down-sweep of a level with a smoothed transition above it, explicit form (MgLevelDev::rt_valf; pgo_mg_host.hpp) — ONE launch, two independent kinds of workgroups:
 //   the level's own tiles:           v = x_pre + Dinv (r - A x_pre)                                  -> A.y   (the smoothing step; the up-sweep only adds R^T x_next to it)
 //   tiles of consecutive coarse rows: r_next = R r  (R = (Ps - Dinv W)^T, fp32 blocks by coarse row)  -> r_next, and x_next = Dinv_next r_next when the level above is a sparse one
 // instead of the implicit form's two dependent launches (t = r - A x_pre, u = c Dinv t;  r_next = P^T (t - A u)): the same r_next = Ps^T (r - A x_pre) algebraically.
-__global__ __launch_bounds__(CG_BLOCK) void mg_sdown_kernel(MgLevelDev A, double* __restrict__ r_next, double* __restrict__ x_next, const double* __restrict__ Dinv_next, const int32_t* __restrict__ stop) {
-    __shared__ double xch[CG_BLOCK * 7];
+__global__ __launch_bounds__(CG_BLOCK) void mg_sdown_kernel(MgLevelDev A, double* __restrict__ r_next, double* __restrict__ x_next, const double* __restrict__ Dinv_next, const int32_t* __restrict__ stop,
+                                                             UpdRiderDev U) {
+    __shared__ __attribute__((aligned(16))) double xch[CG_BLOCK * 7];
     __shared__ double tb[CG_BLOCK];
+    if (upd_riders(U, A.tiles_own + A.rT_tiles, stop, xch, tb)) return;
     if ((int)blockIdx.x < A.tiles_own) { mg_smooth_step_tile(A, (int)blockIdx.x + A.tile0, A.r, A.x, nullptr, A.x, nullptr, A.y, 1.0, stop, xch, tb); return; }
     const int stopped = stop ? *stop : 0;
     const int tile = (int)blockIdx.x - A.tiles_own;
@@ -921,10 +989,11 @@ extern "C" int pgo_debug_mg_timeline(unsigned long long* out, int n) {
 // tile_info -> rowptr -> col -> x is the only chain here; everything else a lane will need (its r entry, its row's offset d, the member
 // range of its aggregate, the Dinv row of the next level) is requested up front, before the first barrier.
 __global__ __launch_bounds__(CG_BLOCK) void mg_down_kernel(MgLevelDev A, double* __restrict__ r_next, double* __restrict__ x_next, const double* __restrict__ Dinv_next,
-                                                            const int32_t* __restrict__ stop) {
-    __shared__ double xch[CG_BLOCK * 7];
+                                                            const int32_t* __restrict__ stop, UpdRiderDev U) {
+    __shared__ __attribute__((aligned(16))) double xch[CG_BLOCK * 7];
     __shared__ double tb[CG_BLOCK];
     __shared__ double cb[CG_BLOCK];
+    if (upd_riders(U, A.tiles_own, stop, xch, tb)) return;
     MG_TL(0);
     const int stopped = stop ? *stop : 0;
     const int q6 = threadIdx.x / 6, c = threadIdx.x % 6;
@@ -1022,10 +1091,11 @@ __global__ __launch_bounds__(384) void mg_dense_solve_kernel(CoarseDev K, MgLeve
 template <bool FINE>
 __global__ __launch_bounds__(CG_BLOCK) void mg_up_kernel(MgLevelDev A, MgLevelDev Below, int has_below, double scale, const int32_t* __restrict__ stop,
                                                           MgDev M, const double* __restrict__ rfine, double* __restrict__ zfine, double* __restrict__ part_extra,
-                                                          const double* __restrict__ xnext = nullptr) {
-    __shared__ double xch[CG_BLOCK * 7];
+                                                          const double* __restrict__ xnext, UpdRiderDev U) {
+    __shared__ __attribute__((aligned(16))) double xch[CG_BLOCK * 7];
     __shared__ double tb[CG_BLOCK];
     __shared__ double xb[CG_BLOCK];
+    if (!FINE && upd_riders(U, A.tiles_own, stop, xch, tb)) return;      // (FINE: the level-1 up-sweep reads what the riders write)
     const int stopped = stop ? *stop : 0;
     const int q6 = threadIdx.x / 6, c = threadIdx.x % 6;
     const int li = q6 & ((MG_TILE_ROWS >> A.seg_shift) - 1), sg = q6 >> (5 - A.seg_shift);
@@ -1173,9 +1243,13 @@ __global__ __launch_bounds__(CG_BLOCK) void mg_prolong0_kernel(GraphDev G, MgDev
 #else
 #define PGO_SR_MG_WAVES 3
 #endif
-template <bool SR>
-__global__ __launch_bounds__(CG_BLOCK, SR ? PGO_SR_MG_WAVES : 1) void cg_update_mg_kernel(GraphDev G, CgDev C, MgDev M, double* __restrict__ r1_out, double* __restrict__ x1_out, const double* __restrict__ Dinv1,
-                                                                 int parity, int nparts_pq, int nparts, int first) {
+// CRIT (single-reduction form only): the half of the update the cycle waits for — the head, s = w + beta s, r -= alpha s, r_1, x_1.  The other half (p, x, the block-Jacobi
+// part of the next u and the partials of r.u) rides in two of the cycle's sparse-level launches: upd_rider_direction / upd_rider_jacobi above evaluate the SAME source
+// expressions (-ffp-contract=on fuses inside one expression only), so every vector entry and every partial-sum slot holds the bits the unsplit kernel leaves.
+template <bool SR, bool CRIT>
+__device__ __forceinline__ void cg_update_mg_body(GraphDev G, CgDev C, MgDev M, double* __restrict__ r1_out, double* __restrict__ x1_out, const double* __restrict__ Dinv1,
+                                                  int parity, int nparts_pq, int nparts, int first) {
+    static_assert(SR || !CRIT, "the split update exists in the single-reduction form only");
     static_assert(CG_BLOCK / 3 == MG_BLOCK0, "one workgroup trip of the vector update = one run of the slot table");
     __shared__ double red[2 * (CG_BLOCK / 64) + 1];
     const double2* __restrict__ rin = reinterpret_cast<const double2*>(SR ? C.r : (parity ? C.r2 : C.r));
@@ -1207,14 +1281,17 @@ __global__ __launch_bounds__(CG_BLOCK, SR ? PGO_SR_MG_WAVES : 1) void cg_update_
             tab1 = M.blk_tab[(size_t)run * MG_BLOCK0 + (t + CG_BLOCK) / 6];
         }
         if (i < pairs) {
-            r0 = rin[i]; q0 = qv[i]; p0 = pcur[i]; x0 = xv[i];
-            if (SR) { u0 = zv[i]; s0 = sv[i]; }
+            r0 = rin[i]; q0 = qv[i];
+            if (!CRIT) { p0 = pcur[i]; x0 = xv[i]; }
+            if (SR) { if (!CRIT) u0 = zv[i]; s0 = sv[i]; }
             const double* d = M.d0 + (size_t)(i / 3) * 3; d0 = d[0]; d1 = d[1]; d2 = d[2];
         }
         const int64_t first_node = base / 3;
-        const float4* lp = reinterpret_cast<const float4*>(C.Lf + (size_t)first_node * LF_STRIDE);
-        if (first_node + t / 6 < G.N) lf0 = lp[t];
-        if (first_node + (t + CG_BLOCK) / 6 < G.N) lf1 = lp[t + CG_BLOCK];
+        if (!CRIT) {
+            const float4* lp = reinterpret_cast<const float4*>(C.Lf + (size_t)first_node * LF_STRIDE);
+            if (first_node + t / 6 < G.N) lf0 = lp[t];
+            if (first_node + (t + CG_BLOCK) / 6 < G.N) lf1 = lp[t + CG_BLOCK];
+        }
 #pragma unroll
         for (int jj = 0; jj < 6; ++jj) { Dk0[jj] = 0.0; Dk1[jj] = 0.0; }
         if (x1_out) {
@@ -1249,18 +1326,19 @@ __global__ __launch_bounds__(CG_BLOCK, SR ? PGO_SR_MG_WAVES : 1) void cg_update_
         double2 rr = make_double2(0.0, 0.0);
         if (live) {
             if (SR) {
-                p0.x = u0.x + beta * p0.x; p0.y = u0.y + beta * p0.y;
+                if (!CRIT) { p0.x = u0.x + beta * p0.x; p0.y = u0.y + beta * p0.y; }
                 s0.x = q0.x + beta * s0.x; s0.y = q0.y + beta * s0.y;
                 rr = make_double2(r0.x - alpha * s0.x, r0.y - alpha * s0.y);
-                x0.x += alpha * p0.x; x0.y += alpha * p0.y;
-                pout[i] = p0; sv[i] = s0;
+                if (!CRIT) { x0.x += alpha * p0.x; x0.y += alpha * p0.y; pout[i] = p0; }
+                sv[i] = s0;
             } else {
                 rr = make_double2(r0.x - alpha * q0.x, r0.y - alpha * q0.y);
                 x0.x += alpha * p0.x; x0.y += alpha * p0.y;
             }
-            rout[i] = rr; xv[i] = x0;
+            rout[i] = rr;
+            if (!CRIT) xv[i] = x0;
         }
-        reinterpret_cast<float4*>(lfs)[t] = lf0; reinterpret_cast<float4*>(lfs)[t + CG_BLOCK] = lf1;
+        if (!CRIT) { reinterpret_cast<float4*>(lfs)[t] = lf0; reinterpret_cast<float4*>(lfs)[t + CG_BLOCK] = lf1; }
         rnew[t] = rr;
         const double e0 = d0, e1 = d1, e2 = d2;
         const int4 tb0 = tab0, tb1 = tab1;
@@ -1273,7 +1351,7 @@ __global__ __launch_bounds__(CG_BLOCK, SR ? PGO_SR_MG_WAVES : 1) void cg_update_
             else if (j == 1) b = make_double2(r6[2] + 2.0 * (e0 * r6[4] - e1 * r6[3]), r6[3]);
             else b = make_double2(r6[4], r6[5]);
             btr[t] = b;
-            if (live) {
+            if (!CRIT && live) {
                 const double2 z = lf_apply_pair(lfs + (t / 3) * LF_STRIDE, r6, j);
                 zv[i] = z;
                 acc += rr.x * z.x + rr.y * z.y;
@@ -1316,8 +1394,21 @@ __global__ __launch_bounds__(CG_BLOCK, SR ? PGO_SR_MG_WAVES : 1) void cg_update_
         (void)sum2;
         if (it + 1 < trips) { load_trip(run + gridDim.x); __syncthreads(); }      // (a prefetch during this trip's arithmetic costs 70 VGPRs: 196, two waves per SIMD); the LDS buffers are rewritten by the next trip
     }
+    if (CRIT) return;      // (the partials of r.u are upd_rider_jacobi's)
     const double s = block_sum(acc, red);
     if (threadIdx.x == 0) C.part_rz[(parity ^ 1) * RZ_STRIDE + blockIdx.x] = s;
+}
+template <bool SR>
+__global__ __launch_bounds__(CG_BLOCK, SR ? PGO_SR_MG_WAVES : 1) void cg_update_mg_kernel(GraphDev G, CgDev C, MgDev M, double* __restrict__ r1_out, double* __restrict__ x1_out, const double* __restrict__ Dinv1,
+                                                                 int parity, int nparts_pq, int nparts, int first) {
+    cg_update_mg_body<SR, false>(G, C, M, r1_out, x1_out, Dinv1, parity, nparts_pq, nparts, first);
+}
+#ifndef PGO_SR_CRIT_WAVES      // (variant builds.  3 and 4 compile to the same 101-VGPR code; 5 — 96 VGPRs, 6 spilled — measured no faster: DESIGN.md §9)
+#define PGO_SR_CRIT_WAVES 4
+#endif
+__global__ __launch_bounds__(CG_BLOCK, PGO_SR_CRIT_WAVES) void cg_update_mg_crit_kernel(GraphDev G, CgDev C, MgDev M, double* __restrict__ r1_out, double* __restrict__ x1_out, const double* __restrict__ Dinv1,
+                                                                                       int parity, int nparts_pq, int nparts, int first) {
+    cg_update_mg_body<true, true>(G, C, M, r1_out, x1_out, Dinv1, parity, nparts_pq, nparts, first);
 }
 void launch_cg_update_mg(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int n_pq_partials, hipStream_t st) {
     const int g = cg_grid(G);
@@ -1329,9 +1420,51 @@ void launch_cg_update_mg_sr(const GraphDev& G, const CgDev& C, const MgDev& M, c
     if (M.n_levels == 1) hipLaunchKernelGGL(cg_update_mg_kernel<true>, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, K.rc, (double*)nullptr, (const double*)nullptr, k & 1, n_pq_partials, g, first);
     else hipLaunchKernelGGL(cg_update_mg_kernel<true>, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, levels[0].r, levels[0].x, (const double*)levels[0].Dinv, k & 1, n_pq_partials, g, first);
 }
+void launch_cg_update_mg_crit(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int first, int n_pq_partials, hipStream_t st) {
+    const int g = cg_grid(G);
+    if (M.n_levels == 1) hipLaunchKernelGGL(cg_update_mg_crit_kernel, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, K.rc, (double*)nullptr, (const double*)nullptr, k & 1, n_pq_partials, g, first);
+    else hipLaunchKernelGGL(cg_update_mg_crit_kernel, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, levels[0].r, levels[0].x, (const double*)levels[0].Dinv, k & 1, n_pq_partials, g, first);
+}
+// The launches of a `restricted` cycle on one GPU that can carry riders of the split update, in launch order — the CG_BLOCK-sized sparse-level launches between the update and
+// the kernel that adds P_0 x_1 to z (launch_mg_apply counts the same launches in the same order): tiles[e] = the launch's own workgroups.  Returns their number.
+int mg_rider_hosts(const CgDev& C, const MgDev& M, const MgLevelDev* levels, int* tiles) {
+    const int nl = M.n_levels;
+    const bool fused = C.extra_rz > 0;
+    int n = 0;
+    for (int l = 1; l < nl; ++l) {
+        const MgLevelDev& A = levels[l - 1];
+        if (A.smoothed && A.rt_valf) { if (A.tiles_own + A.rT_tiles > 0) tiles[n++] = A.tiles_own + A.rT_tiles; }
+        else if (A.tiles_own > 0) tiles[n++] = A.tiles_own;
+    }
+    for (int l = nl - 1; l >= 1; --l) {
+        const MgLevelDev& A = levels[l - 1];
+        if (A.tiles_own == 0 || (l == 1 && fused)) continue;
+        tiles[n++] = A.tiles_own;
+    }
+    return n;
+}
 void launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, const double* r, double* z, double* part_rz, double scale, bool inside_iteration, hipStream_t st,
                      bool restricted, double prolong_scale, const MgLevelDev* fine /* transfer view of the keyframe level: smoothed keyframe transition (never `restricted`, never fused) */,
-                     const MgExchangeHook* hook, int* hook_rc) {
+                     const MgExchangeHook* hook, int* hook_rc, const UpdSplit* split, int parity, int first, int* n_hosts) {
+    // the split update's riders: eligible launch number `e` (mg_rider_hosts' order) carries what the split assigns to it, as cg_grid more workgroups
+    UpdRiderDev U0{}; U0.kind = 0;
+    int e_next = 0;
+    unsigned rider_wgs = 0;
+    auto rider = [&]() {
+        UpdRiderDev U = U0;
+        rider_wgs = 0;
+        if (split && split->on()) {
+            const int e = e_next;
+            U.kind = (e == split->host_a ? 1 : 0) | (e == split->host_b ? 2 : 0);
+            if (U.kind) {
+                U.riders = cg_grid(G); U.parity = parity; U.first = first; U.N = G.N;
+                U.scal = C.scal; U.r = r; U.Lf = C.Lf; U.z = z; U.p = C.p; U.x = C.x; U.part_rz = part_rz;
+                rider_wgs = (unsigned)U.riders;
+            }
+        }
+        ++e_next;
+        return U;
+    };
     const int32_t* stop = inside_iteration ? C.flags : nullptr;     // at PCG start the flag still belongs to the previous solve
     const int nl = M.n_levels;
     const unsigned g1 = (unsigned)((std::max(M.a1 - M.a0, 0) + MG_TILE_ROWS - 1) / MG_TILE_ROWS);      // (several ranks: the rank's own aggregates)
@@ -1341,8 +1474,8 @@ void launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const Mg
     if (restricted) {}
     else if (fine) {      // r_1 = Ps_0^T r (and x_1 = Dinv_1 r_1): the restriction half of mg_sdown_kernel on the keyframe level's transfer view, which has no tiles of its own
         MgLevelDev T = *fine; T.tiles = 0; T.tiles_own = 0; T.r = const_cast<double*>(r);
-        if (nl == 1) hipLaunchKernelGGL(mg_sdown_kernel, dim3((unsigned)T.rT_tiles), dim3(CG_BLOCK), 0, st, T, K.rc, (double*)nullptr, (const double*)nullptr, stop);
-        else hipLaunchKernelGGL(mg_sdown_kernel, dim3((unsigned)T.rT_tiles), dim3(CG_BLOCK), 0, st, T, levels[0].r, levels[0].x, (const double*)levels[0].Dinv, stop);
+        if (nl == 1) hipLaunchKernelGGL(mg_sdown_kernel, dim3((unsigned)T.rT_tiles), dim3(CG_BLOCK), 0, st, T, K.rc, (double*)nullptr, (const double*)nullptr, stop, U0);
+        else hipLaunchKernelGGL(mg_sdown_kernel, dim3((unsigned)T.rT_tiles), dim3(CG_BLOCK), 0, st, T, levels[0].r, levels[0].x, (const double*)levels[0].Dinv, stop, U0);
     }
     else if (g1 == 0) {}
     else if (nl == 1) hipLaunchKernelGGL(mg_restrict0_kernel, dim3(g1), dim3(CG_BLOCK), 0, st, M, r, K.rc, (double*)nullptr, (const double*)nullptr, stop);
@@ -1354,8 +1487,9 @@ void launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const Mg
         if (A.smoothed && A.rt_valf) {      // explicit transfer operator: smoothing step and restriction in one launch (two kinds of workgroups)
             const unsigned g = (unsigned)(A.tiles_own + A.rT_tiles);
             if (g == 0) continue;
-            if (l + 1 == nl) hipLaunchKernelGGL(mg_sdown_kernel, dim3(g), dim3(CG_BLOCK), 0, st, A, K.rc, (double*)nullptr, (const double*)nullptr, stop);
-            else hipLaunchKernelGGL(mg_sdown_kernel, dim3(g), dim3(CG_BLOCK), 0, st, A, levels[l].r, levels[l].x, (const double*)levels[l].Dinv, stop);
+            const UpdRiderDev U = rider();
+            if (l + 1 == nl) hipLaunchKernelGGL(mg_sdown_kernel, dim3(g + rider_wgs), dim3(CG_BLOCK), 0, st, A, K.rc, (double*)nullptr, (const double*)nullptr, stop, U);
+            else hipLaunchKernelGGL(mg_sdown_kernel, dim3(g + rider_wgs), dim3(CG_BLOCK), 0, st, A, levels[l].r, levels[l].x, (const double*)levels[l].Dinv, stop, U);
             continue;
         }
         if (A.tiles_own == 0) continue;
@@ -1364,8 +1498,9 @@ void launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const Mg
             hipLaunchKernelGGL(mg_smooth_step_kernel, dim3((unsigned)A.tiles_own), dim3(CG_BLOCK), 0, st, A, (const double*)A.r, (const double*)A.x, A.t, (const double*)nullptr, (const double*)nullptr, A.u, prolong_scale, stop);
             A.r = A.t; A.x = A.u;
         }
-        if (l + 1 == nl) hipLaunchKernelGGL(mg_down_kernel, dim3((unsigned)A.tiles_own), dim3(CG_BLOCK), 0, st, A, K.rc, (double*)nullptr, (const double*)nullptr, stop);
-        else hipLaunchKernelGGL(mg_down_kernel, dim3((unsigned)A.tiles_own), dim3(CG_BLOCK), 0, st, A, levels[l].r, levels[l].x, (const double*)levels[l].Dinv, stop);
+        const UpdRiderDev U = rider();
+        if (l + 1 == nl) hipLaunchKernelGGL(mg_down_kernel, dim3((unsigned)A.tiles_own + rider_wgs), dim3(CG_BLOCK), 0, st, A, K.rc, (double*)nullptr, (const double*)nullptr, stop, U);
+        else hipLaunchKernelGGL(mg_down_kernel, dim3((unsigned)A.tiles_own + rider_wgs), dim3(CG_BLOCK), 0, st, A, levels[l].r, levels[l].x, (const double*)levels[l].Dinv, stop, U);
     }
     // the level below a kernel that prolongs: with a smoothed transition it must receive the bare correction e = P x (xt = 0 + P x), smoothed afterwards
     auto below_of = [&](int idx) { MgLevelDev B = levels[idx]; if (B.smoothed) B.x = const_cast<double*>(B.zero); return B; };
@@ -1382,8 +1517,11 @@ void launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const Mg
         if (A.tiles_own == 0) continue;
         if (expl_at(l - 1)) {      // x = v + s R^T x_next: prolongation and post-smoothing in one launch
             const double* xn = l + 1 == nl ? (const double*)K.yc : (const double*)levels[l].xf;
-            if (l == 1 && fused) hipLaunchKernelGGL(mg_up_kernel<true>, dim3((unsigned)(A.tiles_own < MAX_PARTIALS ? A.tiles_own : MAX_PARTIALS)), dim3(CG_BLOCK), 0, st, A, A, 0, scale, stop, M, r, z, part_rz + g0, xn);
-            else hipLaunchKernelGGL(mg_up_kernel<false>, dim3((unsigned)A.tiles_own), dim3(CG_BLOCK), 0, st, A, l >= 2 ? below_of(l - 2) : levels[0], l >= 2 && !expl_at(l - 2) ? 1 : 0, scale, stop, M, r, z, part_rz, xn);
+            if (l == 1 && fused) hipLaunchKernelGGL(mg_up_kernel<true>, dim3((unsigned)(A.tiles_own < MAX_PARTIALS ? A.tiles_own : MAX_PARTIALS)), dim3(CG_BLOCK), 0, st, A, A, 0, scale, stop, M, r, z, part_rz + g0, xn, U0);
+            else {
+                const UpdRiderDev U = rider();
+                hipLaunchKernelGGL(mg_up_kernel<false>, dim3((unsigned)A.tiles_own + rider_wgs), dim3(CG_BLOCK), 0, st, A, l >= 2 ? below_of(l - 2) : levels[0], l >= 2 && !expl_at(l - 2) ? 1 : 0, scale, stop, M, r, z, part_rz, xn, U);
+            }
             continue;
         }
         if (A.smoothed) {
@@ -1391,11 +1529,15 @@ void launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const Mg
             hipLaunchKernelGGL(mg_smooth_step_kernel, dim3((unsigned)A.tiles_own), dim3(CG_BLOCK), 0, st, A, (const double*)nullptr, (const double*)A.xt, (double*)nullptr, (const double*)A.x, (const double*)A.xt, A.y, prolong_scale, stop);
             A.xt = A.y;
         }
-        if (l == 1 && fused) hipLaunchKernelGGL(mg_up_kernel<true>, dim3((unsigned)(A.tiles_own < MAX_PARTIALS ? A.tiles_own : MAX_PARTIALS)), dim3(CG_BLOCK), 0, st, A, A, 0, scale, stop, M, r, z, part_rz + g0, (const double*)nullptr);
-        else hipLaunchKernelGGL(mg_up_kernel<false>, dim3((unsigned)A.tiles_own), dim3(CG_BLOCK), 0, st, A, l >= 2 ? below_of(l - 2) : levels[0], l >= 2 && !expl_at(l - 2) ? 1 : 0, scale, stop, M, r, z, part_rz, (const double*)nullptr);
+        if (l == 1 && fused) hipLaunchKernelGGL(mg_up_kernel<true>, dim3((unsigned)(A.tiles_own < MAX_PARTIALS ? A.tiles_own : MAX_PARTIALS)), dim3(CG_BLOCK), 0, st, A, A, 0, scale, stop, M, r, z, part_rz + g0, (const double*)nullptr, U0);
+        else {
+            const UpdRiderDev U = rider();
+            hipLaunchKernelGGL(mg_up_kernel<false>, dim3((unsigned)A.tiles_own + rider_wgs), dim3(CG_BLOCK), 0, st, A, l >= 2 ? below_of(l - 2) : levels[0], l >= 2 && !expl_at(l - 2) ? 1 : 0, scale, stop, M, r, z, part_rz, (const double*)nullptr, U);
+        }
     }
     xchg(2, 1);
     if (hook_failed) return;
     if (fine) hipLaunchKernelGGL(mg_prolong0s_kernel, dim3(g0), dim3(CG_BLOCK), 0, st, G, *fine, (const double*)(nl == 1 ? K.yc : levels[0].xf), r, z, part_rz, scale, stop);
     else if (!fused) hipLaunchKernelGGL(mg_prolong0_kernel, dim3(g0), dim3(CG_BLOCK), 0, st, G, M, (const double*)(nl == 1 ? K.yc : levels[0].xf), r, z, part_rz, scale, stop);
+    if (n_hosts) *n_hosts = e_next;
 }

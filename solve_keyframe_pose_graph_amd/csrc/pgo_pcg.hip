@@ -185,6 +185,24 @@ bool single_reduction(const pgo_problem* p) {
     return p->opt.cg_single_reduction != 0 && !p->local_ids && p->built_mf && p->opt.cg_rel_tolerance >= 1e-11 && p->N_global <= SINGLE_REDUCTION_MAX_KEYFRAMES &&
            (!two_level || coarse_group_keyframes(p->coarse.K) > 0);
 }
+// The split update (pgo_internal.hpp: UpdRiderDev): which two launches of the cycle carry its riders — the two eligible launches with the fewest workgroups of their own (most of
+// the GPU idle while they run), the earlier one the direction / solution half, the later one the block-Jacobi half.  A hierarchy with fewer than two eligible launches keeps
+// the unsplit kernel.  A rule on the hierarchy alone: the same for eager launches, captured chunks and pgo_time_kernel.
+static UpdSplit choose_split(const pgo_problem* p) {
+    UpdSplit sp;
+    if (debug_no_split_update() || mg_fine_view(p)) return sp;
+    int tiles[2 * MG_MAX_LEVELS];
+    const int n = mg_rider_hosts(p->C, p->mg.M, p->mg.levels, tiles);
+    if (n < 2) return sp;
+    int a = 0;
+    for (int e = 1; e < n; ++e) if (tiles[e] < tiles[a]) a = e;
+    int b = a == 0 ? 1 : 0;
+    for (int e = 0; e < n; ++e) if (e != a && tiles[e] < tiles[b]) b = e;
+    sp.host_a = std::min(a, b); sp.host_b = std::max(a, b);
+    int da, db;
+    if (debug_split_hosts(&da, &db) && db < n) { sp.host_a = da; sp.host_b = db; }
+    return sp;
+}
 PcgForm choose_form(const pgo_problem* p, bool this_rank_only) {
     PcgForm f{PcgForm::classic_csr, PcgForm::none, 0};
     const bool mg = p->mg.active, two_level = p->coarse.active && !mg;
@@ -197,6 +215,7 @@ PcgForm choose_form(const pgo_problem* p, bool this_rank_only) {
     if (fused_coarse) f.fused_parts = coarse_update_grid(p->G, p->coarse.K);
     else if (mg) f.post = f.rec != PcgForm::ranks && p->mg.M.blk_tab != nullptr ? PcgForm::mg_restricted : PcgForm::mg_cycle;      // (blk_tab: the vector update also restricts the new residual to level 1)
     else if (two_level) f.post = PcgForm::two_level;
+    if (f.rec == PcgForm::sr && f.post == PcgForm::mg_restricted) f.split = choose_split(p);
     return f;
 }
 // w = A u (with the partials of u.w; the classic forms: the new direction first, and the convergence test against tol2; the fused two-level method: the prolongation inside)
@@ -224,6 +243,7 @@ int pcg_update(pgo_problem* p, const PcgForm& f, int k) {
         ++p->st_pcg_iterations;
     } else if (f.rec == PcgForm::sr_coarse) launch_cg_update_restrict_sr(p->G, p->C, p->coarse.K, k, first, k > 0 ? 1 : 0, n_pq, p->st);
     else if (f.rec == PcgForm::classic_coarse) launch_cg_update_restrict(p->G, p->C, p->coarse.K, k, n_pq, p->st);
+    else if (f.rec == PcgForm::sr && restricted && f.split.on()) launch_cg_update_mg_crit(p->G, p->C, m.M, m.levels, p->coarse.K, k, first, n_pq, p->st);      // (pcg_precond's cycle carries the rest)
     else if (f.rec == PcgForm::sr && restricted) launch_cg_update_mg_sr(p->G, p->C, m.M, m.levels, p->coarse.K, k, first, n_pq, p->st);
     else if (f.rec == PcgForm::sr) launch_cg_update_sr(p->G, p->C, k, first, n_pq, p->st);
     else if (restricted) launch_cg_update_mg(p->G, p->C, m.M, m.levels, p->coarse.K, k, n_pq, p->st);
@@ -236,7 +256,16 @@ int pcg_precond(pgo_problem* p, const PcgForm& f, int k) {
     const double* const r = f.single_red() || (k & 1) ? p->C.r : p->C.r2;
     if (f.fused_coarse()) launch_coarse_solve_dot(p->coarse.K, p->C.flags, part_rz + f.fused_parts, p->st);      // the dense solve: y and the coarse part of r.u
     else if (f.mg() && f.rec == PcgForm::ranks) return mg_apply_ranks(p, true);      // u = D^-1 r + P0 V(P0^T r)
-    else if (f.mg()) launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->coarse.K, r, p->C.z, part_rz, mg_scale(p), true, p->st, f.post == PcgForm::mg_restricted, mg_cs(p), mg_fine_view(p));
+    else if (f.mg()) {
+        const bool split = f.rec == PcgForm::sr && f.post == PcgForm::mg_restricted && f.split.on();
+        int hosts = 0;
+        launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->coarse.K, r, p->C.z, part_rz, mg_scale(p), true, p->st, f.post == PcgForm::mg_restricted, mg_cs(p), mg_fine_view(p), nullptr, nullptr,
+                        split ? &f.split : nullptr, k & 1, k == 0 ? 1 : 0, &hosts);
+        if (split) {      // the riders were assigned by ordinal: the cycle must have made exactly the launches the split was chosen on
+            int tiles[2 * MG_MAX_LEVELS];
+            if (hosts != mg_rider_hosts(p->C, p->mg.M, p->mg.levels, tiles) || f.split.host_b >= hosts) { p->err = "split update: the cycle's launches differ from mg_rider_hosts' list"; return PGO_ERR_STATE; }
+        }
+    }
     else if (f.post == PcgForm::two_level) launch_coarse_apply(p->G, p->C, p->coarse.K, r, p->C.z, part_rz, true, p->st);
     return PGO_OK;
 }

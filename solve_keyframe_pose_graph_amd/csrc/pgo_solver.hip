@@ -1571,7 +1571,7 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
                           PcgForm f = choose_form(p);
                           const bool sr = f.single_red();
                           if (which == 6) { pcg_matvec(p, f, kk, 0.0); if ((rc = pcg_update(p, f, kk)) != PGO_OK) return rc; }
-                          else f.post = PcgForm::mg_cycle;      // (the cycle alone: the restriction is its own)
+                          else { f.post = PcgForm::mg_cycle; f.split = UpdSplit{}; }      // (the cycle alone: the restriction is its own, no update in front and no riders)
                           if ((rc = pcg_precond(p, f, kk)) != PGO_OK) return rc;
                           // Bytes of this design, each array once per kernel that streams it.  Fine level as in case 2 (+ the restriction's per-keyframe offsets and slot table,
                           // the prolongation's read-modify-write of z, offsets and aggregate index); every sparse coarse level: its fp32 blocks and column indices twice
@@ -1587,6 +1587,7 @@ int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg
                               cyc += (A.smoothed ? 4.0 : 2.0) * (double)A.nnzb * (144.0 + 4.0) + (double)A.n * ((A.smoothed ? 4.0 : 2.0) * 288.0 /* Dinv: smoothing steps */ + 24.0 + (A.smoothed ? 18.0 : 10.0) * 48.0 + 16.0);
                           }
                           cyc += (double)p->coarse.K.nc * (double)p->coarse.K.nc * 4.0 + (double)p->coarse.K.nc * 16.0;
+                          if (f.split.on()) cyc += N * 48.0;      // the split update: the block-Jacobi rider reads the new residual back
                           bytes = which == 6 ? fine + cyc : cyc;
                           break; }
                 case 8: {     // this rank's kernels of one multigrid set-up (operators of an LM system incl. the dense inverse), without the exchanges between them
