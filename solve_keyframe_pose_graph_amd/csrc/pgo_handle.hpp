@@ -1,6 +1,7 @@
-// pgo_handle.hpp — the problem handle (struct pgo_problem) and what the host translation units share: pgo_solver.hip (graph build, LM controller, C-ABI),
-// pgo_pcg.hip (the two-level method, the preconditioner of each LM system, the PCG driver) and pgo_multigrid.hip (the multigrid preconditioner's host lifecycle:
-// hierarchy build, install, regroup, operators of each LM system).  Internal: not installed.
+// pgo_handle.hpp — the problem handle (struct pgo_problem) and what the host translation units share: pgo_solver.hip (LM controller, core C-ABI), pgo_graph.hip (host edge
+// lists -> device graph), pgo_shard.hip (everything multi-rank above the transport: rank-local numbering, collectives, exchanges, communicator C-ABI, edge sharding),
+// pgo_pcg.hip (the two-level method, the preconditioner of each LM system, the PCG driver), pgo_multigrid.hip (the multigrid preconditioner's host lifecycle: hierarchy build,
+// install, regroup, operators of each LM system) and pgo_measure.hip (measurement helpers, test diagnostics).  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,6 +81,12 @@ struct DBuf {
         hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
         if (e == hipSuccess) cap = want;
         if (e == hipSuccess && debug_poison()) { e = hipMemset(p, 0xFF, want * sizeof(T)); if (e == hipSuccess) e = hipDeviceSynchronize(); }
+        return e;
+    }
+    // room for max(size, 1) elements, then the host vector's contents on `st`: asynchronous — the vector must outlive the caller's next hipStreamSynchronize(st)
+    hipError_t upload(const std::vector<T>& v, hipStream_t st) {
+        hipError_t e = ensure(v.empty() ? 1 : v.size());
+        if (e == hipSuccess && !v.empty()) e = hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st);
         return e;
     }
 };
@@ -308,7 +315,23 @@ struct pgo_problem {
 #pragma GCC visibility push(hidden)
 namespace pgo {
 
-// ---- pgo_solver.hip: the collectives (no-ops without a communicator) and what a graph without a hierarchy preconditions with
+// scalar slots of d_scal
+enum { S_COST = 0, S_PRIOR_COST = 1, S_MODEL = 2, S_SW_STEP2 = 3, S_SW_XNORM2 = 4, S_GMAX = 5, S_STEP2 = 6, S_XNORM2 = 7, S_N = 8 };
+
+inline int set_device(pgo_problem* p) { HIPCHK(p, hipSetDevice(p->device)); return PGO_OK; }
+inline double* part(pgo_problem* p, int k) { return p->d_part.p + (size_t)k * p->n_part; }      // partial-sum scratch array k
+
+// "A rejection is in the air": the previous step was rejected (rejections come in streaks: the radius shrinks over several steps), or the last accepted step's relative decrease
+// fell below 0.8 — the quadratic model is losing its grip (C3's and C4's first rejected steps follow rho = 0.67 and 0.62; the accepted hard steps of both follow rho >= 0.89).
+// build_system defers the multigrid of a hard system by it, lm_step arms both pauses of the PCG by it (a deferred build waits for the first of them).
+inline bool rejection_likely(const pgo_problem* p) { return p->reuse_diagonal || p->last_rho < 0.8; }
+
+// ---- pgo_graph.hip: host edge lists -> device graph
+int add_edges(pgo_problem* p, HostClass& H, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, const int32_t* sw);
+int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now);
+
+// ---- pgo_shard.hip: the rank-local subgraph, the collectives and neighbour exchanges (no-ops without a communicator), keyframe arrays local <-> global
+int number_rank_local(pgo_problem* p, int64_t n_global, int64_t* n_local);
 int allreduce(pgo_problem* p, double* buf, size_t n, int op /*0 sum, 2 max*/);
 int host_allreduce(pgo_problem* p, std::vector<double>& v, int op);
 int exchange_rows(pgo_problem* p, double* a1, int k1, double* a2, int k2, const int32_t* stop = nullptr);
@@ -316,6 +339,8 @@ int exchange_level(pgo_problem* p, int l, double* v1, double* v2, const int32_t*
 int exchange_blocks_copy(pgo_problem* p, const pgo_mg::ExchangePlan& X, const int32_t* send_idx, const int32_t* recv_idx, double* arr, int K);
 int exchange_blocks_sum(pgo_problem* p, const pgo_mg::BlockPlan& B, const SetupPlanDev& D, double* arr);
 int ensure_exchange_buffers(pgo_problem* p);
+int nodes_to_global(pgo_problem* p, const double* dev, int k, double* host_global);
+int nodes_from_global(pgo_problem* p, const double* host_global, int k, double* dev);
 
 // ---- pgo_pcg.hip: the two-level method, the preconditioner of each LM system, the PCG driver
 int build_two_level_aggregates(pgo_problem* p);

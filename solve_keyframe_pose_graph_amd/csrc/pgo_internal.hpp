@@ -1,5 +1,5 @@
 // pgo_internal.hpp — device data layout and kernel launch interface shared by pgo_kernels.hip (device code),
-// pgo_solver.hip (host LM controller + C-ABI) and pgo_comm.hip (the multi-rank transports: the in-process group's kernels).  gfx950 only.
+// the host units (pgo_solver / pgo_graph / pgo_shard / pgo_measure / pgo_pcg / pgo_multigrid .hip) and pgo_comm.hip (the transports: the in-process group's kernels).  gfx950 only.
 //
 // HBM layout (all fp64 unless noted; "tile" = 64 consecutive edges of one class = one wavefront of K1):
 //   pose8   [N][8]            qx qy qz qw tx ty tz pad — one 64-B record per keyframe (coalesced 16-B/lane loads,
@@ -181,7 +181,7 @@ struct MgLevelDev {
     int32_t tile0, tiles_own, rT_row0, rT_row1;
     // several ranks, distributed SET-UP (round 6): the set-up kernels of a distributed level work on this rank's rows [su_row0, su_row1) — its blocks [su_blk0, su_blk1), its blocks
     // of Ps [su_ps0, su_ps1) and of W [su_w0, su_w1) — and the product Ps^T W on the blocks of the level above its rows contribute to (su_prod, ascending; null: every block, the
-    // whole sum); what they read of other ranks' rows the block exchanges of pgo_solver.hip bring in.  One GPU, and levels every rank sets up completely: the whole level.
+    // whole sum); what they read of other ranks' rows the block exchanges of pgo_shard.hip bring in.  One GPU, and levels every rank sets up completely: the whole level.
     int32_t su_row0, su_row1, su_ps0, su_ps1, su_w0, su_w1, n_su_prod, pad4_;
     int64_t su_blk0, su_blk1;
     const int32_t* su_prod;
@@ -331,7 +331,7 @@ void launch_mg_transition_w(const MgLevelDev& A, hipStream_t st);               
 void launch_mg_transition_product(const MgLevelDev& A, const MgLevelDev& B, hipStream_t st);          // B = Ps^T W (several ranks: this rank's rows' part of it)
 void launch_mg_level_galerkin(const MgLevelDev& A, const MgLevelDev& B, hipStream_t st);              // B = P^T A P (plain transition)
 void launch_mg_dense_top(const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, hipStream_t st);
-// Several ranks: the cycle is cut into segments by the exchanges its kernels need (pgo_solver.hip issues them); launch_mg_apply calls the hook BEFORE the kernel that reads the
+// Several ranks: the cycle is cut into segments by the exchanges its kernels need (pgo_shard.hip issues them); launch_mg_apply calls the hook BEFORE the kernel that reads the
 // exchanged vectors.  point: 0 = down-sweep of `level` (1-based; n_levels = the dense solve) is about to read x (and r) of that level, 1 = the up-sweep of `level` is about to
 // read xt of that level (plain transition) or xf of level + 1 (explicit transfer operator), 2 = the prolongation to the keyframes is about to read xf of level 1.
 struct MgExchangeHook { void* ctx; int (*fn)(void* ctx, int point, int level); };

@@ -1,0 +1,291 @@
+// pgo_measure.hip — measurement helpers and test diagnostics of the C-ABI: HIP-event times and algorithmic bytes of the solver's kernels on the state of an open solve
+// (pgo_time_kernel), of K0 (pgo_time_vio_odometry_kernel) and of the dense inverse (pgo_dense_spd_inverse), and the sums of squares of a multigrid level's operators
+// (pgo_mg_level_norms).  Nothing here runs inside a solve's own steps.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "pgo_handle.hpp"
+
+namespace {
+
+// ---- pgo_time_kernel: what it measures
+//   0  K1 with Jacobians at the current state        3  K1 without Jacobians at the candidate state        1  K2
+//   2  one PCG iteration of the form the solver runs on this handle, block-Jacobi preconditioner (several ranks: the rank's own iteration, no exchanges);
+//   4  its matvec alone;  5  its vector update alone
+//   6  one multigrid-preconditioned PCG iteration;  7  the cycle's level kernels alone (several ranks: this rank's share, no exchanges)
+//   8  this rank's kernels of one multigrid set-up (operators of an LM system incl. the dense inverse), without the exchanges between them
+
+int build_lm_system(pgo_problem* p) {
+    const pgo_options& o = p->opt;
+    if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, o.min_lm_diagonal, o.max_lm_diagonal, p->st);
+    bool ok = true;
+    return build_system(p, &ok);
+}
+
+// 2 / 4 / 5: a live block-Jacobi PCG state to iterate on (tolerance 0: never converges during the timed launches)
+int setup_block_jacobi(pgo_problem* p) {
+    int rc;
+    if ((rc = build_lm_system(p)) != PGO_OK) return rc;
+    p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0;   // the timed iteration is the plain block-Jacobi one: no partial-sum slots of a multigrid / two-level solve
+    launch_cg_init(p->G, p->C, 0, 0.0, p->st);
+    return PGO_OK;
+}
+
+// 6 / 7 / 8: the multigrid operators of the current LM system and a live PCG state on them
+int setup_multigrid(pgo_problem* p, int which) {
+    if (!p->mg.built || !p->built_mf || (p->local_ids && which == 6)) { p->err = "pgo_time_kernel: this graph has no multigrid hierarchy (mg_min_keyframes) / several ranks: only the level kernels (7) can be timed"; return PGO_ERR_STATE; }
+    int rc;
+    if ((rc = build_lm_system(p)) != PGO_OK) return rc;
+    if (!p->mg.active && (rc = build_mg(p)) != PGO_OK) return rc;
+    if (!p->mg.active) { p->err = "pgo_time_kernel: the multigrid operators of this system are not positive definite"; return PGO_ERR_NUMERIC; }
+    if (!p->local_ids) return pcg_start(p, choose_form(p), false, 0.0);      // (tolerance 0: never converges during the timed launches)
+    launch_cg_init_vectors(p->G, p->C, 0, p->st);
+    if ((rc = mg_apply_ranks(p, false)) != PGO_OK) return rc;      // (one full distributed cycle: every level vector holds finite numbers)
+    launch_cg_set_tolerance(p->C, 0.0, p->st);
+    return PGO_OK;
+}
+
+// the form measurement `which` (6 / 7) runs: 7 is the cycle alone — the restriction is its own, no update in front and no riders
+PcgForm multigrid_form(const pgo_problem* p, int which) {
+    PcgForm f = choose_form(p);
+    if (which == 7) { f.post = PcgForm::mg_cycle; f.split = UpdSplit{}; }
+    return f;
+}
+
+// one launch of measurement `which`; kk: the PCG iteration it stands for (0: the untimed launch)
+int enqueue(pgo_problem* p, int which, int kk) {
+    const GraphDev& G = p->G;
+    int np = 0, rc;
+    switch (which) {
+        case 0: launch_k1(G, p->d_pose[p->cur].p, p->d_swv[p->cur].p, true, part(p, 0), &np, p->st); return PGO_OK;
+        case 1: launch_k2(G, p->L, !p->built_mf, p->st, p->built_mf ? &p->F : nullptr); return PGO_OK;
+        case 2: case 4: case 5: {
+            const PcgForm f = choose_form(p, true);      // the form the solver runs on this handle (several ranks: the rank's own iteration, no exchanges)
+            if (which != 5) pcg_matvec(p, f, kk, 0.0);
+            return which != 4 ? pcg_update(p, f, kk) : PGO_OK; }
+        case 3: launch_k1(G, p->d_pose[p->cur ^ 1].p, p->d_swv[p->cur ^ 1].p, false, part(p, 5), &np, p->st); return PGO_OK;
+        case 6: case 7: {
+            if (p->local_ids) {      // several ranks (7 only): this rank's share of the cycle's kernels, no exchanges (what its GPU computes per cycle)
+                launch_mg_apply(G, p->C, p->mg.M, p->mg.levels, p->coarse.K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), nullptr);
+                return PGO_OK;
+            }
+            const PcgForm f = multigrid_form(p, which);
+            if (which == 6) { pcg_matvec(p, f, kk, 0.0); if ((rc = pcg_update(p, f, kk)) != PGO_OK) return rc; }
+            return pcg_precond(p, f, kk); }
+        case 8: return mg_operators(p, p->coarse.d_cinfo.p, !p->built_mf || p->hoff_epoch == p->lin_epoch, true, -1.0);
+        default: return PGO_ERR_INVALID_ARG;
+    }
+}
+
+// Bytes the fine-level PCG iteration moves, each array once.  Matrix-free matvec: per LANE (a relative-pose edge with both keyframes in one tile is one lane, every other edge
+// side its own) the compact record (8 double2 planes; 11 for switchable sides) + 12 B of index data (+ a_inv for switchable sides); per keyframe z and p_prev read, p and q
+// written (4 x 48), damping 48, side ranges / regulariser index / free flag 13.  Update: r, q, p, x read, r, x, z written (7 x 48), the fp32 block-Jacobi factor 96.
+// Block-CSR matvec: SURVEY.md 8d's assembled form.  Single-reduction form (sr): the matvec reads u and writes w (2 x 48 per keyframe instead of 4 x 48); the update reads
+// u, w, p, s, x, r and writes p, s, x, r, u (11 x 48).
+struct FineBytes { double matvec, update; };
+FineBytes fine_iteration_bytes(const pgo_problem* p, bool sr) {
+    const double N = (double)p->G.N, E = (double)(p->G.rel.E + p->G.sw.E);
+    const double lanes_rel = (double)(p->mf_pair_lanes + p->mf_rel_side_lanes), lanes_sw = (double)p->mf_sw_lanes;
+    const double mv = p->built_mf ? lanes_rel * (128.0 + 12.0) + lanes_sw * (128.0 + 12.0 + 8.0) + N * ((sr ? 2.0 : 4.0) * 48.0 + 48.0 + 13.0)
+                                  : 288.0 * (N + 2.0 * E) + 4.0 * (N + 2.0 * E) + N * 4.0 * 48.0;
+    return FineBytes{mv, N * ((sr ? 11.0 : 7.0) * 48.0 + 96.0)};
+}
+
+// Bytes of the multigrid cycle, each array once per kernel that streams it: the restriction's per-keyframe offsets and slot table, the prolongation's read-modify-write of z,
+// offsets and aggregate index; every sparse coarse level: its fp32 blocks and column indices twice (down- and up-sweep), Dinv, positions/offsets and its four vectors; the
+// dense level: the fp32 inverse once.
+double cycle_bytes(const pgo_problem* p, bool split_update) {
+    const double N = (double)p->G.N;
+    double cyc = N * (24.0 + 16.0 / 8.0 * 8.0) /* d0 + slot table (restriction) */ + N * (2.0 * 48.0 + 24.0 + 4.0 + 4.0) /* z read + write, d0, agg0, member list (prolongation) */;
+    for (int l = 0; l + 1 < p->mg.M.n_levels; ++l) {
+        const MgLevelDev& A = p->mg.levels[l];
+        if (A.smoothed && A.rt_valf)      // explicit transfer operator: the level's own blocks once (smoothing step), R and R^T once each, Dinv once, r / x / y / xf and the level above's r, x
+            cyc += (double)A.nnzb * (144.0 + 4.0) + 2.0 * (double)A.n_w * (144.0 + 4.0) + (double)A.n * (288.0 + 24.0 + 8.0 * 48.0 + 16.0) + (double)A.n_next * (288.0 + 2.0 * 48.0 + 8.0);
+        else
+            cyc += (A.smoothed ? 4.0 : 2.0) * (double)A.nnzb * (144.0 + 4.0) + (double)A.n * ((A.smoothed ? 4.0 : 2.0) * 288.0 /* Dinv: smoothing steps */ + 24.0 + (A.smoothed ? 18.0 : 10.0) * 48.0 + 16.0);
+    }
+    cyc += (double)p->coarse.K.nc * (double)p->coarse.K.nc * 4.0 + (double)p->coarse.K.nc * 16.0;
+    if (split_update) cyc += N * 48.0;      // the split update: the block-Jacobi rider reads the new residual back
+    return cyc;
+}
+
+// what one launch of measurement `which` moves, on the state its set-up left
+double algorithmic_bytes(const pgo_problem* p, int which) {
+    const GraphDev& G = p->G;
+    const double N = (double)G.N, E = (double)(G.rel.E + G.sw.E), Es = (double)G.sw.E;
+    switch (which) {
+        case 0: return k1_algorithmic_bytes(G, true);
+        case 1: return (624.0 * G.rel.E + 688.0 * Es) + 288.0 * E + 336.0 * N + 112.0 * Es;
+        case 2: case 4: case 5: {
+            const FineBytes fine = fine_iteration_bytes(p, choose_form(p, true).single_red());
+            return which == 2 ? fine.matvec + fine.update : which == 4 ? fine.matvec : fine.update; }
+        case 3: return k1_algorithmic_bytes(G, false);
+        case 6: case 7: {
+            if (p->local_ids) return (double)p->mg.blocks_own * 148.0 + (double)p->mg.rows_own * (288.0 + 24.0 + 8.0 * 48.0 + 16.0) + (double)p->coarse.K.nc * (double)p->coarse.K.nc * 4.0 + (double)p->coarse.K.nc * 16.0;
+            const PcgForm f = multigrid_form(p, which);
+            const double cyc = cycle_bytes(p, f.split.on());
+            if (which == 7) return cyc;
+            const FineBytes fine = fine_iteration_bytes(p, f.single_red());
+            return fine.matvec + fine.update + cyc; }
+        default: return 0.0;
+    }
+}
+
+// One untimed launch first (instruction cache, TLB), then `batches` x `launches` between events; the fastest batch counts.  Several ranks (7 / 8): the timed launches take
+// turns (every rank's figure is what its GPU would need on its own); only the in-process ranks, which share the GPU(s), wait for each other.  In-process ranks: three timed
+// batches — the first batch after a solve_begin that regrouped the hierarchy was measured at 3-5x the steady figure on every rank (C5 on 8 ranks: 0.47-0.82 ms, then
+// 0.146-0.168 ms call after call): eight handles' old images going back to the system stall the GPU's address translation for tens of milliseconds.
+int time_launches(pgo_problem* p, int which, int launches, double* best_ms) {
+    int rc;
+    EventPair ev;
+    HIPCHK(p, ev.create());
+    const int turns = (p->comm && (which == 7 || which == 8)) ? p->world() : 1;
+    const int batches = turns > 1 ? 3 : 1;
+    *best_ms = -1.0;
+    for (int turn = 0; turn < turns; ++turn) {
+        if (turns > 1) {
+            HIPCHK(p, hipStreamSynchronize(p->st));
+            if (!p->comm->barrier()) { p->err = "in-process communicator: a rank left during pgo_time_kernel"; return PGO_ERR_COMM; }
+            if (turn != p->rank()) continue;
+        }
+        for (int rep = 0; rep < 1 + batches; ++rep) {
+            const int n = rep == 0 ? 1 : launches;
+            if (rep >= 1) HIPCHK(p, hipEventRecord(ev.e0, p->st));
+            for (int i = 0; i < n; ++i) if ((rc = enqueue(p, which, rep == 0 ? 0 : i + 1)) != PGO_OK) return rc;
+            if (rep >= 1) HIPCHK(p, hipEventRecord(ev.e1, p->st));
+            HIPCHK(p, hipStreamSynchronize(p->st));
+            if (rep >= 1) { float msb = 0; HIPCHK(p, hipEventElapsedTime(&msb, ev.e0, ev.e1)); if (*best_ms < 0.0 || (double)msb < *best_ms) *best_ms = (double)msb; }
+        }
+    }
+    if (turns > 1 && !p->comm->barrier()) { p->err = "in-process communicator: a rank left during pgo_time_kernel"; return PGO_ERR_COMM; }
+    return PGO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pgo_time_kernel(pgo_problem* p, int32_t which, int32_t launches, double* avg_ms, double* algorithmic_bytes_out) {
+    if (!p || launches <= 0 || !avg_ms) return PGO_ERR_INVALID_ARG;
+    if (!p->in_solve) { p->err = "pgo_time_kernel needs an open solve (pgo_solve_begin)"; return PGO_ERR_STATE; }
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    if (which < 0 || which > 8) return PGO_ERR_INVALID_ARG;
+    if (which == 5 && single_reduction(p)) {      // (its head needs the u.w partials of a matvec on the CURRENT u: launched back to back it sees stale ones, breaks down and returns early)
+        p->err = "pgo_time_kernel(5): the single-reduction update cannot be timed without its matvec; time the iteration (2) and the matvec (4) and subtract"; return PGO_ERR_STATE;
+    }
+    if ((which == 2 || which == 4 || which == 5) && (rc = setup_block_jacobi(p)) != PGO_OK) return rc;
+    if (which >= 6 && (rc = setup_multigrid(p, which)) != PGO_OK) return rc;
+    const double bytes = algorithmic_bytes(p, which);
+    double best_ms = -1.0;
+    if ((rc = time_launches(p, which, launches, &best_ms)) != PGO_OK) return rc;
+    if (which == 8) { p->mg.active = false; if ((rc = build_mg(p)) != PGO_OK) return rc; }      // (several ranks: the timed kernels ran without their exchanges — the operators are formed again, properly)
+    *avg_ms = best_ms / launches;
+    if (algorithmic_bytes_out) *algorithmic_bytes_out = bytes;
+    return PGO_OK;
+}
+int pgo_time_linearize_kernel(pgo_problem* p, int32_t launches, double* avg_ms, double* bytes) { return pgo_time_kernel(p, 0, launches, avg_ms, bytes); }
+
+int pgo_time_vio_odometry_kernel(pgo_problem* p, int32_t f_max, int32_t launches, double* avg_ms, double* algorithmic_bytes) {
+    if (!p || launches <= 0 || !avg_ms || f_max < 1) return PGO_ERR_INVALID_ARG;
+    if (p->n_vio < 2) { p->err = "no resident VIO poses"; return PGO_ERR_STATE; }
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    std::vector<int32_t> c;
+    for (int64_t u = 0; u < p->n_vio; ++u) for (int f = 1; f <= f_max; ++f) if (u - f >= 0) c.push_back((int32_t)u);
+    const int64_t n = (int64_t)c.size();
+    for (int64_t u = 0; u < p->n_vio; ++u) for (int f = 1; f <= f_max; ++f) if (u - f >= 0) c.push_back((int32_t)(u - f));
+    DBuf<int32_t> d_c; DBuf<double> d_meas;
+    HIPCHK(p, d_c.ensure((size_t)2 * n)); HIPCHK(p, d_meas.ensure((size_t)8 * n));
+    HIPCHK(p, hipMemcpyAsync(d_c.p, c.data(), (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
+    EventPair ev;
+    HIPCHK(p, ev.create());
+    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    launch_vio_odometry(n, d_c.p, d_c.p + n, p->d_vio.p, 1, d_meas.p, p->st);
+    HIPCHK(p, hipEventRecord(e0, p->st));
+    for (int i = 0; i < launches; ++i) launch_vio_odometry(n, d_c.p, d_c.p + n, p->d_vio.p, 1, d_meas.p, p->st);
+    HIPCHK(p, hipEventRecord(e1, p->st));
+    HIPCHK(p, hipStreamSynchronize(p->st));
+    float ms = 0;
+    HIPCHK(p, hipEventElapsedTime(&ms, e0, e1));
+    *avg_ms = (double)ms / launches;
+    if (algorithmic_bytes) *algorithmic_bytes = 128.0 * (double)p->n_vio + (8.0 + 64.0) * (double)n;   // each pose once + 2 indices + one record per edge
+    return PGO_OK;
+}
+
+int pgo_dense_spd_inverse(pgo_problem* p, int32_t n, const double* a, double* a_inv, int32_t launches, double* avg_ms) {
+    if (!p || n <= 0 || !a || !a_inv || launches < 1) return PGO_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    const int nc = (n + 63) / 64 * 64;
+    std::vector<double> h((size_t)nc * nc, 0.0);
+    for (int i = 0; i < nc; ++i) {
+        if (i < n) std::memcpy(&h[(size_t)i * nc], a + (size_t)i * n, (size_t)n * sizeof(double));
+        else h[(size_t)i * nc + i] = 1.0;
+    }
+    DBuf<double> d_a, d_scr; DBuf<int32_t> d_fail;
+    HIPCHK(p, d_a.ensure((size_t)nc * nc)); HIPCHK(p, d_scr.ensure((size_t)nc * 64 + 4096)); HIPCHK(p, d_fail.ensure(1));
+    CoarseDev K{}; K.nc = nc; K.Ac = d_a.p;
+    EventPair ev;
+    HIPCHK(p, ev.create());
+    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    float total = 0;
+    for (int l = 0; l < launches; ++l) {
+        HIPCHK(p, hipMemcpyAsync(d_a.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, p->st));
+        HIPCHK(p, hipMemsetAsync(d_fail.p, 0, sizeof(int32_t), p->st));
+        HIPCHK(p, hipEventRecord(e0, p->st));
+        launch_coarse_invert(K, d_scr.p, d_fail.p, p->st);
+        HIPCHK(p, hipEventRecord(e1, p->st));
+        HIPCHK(p, hipStreamSynchronize(p->st));
+        float ms = 0;
+        HIPCHK(p, hipEventElapsedTime(&ms, e0, e1));
+        total += ms;
+    }
+    int32_t fail = 1;
+    HIPCHK(p, hipMemcpy(&fail, d_fail.p, sizeof(fail), hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(h.data(), d_a.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) std::memcpy(a_inv + (size_t)i * n, &h[(size_t)i * nc], (size_t)n * sizeof(double));
+    if (avg_ms) *avg_ms = (double)total / launches;
+    if (fail) { p->err = "matrix is not numerically positive definite"; return PGO_ERR_NUMERIC; }
+    return PGO_OK;
+}
+
+// Diagnostic (tests): sums of squares of what this rank's cycle kernels read of level `level` (1-based) — the same whichever way the set-up ran (pgo_options.mg_dist_setup)
+int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8) {
+    if (!p || !out8) return PGO_ERR_INVALID_ARG;
+    for (int k = 0; k < 8; ++k) out8[k] = 0.0;
+    if (!p->mg.built || p->mg.fresh_pending() || level < 1 || level > p->mg.M.n_levels || (size_t)(level - 1) >= p->mg.own.size()) { p->err = "pgo_mg_level_norms: no such level (is a hierarchy installed?)"; return PGO_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    const MgLevelDev& A = p->mg.levels[level - 1];
+    const OwnRange& R = p->mg.own[(size_t)level - 1];
+    HIPCHK(p, hipStreamSynchronize(p->st));
+    auto sq64 = [&](const double* dev, int64_t first, int64_t count, double* out) -> int {
+        if (!dev || count <= 0) return PGO_OK;
+        std::vector<double> h((size_t)count);
+        HIPCHK(p, hipMemcpy(h.data(), dev + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+        long double s = 0.0L; for (double v : h) s += (long double)v * v;
+        *out = (double)s; return PGO_OK;
+    };
+    auto sq32 = [&](const float* dev, int64_t first, int64_t count, double* out) -> int {
+        if (!dev || count <= 0) return PGO_OK;
+        std::vector<float> h((size_t)count);
+        HIPCHK(p, hipMemcpy(h.data(), dev + first, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+        long double s = 0.0L; for (float v : h) s += (long double)v * v;
+        *out = (double)s; return PGO_OK;
+    };
+    const bool sparse = level < p->mg.M.n_levels;
+    if ((rc = sq64(A.val, R.blk0 * 36, (R.blk1 - R.blk0) * 36, out8 + 0)) != PGO_OK) return rc;
+    if (sparse) {
+        if ((rc = sq32(A.valf, R.blk0 * 36, (R.blk1 - R.blk0) * 36, out8 + 1)) != PGO_OK) return rc;
+        if ((rc = sq64(A.Dinv, R.row0 * 36, (R.row1 - R.row0) * 36, out8 + 2)) != PGO_OK) return rc;
+        if (A.smoothed && A.rt_valf) {
+            if ((rc = sq32(A.rt_valf, R.w0 * 36, (R.w1 - R.w0) * 36, out8 + 3)) != PGO_OK) return rc;
+            if ((rc = sq32(A.r_valf, R.rT0 * 36, (R.rT1 - R.rT0) * 36, out8 + 4)) != PGO_OK) return rc;
+        }
+    } else if ((rc = sq64(p->coarse.K.Ac, 0, (int64_t)p->coarse.K.nc * p->coarse.K.nc, out8 + 5)) != PGO_OK) return rc;      // the dense level: its inverse
+    return PGO_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // pgo_mg_host.hpp — host side of the aggregation-multigrid preconditioner: builds, once per graph, the level hierarchy the device
-// kernels of pgo_mg_kernels.hpp work on.  Included by pgo_solver.hip only.
+// kernels of pgo_mg_kernels.hpp work on.  Included by the host units through pgo_handle.hpp.
 //
 // What it replaces in the reference: nothing one-to-one — Ceres factorises the normal equations exactly
 // (SPARSE_NORMAL_CHOLESKY, reference src/PoseGraphSLAM.cpp:1270); here the PCG that stands in for that factorisation is
@@ -248,7 +248,7 @@ struct LocalContrib {
 };
 
 // What build_hierarchy keeps between two builds of the SAME graph (same keyframes, edges, fixed keyframes, relative-pose weights, options) when only the SWITCH values
-// have changed — a regroup of the levels above level 1 inside a solve (pgo_solver.hip: regroup): the keyframes' level-1 aggregates (matched along relative-pose edges
+// have changed — a regroup of the levels above level 1 inside a solve (pgo_multigrid.hip: regroup): the keyframes' level-1 aggregates (matched along relative-pose edges
 // only: they do not depend on the switches), the structure of level 1 in their provisional numbering, and the level-1 couplings with the switchable part kept per pair.
 // With a valid cache a rebuild skips the two expensive sorts (level-0 matching, level-1 block structure) and costs what the small upper levels cost.
 struct BuildCache {

@@ -1,6 +1,6 @@
 // pgo_multigrid.hip — host lifecycle of the aggregation multigrid preconditioner: the hierarchy's host half (pgo_mg_host.hpp + the pooled arrays and device descriptors of its
 // image), its install, the one host build that may be in flight (a fresh graph's hierarchy or a regroup), the operators of each LM system and the several-rank cycle's exchanges.
-// The kernels are pgo_mg_kernels.hpp's; the handle, the collectives and the two-level method are pgo_solver.hip's (pgo_handle.hpp).
+// The kernels are pgo_mg_kernels.hpp's; the handle is pgo_handle.hpp's, the collectives pgo_shard.hip's, the two-level method pgo_pcg.hip's.
 #include <algorithm>
 #include <atomic>
 #include <cmath>

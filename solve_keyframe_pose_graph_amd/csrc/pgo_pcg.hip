@@ -59,12 +59,8 @@ int build_two_level_aggregates(pgo_problem* p) {
         const int n_blk = (int)blk_ab.size() / 2;
         const int nc = (6 * n_agg + 63) / 64 * 64;      // padded with a decoupled identity block (the dense kernels work on 64-wide tiles)
         HIPCHK(p, c.d_ccen.ensure((size_t)n_agg * 3)); HIPCHK(p, c.d_cd.ensure((size_t)N * 3)); HIPCHK(p, c.d_cAc.ensure((size_t)nc * nc)); HIPCHK(p, c.d_cAcf.ensure((size_t)nc * nc));
-        HIPCHK(p, c.d_crc.ensure((size_t)nc * 2)); HIPCHK(p, c.d_cscr.ensure((size_t)nc * 64 + 4096)); HIPCHK(p, hipMemsetAsync(c.d_crc.p, 0, (size_t)nc * 2 * sizeof(double), p->st)); HIPCHK(p, c.d_cblk_ptr.ensure(blk_ptr.size())); HIPCHK(p, c.d_ccontrib.ensure(std::max<size_t>(contrib.size(), 1)));
-        HIPCHK(p, c.d_cblk_ab.ensure(blk_ab.size())); HIPCHK(p, c.d_cagg_free.ensure(n_agg)); HIPCHK(p, c.d_cinfo.ensure(4));
-        HIPCHK(p, hipMemcpyAsync(c.d_cblk_ptr.p, blk_ptr.data(), blk_ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, p->st));
-        if (!contrib.empty()) HIPCHK(p, hipMemcpyAsync(c.d_ccontrib.p, contrib.data(), contrib.size() * sizeof(int64_t), hipMemcpyHostToDevice, p->st));
-        HIPCHK(p, hipMemcpyAsync(c.d_cblk_ab.p, blk_ab.data(), blk_ab.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
-        HIPCHK(p, hipMemcpyAsync(c.d_cagg_free.p, agg_free.data(), n_agg * sizeof(int32_t), hipMemcpyHostToDevice, p->st));
+        HIPCHK(p, c.d_crc.ensure((size_t)nc * 2)); HIPCHK(p, c.d_cscr.ensure((size_t)nc * 64 + 4096)); HIPCHK(p, hipMemsetAsync(c.d_crc.p, 0, (size_t)nc * 2 * sizeof(double), p->st)); HIPCHK(p, c.d_cinfo.ensure(4));
+        HIPCHK(p, c.d_cblk_ptr.upload(blk_ptr, p->st)); HIPCHK(p, c.d_ccontrib.upload(contrib, p->st)); HIPCHK(p, c.d_cblk_ab.upload(blk_ab, p->st)); HIPCHK(p, c.d_cagg_free.upload(agg_free, p->st));
         HIPCHK(p, hipStreamSynchronize(p->st));
         c.K = CoarseDev{n_agg, nc, m, n_blk, c.d_ccen.p, c.d_cd.p, c.d_cAc.p, c.d_crc.p, c.d_crc.p + nc, c.d_cblk_ptr.p, c.d_cblk_ab.p, c.d_ccontrib.p, c.d_cagg_free.p, c.d_cAcf.p};
         c.built = true;
@@ -158,11 +154,9 @@ int build_system(pgo_problem* p, bool* ok) {
         // accepted one at a large radius, i.e. exactly the systems predicted hard, and block-Jacobi reaches the first pause (cg_early_tolerance, a few dozen iterations)
         // for a fraction of what the operators cost (C3, step 4: 32 ms for a step thrown away at 21 iterations).  Then the build waits for the pause (lm_step).
         const bool hard = p->opt.mg_switch_iterations <= 0 || predicted >= start_factor * (double)p->opt.mg_switch_iterations;
-        // ... and only where a rejection is in the air: the previous step was rejected (rejections come in streaks: the radius shrinks over several steps), or the last accepted
-        // step's relative decrease fell below 0.8 — the quadratic model is losing its grip (C3's and C4's first rejected steps follow rho = 0.67 and 0.62; the accepted hard steps
-        // of both follow rho >= 0.89, and a prelude there is 74 block-Jacobi iterations the multigrid would not have needed: 3 ms x 5 on C3, 5 ms x 12 on C4)
-        const bool rejection_likely = p->reuse_diagonal || p->last_rho < 0.8;
-        s.mg_start_deferred = hard && rejection_likely && p->opt.mg_switch_iterations > 0 && p->opt.cg_early_tolerance > p->opt.cg_rel_tolerance;
+        // ... and only where a rejection is in the air (rejection_likely, pgo_handle.hpp): elsewhere — the accepted hard steps of C3 and C4 follow rho >= 0.89 — a prelude is
+        // 74 block-Jacobi iterations the multigrid would not have needed: 3 ms x 5 on C3, 5 ms x 12 on C4
+        s.mg_start_deferred = hard && rejection_likely(p) && p->opt.mg_switch_iterations > 0 && p->opt.cg_early_tolerance > p->opt.cg_rel_tolerance;
         if (s.mg_start_deferred) {      // ... but not for long: a step that has not reached the pause within the prelude is a hard one that stays (late C3 systems need ~300 block-Jacobi iterations to 1e-2)
             const int prelude = 72;      // three chunks (measured on C3 / C4, 20 steps: 48 -> 0.392 / 1.500 s — C3's rejected step 4 needs 53 —, 72 -> 0.322 / 1.515 s, 96 -> 0.324 / 1.524 s)
             s.mg_switch_at = std::min(s.mg_switch_at, prelude);

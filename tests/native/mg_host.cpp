@@ -37,7 +37,7 @@ void* mgh_build_sharded(long long N, const unsigned char* node_free, long long E
     return H;
 }
 // Regroup path: the hierarchy for switch weights `sw_w`; use_cache != 0: a first build with `sw_w_first` fills a BuildCache and the returned hierarchy is the REBUILD
-// with `sw_w` from that cache (what pgo_solver.hip's regroup does); use_cache == 0: a fresh build with `sw_w`.  The two must be identical.
+// with `sw_w` from that cache (what pgo_multigrid.hip's regroup does); use_cache == 0: a fresh build with `sw_w`.  The two must be identical.
 void* mgh_build_regroup(long long N, const unsigned char* node_free, long long Er, const int* rc1, const int* rc2, const double* rw, long long Es, const int* sc1, const int* sc2,
                         const double* sw_w_first, const double* sw_w, int use_cache, int passes0, int passes, int dense_max, int tile_rows, int max_levels, int smoothed_levels, double loop_discount,
                         int level0_block) {
@@ -55,7 +55,7 @@ void* mgh_build_regroup(long long N, const unsigned char* node_free, long long E
     if (!ok) { delete H; return nullptr; }
     return H;
 }
-// Smoothed transition keyframes -> level 1: the keyframe level's block pattern built as pgo_solver.hip's build_graph builds it (row i: block (i, i), then one block per incident
+// Smoothed transition keyframes -> level 1: the keyframe level's block pattern built as pgo_graph.hip's incident_lists builds it (row i: block (i, i), then one block per incident
 // edge — relative-pose edges first, in edge order —, parallel edges repeating a column), handed to build_hierarchy with level0_block as the solver does.
 void* mgh_build_fine(long long N, const unsigned char* node_free, long long Er, const int* rc1, const int* rc2, const double* rw, long long Es, const int* sc1, const int* sc2,
                      int passes0, int passes, int dense_max, int tile_rows, int max_levels, int smoothed_levels, int level0_block) {
