@@ -327,6 +327,27 @@ int pgo_reserve(pgo_problem* p, int64_t n_nodes, int64_t n_edges);
 int pgo_add_relpose_edges(pgo_problem* p, int64_t n, const int32_t* c1, const int32_t* c2,
                           const double* c1_T_c2, const double* weight);
 
+/* Robust losses for relative-pose edges: ceres::HuberLoss(a) / ceres::CauchyLoss(a) as the reference builds them (`robust_norm`,
+ * src/PoseGraphSLAM.cpp:401-402 and :1279-1280: HuberLoss(0.1), CauchyLoss(1.0) as the commented alternative).  With s = |r|^2 of the block
+ * (r already carries the edge weight) and b = a^2:
+ *   PGO_LOSS_HUBER   rho = s for s <= b, 2 a sqrt(s) - b beyond        PGO_LOSS_CAUCHY   rho = b log(1 + s / b)
+ * The block costs 0.5 rho(s); residual and Jacobian blocks are scaled by sqrt(rho'(s)) (Ceres' Corrector; rho'' <= 0 for both losses, so
+ * there is no second-order term).  Out of scope: a loss on switchable edges (the reference combines the two only in a routine this library
+ * does not replace, :803) and losses with rho'' > 0 (ceres::TolerantLoss). */
+enum { PGO_LOSS_TRIVIAL = 0, PGO_LOSS_HUBER = 1, PGO_LOSS_CAUCHY = 2 };
+/* pgo_add_relpose_edges with `AddResidualBlock(SixDOFError::Create(..), new ceres::HuberLoss(a) / CauchyLoss(a), ...)`
+ * — reference src/PoseGraphSLAM.cpp:793-796 with :401-402.  PGO_LOSS_TRIVIAL is exactly pgo_add_relpose_edges (loss_a ignored); an unknown
+ * `loss`, or a `loss_a` that is not finite or <= 0 for a non-trivial loss, returns PGO_ERR_INVALID_ARG and adds nothing.  Robust and plain
+ * relative-pose edges share one add order and one index space (residual order of pgo_evaluate, edge indices of the parity hooks); the edges of
+ * pgo_add_odometry_edges_from_vio are trivial.  On robust edges the parity hooks follow Ceres' Problem::Evaluate with apply_loss_function =
+ * true: pgo_evaluate returns the corrected residuals, the cost with 0.5 rho(s) for these blocks and the gradient of the robust objective,
+ * pgo_get_jacobian_blocks and pgo_get_normal_blocks the corrected blocks; pgo_iteration.model_cost_change is formed from the corrected r and J,
+ * cost and cost_change from rho. */
+int pgo_add_relpose_edges_robust(pgo_problem* p, int64_t n, const int32_t* c1, const int32_t* c2,
+                                 const double* c1_T_c2, const double* weight, int32_t loss, double loss_a);
+/* The loss of relative-pose edges [first, first+n): loss[k] = PGO_LOSS_*, loss_a[k] = its parameter (0 for a trivial edge).  Either output may be NULL. */
+int pgo_get_relpose_edge_loss(const pgo_problem* p, int64_t first, int64_t n, int32_t* loss, double* loss_a);
+
 /* n x `AddResidualBlock(SixDOFErrorWithSwitchingConstraints::Create(bTa, weight), NULL,
  *                       q[c1], t[c1], q[c2], t[c2], &switch[switch_idx])`
  * — reference src/PoseGraphSLAM.cpp:1550-1556 with functor src/CeresResidues.h:145-222.

@@ -13,6 +13,8 @@ from . import _build
 PGO_MAX_ITERATION_LOG = 256
 PGO_COMM_ID_BYTES = 128
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
+LOSS_TRIVIAL, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2      # PGO_LOSS_* (include/pgo.h)
+LOSS_NAMES = {"trivial": LOSS_TRIVIAL, "huber": LOSS_HUBER, "cauchy": LOSS_CAUCHY}
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -72,7 +74,7 @@ class ShardingStats(C.Structure):
 ABI_VERSION = 7      # PGO_ABI_VERSION of the include/pgo.h this view mirrors
 EXPORTS = [
     "pgo_abi_version", "pgo_abi_sizeof", "pgo_options_init", "pgo_create", "pgo_destroy", "pgo_set_options", "pgo_reserve",
-    "pgo_add_relpose_edges", "pgo_add_switchable_edges", "pgo_set_node_regularizers", "pgo_set_nodes_constant",
+    "pgo_add_relpose_edges", "pgo_add_relpose_edges_robust", "pgo_get_relpose_edge_loss", "pgo_add_switchable_edges", "pgo_set_node_regularizers", "pgo_set_nodes_constant",
     "pgo_num_relpose_edges", "pgo_num_switchable_edges", "pgo_num_regularizers",
     "pgo_set_vio_poses", "pgo_num_vio_poses", "pgo_add_odometry_edges_from_vio", "pgo_initial_guess_from_vio", "pgo_get_relpose_edge_records",
     "pgo_solve", "pgo_solve_begin", "pgo_lm_step", "pgo_solve_end", "pgo_evaluate",
@@ -191,12 +193,31 @@ class Problem:
         self._check(self.lib.pgo_set_options(self.h, C.byref(self.options)))
 
     # ---- problem construction ----
-    def add_relpose_edges(self, c1, c2, c1_T_c2, weight):
+    def add_relpose_edges(self, c1, c2, c1_T_c2, weight, loss=None):
+        """loss: None (plain, `AddResidualBlock(.., NULL, ..)`) or ("huber", a) / ("cauchy", a) = ceres::HuberLoss(a) / ceres::CauchyLoss(a) on these blocks
+        (reference src/PoseGraphSLAM.cpp:793-796 with :401-402); the kind may also be given as its PGO_LOSS_* number"""
         c1, c2, T, w = _i(c1), _i(c2), _d(c1_T_c2), _d(weight)
         n = len(c1)
         assert len(c2) == n and T.size == 16 * n and w.size == n
-        self._check(self.lib.pgo_add_relpose_edges(self.h, C.c_int64(n), _pi(c1), _pi(c2), _pd(T), _pd(w)))
+        if loss is None:
+            self._check(self.lib.pgo_add_relpose_edges(self.h, C.c_int64(n), _pi(c1), _pi(c2), _pd(T), _pd(w)))
+        else:
+            kind, a = loss
+            kind = LOSS_NAMES[kind] if isinstance(kind, str) else int(kind)
+            self._check(self.lib.pgo_add_relpose_edges_robust(self.h, C.c_int64(n), _pi(c1), _pi(c2), _pd(T), _pd(w), C.c_int32(kind), C.c_double(a)))
         self.n_rel += n
+
+    def relpose_edge_loss(self, first=0, n=None):
+        """(PGO_LOSS_* kind, parameter a) of relative-pose edges [first, first + n) in add order; a = 0 for plain edges"""
+        n = self.num_relpose_edges() - first if n is None else n
+        kind = np.zeros(n, np.int32); a = np.zeros(n)
+        self._check(self.lib.pgo_get_relpose_edge_loss(self.h, C.c_int64(first), C.c_int64(n), _pi(kind), _pd(a)))
+        return kind, a
+
+    def num_relpose_edges(self):
+        n = C.c_int64()
+        self._check(self.lib.pgo_num_relpose_edges(self.h, C.byref(n)))
+        return n.value
 
     def add_switchable_edges(self, c1, c2, c1_T_c2, weight, switch_idx):
         c1, c2, T, s = _i(c1), _i(c2), _d(c1_T_c2), _i(switch_idx)
@@ -433,10 +454,13 @@ def partition_edges(policy, world, positions, rel_c1, rel_c2, sw_c1, sw_c2):
     return part, rr, sr
 
 
-def problem_from_graph(g, switchable=True, options=None, edge_slice=None, **opt_kw):
+def problem_from_graph(g, switchable=True, options=None, edge_slice=None, loop_loss=None, **opt_kw):
     """Builds a Problem from a graphgen.PoseGraph the way the reference's trigger adds residual blocks
     (odometry -> SixDOFError, loop closures -> switchable / plain, regularisers).  `edge_slice(kind, n)`
-    optionally returns the index subset this rank owns (edge sharding)."""
+    optionally returns the index subset this rank owns (edge sharding).  loop_loss = ("huber", a) / ("cauchy", a):
+    the robust loss of the loop closures when they are plain relative-pose edges (switchable=False)."""
+    if loop_loss is not None and switchable:
+        raise ValueError("a robust loss on switchable edges is not supported: pass switchable=False")
     P = Problem(options, **opt_kw)
     sel = (lambda kind, n: np.arange(n)) if edge_slice is None else edge_slice
     io = sel("odom", g.n_odom)
@@ -447,7 +471,7 @@ def problem_from_graph(g, switchable=True, options=None, edge_slice=None, **opt_
         if switchable:
             P.add_switchable_edges(g.loop_c1[il], g.loop_c2[il], g.loop_T[il], g.loop_w[il], il.astype(np.int32))
         else:
-            P.add_relpose_edges(g.loop_c1[il], g.loop_c2[il], g.loop_T[il], g.loop_w[il])
+            P.add_relpose_edges(g.loop_c1[il], g.loop_c2[il], g.loop_T[il], g.loop_w[il], loss=loop_loss)
     ir = sel("reg", len(g.reg_node))
     if len(ir):
         P.set_node_regularizers(g.reg_node[ir], g.reg_T[ir], g.reg_w[ir])

@@ -121,6 +121,47 @@ PGO_HD void relpose_residual(const Pose& c1, const Pose& c2, const Meas& m, doub
 }
 
 // ---------------------------------------------------------------------------------------------
+// Robust loss of a relative-pose block (ceres::HuberLoss / ceres::CauchyLoss as the reference builds them, src/PoseGraphSLAM.cpp:401-402,
+// applied to the SixDOFError loop edge of :793-796) with Ceres' Corrector.  One double per edge encodes the loss: +a Huber(a), -a Cauchy(a),
+// 0 trivial.  With s = |r|^2 (r already carries the edge weight) and b = a^2:
+//   Huber   s <= b: rho = s, rho' = 1          s > b: rho = 2 a sqrt(s) - b, rho' = a / sqrt(s)
+//   Cauchy  rho = b log(1 + s / b), rho' = 1 / (1 + s / b)
+// The block costs 0.5 rho(s).  rho'' <= 0 for both, so the Corrector is the pure scaling r <- c r, J <- c J with c = sqrt(rho'(s)):
+// at a given point the robust edge IS the plain edge of weight w c.  robust_loss returns rho and sets c.
+// ---------------------------------------------------------------------------------------------
+PGO_HD double robust_loss(double enc, double s, double& c) {
+    const double b = enc * enc;
+    if (enc > 0.0) {
+        if (s <= b) { c = 1.0; return s; }
+        const double n = sqrt(s);
+        c = sqrt(enc / n);
+        return 2.0 * enc * n - b;
+    }
+    if (enc < 0.0) {
+        const double u = 1.0 + s / b;
+        c = sqrt(1.0 / u);
+        return b * log(u);
+    }
+    c = 1.0;
+    return s;
+}
+
+// The relative-pose block under the loss `enc`: r, J1, J2 corrected (= relpose_residual at weight w c), c = sqrt(rho') at this point; returns rho(s).
+// The residual is evaluated once at weight w for s and then, with its Jacobian blocks, at weight w c: the second pass shares every
+// subexpression with the first but the weight, and no Jacobian entry is live while the loss (sqrt / log) is evaluated.
+template <bool WANT_J>
+PGO_HD double relpose_residual_robust(const Pose& c1, const Pose& c2, const Meas& m, double enc, double* r, double* J1, double* J2, double& c) {
+    double r0[6];
+    relpose_residual<false>(c1, c2, m, m.w, r0, nullptr, nullptr);
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s += r0[i] * r0[i];
+    const double rho = robust_loss(enc, s, c);
+    relpose_residual<WANT_J>(c1, c2, m, m.w * c, r, J1, J2);
+    return rho;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Switchable residual (SixDOFErrorWithSwitchingConstraints): with r6, A1, A2 the relative-pose residual
 // and blocks at w = 1 (the edge weight is ignored exactly as CeresResidues.h:198 ignores it):
 //   r = [ s r6 ; s (1 - s) ]   J1 = s A1, J2 = s A2 (7th row zero, not stored)   dr/ds = [ r6 ; 1 - 2 s ]

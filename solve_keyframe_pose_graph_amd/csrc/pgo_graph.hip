@@ -61,6 +61,7 @@ std::vector<uint8_t> free_flags(const HostClass& rel, const HostClass& swe, cons
 struct PackedClass {
     std::vector<int32_t> c1, c2, sw;
     std::vector<double> meas;
+    std::vector<double> loss;      // [Epad] encoded robust loss in the edges' packed order, or empty: no edge of the class carries one
     std::vector<int4> win;
     int64_t E = 0, Epad = 0;
     int tiles() const { return (int)win.size(); }
@@ -71,10 +72,12 @@ PackedClass pack_class(const HostClass& H, bool is_sw, LocalIndex L) {
     const int64_t Epad = P.Epad = (E + TILE - 1) / TILE * TILE;
     const int tiles = (int)(Epad / TILE);
     P.c1.resize(Epad); P.c2.resize(Epad); P.sw.resize(is_sw ? Epad : 0); P.meas.resize((size_t)8 * Epad); P.win.resize(tiles);
+    if (std::any_of(H.loss.begin(), H.loss.end(), [](double a) { return a != 0.0; })) P.loss.assign((size_t)Epad, 0.0);
     for (int64_t e = 0; e < Epad; ++e) {
         const int64_t s = e < E ? e : E - 1;   // padding lanes replicate the last edge (computed, never stored or counted)
         P.c1[e] = L(H.c1[s]); P.c2[e] = L(H.c2[s]);
         if (is_sw) P.sw[e] = H.sw[s];
+        if (!P.loss.empty() && s < (int64_t)H.loss.size()) P.loss[e] = H.loss[s];      // the plane goes with the edge, wherever the packing puts it
         for (int k = 0; k < 8; ++k) P.meas[(size_t)k * Epad + e] = H.meas[(size_t)s * 8 + k];
     }
     for (int t = 0; t < tiles; ++t) {
@@ -248,13 +251,16 @@ const char* pack_mf_tiles(const IncidentLists& I, const HostClass& rel, const Ho
 
 // ---- uploads.  Each waits for its copies: the host struct may go when it returns.
 int upload_class(pgo_problem* p, const PackedClass& P, DBuf<int32_t>& dc1, DBuf<int32_t>& dc2, DBuf<int32_t>* dsw, DBuf<double>& dmeas, DBuf<int4>& dwin, EdgeClassDev& out) {
+    const bool robust = !dsw && !P.loss.empty();      // (the relative-pose class of a handle with a robust edge)
     if (P.Epad > 0) {
         HIPCHK(p, dc1.upload(P.c1, p->st)); HIPCHK(p, dc2.upload(P.c2, p->st)); HIPCHK(p, dmeas.upload(P.meas, p->st)); HIPCHK(p, dwin.upload(P.win, p->st));
         if (dsw) HIPCHK(p, dsw->upload(P.sw, p->st));
+        if (robust) { HIPCHK(p, p->d_rloss.upload(P.loss, p->st)); HIPCHK(p, p->d_rlossc.ensure((size_t)P.Epad)); }
         HIPCHK(p, hipStreamSynchronize(p->st));
     }
     out.c1 = dc1.p; out.c2 = dc2.p; out.meas = dmeas.p; out.swidx = dsw ? dsw->p : nullptr; out.win = dwin.p;
     out.E = P.E; out.Epad = P.Epad; out.tiles = P.tiles(); out.J = nullptr;
+    out.loss = robust ? p->d_rloss.p : nullptr; out.lossc = robust ? p->d_rlossc.p : nullptr;
     return PGO_OK;
 }
 
@@ -324,7 +330,7 @@ void bind_descriptors(pgo_problem* p) {
 
 namespace pgo {
 
-int add_edges(pgo_problem* p, HostClass& H, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, const int32_t* sw) {
+int add_edges(pgo_problem* p, HostClass& H, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, const int32_t* sw, double loss_enc) {
     if (n < 0 || (n > 0 && (!c1 || !c2 || !T))) { p->err = "null edge array"; return PGO_ERR_INVALID_ARG; }
     for (int64_t k = 0; k < n; ++k) if (c1[k] < 0 || c2[k] < 0 || c1[k] == c2[k] || (sw && sw[k] < 0)) { p->err = "negative index or self edge"; return PGO_ERR_INVALID_ARG; }
     mg_drop_pending(p);      // (the worker reads the edge lists)
@@ -334,6 +340,7 @@ int add_edges(pgo_problem* p, HostClass& H, int64_t n, const int32_t* c1, const 
     if (sw) H.sw.insert(H.sw.end(), sw, sw + n);
     H.meas.resize((base + n) * 8);
     for (int64_t k = 0; k < n; ++k) meas_from_matrix(T + 16 * k, w ? w[k] : 1.0, &H.meas[(base + k) * 8]);
+    if (loss_enc != 0.0 && n > 0) { H.loss.resize(base, 0.0); H.loss.resize(base + n, loss_enc); }      // (trivial edges never touch the plane: see HostClass)
     p->graph_dirty = true;
     return PGO_OK;
 }

@@ -101,6 +101,8 @@ struct EventPair {
 struct HostClass {
     std::vector<int32_t> c1, c2, sw;
     std::vector<double> meas;   // 8 per edge: q_obs(4) t_obs(3) w
+    std::vector<double> loss;   // relative-pose class only: the encoded robust loss (+a Huber, -a Cauchy, 0 trivial) of edges [0, loss.size()); the edges beyond it — and all
+                                // of them while it is empty (no robust edge was ever added) — are trivial
     int64_t size() const { return (int64_t)c1.size(); }
 };
 
@@ -246,6 +248,7 @@ struct pgo_problem {
     int64_t st_exchanges = 0, st_allreduces = 0, st_pcg_iterations = 0; double st_bytes_neighbour = 0.0, st_bytes_allreduce = 0.0;
     DBuf<int32_t> d_rc1, d_rc2, d_sc1, d_sc2, d_sidx, d_bsr_col;
     DBuf<double> d_rmeas, d_smeas;
+    DBuf<double> d_rloss, d_rlossc;   // robust loss plane of the relative-pose class and K1's corrector scales (allocated only for a handle with a robust edge)
     DBuf<int4> d_rwin, d_swin;
     DBuf<PriorDev> d_prior;
     DBuf<int64_t> d_inc_rowptr, d_inc, d_bsr_rowptr;
@@ -327,7 +330,7 @@ inline double* part(pgo_problem* p, int k) { return p->d_part.p + (size_t)k * p-
 inline bool rejection_likely(const pgo_problem* p) { return p->reuse_diagonal || p->last_rho < 0.8; }
 
 // ---- pgo_graph.hip: host edge lists -> device graph
-int add_edges(pgo_problem* p, HostClass& H, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, const int32_t* sw);
+int add_edges(pgo_problem* p, HostClass& H, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, const int32_t* sw, double loss_enc = 0.0);
 int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now);
 
 // ---- pgo_shard.hip: the rank-local subgraph, the collectives and neighbour exchanges (no-ops without a communicator), keyframe arrays local <-> global

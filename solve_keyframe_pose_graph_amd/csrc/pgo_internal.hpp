@@ -7,6 +7,7 @@
 //   sw      [S]               switch variables
 //   edge inputs per class (relpose / switchable), SoA planes padded to a multiple of 64:
 //     c1,c2 [Epad] int32      endpoint keyframes           meas [8][Epad]  q_obs(4) t_obs(3) weight
+//     loss  [Epad]            (relpose only, optional) encoded robust loss per edge; lossc [Epad] its corrector scale at the last linearisation
 //     swidx [Epad] int32      (switchable only)            win  [tiles] int4 {lo1,n1,lo2,n2} pose windows for LDS staging
 //   K1 output per tile, AoSoA [tile][k/2][lane][2] so every store is 16 B/lane, 1 KiB/wave-instruction:
 //     relpose   78 doubles/edge: r[6]  J1[36] J2[36]                (row-major 6x6, cols [dtheta, dt])
@@ -72,6 +73,9 @@ struct EdgeClassDev {
     double* J;              // tiles x DOUBLES x 64
     int64_t E, Epad;
     int32_t tiles;
+    // robust loss (relative-pose class only; both null when the handle has no robust edge: K1 and the compaction then run their plain instantiations)
+    const double* loss;     // [Epad] +a Huber(a), -a Cauchy(a), 0 trivial (robust_loss, pgo_device_math.hpp)
+    double* lossc;          // [Epad] c = sqrt(rho') of every edge at the last linearisation, written by K1 with Jacobians, read by the matrix-free compaction
 };
 
 struct GraphDev {

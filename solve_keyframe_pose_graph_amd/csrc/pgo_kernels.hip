@@ -182,7 +182,8 @@ __device__ __forceinline__ void k1_store(double2* p, double a, double b) {
     }
 }
 
-template <bool WANT_J, bool NT>
+// LOSS: some relative-pose edge carries a robust loss (rel.loss / rel.lossc non-null; launch_k1 picks it by that alone, so a handle without one runs the plain code)
+template <bool WANT_J, bool NT, bool LOSS = false>
 __global__ __launch_bounds__(K1_WAVES * 64) void k1_edges_kernel(EdgeClassDev rel, EdgeClassDev sw, const double* __restrict__ pose8,
                                                                   const double* __restrict__ swv, double* __restrict__ partials) {
     __shared__ __attribute__((aligned(16))) char lds_win[K1_WAVES * 2 * WIN_MAX * WIN_STRIDE];
@@ -214,10 +215,19 @@ __global__ __launch_bounds__(K1_WAVES * 64) void k1_edges_kernel(EdgeClassDev re
         const Meas M{mp[0], mp[ep], mp[2 * ep], mp[3 * ep], mp[4 * ep], mp[5 * ep], mp[6 * ep], mp[7 * ep]};
         if (!is_sw) {
             double r[6], J1[36], J2[36];
-            relpose_residual<WANT_J>(P1, P2, M, M.w, r, J1, J2);
-            if (valid) {
+            if (LOSS) {      // corrected r, J1, J2 (a plain edge of weight w c at this point); the block costs rho(s), not |c r|^2 — in the cost-only form too
+                double c;
+                const double rho = relpose_residual_robust<WANT_J>(P1, P2, M, rel.loss[e], r, J1, J2, c);
+                if (valid) {
+                    cost += rho;
+                    if (WANT_J) rel.lossc[e] = c;
+                }
+            } else {
+                relpose_residual<WANT_J>(P1, P2, M, M.w, r, J1, J2);
+                if (valid) {
 #pragma unroll
-                for (int i = 0; i < 6; ++i) cost += r[i] * r[i];
+                    for (int i = 0; i < 6; ++i) cost += r[i] * r[i];
+                }
             }
             double2* out = reinterpret_cast<double2*>(C.J) + (size_t)tile * (REL_DOUBLES / 2 * TILE) + lane;
             if (!valid) {
@@ -295,6 +305,12 @@ void launch_k1(const GraphDev& G, const double* pose8, const double* sw, bool wa
     if (grid == 0) return;
     const double out_bytes = 8.0 * TILE * ((double)G.rel.tiles * REL_DOUBLES + (double)G.sw.tiles * SW_DOUBLES);
     const bool nt = out_bytes > 224.0e6;   // beyond what the Infinity Cache absorbs (see k1_store)
+    if (G.rel.loss) {
+        if (!want_jacobian) hipLaunchKernelGGL((k1_edges_kernel<false, false, true>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
+        else if (nt) hipLaunchKernelGGL((k1_edges_kernel<true, true, true>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
+        else hipLaunchKernelGGL((k1_edges_kernel<true, false, true>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
+        return;
+    }
     if (!want_jacobian) hipLaunchKernelGGL((k1_edges_kernel<false, false>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
     else if (nt) hipLaunchKernelGGL((k1_edges_kernel<true, true>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
     else hipLaunchKernelGGL((k1_edges_kernel<true, false>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
@@ -309,6 +325,7 @@ double k1_algorithmic_bytes(const GraphDev& G, bool want_jacobian) {
     const double N = (double)G.N, Er = (double)G.rel.E, Es = (double)G.sw.E, Eg = (double)G.n_prior;
     double b = 56.0 * N + 8.0 * Es + 72.0 * (Er + Es) + 68.0 * Eg;
     if (want_jacobian) b += 624.0 * Er + 688.0 * Es + 336.0 * Eg;
+    if (G.rel.loss) b += (want_jacobian ? 16.0 : 8.0) * Er;      // the loss plane in, the corrector scales out
     return b;
 }
 
@@ -1278,6 +1295,7 @@ void launch_apply_operator(const GraphDev& G, const CgDev& C, const double* x, d
 //   phase A  one lane per edge-side of the workgroup's keyframes: y_e = J_side^T (I - k k^T)(J1 p1 + J2 p2)  -> LDS
 //   phase B  one lane per (keyframe, row): sum of the keyframe's edge-sides in list order (deterministic) + damping + regulariser
 // ------------------------------------------------------------------------------------------------
+template <bool LOSS>      // LOSS: the record's weight of a relative-pose edge is w c, c = K1's corrector scale at this linearisation (G.rel.lossc) — the bits K1's own blocks carry
 __global__ __launch_bounds__(256) void mf_compact_kernel(GraphDev G, MfDev F, const double* __restrict__ pose8, const double* __restrict__ swv) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= F.ninc) return;
@@ -1290,7 +1308,7 @@ __global__ __launch_bounds__(256) void mf_compact_kernel(GraphDev G, MfDev F, co
     const double* mp = C.meas + e;
     const size_t ep = (size_t)C.Epad;
     const Meas M{mp[0], mp[ep], mp[2 * ep], mp[3 * ep], mp[4 * ep], mp[5 * ep], mp[6 * ep], mp[7 * ep]};
-    const double ws = is_sw ? swv[C.swidx[e]] : M.w;
+    const double ws = is_sw ? swv[C.swidx[e]] : LOSS ? M.w * G.rel.lossc[e] : M.w;
     double rec[COMPACT_DOUBLES];
     edge_compact(P1, P2, M, ws, is_sw, rec);
     for (int pl = 0; pl < MF_PLANES; ++pl) F.rec[(size_t)pl * F.ninc_pad + i] = make_double2(rec[2 * pl], rec[2 * pl + 1]);
@@ -1541,7 +1559,9 @@ __global__ __launch_bounds__(MF_BLOCK, PGO_MF_WAVES) void mf_spmv_kernel(GraphDe
 static inline int mf_grid(const MfDev& F) { const int g = F.tiles < MF_MAX_GRID ? F.tiles : MF_MAX_GRID; return g < 1 ? 1 : g; }
 int mf_grid_size(const MfDev& F) { return mf_grid(F); }
 void launch_mf_compact(const GraphDev& G, const MfDev& F, const double* pose8, const double* sw, hipStream_t st) {
-    if (F.ninc > 0) hipLaunchKernelGGL(mf_compact_kernel, dim3((unsigned)((F.ninc + 255) / 256)), dim3(256), 0, st, G, F, pose8, sw);
+    if (F.ninc <= 0) return;
+    if (G.rel.lossc) hipLaunchKernelGGL(mf_compact_kernel<true>, dim3((unsigned)((F.ninc + 255) / 256)), dim3(256), 0, st, G, F, pose8, sw);
+    else hipLaunchKernelGGL(mf_compact_kernel<false>, dim3((unsigned)((F.ninc + 255) / 256)), dim3(256), 0, st, G, F, pose8, sw);
 }
 void launch_mf_spmv(const GraphDev& G, const MfDev& F, const ScaleDev& Sc, const CgDev& C, int k, double tol2, hipStream_t st) {
     const int g = mf_grid(F);

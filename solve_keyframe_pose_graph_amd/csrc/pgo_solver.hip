@@ -509,6 +509,22 @@ int pgo_add_relpose_edges(pgo_problem* p, int64_t n, const int32_t* c1, const in
     if (n > 0 && !w) { p->err = "weight array required for relative-pose edges"; return PGO_ERR_INVALID_ARG; }
     return add_edges(p, p->rel, n, c1, c2, T, w, nullptr);
 }
+int pgo_add_relpose_edges_robust(pgo_problem* p, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, int32_t loss, double loss_a) {
+    if (!p) return PGO_ERR_INVALID_ARG;
+    if (loss != PGO_LOSS_TRIVIAL && loss != PGO_LOSS_HUBER && loss != PGO_LOSS_CAUCHY) { p->err = "unknown robust loss"; return PGO_ERR_INVALID_ARG; }
+    if (loss != PGO_LOSS_TRIVIAL && !(std::isfinite(loss_a) && loss_a > 0.0)) { p->err = "the robust loss parameter must be finite and positive"; return PGO_ERR_INVALID_ARG; }
+    if (n > 0 && !w) { p->err = "weight array required for relative-pose edges"; return PGO_ERR_INVALID_ARG; }
+    return add_edges(p, p->rel, n, c1, c2, T, w, nullptr, loss == PGO_LOSS_HUBER ? loss_a : loss == PGO_LOSS_CAUCHY ? -loss_a : 0.0);
+}
+int pgo_get_relpose_edge_loss(const pgo_problem* p, int64_t first, int64_t n, int32_t* loss, double* loss_a) {
+    if (!p || first < 0 || n < 0 || first + n > p->rel.size()) return PGO_ERR_INVALID_ARG;
+    for (int64_t k = 0; k < n; ++k) {
+        const double enc = first + k < (int64_t)p->rel.loss.size() ? p->rel.loss[first + k] : 0.0;
+        if (loss) loss[k] = enc > 0.0 ? PGO_LOSS_HUBER : enc < 0.0 ? PGO_LOSS_CAUCHY : PGO_LOSS_TRIVIAL;
+        if (loss_a) loss_a[k] = std::fabs(enc);
+    }
+    return PGO_OK;
+}
 int pgo_add_switchable_edges(pgo_problem* p, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, const int32_t* sw) {
     if (!p) return PGO_ERR_INVALID_ARG;
     if (n > 0 && !sw) { p->err = "switch index array required"; return PGO_ERR_INVALID_ARG; }
