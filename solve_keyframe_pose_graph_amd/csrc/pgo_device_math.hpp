@@ -121,6 +121,89 @@ PGO_HD void relpose_residual(const Pose& c1, const Pose& c2, const Meas& m, doub
 }
 
 // ---------------------------------------------------------------------------------------------
+// Yaw/pitch/roll-weighted relative-pose residual (FourDOFError, src/CeresResidues.h:252-333, created at src/PoseGraphSLAM.cpp:1630) at weight w
+// and gains g = (g_y, g_p, g_r) — the reference's are (4, 10, 10).  dt and dq as in relpose_residual; R = R(dq) by quat_to_rot; R2ypr
+// (PoseManipUtils.cpp:143-158) restated with h = sqrt(R00^2 + R10^2), c_y = R00 / h, s_y = R10 / h (so that R00 c_y + R10 s_y = h):
+//   y = atan2(R10, R00)   p = atan2(-R20, h)   r = atan2(R02 s_y - R12 c_y, -R01 s_y + R11 c_y)      taken in degrees
+//   r6 = w [ dt ; g_y y ; g_p p ; g_r r ]
+// Rows 0..2 of the blocks are those of relpose_residual.  A left perturbation moves R by dR = [phi]x R, phi = 2 R2^T (theta1 - theta2), and
+// d(y, p, r)/dphi = E, the inverse Euler-rate matrix of R = Rz(y) Ry(p) Rx(r), with s_p = -R20:
+//   E = [ s_p c_y / h , s_p s_y / h , 1 ;  -s_y , c_y , 0 ;  c_y / h , s_y / h , 0 ]
+//   dr[3..5]/dtheta1 = w diag(g) (180/pi) E 2 R2^T = -dr[3..5]/dtheta2        dr[3..5]/dt1 = dr[3..5]/dt2 = 0
+// h -> 0 (pitch error +-90 degrees) is the Euler singularity of the reference's own functor and is not handled: the block turns non-finite.
+// No kernel instantiates these forms yet: the library's kernels build SixDOFError edges only.  They are checked on the host against tests/golden/ypr_goldens.json.
+// ---------------------------------------------------------------------------------------------
+constexpr double YPR_DEG = 180.0 / 3.14159265358979323846;
+
+// the first column of R(dq), dq = q2* (x) b, decides E: T = diag(k) E with k = g (180/pi); T[7] = { T00 T01 T02 | T10 T11 | T20 T21 }
+PGO_HD void ypr_rate_rows(double R00, double R10, double R20, const double* g, double* T) {
+    const double h = sqrt(R00 * R00 + R10 * R10);
+    const double cy = R00 / h, sy = R10 / h, sp = -R20;
+    const double k0 = g[0] * YPR_DEG, k1 = g[1] * YPR_DEG, k2 = g[2] * YPR_DEG;
+    const double ch = cy / h, sh = sy / h;
+    T[0] = k0 * (sp * ch); T[1] = k0 * (sp * sh); T[2] = k0;
+    T[3] = -k1 * sy;       T[4] = k1 * cy;
+    T[5] = k2 * ch;        T[6] = k2 * sh;
+}
+
+template <bool WANT_J>
+PGO_HD void relpose_residual_ypr(const Pose& c1, const Pose& c2, const Meas& m, double w, const double* g, double* r, double* J1, double* J2) {
+    double R1[9], R2[9], Rd[9];
+    quat_to_rot(c1.qx, c1.qy, c1.qz, c1.qw, R1);
+    quat_to_rot(c2.qx, c2.qy, c2.qz, c2.qw, R2);
+    const double a0 = R1[0] * m.tx + R1[1] * m.ty + R1[2] * m.tz;
+    const double a1 = R1[3] * m.tx + R1[4] * m.ty + R1[5] * m.tz;
+    const double a2 = R1[6] * m.tx + R1[7] * m.ty + R1[8] * m.tz;
+    const double v0 = c1.tx + a0 - c2.tx, v1 = c1.ty + a1 - c2.ty, v2 = c1.tz + a2 - c2.tz;
+    const double d0 = R2[0] * v0 + R2[3] * v1 + R2[6] * v2;
+    const double d1 = R2[1] * v0 + R2[4] * v1 + R2[7] * v2;
+    const double d2 = R2[2] * v0 + R2[5] * v1 + R2[8] * v2;
+    const double q1[4] = {c1.qx, c1.qy, c1.qz, c1.qw};
+    const double qo[4] = {m.qx, m.qy, m.qz, m.qw};
+    const double q2c[4] = {-c2.qx, -c2.qy, -c2.qz, c2.qw};
+    double b[4], dq[4];
+    quat_mul(q1, qo, b);
+    quat_mul(q2c, b, dq);
+    quat_to_rot(dq[0], dq[1], dq[2], dq[3], Rd);
+    const double h = sqrt(Rd[0] * Rd[0] + Rd[3] * Rd[3]);
+    const double cy = Rd[0] / h, sy = Rd[3] / h;
+    const double yaw = atan2(Rd[3], Rd[0]);
+    const double pitch = atan2(-Rd[6], h);
+    const double roll = atan2(Rd[2] * sy - Rd[5] * cy, -Rd[1] * sy + Rd[4] * cy);
+    r[0] = w * d0; r[1] = w * d1; r[2] = w * d2;
+    r[3] = w * (g[0] * (yaw * YPR_DEG)); r[4] = w * (g[1] * (pitch * YPR_DEG)); r[5] = w * (g[2] * (roll * YPR_DEG));
+    if (WANT_J) {
+        const double p0 = R2[0] * a0 + R2[3] * a1 + R2[6] * a2;
+        const double p1 = R2[1] * a0 + R2[4] * a1 + R2[7] * a2;
+        const double p2 = R2[2] * a0 + R2[5] * a1 + R2[8] * a2;
+        double T[7];
+        ypr_rate_rows(Rd[0], Rd[3], Rd[6], g, T);
+        const double w2 = 2.0 * w;
+#define PGO_CROSS_RT(X0, X1, X2, i, j) \
+        ((i) == 0 ? (-(X2) * R2[(j) * 3 + 1] + (X1) * R2[(j) * 3 + 2]) : (i) == 1 ? ((X2) * R2[(j) * 3 + 0] - (X0) * R2[(j) * 3 + 2]) : (-(X1) * R2[(j) * 3 + 0] + (X0) * R2[(j) * 3 + 1]))
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double rt = R2[j * 3 + i];                         // R2^T(i,j)
+                J1[i * 6 + j] = -w2 * PGO_CROSS_RT(p0, p1, p2, i, j);    // -2 w [a']x R2^T
+                J1[i * 6 + 3 + j] = w * rt;
+                J2[i * 6 + j] = w2 * PGO_CROSS_RT(d0, d1, d2, i, j);     //  2 w [dt]x R2^T
+                J2[i * 6 + 3 + j] = -w * rt;
+                // (T R2^T)(i,j) = sum_k T(i,k) R2(j,k); rows 1 and 2 of T have no third entry
+                const double te = i == 0 ? T[0] * R2[j * 3] + T[1] * R2[j * 3 + 1] + T[2] * R2[j * 3 + 2]
+                                : i == 1 ? T[3] * R2[j * 3] + T[4] * R2[j * 3 + 1] : T[5] * R2[j * 3] + T[6] * R2[j * 3 + 1];
+                J1[(3 + i) * 6 + j] = w2 * te;
+                J1[(3 + i) * 6 + 3 + j] = 0.0;
+                J2[(3 + i) * 6 + j] = -w2 * te;
+                J2[(3 + i) * 6 + 3 + j] = 0.0;
+            }
+        }
+#undef PGO_CROSS_RT
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Robust loss of a relative-pose block (ceres::HuberLoss / ceres::CauchyLoss as the reference builds them, src/PoseGraphSLAM.cpp:401-402,
 // applied to the SixDOFError loop edge of :793-796) with Ceres' Corrector.  One double per edge encodes the loss: +a Huber(a), -a Cauchy(a),
 // 0 trivial.  With s = |r|^2 (r already carries the edge weight) and b = a^2:
@@ -158,6 +241,19 @@ PGO_HD double relpose_residual_robust(const Pose& c1, const Pose& c2, const Meas
     for (int i = 0; i < 6; ++i) s += r0[i] * r0[i];
     const double rho = robust_loss(enc, s, c);
     relpose_residual<WANT_J>(c1, c2, m, m.w * c, r, J1, J2);
+    return rho;
+}
+
+// ... and of a yaw/pitch/roll-weighted block: that residual is linear in w as well, so the Corrector is the same re-evaluation at weight w c
+template <bool WANT_J>
+PGO_HD double relpose_residual_ypr_robust(const Pose& c1, const Pose& c2, const Meas& m, const double* g, double enc, double* r, double* J1, double* J2, double& c) {
+    double r0[6];
+    relpose_residual_ypr<false>(c1, c2, m, m.w, g, r0, nullptr, nullptr);
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s += r0[i] * r0[i];
+    const double rho = robust_loss(enc, s, c);
+    relpose_residual_ypr<WANT_J>(c1, c2, m, m.w * c, g, r, J1, J2);
     return rho;
 }
 
@@ -236,8 +332,13 @@ PGO_HD void prior_residual(const Pose& c1, const double* Rf, const double* tf, c
 //   J1 = ws [ -2 [a']x R2^T , R2^T ; 2 M , 0 ]      J2 = ws [ 2 [dt]x R2^T , -R2^T ; -2 M , 0 ]      M = M(q2*, b)
 // (+ r6 = [dt ; 2 (q2* (x) b).vec] for switchable edges, whose Schur term is  u <- u - k (k.u),  k = r6 sqrt(1/(Js^T Js + lambda_s))).
 // compact_apply returns this edge's contribution to (J^T J p) at ONE endpoint: y = J_side^T (J1 p1 + J2 p2).
+// A yaw/pitch/roll-weighted edge (relpose_residual_ypr; never switchable) has M' = T R2^T, T = diag(k) E, k = g (180/pi), where M stands, and needs b for nothing else.
+// T's seven entries are five numbers,  T = [ rho a, rho bb, k0 ; -kappa bb, kappa a, 0 ; a, bb, 0 ]  with  a = k2 c_y / h, bb = k2 s_y / h, rho = k0 s_p / k2, kappa = k1 h / k2,
+// which compact_mark_ypr puts where b and the pad were: rec[4..7] = a, bb, rho, k0 and rec[15] = kappa > 0, the flag.  The record keeps its size and its stored planes, and the
+// matvec of such an edge needs no square root, division or further load.  Only the YPR instantiations of the functions below look at rec[15]; the kernels use the plain ones,
+// whose code is what it was.
 // ---------------------------------------------------------------------------------------------
-constexpr int COMPACT_DOUBLES = 22;   // q2[4] b[4] ap[3] dt[3] | ws pad | r6[6]   (rec[14] = ws, rec[16..21] = r6)
+constexpr int COMPACT_DOUBLES = 22;   // q2[4] b[4] ap[3] dt[3] | ws pad | r6[6]   (rec[14] = ws, rec[16..21] = r6; a yaw/pitch/roll edge: rec[4..7] and rec[15] hold T, see above)
 
 PGO_HD void edge_compact(const Pose& c1, const Pose& c2, const Meas& m, double ws, bool want_r6, double* rec) {
     double R1[9], R2[9];
@@ -289,7 +390,22 @@ PGO_HD void rot_fwd(const double* q, double v0, double v1, double v2, double& o0
     o1 = v1 + q[3] * t1 + (q[2] * t0 - q[0] * t2);
     o2 = v2 + q[3] * t2 + (q[0] * t1 - q[1] * t0);
 }
+// turns the record edge_compact wrote into that of a yaw/pitch/roll-weighted edge with gains g (work of the compaction, once per linearisation, not of the matvec).
+// The flag is kappa itself: at the Euler singularity (h = 0) the record would stay unmarked with non-finite rec[4..7] — the edge's own block (relpose_residual_ypr) is
+// non-finite there too, and that has to stop the step first.  rec[6] divides by the roll gain: every gain must be > 0, which the caller has to enforce.
+PGO_HD void compact_mark_ypr(double* rec, const double* g) {
+    const double q2c[4] = {-rec[0], -rec[1], -rec[2], rec[3]};
+    double dq[4];
+    quat_mul(q2c, rec + 4, dq);
+    const double tx = 2.0 * dq[0], ty = 2.0 * dq[1], tz = 2.0 * dq[2];      // (the three entries of quat_to_rot's first column, same expressions)
+    const double R00 = 1.0 - (ty * dq[1] + tz * dq[2]), R10 = ty * dq[0] + tz * dq[3], R20 = tz * dq[0] - ty * dq[3];
+    const double h = sqrt(R00 * R00 + R10 * R10);
+    const double k0 = g[0] * YPR_DEG, k1 = g[1] * YPR_DEG, k2 = g[2] * YPR_DEG;
+    rec[4] = k2 * ((R00 / h) / h); rec[5] = k2 * ((R10 / h) / h); rec[6] = k0 * (-R20) / k2; rec[7] = k0;
+    rec[15] = k1 * h / k2;
+}
 // u = W (J1 p1 + J2 p2) (+ the switch Schur term): the part of an edge's product that both endpoints share
+template <bool YPR = false>
 PGO_HD void compact_u(const double* rec, const double* p1, const double* p2, double kscale, double* u) {
     const double* q2 = rec;          // (x, y, z, w)
     const double* b = rec + 4;
@@ -303,6 +419,15 @@ PGO_HD void compact_u(const double* rec, const double* p1, const double* p2, dou
     u[0] = ws * (f0 + 2.0 * ((d1 * g22 - d2 * g21) - (ap1 * g12 - ap2 * g11)));
     u[1] = ws * (f1 + 2.0 * ((d2 * g20 - d0 * g22) - (ap2 * g10 - ap0 * g12)));
     u[2] = ws * (f2 + 2.0 * ((d0 * g21 - d1 * g20) - (ap0 * g11 - ap1 * g10)));
+    if (YPR && rec[15] != 0.0) {      // u_q = 2 ws T R2^T (theta1 - theta2)
+        const double a = rec[4], bb = rec[5], rho = rec[6], k0 = rec[7], kappa = rec[15];
+        const double e0 = g10 - g20, e1 = g11 - g21, e2 = g12 - g22;
+        const double w2 = 2.0 * ws, sab = a * e0 + bb * e1;
+        u[3] = w2 * (rho * sab + k0 * e2);
+        u[4] = w2 * (kappa * (a * e1 - bb * e0));
+        u[5] = w2 * sab;
+        return;
+    }
     // M(a, b) with a = conj(q2): av = -q2.vec, aw = q2.w;  M = dd I - av bv^T - bv av^T + [c]x,  c = bw av - aw bv
     const double av0 = -q2[0], av1 = -q2[1], av2 = -q2[2], aw = q2[3];
     const double dd = aw * b[3] + (av0 * b[0] + av1 * b[1] + av2 * b[2]);
@@ -324,10 +449,31 @@ PGO_HD void compact_u(const double* rec, const double* p1, const double* p2, dou
     }
 }
 // y = J_side^T u
+template <bool YPR = false>
 PGO_HD void compact_side(const double* rec, const double* u, int side, double* y) {
     const double* q2 = rec;
     const double* b = rec + 4;
     const double ap0 = rec[8], ap1 = rec[9], ap2 = rec[10], d0 = rec[11], d1 = rec[12], d2 = rec[13], ws = rec[14];
+    if (YPR && rec[15] != 0.0) {      // w3 = R2 (x + T^T u_q)
+        const double a = rec[4], bb = rec[5], rho = rec[6], k0 = rec[7], kappa = rec[15];
+        const double s0 = side ? d0 : ap0, s1 = side ? d1 : ap1, s2 = side ? d2 : ap2;
+        const double x0 = s1 * u[2] - s2 * u[1], x1 = s2 * u[0] - s0 * u[2], x2 = s0 * u[1] - s1 * u[0];
+        const double c = rho * u[3] + u[5], ku = kappa * u[4];
+        const double m0 = a * c - bb * ku;
+        const double m1 = bb * c + a * ku;
+        const double m2 = k0 * u[3];
+        const double sg = side ? -ws : ws;
+        double rx0, rx1, rx2, ru0, ru1, ru2;
+        rot_fwd(q2, x0 + m0, x1 + m1, x2 + m2, rx0, rx1, rx2);
+        rot_fwd(q2, u[0], u[1], u[2], ru0, ru1, ru2);
+        y[0] = 2.0 * sg * rx0;
+        y[1] = 2.0 * sg * rx1;
+        y[2] = 2.0 * sg * rx2;
+        y[3] = sg * ru0;
+        y[4] = sg * ru1;
+        y[5] = sg * ru2;
+        return;
+    }
     const double av0 = -q2[0], av1 = -q2[1], av2 = -q2[2], aw = q2[3];
     const double dd = aw * b[3] + (av0 * b[0] + av1 * b[1] + av2 * b[2]);
     const double c0 = b[3] * av0 - aw * b[0], c1 = b[3] * av1 - aw * b[1], c2 = b[3] * av2 - aw * b[2];
@@ -349,18 +495,20 @@ PGO_HD void compact_side(const double* rec, const double* u, int side, double* y
     y[4] = sg * ru1;
     y[5] = sg * ru2;
 }
+template <bool YPR = false>
 PGO_HD void compact_apply(const double* rec, int side, const double* p_own, const double* p_other, double kscale, double* y) {
     double u[6];
-    compact_u(rec, side ? p_other : p_own, side ? p_own : p_other, kscale, u);
-    compact_side(rec, u, side, y);
+    compact_u<YPR>(rec, side ? p_other : p_own, side ? p_own : p_other, kscale, u);
+    compact_side<YPR>(rec, u, side, y);
 }
 // both endpoints of one edge from ONE evaluation of u (the lane of an edge whose two keyframes sit in the same matvec tile): the same
 // expressions as two compact_apply calls, so the results are bit-identical to them; what the two sides share (M^T u_q, R2 u_t) is computed once
+template <bool YPR = false>
 PGO_HD void compact_apply_both(const double* rec, const double* p1, const double* p2, double kscale, double* y1, double* y2) {
     double u[6];
-    compact_u(rec, p1, p2, kscale, u);
-    compact_side(rec, u, 0, y1);
-    compact_side(rec, u, 1, y2);
+    compact_u<YPR>(rec, p1, p2, kscale, u);
+    compact_side<YPR>(rec, u, 0, y1);
+    compact_side<YPR>(rec, u, 1, y2);
 }
 
 // ceres::EigenQuaternionParameterization::Plus:  q+ = [sin|d| d/|d| ; cos|d|] (x) q
