@@ -515,6 +515,27 @@ int pgo_get_sharding_stats(pgo_problem* p, pgo_sharding_stats* out);
  * inverse (coarsest level only), 0, 0}.  The same numbers whichever way the set-up ran (pgo_options.mg_dist_setup), up to the order of the sums. */
 int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8);
 
+/* Test diagnostics of the preconditioners as linear operators (tests/test_gpu_precond_operator.py; one GPU only: PGO_ERR_STATE with a communicator attached).
+ *
+ * pgo_apply_preconditioner: Z[v] = M^-1 R[v] for n_vec host vectors of 6 n_nodes doubles (global keyframe order), M^-1 = the block-Jacobi, two-level or multigrid
+ * preconditioner (which = PGO_PRECOND_BLOCK_JACOBI / _TWO_LEVEL / _MULTIGRID) of the open solve's current LM system at trust-region radius `radius` (<= 0: the current
+ * one).  The system is built once, as pgo_apply_normal_operator builds it (damping, reduced diagonal, block-Jacobi factors); the asked-for preconditioner's operators
+ * are built whatever the solver's own rules would choose for this system; every vector then takes the launches of the PCG's start (z = D^-1 r, the coarse correction
+ * added by the two-level method's / the multigrid's own start-up kernels).  Rows of constant and unreferenced keyframes are read as zero and come back as zero.
+ * PGO_ERR_STATE (text: pgo_last_error) without an open solve, for an invalid argument, and when the preconditioner cannot be built for this graph or system (a graph
+ * with a multigrid hierarchy has no two-level aggregates and the other way round; a coarse operator that is not positive definite at this radius).  The radius is
+ * restored; the system and the operators the call leaves behind are rebuilt by the next pgo_lm_step before anything reads them.
+ *
+ * pgo_get_linear_solution: the iterate x of the last PCG of the open solve (6 n_nodes doubles, global keyframe order, in the coordinates the manifold update
+ * consumes: delta_theta, delta_t per keyframe); PGO_ERR_STATE before the solve's first pgo_lm_step.
+ *
+ * pgo_mg_level_parents: the installed hierarchy's aggregate of every row of `level` — level 0: the level-1 node of every keyframe (-1: outside the system), level
+ * l >= 1: the level-(l+1) node of every level-l node; the coarsest level has none (PGO_ERR_INVALID_ARG).  *n receives the rows of that level; parent == NULL only
+ * asks for it, else capacity >= *n int32.  PGO_ERR_STATE when no hierarchy is installed (before the first pgo_solve_begin, or a graph below mg_min_keyframes). */
+int pgo_apply_preconditioner(pgo_problem* p, int32_t which, double radius, int64_t n_vec, const double* R, double* Z);
+int pgo_get_linear_solution(pgo_problem* p, double* x);
+int pgo_mg_level_parents(pgo_problem* p, int32_t level, int32_t* parent, int64_t capacity, int64_t* n);
+
 /* ------------------------------------------------------------------------------------------ */
 /* graph construction on the device from the raw VIO poses                   */
 /* ------------------------------------------------------------------------------------------ */

@@ -81,6 +81,7 @@ EXPORTS = [
     "pgo_get_jacobian_blocks", "pgo_get_normal_blocks", "pgo_apply_normal_operator", "pgo_manifold_plus",
     "pgo_comm_get_unique_id", "pgo_comm_init", "pgo_comm_destroy", "pgo_comm_init_custom", "pgo_comm_set_exchange", "pgo_local_group_create", "pgo_local_group_abort", "pgo_local_group_destroy", "pgo_comm_init_local",
     "pgo_get_sharding_stats", "pgo_mg_level_norms", "pgo_partition_edges",
+    "pgo_apply_preconditioner", "pgo_get_linear_solution", "pgo_mg_level_parents",
     "pgo_time_linearize_kernel", "pgo_time_kernel", "pgo_time_vio_odometry_kernel", "pgo_dense_spd_inverse", "pgo_device_synchronize", "pgo_strerror", "pgo_last_error", "pgo_build_info",
 ]
 
@@ -416,6 +417,30 @@ class Problem:
         """diagnostic: sums of squares of what this rank's cycle kernels read of multigrid level `level` (1-based) after the last set-up"""
         out = np.zeros(8)
         self._check(self.lib.pgo_mg_level_norms(self.h, C.c_int32(level), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def apply_preconditioner(self, which, R, radius=0.0):
+        """test diagnostic: Z[v] = M^-1 R[v] for the rows of R (n_vec x 6 n_nodes), M^-1 = the PRECOND_* preconditioner of the open solve's current LM system at
+        `radius` (<= 0: the current one), built once for the whole batch"""
+        R = _d(R)
+        n_vec = 1 if R.ndim == 1 else R.shape[0]
+        Z = np.zeros_like(R)
+        self._check(self.lib.pgo_apply_preconditioner(self.h, C.c_int32(which), C.c_double(radius), C.c_int64(n_vec), _pd(R), _pd(Z)))
+        return Z
+
+    def linear_solution(self):
+        """test diagnostic: the iterate of the last PCG of the open solve (6 n_nodes)"""
+        N, _ = self._shape
+        x = np.zeros(6 * N)
+        self._check(self.lib.pgo_get_linear_solution(self.h, _pd(x)))
+        return x
+
+    def mg_level_parents(self, level):
+        """test diagnostic: the installed hierarchy's aggregate of every row of `level` (0: the keyframes, -1 outside the system)"""
+        n = C.c_int64(0)
+        self._check(self.lib.pgo_mg_level_parents(self.h, C.c_int32(level), None, C.c_int64(0), C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        self._check(self.lib.pgo_mg_level_parents(self.h, C.c_int32(level), _pi(out), C.c_int64(out.size), C.byref(n)))
         return out
 
     def comm_destroy(self):

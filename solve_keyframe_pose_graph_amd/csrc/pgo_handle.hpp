@@ -349,6 +349,7 @@ int nodes_from_global(pgo_problem* p, const double* host_global, int k, double* 
 int build_two_level_aggregates(pgo_problem* p);
 void two_level_solve_begin(pgo_problem* p);
 void two_level_solve_end(pgo_problem* p);
+int build_coarse(pgo_problem* p, bool force = false);
 int build_system(pgo_problem* p, bool* ok);
 bool single_reduction(const pgo_problem* p);
 // The form of a PCG iteration: its recurrence, and what follows the vector update.  Chosen once per PCG phase (choose_form), again where the in-flight switch installs the multigrid.

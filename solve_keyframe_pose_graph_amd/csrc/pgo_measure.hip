@@ -1,7 +1,9 @@
 // pgo_measure.hip — measurement helpers and test diagnostics of the C-ABI: HIP-event times and algorithmic bytes of the solver's kernels on the state of an open solve
-// (pgo_time_kernel), of K0 (pgo_time_vio_odometry_kernel) and of the dense inverse (pgo_dense_spd_inverse), and the sums of squares of a multigrid level's operators
-// (pgo_mg_level_norms).  Nothing here runs inside a solve's own steps.
+// (pgo_time_kernel), of K0 (pgo_time_vio_odometry_kernel) and of the dense inverse (pgo_dense_spd_inverse), the sums of squares of a multigrid level's operators
+// (pgo_mg_level_norms), a preconditioner applied to the caller's vectors (pgo_apply_preconditioner), the last PCG's iterate (pgo_get_linear_solution) and the installed
+// hierarchy's aggregates (pgo_mg_level_parents).  Nothing here runs inside a solve's own steps.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -285,6 +287,96 @@ int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8) {
             if ((rc = sq32(A.r_valf, R.rT0 * 36, (R.rT1 - R.rT0) * 36, out8 + 4)) != PGO_OK) return rc;
         }
     } else if ((rc = sq64(p->coarse.K.Ac, 0, (int64_t)p->coarse.K.nc * p->coarse.K.nc, out8 + 5)) != PGO_OK) return rc;      // the dense level: its inverse
+    return PGO_OK;
+}
+
+// Test diagnostic: Z[v] = M^-1 R[v] with the asked-for preconditioner of the current LM system at `radius` (<= 0: the current one).  The system is built ONCE, the way
+// pgo_apply_normal_operator builds it; then the preconditioner's operators, whatever build_system's own rules would choose for this system; then every vector takes the
+// unfused start path of pcg_start: cg_init (r = R[v], z = D^-1 r) and launch_coarse_apply / launch_mg_apply as the PCG start launches them.  One GPU only.
+int pgo_apply_preconditioner(pgo_problem* p, int32_t which, double radius, int64_t n_vec, const double* R, double* Z) {
+    if (!p) return PGO_ERR_INVALID_ARG;
+    auto refuse = [&](const char* why) { p->err = std::string("pgo_apply_preconditioner: ") + why; return PGO_ERR_STATE; };
+    if (p->comm || p->local_ids) return refuse("one GPU only: a communicator is attached");
+    if (!p->in_solve) return refuse("needs an open solve (pgo_solve_begin)");
+    if (which != PGO_PRECOND_BLOCK_JACOBI && which != PGO_PRECOND_TWO_LEVEL && which != PGO_PRECOND_MULTIGRID) return refuse("invalid argument: which is not one of PGO_PRECOND_BLOCK_JACOBI / TWO_LEVEL / MULTIGRID");
+    if (n_vec < 1 || !R || !Z || !std::isfinite(radius)) return refuse("invalid argument: null array, no vector, or a radius that is not finite");
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    if ((rc = mg_fresh_install(p)) != PGO_OK) return rc;      // a fresh graph's hierarchy decides which preconditioners this graph has
+    // what the call must leave as it found it: the radius, and the two-level method's comparison state (build_system may spend a retest)
+    struct Restore {
+        pgo_problem* p; double radius; int mode, retests;
+        ~Restore() { p->radius = radius; p->coarse.mode = mode; p->coarse.retests = retests; p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0; }
+    } restore{p, p->radius, p->coarse.mode, p->coarse.retests};
+    if (radius > 0.0) p->radius = radius;
+    if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);
+    bool ok = true;
+    if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
+    if (!ok) return refuse("a diagonal block of the system is not positive definite at this radius");
+    if (which == PGO_PRECOND_BLOCK_JACOBI) { p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0; }
+    else if (which == PGO_PRECOND_TWO_LEVEL) {
+        if (p->mg.built || !p->coarse.built) return refuse("this graph has no two-level aggregates (it has a multigrid hierarchy, or coarse_aggregates is off)");
+        p->mg.active = false; p->C.extra_rz = 0;
+        if ((rc = build_coarse(p, true)) != PGO_OK) return rc;
+        if (!p->coarse.active) return refuse("the coarse operator of the two-level method is not positive definite at this radius");
+    } else {
+        if (!p->mg.built) return refuse("this graph has no multigrid hierarchy (mg_min_keyframes, or it does not coarsen)");
+        p->coarse.active = false;
+        if (!p->mg.active && (rc = build_mg(p)) != PGO_OK) return rc;
+        if (!p->mg.active) return refuse("the multigrid operators of this system are not positive definite");
+    }
+    const int64_t n6 = p->N * 6;
+    DBuf<double> d_in;      // the vector in b's place, and a solution vector for cg_init to zero instead of the last PCG's
+    HIPCHK(p, d_in.ensure((size_t)n6 * 2));
+    CgDev C = p->C;
+    C.b = d_in.p; C.x = d_in.p + n6;
+    std::vector<double> h((size_t)n6);
+    for (int64_t v = 0; v < n_vec; ++v) {
+        std::memcpy(h.data(), R + (size_t)v * n6, (size_t)n6 * sizeof(double));
+        for (int64_t n = 0; n < p->N; ++n) if (!p->h_node_free[n]) for (int c = 0; c < 6; ++c) h[(size_t)n * 6 + c] = 0.0;      // rows outside the system: their residual is zero in every PCG
+        HIPCHK(p, hipMemcpyAsync(d_in.p, h.data(), (size_t)n6 * sizeof(double), hipMemcpyHostToDevice, p->st));
+        if (which == PGO_PRECOND_BLOCK_JACOBI) launch_cg_init(p->G, C, 0, 0.0, p->st);
+        else {
+            launch_cg_init_vectors(p->G, C, 0, p->st);
+            if (which == PGO_PRECOND_MULTIGRID) launch_mg_apply(p->G, C, p->mg.M, p->mg.levels, p->coarse.K, C.r, C.z, C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
+            else launch_coarse_apply(p->G, C, p->coarse.K, C.r, C.z, C.part_rz, false, p->st);
+        }
+        double* out = Z + (size_t)v * n6;
+        HIPCHK(p, hipMemcpyAsync(out, C.z, (size_t)n6 * sizeof(double), hipMemcpyDeviceToHost, p->st));
+        HIPCHK(p, hipStreamSynchronize(p->st));
+        for (int64_t n = 0; n < p->N; ++n) if (!p->h_node_free[n]) for (int c = 0; c < 6; ++c) out[(size_t)n * 6 + c] = 0.0;
+    }
+    return PGO_OK;
+}
+
+// Test diagnostic: the iterate C.x of the last PCG of the open solve, in the coordinates plus_kernel consumes
+int pgo_get_linear_solution(pgo_problem* p, double* x) {
+    if (!p || !x) return PGO_ERR_INVALID_ARG;
+    if (p->comm || p->local_ids) { p->err = "pgo_get_linear_solution: one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
+    if (!p->in_solve) { p->err = "pgo_get_linear_solution needs an open solve (pgo_solve_begin)"; return PGO_ERR_STATE; }
+    if (p->iteration < 1) { p->err = "pgo_get_linear_solution: no PCG has run in this solve yet (pgo_lm_step)"; return PGO_ERR_STATE; }
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    return nodes_to_global(p, p->C.x, 6, x);
+}
+
+// Test diagnostic: the aggregate of every row of `level` of the installed hierarchy (level 0: the keyframes, -1 outside the system); *n = the rows of that level
+int pgo_mg_level_parents(pgo_problem* p, int32_t level, int32_t* parent, int64_t capacity, int64_t* n) {
+    if (!p || !n) return PGO_ERR_INVALID_ARG;
+    *n = 0;
+    if (p->comm || p->local_ids) { p->err = "pgo_mg_level_parents: one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    if (!p->graph_dirty && (rc = mg_fresh_install(p)) != PGO_OK) return rc;
+    if (p->graph_dirty || !p->mg.built || p->mg.fresh_pending()) { p->err = "pgo_mg_level_parents: no hierarchy is installed (pgo_solve_begin builds it; mg_min_keyframes)"; return PGO_ERR_STATE; }
+    if (level < 0 || level >= p->mg.M.n_levels) { p->err = "pgo_mg_level_parents: no such level (the coarsest level has no parents)"; return PGO_ERR_INVALID_ARG; }
+    const int64_t rows = level == 0 ? p->N : (int64_t)p->mg.levels[level - 1].n;
+    *n = rows;
+    if (!parent) return PGO_OK;      // (size query)
+    if (capacity < rows) { p->err = "pgo_mg_level_parents: the array is too short for this level"; return PGO_ERR_INVALID_ARG; }
+    const int32_t* src = level == 0 ? p->mg.M.agg0 : p->mg.levels[level - 1].parent;
+    HIPCHK(p, hipStreamSynchronize(p->st));
+    HIPCHK(p, hipMemcpy(parent, src, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
     return PGO_OK;
 }
 

@@ -70,7 +70,8 @@ int build_two_level_aggregates(pgo_problem* p) {
 
 // Coarse operator of the two-level preconditioner for the system just built: Ac = P^T A P (deterministic assembly) and its dense inverse
 // (blocked Gauss-Jordan kernels).  A coarse operator that is not numerically positive definite leaves the coarse space off for this iteration.
-static int build_coarse(pgo_problem* p) {
+// force (pgo_apply_preconditioner): built whatever the solve's own comparison and the radius rule say, and without touching their state.
+int build_coarse(pgo_problem* p, bool force) {
     CoarseState& c = p->coarse;
     c.active = false;
     const double t_coarse0 = now_s();
@@ -78,13 +79,13 @@ static int build_coarse(pgo_problem* p) {
     // ~64 x coarse_aggregates keyframes), otherwise only at large trust regions, where the slow modes are the long wavelengths
     // (measured: scripts/gpu_coarse_ab.py).
     if (!c.built || p->opt.coarse_aggregates <= 0) return PGO_OK;
-    if (c.mode == 2) {
+    if (!force && c.mode == 2) {
         // dropped at a smaller trust region: the long wavelengths it removes dominate more and more as the radius grows, so it gets another
         // comparison once the radius is 9x (two accepted steps) beyond the one it lost at — at most twice per solve
         if (c.retests >= 2 || c.skip_all || !(p->radius >= 9.0 * c.drop_radius)) return PGO_OK;   // (eligibility by aggregate size / coarse_min_radius is checked below)
         ++c.retests; c.mode = 0;
     }
-    if (!(c.K.m <= 64 || (p->radius >= p->opt.coarse_min_radius && c.K.m <= 1024))) return PGO_OK;   // aggregates of thousands of keyframes are too coarse to help
+    if (!force && !(c.K.m <= 64 || (p->radius >= p->opt.coarse_min_radius && c.K.m <= 1024))) return PGO_OK;   // aggregates of thousands of keyframes are too coarse to help
     if (c.geometry_epoch != p->lin_epoch) {          // the aggregates' centroids follow the poses of the current linearisation
         launch_coarse_geometry(p->G, c.K, p->d_pose[p->cur].p, p->st);
         c.geometry_epoch = p->lin_epoch;

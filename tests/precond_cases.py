@@ -1,0 +1,130 @@
+"""What tests/test_precond_model.py (CPU) and tests/test_gpu_precond_operator.py (GPU) share: the graphs, their linearisations by the CPU checker (computed once
+per process), the constant-keyframe sets, and — CPU only — the multigrid aggregates from the host shim (tests/native/mg_host.cpp) built with the arguments
+pgo_multigrid.hip hands build_hierarchy on one GPU.
+
+The multigrid graph's seed was picked on the CPU: the smoother-limit estimate omega * lambda (launch_mg_level_power, emulated by precond_model.power_estimate) of
+every sparse level of every hierarchy used here is 1.68 - 1.72 at both radii, in fp64 and with the fp32 level matrices, i.e. clear of the limit 1.75 the rescaling
+starts at (seeds 3, 7 and 11 sit at 1.72 - 1.755: the decision would then hang on the last digits of the estimate)."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+
+from tests import precond_model as pm
+from tests import util
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+RADII = (1e4, 1e7)      # the second: the largest of the decades 1e4 .. 1e7 the solver's radius rule reaches on these graphs; the model's fp32 Ac^-1 is positive definite at all of them (test_precond_model.py)
+PERTURB, STATE_SEED = 0.02, 6
+
+# name -> (keyframes, loops, f, seed)
+GRAPHS = {
+    "bj300": (300, 40, 4, 11),
+    "tl200": (200, 25, 2, 11),
+    "tl600": (600, 75, 3, 11),
+    "tl601": (601, 75, 3, 11),
+    "mg640": (640, 80, 5, 5),
+}
+# constant keyframes: a whole aggregate of ten (20-29), half of another (45-49) and — unreferenced, see graph() — the last three keyframes of the two-level graph; a run in mid-trajectory
+# of the multigrid graph
+CONSTANT_TL600 = tuple(range(20, 30)) + tuple(range(45, 50))
+CONSTANT_MG640 = tuple(range(300, 330))
+
+
+@functools.lru_cache(maxsize=None)
+def graph(name, drop_last=0):
+    """drop_last: the last `drop_last` keyframes lose every edge (unreferenced keyframes at the end of the trajectory)"""
+    n, loops, f, seed = GRAPHS[name]
+    g = util.small_graph(n, loops, f=f, seed=seed)
+    if drop_last:
+        lim = n - drop_last
+        ko = (g.odom_c1 < lim) & (g.odom_c2 < lim)
+        kl = (g.loop_c1 < lim) & (g.loop_c2 < lim)
+        kr = g.reg_node < lim
+        g.odom_c1, g.odom_c2, g.odom_T, g.odom_w = g.odom_c1[ko], g.odom_c2[ko], g.odom_T[ko], g.odom_w[ko]
+        g.loop_c1, g.loop_c2, g.loop_T, g.loop_w, g.loop_is_outlier = g.loop_c1[kl], g.loop_c2[kl], g.loop_T[kl], g.loop_w[kl], g.loop_is_outlier[kl]
+        g.reg_node, g.reg_T, g.reg_w = g.reg_node[kr], g.reg_T[kr], g.reg_w[kr]
+    return g
+
+
+def state(g):
+    return util.initial_state(g, True, perturb=PERTURB, seed=STATE_SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def linearisation(name, constant=(), drop_last=0):
+    g = graph(name, drop_last)
+    q, t, s = state(g)
+    return pm.Linearisation(util.oracle_problem(g, True), g, q, t, s, constant)
+
+
+@functools.lru_cache(maxsize=None)
+def system(name, radius, constant=(), drop_last=0):
+    return linearisation(name, constant, drop_last).system(radius)
+
+
+# ---- CPU only: the aggregates of the host hierarchy builder ----
+def _shim():
+    so = os.path.join(HERE, "native", "libmg_host.so")
+    src = os.path.join(HERE, "native", "mg_host.cpp")
+    hdr = os.path.join(ROOT, "solve_keyframe_pose_graph_amd", "csrc", "pgo_mg_host.hpp")
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", os.path.dirname(hdr), "-o", so, src])
+    lib = C.CDLL(so)
+    lib.mgh_build_regroup.restype = C.c_void_p
+    return lib
+
+
+def host_hierarchy(g, free, s, passes, dense_max, smoothed_levels):
+    """(agg0 [N], parents per sparse level, level sizes) as pgo_multigrid.hip builds them on one GPU: three first passes, level-1 aggregates inside runs of 64 keyframes,
+    loop discount 3, switch weights s^2"""
+    lib = _shim()
+    I32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+    ptr = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    N = g.n_poses
+    nf = np.ascontiguousarray(free, dtype=np.uint8)
+    rc1, rc2, sc1, sc2 = I32(g.odom_c1), I32(g.odom_c2), I32(g.loop_c1), I32(g.loop_c2)
+    rw = np.ascontiguousarray(g.odom_w, dtype=np.float64)
+    sw = np.ascontiguousarray(np.asarray(s, dtype=np.float64) ** 2)
+    h = lib.mgh_build_regroup(C.c_longlong(N), ptr(nf, C.c_ubyte), C.c_longlong(len(rc1)), ptr(rc1, C.c_int), ptr(rc2, C.c_int), ptr(rw, C.c_double), C.c_longlong(len(sc1)), ptr(sc1, C.c_int),
+                              ptr(sc2, C.c_int), ptr(sw, C.c_double), ptr(sw, C.c_double), 0, 3, passes, dense_max, 32, 12, smoothed_levels, C.c_double(3.0), 64)
+    assert h, "the graph does not coarsen"
+    h = C.c_void_p(h)
+    parents, sizes = [], []
+    nl = lib.mgh_levels(h)
+    for l in range(nl):
+        sz = np.zeros(6, np.int64)
+        lib.mgh_sizes(h, l, ptr(sz, C.c_longlong))
+        n, nnzb, nent, npar, nagg, ntile = [int(x) for x in sz]
+        rowptr, col, g_ptr, g_ent = np.zeros(n + 1, np.int64), np.zeros(nnzb, np.int32), np.zeros(nnzb + 1, np.int64), np.zeros(nent, np.int64)
+        parent, agg_ptr, tile_agg0 = np.zeros(npar, np.int32), np.zeros(nagg, np.int32), np.zeros(ntile, np.int32)
+        lib.mgh_level(h, l, ptr(rowptr, C.c_longlong), ptr(col, C.c_int), ptr(g_ptr, C.c_longlong), ptr(g_ent, C.c_longlong), ptr(parent, C.c_int), ptr(agg_ptr, C.c_int), ptr(tile_agg0, C.c_int))
+        sizes.append(n)
+        if l + 1 < nl:
+            parents.append(parent)
+    agg0 = np.zeros(N, np.int32)
+    mem0_ptr = np.zeros(sizes[0] + 1, np.int32)
+    mem0 = np.zeros(int((nf != 0).sum()), np.int32)
+    lib.mgh_level0(h, ptr(agg0, C.c_int), ptr(mem0_ptr, C.c_int), ptr(mem0, C.c_int))
+    lib.mgh_free(h)
+    return agg0, parents, sizes
+
+
+# the multigrid cases: name -> (solver options that shape the hierarchy, model arguments)
+MG_CASES = {
+    "dense":         (dict(mg_smoothed_levels=0, mg_dense_max_nodes=512), dict(passes=3, dense_max=512, smoothed_levels=0, explicit=False), 1),
+    "one_sparse":    (dict(mg_smoothed_levels=0, mg_dense_max_nodes=64), dict(passes=3, dense_max=64, smoothed_levels=0, explicit=False), 2),
+    "three_levels":  (dict(mg_smoothed_levels=0, mg_dense_max_nodes=16, mg_passes=2), dict(passes=2, dense_max=16, smoothed_levels=0, explicit=False), 3),
+    "smoothed_impl": (dict(mg_smoothed_levels=1, mg_dense_max_nodes=64, mg_explicit_transfer=0), dict(passes=2, dense_max=64, smoothed_levels=1, explicit=False), 2),
+    "smoothed_expl": (dict(mg_smoothed_levels=1, mg_dense_max_nodes=64, mg_explicit_transfer=1), dict(passes=2, dense_max=64, smoothed_levels=1, explicit=True), 2),
+}
+MG_BASE = dict(mg_min_keyframes=1, mg_min_keyframes_switchable=1, mg_smoothed_fine=0, mg_switch_iterations=0)
+
+
+def limit_margin(model, omega=pm.OMEGA):
+    """distance of the smoother-limit estimate of every sparse level from the limit the rescaling starts at"""
+    return min([abs(omega * e - pm.SMOOTHER_LIMIT) for e in model["lam_est"]] or [1.0])

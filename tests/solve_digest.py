@@ -23,14 +23,16 @@ def graph(name):
     raise SystemExit("unknown graph %r" % name)
 
 
-def digest(name, **opt):
+def digest(name, handle=None, **opt):
+    """handle: solve on this handle (built by problem(name, ...); it stays open) instead of a fresh one"""
     from solve_keyframe_pose_graph_amd import capi
     from tests import util
     g, switchable = graph(name)
     q, t, s = util.initial_state(g, switchable)
-    P = util.pgo_problem(g, switchable, **opt)
+    P = handle if handle is not None else util.pgo_problem(g, switchable, **opt)
     qo, to, so, sm = P.solve(q, t, s)
-    P.close()
+    if handle is None:
+        P.close()
     h = hashlib.sha256(np.ascontiguousarray(qo).tobytes() + np.ascontiguousarray(to).tobytes() + np.ascontiguousarray(so).tobytes()).hexdigest()
     log = [[it.iteration, it.step_is_valid, it.step_is_successful, capi.STEP_REASONS[it.reason], it.preconditioner, it.cg_iterations, float(it.cost).hex(), float(it.relative_decrease).hex()]
            for it in (sm.iterations[k] for k in range(sm.num_logged))]
