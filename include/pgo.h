@@ -64,8 +64,23 @@ enum {
  *      src/PoseGraphSLAM.cpp:1270) ---- */
 enum {
     PGO_LINEAR_PCG_BLOCK_JACOBI = 0, /* device PCG on the Schur-reduced pose system, 6x6 block-Jacobi, assembled block-CSR matrix */
-    PGO_LINEAR_PCG_MATRIX_FREE = 1   /* same PCG, the matvec evaluated matrix-free from one compact record per edge side (default) */
+    PGO_LINEAR_PCG_MATRIX_FREE = 1,  /* same PCG, the matvec evaluated matrix-free from one compact record per edge side (default) */
+    PGO_LINEAR_DENSE_CHOLESKY = 2    /* EXACT: the reduced, damped system scattered into a dense matrix, blocked fp64 Cholesky factorisation and two triangular sweeps on the
+                                      * device — every step is the solution of the system to backward-stable fp64 accuracy, as with Ceres' SPARSE_NORMAL_CHOLESKY.  With it
+                                      *   - cg_*, coarse_* and mg_* are ignored: no tolerance, no preconditioner, no early-rejection pause (every valid step gets the full candidate
+                                      *     evaluation, Ceres' rule), no warm start, no multigrid hierarchy or two-level aggregates, no worker thread;
+                                      *   - a pivot that is not > 0 (or NaN) makes the step invalid with reason PGO_STEP_INVALID_FACTORIZATION: the radius halves, the solve goes on;
+                                      *   - an iteration record carries cg_iterations = cg_iterations_multigrid = single_reduction = 0, cg_residual = 0, preconditioner =
+                                      *     PGO_PRECOND_DIRECT, seconds_system = assembly + factorisation, seconds_pcg = the two triangular sweeps;
+                                      *   - pgo_solve_begin / pgo_solve refuse more than PGO_DENSE_MAX_KEYFRAMES keyframes (PGO_ERR_INVALID_ARG) and a handle with a communicator
+                                      *     attached (PGO_ERR_STATE): one GPU only.
+                                      * Not the default: the claim is exactness, not speed (see PGO_DENSE_MAX_KEYFRAMES). */
 };
+/* Largest graph PGO_LINEAR_DENSE_CHOLESKY accepts.  A MEMORY choice: the dense matrix has 6 rows per keyframe of the handle, padded to a multiple of 64 — 1024 keyframes are
+ * n = 6144, a 302 MB fp64 matrix.  It says nothing about time.  The time against the PCG is a measurement, kept in profiles/dense_cholesky_times.txt (DESIGN.md
+ * section 3.4): on session-structured graphs of 200 - 1024 keyframes the dense solver was never faster (2.0 - 11.0 ms per LM system against 0.9 - 2.4 ms) — there is no
+ * crossover below the limit. */
+#define PGO_DENSE_MAX_KEYFRAMES 1024
 
 /* Options.  Defaults (pgo_options_init) are the Ceres defaults the reference runs with, plus
  * max_num_iterations = 10 (src/PoseGraphSLAM.cpp:1268-1272).  See SURVEY.md Appendix B. */
@@ -263,7 +278,7 @@ enum {
     PGO_STEP_INVALID_MODEL = 5,          /* model_cost_change <= 0 or not finite */
     PGO_STEP_CONVERGED = 6               /* parameter or function tolerance fired on this step: the minimiser stopped, the step is not applied (Ceres) */
 };
-enum { PGO_PRECOND_BLOCK_JACOBI = 0, PGO_PRECOND_TWO_LEVEL = 1, PGO_PRECOND_MULTIGRID = 2, PGO_PRECOND_RETRIED = 16 };
+enum { PGO_PRECOND_BLOCK_JACOBI = 0, PGO_PRECOND_TWO_LEVEL = 1, PGO_PRECOND_MULTIGRID = 2, PGO_PRECOND_DIRECT = 3 /* no PCG ran: PGO_LINEAR_DENSE_CHOLESKY */, PGO_PRECOND_RETRIED = 16 };
 
 /* pgo_summary.iterations[] keeps the first PGO_MAX_ITERATION_LOG records (iteration 0 included); a stepping run that goes on longer
  * (pgo_lm_step with ignore_termination) still counts every iteration in num_iterations / cg_iterations — compare num_logged. */
@@ -609,6 +624,11 @@ int pgo_time_vio_odometry_kernel(pgo_problem* p, int32_t f_max, int32_t launches
  * with the blocked Gauss-Jordan kernels the two-level preconditioner uses for its coarse operator, `launches` times; `a_inv` (host) gets
  * the result, *avg_ms (may be NULL) the HIP-event average of one inversion.  PGO_ERR_NUMERIC when a pivot is not positive. */
 int pgo_dense_spd_inverse(pgo_problem* p, int32_t n, const double* a, double* a_inv, int32_t launches, double* avg_ms);
+/* The dense Cholesky solver's kernels on their own (test and measurement hook): solves a x = b for the symmetric positive definite n x n matrix `a` (row-major, host; its
+ * lower triangle is what is read) with exactly the factor and sweep launches PGO_LINEAR_DENSE_CHOLESKY runs per LM system, `launches` times; the matrix is padded to a
+ * multiple of 64 by an identity block.  `x` (host, n) gets the solution, *avg_ms (may be NULL) the HIP-event average of one factorisation + solve.  PGO_ERR_NUMERIC when
+ * the factorisation reports a pivot that is not positive (x is then left alone). */
+int pgo_dense_spd_solve(pgo_problem* p, int32_t n, const double* a, const double* b, double* x, int32_t launches, double* avg_ms);
 
 /* Waits for everything the handle has in flight: its stream and — after a pgo_solve_begin that (re)built the device graph — the worker thread that prepares the multigrid
  * hierarchy's host half beside the build (otherwise installed where the solve first needs it).  bench.py calls it before its timed region starts. */

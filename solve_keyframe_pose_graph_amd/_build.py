@@ -10,8 +10,8 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIBPGO = os.path.join(_HERE, "libpgo.so")
 LIBGEN = os.path.join(_HERE, "libpgo_graphgen.so")
 
-HIP_SOURCES = ["pgo_kernels.hip", "pgo_solver.hip", "pgo_graph.hip", "pgo_shard.hip", "pgo_measure.hip", "pgo_pcg.hip", "pgo_multigrid.hip", "pgo_comm.hip"]
-HIP_HEADERS = ["pgo_handle.hpp", "pgo_internal.hpp", "pgo_device_math.hpp", "pgo_mg_kernels.hpp", "pgo_mg_host.hpp", "pgo_comm.hpp"]
+HIP_SOURCES = ["pgo_kernels.hip", "pgo_solver.hip", "pgo_graph.hip", "pgo_shard.hip", "pgo_measure.hip", "pgo_pcg.hip", "pgo_multigrid.hip", "pgo_comm.hip", "pgo_dense.hip"]
+HIP_HEADERS = ["pgo_handle.hpp", "pgo_internal.hpp", "pgo_device_math.hpp", "pgo_mg_kernels.hpp", "pgo_mg_host.hpp", "pgo_comm.hpp", "pgo_dense_math.hpp"]
 
 
 def _stale(target, deps):

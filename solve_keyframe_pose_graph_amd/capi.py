@@ -47,6 +47,10 @@ class Iteration(C.Structure):
 STEP_ACCEPTED, STEP_REJECTED_RHO, STEP_REJECTED_AT_PAUSE, STEP_INVALID_FACTORIZATION, STEP_INVALID_BREAKDOWN, STEP_INVALID_MODEL, STEP_CONVERGED = range(7)
 STEP_REASONS = ["accepted", "rejected-rho", "rejected-at-pause", "invalid-factorization", "invalid-breakdown", "invalid-model", "converged"]
 PRECOND_BLOCK_JACOBI, PRECOND_TWO_LEVEL, PRECOND_MULTIGRID, PRECOND_RETRIED = 0, 1, 2, 16
+PRECOND_DIRECT = 3                      # no PCG ran: the dense Cholesky solver
+# pgo_options.linear_solver
+LINEAR_PCG_BLOCK_JACOBI, LINEAR_PCG_MATRIX_FREE, LINEAR_DENSE_CHOLESKY = 0, 1, 2
+DENSE_MAX_KEYFRAMES = 1024              # PGO_DENSE_MAX_KEYFRAMES
 
 
 class Summary(C.Structure):
@@ -82,7 +86,7 @@ EXPORTS = [
     "pgo_comm_get_unique_id", "pgo_comm_init", "pgo_comm_destroy", "pgo_comm_init_custom", "pgo_comm_set_exchange", "pgo_local_group_create", "pgo_local_group_abort", "pgo_local_group_destroy", "pgo_comm_init_local",
     "pgo_get_sharding_stats", "pgo_mg_level_norms", "pgo_partition_edges",
     "pgo_apply_preconditioner", "pgo_get_linear_solution", "pgo_mg_level_parents",
-    "pgo_time_linearize_kernel", "pgo_time_kernel", "pgo_time_vio_odometry_kernel", "pgo_dense_spd_inverse", "pgo_device_synchronize", "pgo_strerror", "pgo_last_error", "pgo_build_info",
+    "pgo_time_linearize_kernel", "pgo_time_kernel", "pgo_time_vio_odometry_kernel", "pgo_dense_spd_inverse", "pgo_dense_spd_solve", "pgo_device_synchronize", "pgo_strerror", "pgo_last_error", "pgo_build_info",
 ]
 
 _lib = None
@@ -356,6 +360,16 @@ class Problem:
         n = a.shape[0]
         out = np.empty_like(a); ms = C.c_double(0)
         self._check(self.lib.pgo_dense_spd_inverse(self.h, C.c_int32(n), _pd(a), _pd(out), C.c_int32(launches), C.byref(ms)))
+        return out, ms.value
+
+    def dense_spd_solve(self, a, b, launches=1):
+        """the dense Cholesky solver's factor and sweep launches on a symmetric positive definite matrix; returns (solution, average milliseconds)."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        n = a.shape[0]
+        assert a.shape == (n, n) and b.shape == (n,)
+        out = np.empty(n); ms = C.c_double(0)
+        self._check(self.lib.pgo_dense_spd_solve(self.h, C.c_int32(n), _pd(a), _pd(b), _pd(out), C.c_int32(launches), C.byref(ms)))
         return out, ms.value
 
     def synchronize(self):

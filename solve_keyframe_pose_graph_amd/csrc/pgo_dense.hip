@@ -1,0 +1,284 @@
+// pgo_dense.hip — the exact dense linear solver (PGO_LINEAR_DENSE_CHOLESKY): the block-CSR system of an LM step scattered into a dense row-major matrix, a blocked
+// right-looking Cholesky factorisation in place on its lower triangle, and the two triangular sweeps.  The algorithm, the block routines and the order of the block steps
+// are pgo_dense_math.hpp's (which also runs them serially on the host); this file holds the kernels, their launchers and the handle's side of a dense step (dense_step).
+//
+// Launches of one system of order n = 64 nt:  1 (first diagonal block) + 2 (nt - 1) (panel, update) for the factor, 2 nt for the sweeps.  Nothing waits on another workgroup
+// inside a launch, there are no atomics, and every sum has a fixed order.  All fp64; the panel's and the update's products run on v_mfma_f64_16x16x4_f64 (operand maps: the
+// comment above gj_block_inverse in pgo_kernels.hip).
+#include <algorithm>
+#include <cstdlib>
+
+#include "pgo_handle.hpp"
+#include "pgo_dense_math.hpp"
+
+namespace pgo {
+
+namespace {
+
+typedef double dc_d4 __attribute__((ext_vector_type(4)));
+constexpr int DC_THREADS = 256;
+
+struct DcTeam {
+    __device__ __forceinline__ int rank() const { return (int)threadIdx.x; }
+    __device__ __forceinline__ int size() const { return DC_THREADS; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+};
+
+// the 64 x 64 block at (k0, k0) -> LDS, all of it (the part above the diagonal is never read)
+__device__ __forceinline__ void dc_load_block(const double* __restrict__ A, int n, int k0, double* __restrict__ l) {
+    for (int idx = threadIdx.x; idx < DC_NB * DC_NB; idx += DC_THREADS) {
+        const int r = idx >> 6, c = idx & 63;
+        l[r * DC_LD + c] = A[(size_t)(k0 + r) * n + k0 + c];
+    }
+}
+// the factored block's lower triangle -> A
+__device__ __forceinline__ void dc_store_lower(double* __restrict__ A, int n, int k0, const double* __restrict__ l) {
+    for (int idx = threadIdx.x; idx < DC_NB * DC_NB; idx += DC_THREADS) {
+        const int r = idx >> 6, c = idx & 63;
+        if (c <= r) A[(size_t)(k0 + r) * n + k0 + c] = l[r * DC_LD + c];
+    }
+}
+
+// the diagonal block of step 0 (the later ones are factored by dc_update_kernel one step ahead).  force_fail: PGO_DEBUG_BREAK_DENSE
+__global__ __launch_bounds__(DC_THREADS) void dc_first_block_kernel(double* __restrict__ A, int n, int32_t* __restrict__ fail, int force_fail) {
+    __shared__ double l[DC_NB * DC_LD];
+    dc_load_block(A, n, 0, l);
+    __syncthreads();
+    const bool bad = dc_factor_block(DcTeam{}, l);
+    dc_store_lower(A, n, 0, l);
+    if (threadIdx.x == 0 && (bad || force_fail)) *fail = 1;
+}
+
+// Panel of step k: one workgroup per tile row i > k, one wavefront per 16 rows x of it.  The wavefront solves L_kk Y = (A_xk)^T by 16-wide block rows j: the products with
+// the block rows solved before it on the MFMA — Y_m leaves the accumulator in the D layout (row lk + 4 reg, column lr), which IS the B layout of the next product's k = 4 kk + lk
+// for reg = kk, so it never leaves the registers — then 16 substitution steps inside the 16 x 16 diagonal sub-block, the pivot row's value fetched with one cross-lane shuffle.
+// Writes L_ik over A_ik and, k-major, into LT[64][ldu] for the update's coalesced operand loads.
+__global__ __launch_bounds__(DC_THREADS) void dc_panel_kernel(double* __restrict__ A, int n, int ldu, int k, double* __restrict__ LT) {
+    __shared__ double l[DC_NB * DC_LD];
+    const int k0 = k * DC_NB;
+    dc_load_block(A, n, k0, l);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int x0 = (k + 1 + (int)blockIdx.x) * DC_NB + wave * DC_SUB;      // < n: the grid has nt - k - 1 workgroups
+    double* __restrict__ arow = A + (size_t)(x0 + lr) * n + k0;
+    dc_d4 Y[DC_NB / DC_SUB];
+#pragma unroll
+    for (int j = 0; j < DC_NB / DC_SUB; ++j) {
+        double r[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = arow[j * DC_SUB + lk + 4 * reg];
+        dc_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int m = 0; m < j; ++m)
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(j * DC_SUB + lr) * DC_LD + m * DC_SUB + 4 * kk + lk], Y[m][kk], acc, 0, 0, 0);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = r[reg] - acc[reg];
+#pragma unroll
+        for (int p = 0; p < DC_SUB; ++p) {
+            const double yp = __shfl(r[p >> 2], (p & 3) * 16 + lr) / l[(j * DC_SUB + p) * DC_LD + j * DC_SUB + p];
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int q = lk + 4 * reg;
+                const double lqp = l[(j * DC_SUB + (q > p ? q : p)) * DC_LD + j * DC_SUB + p];      // (q <= p: the diagonal entry, unused)
+                r[reg] = q == p ? yp : (q > p ? r[reg] - lqp * yp : r[reg]);
+            }
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            Y[j][reg] = r[reg];
+            arow[j * DC_SUB + lk + 4 * reg] = r[reg];
+            LT[(size_t)(j * DC_SUB + lk + 4 * reg) * ldu + x0 + lr] = r[reg];
+        }
+    }
+}
+
+// Trailing update of step k: one workgroup per 64 x 64 tile (bi, bj), k < bj <= bi, 32 x 32 per wavefront as 2 x 2 MFMA tiles over K = 64, operands from the k-major
+// copy of the panel.  The workgroup of tile (k + 1, k + 1) — dispatched first — keeps its tile in LDS, factors it there and writes the factor's lower triangle: the next
+// step's diagonal block is never a launch of its own.
+__global__ __launch_bounds__(DC_THREADS) void dc_update_kernel(double* __restrict__ A, int n, int ldu, int k, const double* __restrict__ LT, int32_t* __restrict__ fail) {
+    __shared__ double a[DC_NB * DC_LD];
+    const int bi = k + 1 + (int)blockIdx.y, bj = k + 1 + (int)blockIdx.x;      // < nt: the grid is (nt - k - 1)^2
+    if (bj > bi) return;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int i0 = bi * DC_NB + wr * 32, j0 = bj * DC_NB + wc * 32;
+    const int k1 = (k + 1) * DC_NB;
+    const bool ahead = bi == k + 1 && bj == k + 1;                 // this workgroup owns the next diagonal block
+    if (!(bi == bj && wr == 0 && wc == 1)) {                       // (that quadrant lies above the diagonal)
+        dc_d4 acc[2][2];
+        double old[2][2][4];                                       // the tile's current values: all 16 loads in flight before the first store
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                acc[s][t] = dc_d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) old[s][t][reg] = A[(size_t)(i0 + s * 16 + lk + 4 * reg) * n + j0 + t * 16 + lr];
+            }
+#pragma unroll
+        for (int kk = 0; kk < DC_NB / 4; ++kk) {
+            const size_t row = (size_t)(kk * 4 + lk) * ldu;
+            const double a0 = LT[row + i0 + lr], a1 = LT[row + i0 + 16 + lr], b0 = LT[row + j0 + lr], b1 = LT[row + j0 + 16 + lr];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int i = i0 + s * 16 + lk + 4 * reg, j = j0 + t * 16 + lr;
+                    const double v = old[s][t][reg] - acc[s][t][reg];
+                    if (ahead) a[(i - k1) * DC_LD + (j - k1)] = v;      // (written to A once, as the factor)
+                    else A[(size_t)i * n + j] = v;
+                }
+    }
+    if (!ahead) return;
+    __syncthreads();
+    const bool bad = dc_factor_block(DcTeam{}, a);
+    dc_store_lower(A, n, k1, a);
+    if (threadIdx.x == 0 && bad) *fail = 1;
+}
+
+// Forward sweep, step k: every workgroup solves L_kk y_k = w_k in LDS; the one of tile k writes y_k, the one of tile i > k takes L_ik y_k off its 64 rows of w
+__global__ __launch_bounds__(DC_THREADS) void dc_forward_kernel(const double* __restrict__ A, int n, int k, double* __restrict__ w, double* __restrict__ yv) {
+    __shared__ double l[DC_NB * DC_LD];
+    __shared__ double v[DC_NB], y[DC_NB], part[DC_NB * 4];
+    const int k0 = k * DC_NB, tid = threadIdx.x;
+    const int i0 = (k + (int)blockIdx.x) * DC_NB;                  // < n: the grid has nt - k workgroups
+    dc_load_block(A, n, k0, l);
+    if (tid < DC_NB) v[tid] = w[k0 + tid];
+    __syncthreads();
+    dc_forward_block(DcTeam{}, l, v, y);
+    if (blockIdx.x == 0) { if (tid < DC_NB) yv[k0 + tid] = y[tid]; return; }
+    const int r = tid >> 2, q = tid & 3;
+    const double* __restrict__ arow = A + (size_t)(i0 + r) * n + k0;
+    double s = 0.0;
+#pragma unroll
+    for (int c = 16 * q; c < 16 * q + 16; ++c) s += arow[c] * y[c];
+    part[r * 4 + q] = s;
+    __syncthreads();
+    if (tid < DC_NB) w[i0 + tid] -= dc_sum4(part[tid * 4], part[tid * 4 + 1], part[tid * 4 + 2], part[tid * 4 + 3]);
+}
+
+// Backward sweep, step k: every workgroup solves L_kk^T x_k = y_k; the one of tile k writes x_k (entries below n_out only), the one of tile j < k takes L_kj^T x_k off its
+// 64 entries of y
+__global__ __launch_bounds__(DC_THREADS) void dc_backward_kernel(const double* __restrict__ A, int n, int k, double* __restrict__ yv, double* __restrict__ x, int n_out) {
+    __shared__ double l[DC_NB * DC_LD];
+    __shared__ double v[DC_NB], xs[DC_NB], part[DC_NB * 4];
+    const int k0 = k * DC_NB, tid = threadIdx.x;
+    const int j0 = (int)blockIdx.x * DC_NB;                        // <= k0: the grid has k + 1 workgroups
+    dc_load_block(A, n, k0, l);
+    if (tid < DC_NB) v[tid] = yv[k0 + tid];
+    __syncthreads();
+    dc_backward_block(DcTeam{}, l, v, xs);
+    if ((int)blockIdx.x == k) { if (tid < DC_NB && k0 + tid < n_out) x[k0 + tid] = xs[tid]; return; }
+    const int c = tid & 63, q = tid >> 6;
+    double s = 0.0;
+#pragma unroll
+    for (int r = 16 * q; r < 16 * q + 16; ++r) s += A[(size_t)(k0 + r) * n + j0 + c] * xs[r];
+    part[c * 4 + q] = s;
+    __syncthreads();
+    if (tid < DC_NB) yv[j0 + tid] -= dc_sum4(part[tid * 4], part[tid * 4 + 1], part[tid * 4 + 2], part[tid * 4 + 3]);
+}
+
+// The reduced, damped block-CSR system (C.val, written by build_rows) -> the lower triangle of the zeroed dense matrix, and C.b -> w.  One thread per entry (a, c) of a block
+// row: it walks the row's blocks in their stored order and ADDS (two edges between the same keyframes give two blocks at the same place), so no two threads meet at an
+// address.  Rows and columns of keyframes outside the system (constant, unreferenced) and the padding up to n: identity, right-hand side 0.
+__global__ __launch_bounds__(DC_THREADS) void dc_scatter_kernel(GraphDev G, CgDev C, double* __restrict__ A, int n, double* __restrict__ w) {
+    const int64_t gid = (int64_t)blockIdx.x * DC_THREADS + threadIdx.x;
+    const int64_t n6 = G.N * 6;
+    if (gid >= G.N * 36) {
+        const int64_t i = n6 + (gid - G.N * 36);
+        if (i < n) { A[(size_t)i * n + i] = 1.0; w[i] = 0.0; }
+        return;
+    }
+    const int64_t node = gid / 36;
+    const int e = (int)(gid - node * 36), a = e / 6, c = e - a * 6;
+    const size_t row = (size_t)node * 6 + a;
+    if (!G.node_free[node]) {
+        if (a == c) A[row * n + row] = 1.0;
+        if (c == 0) w[row] = 0.0;
+        return;
+    }
+    const int at = (a >> 1) * 12 + c * 2 + (a & 1);      // column-pair-major block layout
+    for (int64_t b = G.bsr_rowptr[node]; b < G.bsr_rowptr[node + 1]; ++b) {
+        const int32_t col = G.bsr_col[b];
+        if (col > node || !G.node_free[col]) continue;
+        A[row * n + (size_t)col * 6 + c] += C.val[(size_t)b * 36 + at];
+    }
+    if (c == 0) w[row] = C.b[row];
+}
+
+struct DcLaunch {
+    double* A; int n, ldu; double* LT; int32_t* fail; int force_fail; double* w; double* yv; double* x; int n_out; hipStream_t st;
+    int nt() const { return n / DC_NB; }
+    void factor_first() { hipLaunchKernelGGL(dc_first_block_kernel, dim3(1), dim3(DC_THREADS), 0, st, A, n, fail, force_fail); }
+    void panel(int k) { hipLaunchKernelGGL(dc_panel_kernel, dim3((unsigned)(nt() - k - 1)), dim3(DC_THREADS), 0, st, A, n, ldu, k, LT); }
+    void update(int k) { hipLaunchKernelGGL(dc_update_kernel, dim3((unsigned)(nt() - k - 1), (unsigned)(nt() - k - 1)), dim3(DC_THREADS), 0, st, A, n, ldu, k, (const double*)LT, fail); }
+    void forward(int k) { hipLaunchKernelGGL(dc_forward_kernel, dim3((unsigned)(nt() - k)), dim3(DC_THREADS), 0, st, (const double*)A, n, k, w, yv); }
+    void backward(int k) { hipLaunchKernelGGL(dc_backward_kernel, dim3((unsigned)(k + 1)), dim3(DC_THREADS), 0, st, (const double*)A, n, k, yv, x, n_out); }
+};
+
+}  // namespace
+
+size_t dense_scratch_doubles(int n) { return (size_t)DC_NB * (size_t)(n + 16); }
+
+void launch_dense_factor(double* A, int n, double* scratch, int32_t* fail, bool force_fail, hipStream_t st) {
+    DcLaunch D{A, n, n + 16, scratch, fail, force_fail ? 1 : 0, nullptr, nullptr, nullptr, 0, st};
+    dc_factor_steps(n, D);
+}
+void launch_dense_solve(const double* A, int n, double* w, double* yv, double* x, int n_out, hipStream_t st) {
+    DcLaunch D{const_cast<double*>(A), n, n + 16, nullptr, nullptr, 0, w, yv, x, n_out, st};
+    dc_solve_steps(n, D);
+}
+void launch_dense_scatter(const GraphDev& G, const CgDev& C, double* A, int n, double* w, hipStream_t st) {
+    const int64_t threads = G.N * 36 + ((int64_t)n - G.N * 6);
+    hipLaunchKernelGGL(dc_scatter_kernel, dim3((unsigned)((threads + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, st, G, C, A, n, w);
+}
+
+// ---- the handle's side
+bool dense_mode(const pgo_problem* p) { return p->opt.linear_solver == PGO_LINEAR_DENSE_CHOLESKY; }
+
+int dense_allocate(pgo_problem* p) {
+    DenseState& d = p->dense;
+    d.n = (int)((p->N * 6 + DC_NB - 1) / DC_NB * DC_NB);
+    if (d.n < DC_NB) d.n = DC_NB;
+    HIPCHK(p, d.A.ensure((size_t)d.n * d.n)); HIPCHK(p, d.scratch.ensure(dense_scratch_doubles(d.n))); HIPCHK(p, d.vec.ensure((size_t)2 * d.n));
+    d.built = true;
+    return PGO_OK;
+}
+void dense_release(pgo_problem* p) {
+    DenseState& d = p->dense;
+    for (DBuf<double>* b : {&d.A, &d.scratch, &d.vec}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    d.n = 0; d.built = false;
+}
+
+// One dense step on the system build_system has left in C.val / C.b: scatter + factor (timed as the system by lm_step), the failure flag, then the sweeps into C.x.
+// *ok = false: a pivot was not positive (or NaN), nothing was solved.  *t_factored: the host clock between the two halves.
+int dense_step(pgo_problem* p, bool* ok, double* t_factored) {
+    DenseState& d = p->dense;
+    if (!d.built || p->built_mf) { p->err = "dense Cholesky: the graph was not built for it"; return PGO_ERR_STATE; }
+    const int n = d.n;
+    int32_t* fail = p->d_flags.p + 4;
+    HIPCHK(p, hipMemsetAsync(d.A.p, 0, (size_t)n * n * sizeof(double), p->st));
+    HIPCHK(p, hipMemsetAsync(fail, 0, sizeof(int32_t), p->st));
+    launch_dense_scatter(p->G, p->C, d.A.p, n, d.vec.p, p->st);
+    launch_dense_factor(d.A.p, n, d.scratch.p, fail, debug_break_dense(), p->st);
+    int32_t h = 0;
+    HIPCHK(p, hipMemcpyAsync(&h, fail, sizeof(int32_t), hipMemcpyDeviceToHost, p->st));
+    HIPCHK(p, hipStreamSynchronize(p->st));
+    *t_factored = now_s();
+    *ok = h == 0;
+    if (!*ok) return PGO_OK;
+    launch_dense_solve(d.A.p, n, d.vec.p, d.vec.p + n, p->C.x, (int)(p->N * 6), p->st);
+    HIPCHK(p, hipStreamSynchronize(p->st));
+    return PGO_OK;
+}
+
+}  // namespace pgo

@@ -1,0 +1,191 @@
+// pgo_dense_math.hpp — the arithmetic of the dense Cholesky solver (pgo_dense.hip) that does not need a GPU: the factorisation of one 64 x 64 diagonal block, the two
+// triangular solves with such a block, the order of the block steps, and a serial host instantiation of the whole blocked factor and solve on the same order of operations
+// (tests/native/dense_chol_host.cpp).  The block routines are written once for a TEAM of cooperating threads: rank() / size() / sync().  The kernels pass their workgroup
+// (256 threads, sync = __syncthreads), the host passes DcSerial (one thread, no barrier): every entry sees the same operations in the same order on both.
+//
+// The algorithm: blocked right-looking Cholesky A = L L^T on the LOWER triangle of a row-major n x n matrix, n a multiple of 64, in place.  Per block step k
+//   panel   L_ik = A_ik L_kk^-T for every tile row i > k — a true triangular substitution, never a product with an inverse, so the factor is backward stable
+//           whatever the conditioning of L_kk;
+//   update  A_ij -= L_ik L_jk^T for k < j <= i, and the diagonal tile (k + 1, k + 1) is factored as soon as it has been updated.
+// Solve: L y = b by block columns (y_k = L_kk^-1 w_k, then w_i -= L_ik y_k for i > k), L^T x = y by block rows from the bottom (x_k = L_kk^-T y_k, then
+// y_j -= L_kj^T x_k for j < k).  Every sum has a fixed order: two runs give the same bits.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define PGO_DC_HD __host__ __device__ __forceinline__
+#else
+#define PGO_DC_HD inline
+#endif
+
+namespace pgo {
+
+constexpr int DC_NB = 64;           // block size = tile size
+constexpr int DC_LD = DC_NB + 1;    // row stride of a block held in LDS (conflict-free column walks)
+constexpr int DC_SUB = 16;          // the panel's substitution works on 16 x 16 sub-blocks (one MFMA tile)
+
+struct DcSerial {
+    PGO_DC_HD int rank() const { return 0; }
+    PGO_DC_HD int size() const { return 1; }
+    PGO_DC_HD void sync() const {}
+};
+
+// the pivot test of gj_block_inverse: not positive, or NaN
+PGO_DC_HD bool dc_bad_pivot(double d) { return !(d > 0.0); }
+
+// In-place Cholesky factor of the 64 x 64 block in a[DC_NB][DC_LD]; only the lower triangle is read and written.  Returns true when a pivot failed (every thread of the
+// team returns the same value); the block then holds numbers nobody may use.  Team size: 1, or a multiple of 16.  The caller syncs before the call.
+template <class Team>
+PGO_DC_HD bool dc_factor_block(const Team& T, double* a) {
+    bool bad = false;
+    const int nx = T.size() < 16 ? 1 : 16, ny = T.size() < 16 ? 1 : T.size() / 16;
+    const int tx = T.size() < 16 ? 0 : T.rank() % 16, ty = T.size() < 16 ? 0 : T.rank() / 16;
+    for (int p = 0; p < DC_NB; ++p) {
+        const double d = a[p * DC_LD + p];      // (stays in place until the last pass: nobody writes it during this step)
+        bad = bad || dc_bad_pivot(d);
+        const double s = sqrt(d);
+        for (int i = p + 1 + T.rank(); i < DC_NB; i += T.size()) a[i * DC_LD + p] = a[i * DC_LD + p] / s;
+        T.sync();
+        for (int i = p + 1 + ty; i < DC_NB; i += ny) {
+            const double lip = a[i * DC_LD + p];
+            for (int j = p + 1 + tx; j <= i; j += nx) a[i * DC_LD + j] = a[i * DC_LD + j] - lip * a[j * DC_LD + p];
+        }
+        T.sync();
+    }
+    for (int p = T.rank(); p < DC_NB; p += T.size()) a[p * DC_LD + p] = sqrt(a[p * DC_LD + p]);
+    T.sync();
+    return bad;
+}
+
+// L y = v with the factored block in a; v[DC_NB] is used up, y[DC_NB] receives the solution (both shared by the team).  The caller syncs before the call.
+template <class Team>
+PGO_DC_HD void dc_forward_block(const Team& T, const double* a, double* v, double* y) {
+    for (int p = 0; p < DC_NB; ++p) {
+        const double yp = v[p] / a[p * DC_LD + p];
+        if (T.rank() == 0) y[p] = yp;
+        for (int i = p + 1 + T.rank(); i < DC_NB; i += T.size()) v[i] = v[i] - a[i * DC_LD + p] * yp;
+        T.sync();
+    }
+}
+// L^T x = v
+template <class Team>
+PGO_DC_HD void dc_backward_block(const Team& T, const double* a, double* v, double* x) {
+    for (int p = DC_NB - 1; p >= 0; --p) {
+        const double xp = v[p] / a[p * DC_LD + p];
+        if (T.rank() == 0) x[p] = xp;
+        for (int i = T.rank(); i < p; i += T.size()) v[i] = v[i] - a[p * DC_LD + i] * xp;
+        T.sync();
+    }
+}
+
+// the four partial sums of a 64-term product (terms 16 q .. 16 q + 15 each, ascending) in the order the sweeps add them
+PGO_DC_HD double dc_sum4(double p0, double p1, double p2, double p3) { return (p0 + p1) + (p2 + p3); }
+
+// ---- the order of the block steps: what the launcher (one or two launches per call) and the host instantiation both run
+template <class Ops>
+inline void dc_factor_steps(int n, Ops& o) {
+    const int nt = n / DC_NB;
+    o.factor_first();                                   // the diagonal block of step 0
+    for (int k = 0; k + 1 < nt; ++k) { o.panel(k); o.update(k); }      // update(k) leaves the diagonal block of step k + 1 factored
+}
+template <class Ops>
+inline void dc_solve_steps(int n, Ops& o) {
+    const int nt = n / DC_NB;
+    for (int k = 0; k < nt; ++k) o.forward(k);
+    for (int k = nt - 1; k >= 0; --k) o.backward(k);
+}
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- serial host instantiation: the same block steps, the same block routines, scalar loops where the kernels use the fp64 MFMA (sums over k ascending, formed from zero
+// and then subtracted, as the accumulators are)
+struct DcHost {
+    int n; double* A; double* w; double* yv; double* x; bool failed = false;
+    std::vector<double> blk = std::vector<double>((size_t)DC_NB * DC_LD, 0.0);
+    double vec[DC_NB], sol[DC_NB];
+    void load_block(int k0) { for (int i = 0; i < DC_NB; ++i) for (int j = 0; j < DC_NB; ++j) blk[(size_t)i * DC_LD + j] = A[(size_t)(k0 + i) * n + k0 + j]; }
+    void factor_block(int k0) {
+        load_block(k0);
+        failed = dc_factor_block(DcSerial{}, blk.data()) || failed;
+        for (int i = 0; i < DC_NB; ++i) for (int j = 0; j <= i; ++j) A[(size_t)(k0 + i) * n + k0 + j] = blk[(size_t)i * DC_LD + j];
+    }
+    void factor_first() { factor_block(0); }
+    void panel(int k) {
+        const int k0 = k * DC_NB;
+        load_block(k0);
+        const double* l = blk.data();
+        for (int r = k0 + DC_NB; r < n; ++r) {
+            double* row = A + (size_t)r * n + k0;
+            for (int j = 0; j < DC_NB / DC_SUB; ++j) {
+                double rr[DC_SUB];
+                for (int c = 0; c < DC_SUB; ++c) {
+                    double acc = 0.0;
+                    for (int kk = 0; kk < j * DC_SUB; ++kk) acc += l[(size_t)(j * DC_SUB + c) * DC_LD + kk] * row[kk];
+                    rr[c] = row[j * DC_SUB + c] - acc;
+                }
+                for (int p = 0; p < DC_SUB; ++p) {
+                    const double yp = rr[p] / l[(size_t)(j * DC_SUB + p) * DC_LD + j * DC_SUB + p];
+                    rr[p] = yp;
+                    for (int q = p + 1; q < DC_SUB; ++q) rr[q] = rr[q] - l[(size_t)(j * DC_SUB + q) * DC_LD + j * DC_SUB + p] * yp;
+                }
+                for (int c = 0; c < DC_SUB; ++c) row[j * DC_SUB + c] = rr[c];
+            }
+        }
+    }
+    void update(int k) {
+        const int k0 = k * DC_NB, k1 = k0 + DC_NB;
+        for (int i = k1; i < n; ++i)
+            for (int j = k1; j <= i; ++j) {
+                double acc = 0.0;
+                for (int kk = 0; kk < DC_NB; ++kk) acc += A[(size_t)i * n + k0 + kk] * A[(size_t)j * n + k0 + kk];
+                A[(size_t)i * n + j] -= acc;
+            }
+        factor_block(k1);
+    }
+    void forward(int k) {
+        const int k0 = k * DC_NB;
+        load_block(k0);
+        for (int i = 0; i < DC_NB; ++i) vec[i] = w[k0 + i];
+        dc_forward_block(DcSerial{}, blk.data(), vec, sol);
+        for (int i = 0; i < DC_NB; ++i) yv[k0 + i] = sol[i];
+        for (int r = k0 + DC_NB; r < n; ++r) {
+            double part[4];
+            for (int q = 0; q < 4; ++q) { double s = 0.0; for (int c = 16 * q; c < 16 * q + 16; ++c) s += A[(size_t)r * n + k0 + c] * sol[c]; part[q] = s; }
+            w[r] -= dc_sum4(part[0], part[1], part[2], part[3]);
+        }
+    }
+    void backward(int k) {
+        const int k0 = k * DC_NB;
+        load_block(k0);
+        for (int i = 0; i < DC_NB; ++i) vec[i] = yv[k0 + i];
+        dc_backward_block(DcSerial{}, blk.data(), vec, sol);
+        for (int i = 0; i < DC_NB; ++i) x[k0 + i] = sol[i];
+        for (int c = 0; c < k0; ++c) {
+            double part[4];
+            for (int q = 0; q < 4; ++q) { double s = 0.0; for (int r = 16 * q; r < 16 * q + 16; ++r) s += A[(size_t)(k0 + r) * n + c] * sol[r]; part[q] = s; }
+            yv[c] -= dc_sum4(part[0], part[1], part[2], part[3]);
+        }
+    }
+};
+
+// Solves A x = b for the symmetric positive definite n x n matrix `a` (row-major, any n >= 1: padded to a multiple of 64 by an identity block).  Returns false — and leaves
+// x alone — when a pivot failed.
+inline bool dc_host_solve(int n, const double* a, const double* b, double* x) {
+    const int nc = (n + DC_NB - 1) / DC_NB * DC_NB;
+    std::vector<double> A((size_t)nc * nc, 0.0), w((size_t)nc, 0.0), yv((size_t)nc, 0.0), xs((size_t)nc, 0.0);
+    for (int i = 0; i < nc; ++i) {
+        if (i < n) { for (int j = 0; j < n; ++j) A[(size_t)i * nc + j] = a[(size_t)i * n + j]; w[i] = b[i]; }
+        else A[(size_t)i * nc + i] = 1.0;
+    }
+    DcHost H{nc, A.data(), w.data(), yv.data(), xs.data()};
+    dc_factor_steps(nc, H);
+    if (H.failed) return false;
+    dc_solve_steps(nc, H);
+    for (int i = 0; i < n; ++i) x[i] = xs[i];
+    return true;
+}
+#endif
+
+}  // namespace pgo

@@ -393,6 +393,8 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
 
     if ((rc = allocate_work_buffers(p)) != PGO_OK) return rc;
     bind_descriptors(p);
+    if (dense_mode(p)) { if ((rc = dense_allocate(p)) != PGO_OK) return rc; }
+    else dense_release(p);
     phase("work buffers");
 
     // ---- the preconditioner of this graph: the aggregation multigrid for large graphs — a hierarchy of graph-following rigid aggregates (pgo_mg_host.hpp), built by
@@ -401,7 +403,13 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
     phase("multigrid hierarchy");
     if (p->mg.built && p->built_mf) { HIPCHK(p, p->d_Hoff.ensure((size_t)(p->G.rel.Epad + p->G.sw.Epad) * 36)); p->L.Hoff = p->d_Hoff.p; }      // the multigrid's level-1 product reads J1^T J2 per edge
     p->hoff_epoch = 0;
-    if (!p->mg.built && (rc = build_two_level_aggregates(p)) != PGO_OK) return rc;      // (a graph that got the multigrid never uses the two-level method: its dense operator would be built and uploaded for nothing)
+    if (dense_mode(p)) {
+        // no aggregates, and no memory of them: the two-level method's history across solves (kept / dropped, back-off) counts CONSECUTIVE solves that used it, and a graph built
+        // for the exact solver ends every such run — a handle that goes back to a PCG afterwards starts where a fresh handle starts (solves before and after are bitwise equal)
+        CoarseState& c = p->coarse;
+        c.mode = 0; c.retests = 0; c.skip_all = false; c.drop_radius = 0.0; c.backoff = 0; c.skip = 0; c.keep_streak = 0;
+    }
+    if (!p->mg.built && !dense_mode(p) && (rc = build_two_level_aggregates(p)) != PGO_OK) return rc;      // (a graph that got the multigrid never uses the two-level method: its dense operator would be built and uploaded for nothing)
     phase("two-level aggregates");
     mg_guard.committed = true;
     p->graph_dirty = false; p->priors_dirty = false;

@@ -1,6 +1,6 @@
 // pgo_handle.hpp — the problem handle (struct pgo_problem) and what the host translation units share: pgo_solver.hip (LM controller, core C-ABI), pgo_graph.hip (host edge
 // lists -> device graph), pgo_shard.hip (everything multi-rank above the transport: rank-local numbering, collectives, exchanges, communicator C-ABI, edge sharding),
-// pgo_pcg.hip (the two-level method, the preconditioner of each LM system, the PCG driver), pgo_multigrid.hip (the multigrid preconditioner's host lifecycle: hierarchy build,
+// pgo_pcg.hip (the two-level method, the preconditioner of each LM system, the PCG driver), pgo_dense.hip (the dense Cholesky solver), pgo_multigrid.hip (the multigrid preconditioner's host lifecycle: hierarchy build,
 // install, regroup, operators of each LM system) and pgo_measure.hip (measurement helpers, test diagnostics).  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,6 +34,10 @@ inline bool debug_poison() { static const bool on = []() { const char* e = std::
 // PGO_DEBUG_BREAK_COARSE=1 (read at every operator build so that a test can switch it inside one process): the dense coarse inverse of the two-level method /
 // of the multigrid's coarsest level is applied with the wrong sign — a preconditioner that is not positive definite, i.e. a forced PCG breakdown.
 inline bool debug_break_coarse() { if (!debug_hooks_enabled()) return false; const char* e = std::getenv("PGO_DEBUG_BREAK_COARSE"); return e && e[0] == '1' && e[1] == 0; }
+
+// PGO_DEBUG_BREAK_DENSE=1 (read at every factorisation, like PGO_DEBUG_BREAK_COARSE): the dense Cholesky factorisation of that LM system reports a failed pivot — the
+// kernel of the first diagonal block raises the failure flag it owns, nothing else changes — so that a test can drive the invalid-step path of a dense step.
+inline bool debug_break_dense() { if (!debug_hooks_enabled()) return false; const char* e = std::getenv("PGO_DEBUG_BREAK_DENSE"); return e && e[0] == '1' && e[1] == 0; }
 
 // PGO_DEBUG_NO_SPLIT_UPDATE=1 (read once per process): the multigrid PCG keeps the unsplit vector update (cg_update_mg_kernel<true>) where it would split it
 // (tests/test_gpu_split_update.py compares the two bit for bit).
@@ -170,6 +174,15 @@ struct CoarseState {
     uint64_t geometry_epoch = 0;     // the linearisation (lin_epoch) the aggregates' centroids were computed at
 };
 
+// ---- the dense Cholesky solver's state on the handle (pgo_dense.hip; PGO_LINEAR_DENSE_CHOLESKY): sized at graph build, released by a graph build for another solver
+struct DenseState {
+    DBuf<double> A;            // [n][n] row-major: the system, then its factor L on the lower triangle
+    DBuf<double> scratch;      // the current panel, k-major (dense_scratch_doubles)
+    DBuf<double> vec;          // w [n] (right-hand side, used up by the forward sweep) and y [n]
+    int n = 0;                 // 6 keyframes-of-the-handle, padded to a multiple of 64
+    bool built = false;
+};
+
 // the handle's stream.  It goes with the handle, after the PCG's captured graphs and pinned poll buffer (pgo_problem declares it just before PcgState) and before the
 // device buffers: the order in which the handle's resources have always been released
 struct OwnedStream {
@@ -269,6 +282,7 @@ struct pgo_problem {
     DBuf<double> d_vio;              // raw VIO poses [n_vio][16] (graph construction, K0)
     DBuf<int32_t> d_vio_idx; DBuf<double> d_vio_meas;   // K0's edge endpoints and measurements of one call
     CoarseState coarse;                    // the two-level preconditioner (pgo_pcg.hip)
+    DenseState dense;                      // the dense Cholesky solver (pgo_dense.hip)
     uint64_t lin_epoch = 0;                // counts linearisations (the two-level method's centroids follow the poses)
     MgState mg;                            // the aggregation multigrid (pgo_multigrid.hip)
     uint64_t hoff_epoch = 0;               // linearisation whose J1^T J2 blocks L.Hoff holds (matrix-free solver: formed on demand for the multigrid's level-1 product)
@@ -376,6 +390,17 @@ struct CgResult { int iterations; bool breakdown; double rel_residual; bool conv
 struct PcgPhase { double tol; int resume = -1; bool warm = false; bool switch_now = false; int max_iterations = 0; };
 int run_pcg(pgo_problem* p, CgResult* res, const PcgPhase& ph);
 int finish_system(pgo_problem* p, CgResult* cg, bool evaluated, int* precond_used);
+
+// ---- pgo_dense.hip: the exact dense solver (PGO_LINEAR_DENSE_CHOLESKY)
+bool dense_mode(const pgo_problem* p);
+int dense_allocate(pgo_problem* p);      // build_graph: the buffers of this graph
+void dense_release(pgo_problem* p);      // build_graph for another solver
+int dense_step(pgo_problem* p, bool* ok, double* t_factored);      // lm_step: scatter, factor, failure flag, sweeps into C.x
+size_t dense_scratch_doubles(int n);
+// the launches themselves (n a multiple of 64; pgo_dense_spd_solve runs exactly these)
+void launch_dense_scatter(const GraphDev& G, const CgDev& C, double* A, int n, double* w, hipStream_t st);
+void launch_dense_factor(double* A, int n, double* scratch, int32_t* fail, bool force_fail, hipStream_t st);
+void launch_dense_solve(const double* A, int n, double* w, double* yv, double* x, int n_out, hipStream_t st);
 
 // ---- pgo_multigrid.hip
 bool wants_multigrid(const pgo_problem* p);

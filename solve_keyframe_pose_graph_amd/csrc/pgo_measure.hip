@@ -1,5 +1,5 @@
 // pgo_measure.hip — measurement helpers and test diagnostics of the C-ABI: HIP-event times and algorithmic bytes of the solver's kernels on the state of an open solve
-// (pgo_time_kernel), of K0 (pgo_time_vio_odometry_kernel) and of the dense inverse (pgo_dense_spd_inverse), the sums of squares of a multigrid level's operators
+// (pgo_time_kernel), of K0 (pgo_time_vio_odometry_kernel), of the dense inverse (pgo_dense_spd_inverse) and of the dense Cholesky solve (pgo_dense_spd_solve), the sums of squares of a multigrid level's operators
 // (pgo_mg_level_norms), a preconditioner applied to the caller's vectors (pgo_apply_preconditioner), the last PCG's iterate (pgo_get_linear_solution) and the installed
 // hierarchy's aggregates (pgo_mg_level_parents).  Nothing here runs inside a solve's own steps.
 #include <algorithm>
@@ -253,6 +253,43 @@ int pgo_dense_spd_inverse(pgo_problem* p, int32_t n, const double* a, double* a_
     return PGO_OK;
 }
 
+int pgo_dense_spd_solve(pgo_problem* p, int32_t n, const double* a, const double* b, double* x, int32_t launches, double* avg_ms) {
+    if (!p || n <= 0 || !a || !b || !x || launches < 1) return PGO_ERR_INVALID_ARG;
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    const int nc = (n + 63) / 64 * 64;
+    std::vector<double> h((size_t)nc * nc, 0.0), hb((size_t)nc, 0.0);
+    for (int i = 0; i < nc; ++i) {
+        if (i < n) { std::memcpy(&h[(size_t)i * nc], a + (size_t)i * n, (size_t)n * sizeof(double)); hb[i] = b[i]; }
+        else h[(size_t)i * nc + i] = 1.0;
+    }
+    DBuf<double> d_a, d_scr, d_vec, d_x; DBuf<int32_t> d_fail;
+    HIPCHK(p, d_a.ensure((size_t)nc * nc)); HIPCHK(p, d_scr.ensure(dense_scratch_doubles(nc))); HIPCHK(p, d_vec.ensure((size_t)2 * nc)); HIPCHK(p, d_x.ensure((size_t)nc)); HIPCHK(p, d_fail.ensure(1));
+    EventPair ev;
+    HIPCHK(p, ev.create());
+    float total = 0;
+    int32_t fail = 0;
+    for (int l = 0; l < launches && !fail; ++l) {
+        HIPCHK(p, hipMemcpyAsync(d_a.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, p->st));
+        HIPCHK(p, hipMemcpyAsync(d_vec.p, hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice, p->st));
+        HIPCHK(p, hipMemsetAsync(d_fail.p, 0, sizeof(int32_t), p->st));
+        HIPCHK(p, hipEventRecord(ev.e0, p->st));
+        launch_dense_factor(d_a.p, nc, d_scr.p, d_fail.p, false, p->st);
+        launch_dense_solve(d_a.p, nc, d_vec.p, d_vec.p + nc, d_x.p, nc, p->st);      // (a failed factor: the sweeps run on numbers nobody reads — inside their own buffers)
+        HIPCHK(p, hipEventRecord(ev.e1, p->st));
+        HIPCHK(p, hipMemcpyAsync(&fail, d_fail.p, sizeof(fail), hipMemcpyDeviceToHost, p->st));
+        HIPCHK(p, hipStreamSynchronize(p->st));
+        float ms = 0;
+        HIPCHK(p, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+        total += ms;
+    }
+    if (avg_ms) *avg_ms = (double)total / launches;
+    if (fail) { p->err = "matrix is not numerically positive definite"; return PGO_ERR_NUMERIC; }
+    HIPCHK(p, hipMemcpy(hb.data(), d_x.p, hb.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::memcpy(x, hb.data(), (size_t)n * sizeof(double));
+    return PGO_OK;
+}
+
 // Diagnostic (tests): sums of squares of what this rank's cycle kernels read of level `level` (1-based) — the same whichever way the set-up ran (pgo_options.mg_dist_setup)
 int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8) {
     if (!p || !out8) return PGO_ERR_INVALID_ARG;
@@ -298,6 +335,7 @@ int pgo_apply_preconditioner(pgo_problem* p, int32_t which, double radius, int64
     auto refuse = [&](const char* why) { p->err = std::string("pgo_apply_preconditioner: ") + why; return PGO_ERR_STATE; };
     if (p->comm || p->local_ids) return refuse("one GPU only: a communicator is attached");
     if (!p->in_solve) return refuse("needs an open solve (pgo_solve_begin)");
+    if (dense_mode(p)) return refuse("the dense Cholesky solver has no preconditioner");
     if (which != PGO_PRECOND_BLOCK_JACOBI && which != PGO_PRECOND_TWO_LEVEL && which != PGO_PRECOND_MULTIGRID) return refuse("invalid argument: which is not one of PGO_PRECOND_BLOCK_JACOBI / TWO_LEVEL / MULTIGRID");
     if (n_vec < 1 || !R || !Z || !std::isfinite(radius)) return refuse("invalid argument: null array, no vector, or a radius that is not finite");
     int rc;
@@ -365,6 +403,7 @@ int pgo_mg_level_parents(pgo_problem* p, int32_t level, int32_t* parent, int64_t
     if (!p || !n) return PGO_ERR_INVALID_ARG;
     *n = 0;
     if (p->comm || p->local_ids) { p->err = "pgo_mg_level_parents: one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
+    if (dense_mode(p)) { p->err = "pgo_mg_level_parents: the dense Cholesky solver builds no hierarchy"; return PGO_ERR_STATE; }
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
     if (!p->graph_dirty && (rc = mg_fresh_install(p)) != PGO_OK) return rc;

@@ -510,6 +510,7 @@ void mg_drop_pending(pgo_problem* p) {
 // the caller's keyframe and switch counts decide (the same answer on every rank): graphs with switchable loop closures — all of the reference's — take the multigrid from
 // mg_min_keyframes_switchable on, graphs without from mg_min_keyframes; mg_min_keyframes = 0 turns it off altogether
 bool wants_multigrid(const pgo_problem* p) {
+    if (dense_mode(p)) return false;      // the exact dense solver preconditions nothing: no hierarchy, no worker thread
     int64_t mg_from = p->opt.mg_min_keyframes;
     if (mg_from > 0 && p->S > 0 && p->opt.mg_min_keyframes_switchable > 0) mg_from = std::min<int64_t>(mg_from, p->opt.mg_min_keyframes_switchable);
     return mg_from > 0 && p->N_global >= mg_from;

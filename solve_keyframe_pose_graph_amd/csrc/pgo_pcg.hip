@@ -138,6 +138,7 @@ int build_system(pgo_problem* p, bool* ok) {
     p->mg.active = false; s.mg_failed = false; p->C.extra_rz = 0; s.mg_start_deferred = false;
     // block-Jacobi-equivalent iterations this system is expected to need: those of the last fully solved system of this solve x sqrt(radius ratio); 0 = no prediction
     s.cg_predicted = (s.cg_prev_radius > 0.0 && p->radius > 0.0) ? s.cg_prev_equiv * std::sqrt(p->radius / s.cg_prev_radius) : 0.0;
+    if (dense_mode(p)) { s.cg_predicted = 0.0; p->coarse.active = false; return PGO_OK; }      // the exact dense solver: no preconditioner to decide on
     if (*ok && p->mg.built) {
         // Which preconditioner the PCG of this LM system starts with.  Block-Jacobi iterations grow like sqrt(radius) from one accepted step
         // to the next, so the previous step of this solve predicts this one (a multigrid iteration counts as 4 block-Jacobi ones: it costs

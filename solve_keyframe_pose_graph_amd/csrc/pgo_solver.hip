@@ -87,6 +87,10 @@ int solve_begin(pgo_problem* p, const double* quat, const double* t, const doubl
     if (!quat || !t || N <= 0 || S < 0 || (S > 0 && !sw)) { p->err = "null state array or bad size"; return PGO_ERR_INVALID_ARG; }
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
+    if (dense_mode(p)) {      // the exact dense solver: one GPU, and a matrix that fits (PGO_DENSE_MAX_KEYFRAMES)
+        if (p->comm || p->local_ids) { p->err = "PGO_LINEAR_DENSE_CHOLESKY: one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
+        if (N > PGO_DENSE_MAX_KEYFRAMES) { p->err = "PGO_LINEAR_DENSE_CHOLESKY: more than PGO_DENSE_MAX_KEYFRAMES (" + std::to_string(PGO_DENSE_MAX_KEYFRAMES) + ") keyframes"; return PGO_ERR_INVALID_ARG; }
+    }
     p->t_begin = now_s();
     if (p->mg.job.kind == MgJob::regroup) mg_drop_pending(p);
     const bool rebuild = p->graph_dirty || p->priors_dirty || N != p->N_global || S != p->S;
@@ -120,7 +124,7 @@ int solve_begin(pgo_problem* p, const double* quat, const double* t, const doubl
     p->in_solve = true; p->terminated = false; p->scale_ready = false; p->have_prev_step = false;
     p->st_exchanges = p->st_allreduces = p->st_pcg_iterations = 0; p->st_bytes_neighbour = p->st_bytes_allreduce = 0.0;
     p->pcg.cg_prev_equiv = 0.0; p->pcg.cg_prev_radius = 0.0; p->mg.regroups = 0; p->last_rho = 1.0;
-    two_level_solve_begin(p);
+    if (!dense_mode(p)) two_level_solve_begin(p);      // (a dense solve leaves the two-level method's history across solves alone)
     p->radius = p->opt.initial_trust_region_radius; p->decrease_factor = 2.0; p->reuse_diagonal = false; p->iteration = 0; p->invalid = 0;
     p->sum.termination_type = PGO_NO_CONVERGENCE;
     if ((rc = linearize(p, &p->x_cost)) != PGO_OK) return rc;
@@ -154,9 +158,10 @@ int lm_step(pgo_problem* p, int ignore_termination, int* done) {
     if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, o.min_lm_diagonal, o.max_lm_diagonal, p->st);
     bool ok = true;
     if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
-    const double t_built = now_s();
+    double t_built = now_s();
+    const bool dense = dense_mode(p);
     int why_invalid = ok ? PGO_STEP_ACCEPTED : PGO_STEP_INVALID_FACTORIZATION;      // pgo_iteration.reason of an invalid step
-    int precond_used = PGO_PRECOND_BLOCK_JACOBI;
+    int precond_used = dense ? PGO_PRECOND_DIRECT : PGO_PRECOND_BLOCK_JACOBI;
     CgResult cg{0, false, 0.0, false};
     p->pcg.cg_extra = 0;
     const int nxt = p->cur ^ 1;
@@ -175,7 +180,13 @@ int lm_step(pgo_problem* p, int ignore_termination, int* done) {
         return read_scalars(p, h);
     };
     bool evaluated = false;
-    if (ok) {
+    if (ok && dense) {
+        // The exact solver: no PCG, no tolerance, no pause, no warm start.  Scatter + factorisation count as the system, the two sweeps as the solve; a failed pivot is
+        // Ceres' linear-solver failure — the same invalid step a failed 6x6 block gives.
+        if ((rc = dense_step(p, &ok, &t_built)) != PGO_OK) return rc;
+        p->have_prev_step = false;
+        if (!ok) why_invalid = PGO_STEP_INVALID_FACTORIZATION;
+    } else if (ok) {
         // The PCG pauses at up to two intermediate tolerances (cg_early_tolerance > cg_mid_tolerance > cg_rel_tolerance).  A rejected step
         // only changes the trust-region radius (Ceres StepRejected), so a step that is already clearly bad at a pause
         // (relative_decrease below the stage's threshold, and neither convergence test would fire) is rejected without paying for the
@@ -351,7 +362,7 @@ int solve_end(pgo_problem* p, double* quat, double* t, double* sw, pgo_summary* 
         std::memcpy(t, ht.data(), ht.size() * sizeof(double));
         if (sw && p->S > 0) std::memcpy(sw, hs.data(), hs.size() * sizeof(double));
     }
-    two_level_solve_end(p);
+    if (!dense_mode(p)) two_level_solve_end(p);
     if (p->mg.job.kind == MgJob::regroup) mg_drop_pending(p);      // a regroup nobody needed any more: dropped (the hierarchy in place keeps its own switch record)
     if ((rc = mg_fresh_install(p)) != PGO_OK) return rc;      // a fresh graph's hierarchy that this solve never needed: installed now, for the handle's next solves
     p->sum.seconds_total = now_s() - p->t_begin;
