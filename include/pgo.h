@@ -416,6 +416,32 @@ int pgo_evaluate(pgo_problem* p, const double* quat_xyzw, const double* t, const
                  int64_t n_nodes, int64_t n_switch,
                  double* cost, double* residuals, double* gradient);
 
+/* Marginal covariances of keyframe poses = `ceres::Covariance::Compute(pairs, &problem)` + `GetCovarianceBlockInTangentSpace` for pose blocks, from the dense Cholesky
+ * factor (csrc/pgo_dense.hip).  J is the Jacobian pgo_evaluate linearises at the given point, in the tangent layout documented at the top ([dtheta(3), dt(3)] per keyframe,
+ * one entry per switch); robust edges enter with their corrected blocks (Ceres: apply_loss_function = true).  H = J^T J: no LM damping (the LM diagonal, its
+ * min_lm_diagonal clamp and 1 / radius contribute exactly nothing), no scaling.
+ *   cov[k]   (36 doubles, row-major; HOST) = the 6 x 6 block (rows of node_a[k], columns of node_b[k]) of the pose-pose part of H^-1 over all free parameters: the switch
+ *            variables are MARGINALISED, not conditioned on (the inverse of the undamped Schur complement the solver forms).  cov(b, a) is the exact transpose of cov(a, b),
+ *            a diagonal block is exactly symmetric, and two calls return the same bits.
+ *   A constant keyframe is not a parameter: every pair with one gets a zero block (Ceres' rule).  A keyframe no residual block references, or an index outside
+ *   [0, n_nodes): PGO_ERR_INVALID_ARG, nothing is written.
+ * Like pgo_evaluate it is called without an open solve (inside one: PGO_ERR_STATE) and (re)builds the device graph when the problem changed; the handle's summary, its
+ * trust-region state and the two-level method's history across solves are what they were before the call: a solve after it runs as if the call had not happened.
+ * Limits: one GPU (a communicator attached: PGO_ERR_STATE); at most PGO_DENSE_MAX_KEYFRAMES keyframes (PGO_ERR_INVALID_ARG; only the count is looked at, nothing is
+ * allocated); pgo_options.linear_solver = PGO_LINEAR_PCG_BLOCK_JACOBI or PGO_LINEAR_DENSE_CHOLESKY — PGO_LINEAR_PCG_MATRIX_FREE (the default) is refused with
+ * PGO_ERR_STATE, because that graph build keeps no block-CSR values to factor.  A handle whose graph was not built for the dense solver gets the dense buffers at the
+ * first call and keeps them until its next graph build.
+ * Memory: the n x n fp64 matrix of PGO_DENSE_MAX_KEYFRAMES (n = 6 n_nodes padded to 64), plus the right-hand sides: 6 rows of n doubles per DISTINCT requested keyframe,
+ * padded to 64 rows — all 1024 keyframes make a second n x n array (2 x 302 MB).
+ * PGO_ERR_NUMERIC: a pivot of the factorisation was not > 0 (or NaN); cov is untouched and the handle stays usable.  That catches a breakdown and nothing more: a graph
+ * whose gauge is not fixed (no regulariser, no constant keyframe) is singular, and rounding may still let it factor with a tiny pivot — the blocks are then meaningless
+ * large numbers.  Fixing the gauge is the caller's job, as with Ceres' sparse covariance algorithms.
+ * Launches: scatter, the factorisation (2 nt - 1, nt = n / 64), the right-hand sides, 2 (nt - k0) - 1 for the substitutions from the block column k0 of the first
+ * requested keyframe on, one Gram launch.  Times: profiles/dense_covariance_times.txt. */
+int pgo_pose_covariance(pgo_problem* p, const double* quat_xyzw, const double* t, const double* sw,
+                        int64_t n_nodes, int64_t n_switch,
+                        int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cov /* n_pairs x 36, row-major */);
+
 /* Parity hook for the Jacobian blocks K1 produced at the last pgo_evaluate / pgo_solve_begin point.
  * For edge kind k (0 relpose, 1 switchable, 2 regulariser) copies, for edges [first, first+count):
  *   J1[count*36], J2[count*36]  row-major (rows = residual 0..5, cols = [dtheta(3), dt(3)] of c1 / c2;
@@ -629,6 +655,11 @@ int pgo_dense_spd_inverse(pgo_problem* p, int32_t n, const double* a, double* a_
  * multiple of 64 by an identity block.  `x` (host, n) gets the solution, *avg_ms (may be NULL) the HIP-event average of one factorisation + solve.  PGO_ERR_NUMERIC when
  * the factorisation reports a pivot that is not positive (x is then left alone). */
 int pgo_dense_spd_solve(pgo_problem* p, int32_t n, const double* a, const double* b, double* x, int32_t launches, double* avg_ms);
+/* pgo_pose_covariance's kernels on their own (test and measurement hook): the 6 x 6 blocks (rows of "node" ia[k], columns of node ib[k]; node i = rows 6 i .. 6 i + 5,
+ * i < n / 6) of the inverse of the caller's symmetric positive definite matrix, with exactly the factor, substitution and Gram launches of pgo_pose_covariance, `launches`
+ * times; the matrix is padded like pgo_dense_spd_solve's.  cov: n_pairs x 36 (host), n_pairs >= 1; *avg_ms (may be NULL): the HIP-event average of one factorisation +
+ * covariance.  PGO_ERR_NUMERIC when a pivot is not positive (cov is then left alone). */
+int pgo_dense_spd_covariance(pgo_problem* p, int32_t n, const double* a, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms);
 
 /* Waits for everything the handle has in flight: its stream and — after a pgo_solve_begin that (re)built the device graph — the worker thread that prepares the multigrid
  * hierarchy's host half beside the build (otherwise installed where the solve first needs it).  bench.py calls it before its timed region starts. */

@@ -72,7 +72,7 @@ def normalised(ks):
     plain = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
     short = {}
     for n, d in zip(names, plain):
-        d = re.sub(r"\(.*", "", d).replace("void ", "")
+        d = re.sub(r"\(.*", "", d.replace("(anonymous namespace)::", "")).replace("void ", "")      # (kernels in an unnamed namespace would all be cut down to "pgo::")
         for pat, rep in DROPPED_DEFAULTS:
             d = re.sub(pat, rep, d)
         short[n] = d

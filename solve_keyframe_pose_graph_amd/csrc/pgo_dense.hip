@@ -5,8 +5,12 @@
 // Launches of one system of order n = 64 nt:  1 (first diagonal block) + 2 (nt - 1) (panel, update) for the factor, 2 nt for the sweeps.  Nothing waits on another workgroup
 // inside a launch, there are no atomics, and every sum has a fixed order.  All fp64; the panel's and the update's products run on v_mfma_f64_16x16x4_f64 (operand maps: the
 // comment above gj_block_inverse in pgo_kernels.hip).
+//
+// Covariance blocks (pgo_pose_covariance, after scatter and factor): 1 (the right-hand sides) + 2 (nt - k0) - 1 (solve, update from the first requested keyframe's block
+// column k0 on) + 1 (Gram) launches, under the same rules.
 #include <algorithm>
 #include <cstdlib>
+#include <limits>
 
 #include "pgo_handle.hpp"
 #include "pgo_dense_math.hpp"
@@ -215,6 +219,108 @@ __global__ __launch_bounds__(DC_THREADS) void dc_scatter_kernel(GraphDev G, CgDe
     if (c == 0) w[row] = C.b[row];
 }
 
+// ---- covariance blocks: forward substitution with many right-hand sides (the rows of W[m][n]), then one Gram product per requested pair
+
+// the ones of the right-hand sides into the zeroed W (col < 0: a padding row)
+__global__ __launch_bounds__(DC_THREADS) void dcv_rhs_kernel(double* __restrict__ W, int n, int m, const int32_t* __restrict__ col) {
+    const int r = (int)blockIdx.x * DC_THREADS + (int)threadIdx.x;
+    if (r < m && col[r] >= 0) W[(size_t)r * n + col[r]] = 1.0;
+}
+
+// Solve of step k: dc_panel_kernel's substitution on the tile rows of W instead of the tile rows of A below the diagonal (a copy, so that the factor's kernel keeps its
+// machine code): one workgroup per tile row that has started, one wavefront per 16 right-hand sides, Y = W_.k L_kk^-T over W_.k and, k-major, into YT[64][ldm].
+__global__ __launch_bounds__(DC_THREADS) void dcv_solve_kernel(const double* __restrict__ A, int n, int k, double* __restrict__ W, int ldm, double* __restrict__ YT) {
+    __shared__ double l[DC_NB * DC_LD];
+    const int k0 = k * DC_NB;
+    dc_load_block(A, n, k0, l);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int x0 = (int)blockIdx.x * DC_NB + wave * DC_SUB;                // < m: the grid has at most m / 64 workgroups
+    double* __restrict__ wrow = W + (size_t)(x0 + lr) * n + k0;
+    dc_d4 Y[DC_NB / DC_SUB];
+#pragma unroll
+    for (int j = 0; j < DC_NB / DC_SUB; ++j) {
+        double r[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = wrow[j * DC_SUB + lk + 4 * reg];
+        dc_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int m = 0; m < j; ++m)
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(j * DC_SUB + lr) * DC_LD + m * DC_SUB + 4 * kk + lk], Y[m][kk], acc, 0, 0, 0);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = r[reg] - acc[reg];
+#pragma unroll
+        for (int p = 0; p < DC_SUB; ++p) {
+            const double yp = __shfl(r[p >> 2], (p & 3) * 16 + lr) / l[(j * DC_SUB + p) * DC_LD + j * DC_SUB + p];
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int q = lk + 4 * reg;
+                const double lqp = l[(j * DC_SUB + (q > p ? q : p)) * DC_LD + j * DC_SUB + p];      // (q <= p: the diagonal entry, unused)
+                r[reg] = q == p ? yp : (q > p ? r[reg] - lqp * yp : r[reg]);
+            }
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            Y[j][reg] = r[reg];
+            wrow[j * DC_SUB + lk + 4 * reg] = r[reg];
+            YT[(size_t)(j * DC_SUB + lk + 4 * reg) * ldm + x0 + lr] = r[reg];
+        }
+    }
+}
+
+// Update of step k: one workgroup per 64 x 64 tile (tile row R of W, block column bi > k), W_Ri -= Y_R L_ik^T, 32 x 32 per wavefront as 2 x 2 MFMA tiles over K = 64.
+// A operand: the k-major copy of Y (coalesced); B operand: L_ik, loaded row by row into LDS (coalesced) and read from there column-wise.
+__global__ __launch_bounds__(DC_THREADS) void dcv_update_kernel(const double* __restrict__ A, int n, int k, double* __restrict__ W, int ldm, const double* __restrict__ YT) {
+    __shared__ double l[DC_NB * DC_LD];
+    const int bi = k + 1 + (int)blockIdx.y;                                // < nt: the grid is rows x (nt - k - 1)
+    const int k0 = k * DC_NB;
+    for (int idx = threadIdx.x; idx < DC_NB * DC_NB; idx += DC_THREADS) {
+        const int r = idx >> 6, c = idx & 63;
+        l[r * DC_LD + c] = A[(size_t)(bi * DC_NB + r) * n + k0 + c];
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int i0 = (int)blockIdx.x * DC_NB + wr * 32, j0 = wc * 32;        // rows of W (< m), columns inside the block column
+    dc_d4 acc[2][2];
+    double old[2][2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            acc[s][t] = dc_d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) old[s][t][reg] = W[(size_t)(i0 + s * 16 + lk + 4 * reg) * n + bi * DC_NB + j0 + t * 16 + lr];
+        }
+#pragma unroll
+    for (int kk = 0; kk < DC_NB / 4; ++kk) {
+        const size_t row = (size_t)(kk * 4 + lk) * ldm;
+        const double a0 = YT[row + i0 + lr], a1 = YT[row + i0 + 16 + lr];
+        const double b0 = l[(j0 + lr) * DC_LD + kk * 4 + lk], b1 = l[(j0 + 16 + lr) * DC_LD + kk * 4 + lk];
+        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg)
+                W[(size_t)(i0 + s * 16 + lk + 4 * reg) * n + bi * DC_NB + j0 + t * 16 + lr] = old[s][t][reg] - acc[s][t][reg];
+}
+
+// One workgroup per requested pair: cov[pair] = W_a W_b^T (dc_gram_block).  rows[2 pair], rows[2 pair + 1]: the first of the six rows of W of the two keyframes; c0[pair]:
+// the first column class neither of them is still zero in.
+__global__ __launch_bounds__(DC_THREADS) void dcv_gram_kernel(const double* __restrict__ W, int n, const int32_t* __restrict__ rows, const int32_t* __restrict__ c0, double* __restrict__ cov) {
+    __shared__ double part[6 * DC_GRAM];
+    const size_t pair = blockIdx.x;
+    dc_gram_block(DcTeam{}, W + (size_t)rows[2 * pair] * n, W + (size_t)rows[2 * pair + 1] * n, (size_t)n, n, c0[pair], part, cov + 36 * pair);
+}
+
 struct DcLaunch {
     double* A; int n, ldu; double* LT; int32_t* fail; int force_fail; double* w; double* yv; double* x; int n_out; hipStream_t st;
     int nt() const { return n / DC_NB; }
@@ -223,6 +329,12 @@ struct DcLaunch {
     void update(int k) { hipLaunchKernelGGL(dc_update_kernel, dim3((unsigned)(nt() - k - 1), (unsigned)(nt() - k - 1)), dim3(DC_THREADS), 0, st, A, n, ldu, k, (const double*)LT, fail); }
     void forward(int k) { hipLaunchKernelGGL(dc_forward_kernel, dim3((unsigned)(nt() - k)), dim3(DC_THREADS), 0, st, (const double*)A, n, k, w, yv); }
     void backward(int k) { hipLaunchKernelGGL(dc_backward_kernel, dim3((unsigned)(k + 1)), dim3(DC_THREADS), 0, st, (const double*)A, n, k, yv, x, n_out); }
+};
+struct DcCovLaunch {
+    const double* A; int n; double* W; int ldm; double* YT; hipStream_t st;
+    int nt() const { return n / DC_NB; }
+    void cov_solve(int k, int rows) { hipLaunchKernelGGL(dcv_solve_kernel, dim3((unsigned)rows), dim3(DC_THREADS), 0, st, A, n, k, W, ldm, YT); }
+    void cov_update(int k, int rows) { hipLaunchKernelGGL(dcv_update_kernel, dim3((unsigned)rows, (unsigned)(nt() - k - 1)), dim3(DC_THREADS), 0, st, A, n, k, W, ldm, (const double*)YT); }
 };
 
 }  // namespace
@@ -242,6 +354,30 @@ void launch_dense_scatter(const GraphDev& G, const CgDev& C, double* A, int n, d
     hipLaunchKernelGGL(dc_scatter_kernel, dim3((unsigned)((threads + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, st, G, C, A, n, w);
 }
 
+// ---- covariance blocks from the factor in A.  work: dense_cov_doubles(n, Q.m, pairs) doubles — W, the k-major copy of a solved block column, the blocks; idx:
+// dense_cov_ints(Q.m, pairs) — the right-hand sides' columns, then per pair the two row indices, then per pair the Gram's first column.
+size_t dense_cov_doubles(int n, int m, int64_t n_pairs) { return (size_t)m * n + (size_t)DC_NB * (m + 16) + (size_t)36 * n_pairs; }
+size_t dense_cov_ints(int m, int64_t n_pairs) { return (size_t)m + (size_t)3 * n_pairs; }
+int dense_cov_upload(pgo_problem* p, const DcCovPlan& Q, std::vector<int32_t>& staging, int32_t* idx) {
+    const size_t np = Q.row_a.size();
+    staging.assign(Q.col.begin(), Q.col.end());
+    for (size_t k = 0; k < np; ++k) { staging.push_back(Q.row_a[k]); staging.push_back(Q.row_b[k]); }
+    for (size_t k = 0; k < np; ++k) staging.push_back(Q.gram_c0((int64_t)k));
+    HIPCHK(p, hipMemcpyAsync(idx, staging.data(), staging.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->st));      // (staging outlives the caller's next synchronize)
+    return PGO_OK;
+}
+double* dense_cov_blocks(double* work, int n, int m) { return work + (size_t)m * n + (size_t)DC_NB * (m + 16); }
+int launch_dense_covariance(pgo_problem* p, const double* A, int n, const DcCovPlan& Q, double* work, const int32_t* idx) {
+    const int m = Q.m;
+    const int64_t np = (int64_t)Q.row_a.size();
+    HIPCHK(p, hipMemsetAsync(work, 0, (size_t)m * n * sizeof(double), p->st));
+    hipLaunchKernelGGL(dcv_rhs_kernel, dim3((unsigned)((m + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, p->st, work, n, m, idx);
+    DcCovLaunch D{A, n, work, m + 16, work + (size_t)m * n, p->st};
+    dc_cov_steps(n, Q.mt, Q.start_tile.data(), true, D);
+    hipLaunchKernelGGL(dcv_gram_kernel, dim3((unsigned)np), dim3(DC_THREADS), 0, p->st, (const double*)work, n, idx + m, idx + m + 2 * np, dense_cov_blocks(work, n, m));
+    return PGO_OK;
+}
+
 // ---- the handle's side
 bool dense_mode(const pgo_problem* p) { return p->opt.linear_solver == PGO_LINEAR_DENSE_CHOLESKY; }
 
@@ -255,7 +391,8 @@ int dense_allocate(pgo_problem* p) {
 }
 void dense_release(pgo_problem* p) {
     DenseState& d = p->dense;
-    for (DBuf<double>* b : {&d.A, &d.scratch, &d.vec}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    for (DBuf<double>* b : {&d.A, &d.scratch, &d.vec, &d.cov}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    if (d.cov_idx.p) { (void)hipFree(d.cov_idx.p); d.cov_idx.p = nullptr; d.cov_idx.cap = 0; }
     d.n = 0; d.built = false;
 }
 
@@ -277,6 +414,37 @@ int dense_step(pgo_problem* p, bool* ok, double* t_factored) {
     *ok = h == 0;
     if (!*ok) return PGO_OK;
     launch_dense_solve(d.A.p, n, d.vec.p, d.vec.p + n, p->C.x, (int)(p->N * 6), p->st);
+    HIPCHK(p, hipStreamSynchronize(p->st));
+    return PGO_OK;
+}
+
+// The covariance blocks of pgo_pose_covariance on the linearisation solve_begin has left: the undamped reduced system (the damping is diag / (radius s^2): exactly zero
+// at radius = +inf, in the pose rows and in the switches' Schur terms alike) in build_rows' block-CSR values, scattered, factored, then the substitutions and the Gram
+// products of the pairs whose two keyframes are free (ia, ib: those pairs, n_pairs >= 1).  The system build_rows writes is in the tangent coordinates themselves — the
+// Jacobi scaling only shapes the damping — so there is no scaling to undo on the way out.  *ok = false: a pivot failed, out untouched.
+int dense_pose_covariance(pgo_problem* p, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* out, bool* ok) {
+    DenseState& d = p->dense;
+    int rc;
+    if (!d.built && (rc = dense_allocate(p)) != PGO_OK) return rc;      // (a graph built for the block-CSR PCG: until its next graph build)
+    const int n = d.n;
+    const DcCovPlan Q(n_pairs, ia, ib);
+    HIPCHK(p, d.cov.ensure(dense_cov_doubles(n, Q.m, n_pairs))); HIPCHK(p, d.cov_idx.ensure(dense_cov_ints(Q.m, n_pairs)));
+    std::vector<int32_t> staging;
+    if ((rc = dense_cov_upload(p, Q, staging, d.cov_idx.p)) != PGO_OK) return rc;
+    int32_t* fail = p->d_flags.p + 4;
+    launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);      // (finite numbers for the division below, whatever the buffers held)
+    launch_build_rows(p->G, p->L, p->Sc, p->C, std::numeric_limits<double>::infinity(), 1, nullptr, p->st);
+    HIPCHK(p, hipMemsetAsync(d.A.p, 0, (size_t)n * n * sizeof(double), p->st));
+    HIPCHK(p, hipMemsetAsync(fail, 0, sizeof(int32_t), p->st));
+    launch_dense_scatter(p->G, p->C, d.A.p, n, d.vec.p, p->st);
+    launch_dense_factor(d.A.p, n, d.scratch.p, fail, debug_break_dense(), p->st);
+    int32_t h = 0;
+    HIPCHK(p, hipMemcpyAsync(&h, fail, sizeof(int32_t), hipMemcpyDeviceToHost, p->st));
+    HIPCHK(p, hipStreamSynchronize(p->st));
+    *ok = h == 0;
+    if (!*ok) return PGO_OK;
+    if ((rc = launch_dense_covariance(p, d.A.p, n, Q, d.cov.p, d.cov_idx.p)) != PGO_OK) return rc;
+    HIPCHK(p, hipMemcpyAsync(out, dense_cov_blocks(d.cov.p, n, Q.m), (size_t)36 * n_pairs * sizeof(double), hipMemcpyDeviceToHost, p->st));
     HIPCHK(p, hipStreamSynchronize(p->st));
     return PGO_OK;
 }

@@ -9,7 +9,16 @@
 //   update  A_ij -= L_ik L_jk^T for k < j <= i, and the diagonal tile (k + 1, k + 1) is factored as soon as it has been updated.
 // Solve: L y = b by block columns (y_k = L_kk^-1 w_k, then w_i -= L_ik y_k for i > k), L^T x = y by block rows from the bottom (x_k = L_kk^-T y_k, then
 // y_j -= L_kj^T x_k for j < k).  Every sum has a fixed order: two runs give the same bits.
+//
+// Covariance blocks (pgo_pose_covariance): Sigma = (L L^T)^-1 = L^-T L^-1, so the 6 x 6 block of keyframes (a, b) is (L^-1 E_a)^T (L^-1 E_b) with E_c the 6 unit columns of
+// keyframe c: forward substitutions only.  The right-hand sides are the ROWS of W (m x n row-major, m a multiple of 64, sorted by the column of their one), solved in place
+// by block columns k:   solve  Y = W_.k L_kk^-T for every 64-row tile of W (the panel's substitution);   update  W_.i -= Y L_ik^T for i > k.
+// A unit column is zero before its one, so a tile row of W whose first right-hand side starts in tile k0 has nothing but zeros to solve and to subtract in the steps k < k0:
+// they are skipped (dc_cov_steps), and since every skipped operation would have produced or subtracted +0 the result has the same bits with and without the skipping.
+// Then   gram  Sigma_ab = W_a W_b^T over the n columns (dc_gram_block): 256 column classes (column mod 256) summed ascending, then a fixed binary tree over the classes —
+// the same operations whatever the size of the team, and the same for (a, b) and (b, a) with the factors of every product swapped: the block of (b, a) is the exact transpose.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -84,6 +93,30 @@ PGO_DC_HD void dc_backward_block(const Team& T, const double* a, double* v, doub
 // the four partial sums of a 64-term product (terms 16 q .. 16 q + 15 each, ascending) in the order the sweeps add them
 PGO_DC_HD double dc_sum4(double p0, double p1, double p2, double p3) { return (p0 + p1) + (p2 + p3); }
 
+// One 6 x 6 covariance block: out[i * 6 + j] = sum over the columns c0 <= c < n of wa[i * ld + c] * wb[j * ld + c] (wa, wb: 6 consecutive rows of W; c0 a multiple of
+// DC_GRAM: the columns before it hold zeros in one of the two).  part[6 * DC_GRAM] is shared by the team.  Team size: 1, or a divisor of DC_GRAM.  The caller syncs before.
+constexpr int DC_GRAM = 256;
+template <class Team>
+PGO_DC_HD void dc_gram_block(const Team& T, const double* wa, const double* wb, size_t ld, int n, int c0, double* part, double* out) {
+    for (int i = 0; i < 6; ++i) {
+        for (int cls = T.rank(); cls < DC_GRAM; cls += T.size()) {
+            double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            for (int c = c0 + cls; c < n; c += DC_GRAM) {
+                const double a = wa[(size_t)i * ld + c];
+                for (int j = 0; j < 6; ++j) acc[j] = acc[j] + a * wb[(size_t)j * ld + c];
+            }
+            for (int j = 0; j < 6; ++j) part[j * DC_GRAM + cls] = acc[j];
+        }
+        T.sync();
+        for (int s = DC_GRAM / 2; s >= 1; s >>= 1) {
+            for (int e = T.rank(); e < 6 * s; e += T.size()) { const int j = e / s, cls = e - j * s; part[j * DC_GRAM + cls] = part[j * DC_GRAM + cls] + part[j * DC_GRAM + cls + s]; }
+            T.sync();
+        }
+        if (T.rank() == 0) for (int j = 0; j < 6; ++j) out[i * 6 + j] = part[j * DC_GRAM];
+        T.sync();
+    }
+}
+
 // ---- the order of the block steps: what the launcher (one or two launches per call) and the host instantiation both run
 template <class Ops>
 inline void dc_factor_steps(int n, Ops& o) {
@@ -97,6 +130,42 @@ inline void dc_solve_steps(int n, Ops& o) {
     for (int k = 0; k < nt; ++k) o.forward(k);
     for (int k = nt - 1; k >= 0; --k) o.backward(k);
 }
+
+// The forward substitution with many right-hand sides on the mt tile rows of W.  start_tile[R]: the block column of the first right-hand side of tile row R, ascending in R;
+// in step k only the tile rows [0, rows) with start_tile <= k take part (skip = false: all of them, from step 0 — the same bits, tests/test_dense_cov_host.py).
+template <class Ops>
+inline void dc_cov_steps(int n, int mt, const int32_t* start_tile, bool skip, Ops& o) {
+    const int nt = n / DC_NB;
+    int rows = skip ? 0 : mt;
+    for (int k = skip ? start_tile[0] : 0; k < nt; ++k) {
+        while (rows < mt && start_tile[rows] <= k) ++rows;
+        o.cov_solve(k, rows);
+        if (k + 1 < nt) o.cov_update(k, rows);
+    }
+}
+
+// What the host prepares of a covariance request (pgo_dense.hip runs it for the kernels, dc_host_covariance below for the host instantiation): the requested "nodes"
+// (node i = rows 6 i .. 6 i + 5) deduplicated and sorted, six right-hand sides each, padded to whole tile rows.
+struct DcCovPlan {
+    int m = 0, mt = 0;                     // rows of W (a multiple of 64), its tile rows
+    std::vector<int32_t> col;              // [m] the column of the one of every right-hand side; -1: a padding row (all zeros)
+    std::vector<int32_t> start_tile;       // [mt]
+    std::vector<int32_t> row_a, row_b;     // per pair: the first of the six rows of W of node a / node b
+    DcCovPlan(int64_t n_pairs, const int32_t* ia, const int32_t* ib) {
+        std::vector<int32_t> uniq(ia, ia + n_pairs);
+        uniq.insert(uniq.end(), ib, ib + n_pairs);
+        std::sort(uniq.begin(), uniq.end());
+        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+        m = (int)((uniq.size() * 6 + DC_NB - 1) / DC_NB * DC_NB); mt = m / DC_NB;
+        col.assign((size_t)m, -1);
+        for (size_t u = 0; u < uniq.size(); ++u) for (int a = 0; a < 6; ++a) col[u * 6 + a] = uniq[u] * 6 + a;
+        for (int R = 0; R < mt; ++R) start_tile.push_back(col[(size_t)R * DC_NB] / DC_NB);
+        auto row_of = [&](int32_t node) { return (int32_t)(6 * (std::lower_bound(uniq.begin(), uniq.end(), node) - uniq.begin())); };
+        for (int64_t k = 0; k < n_pairs; ++k) { row_a.push_back(row_of(ia[k])); row_b.push_back(row_of(ib[k])); }
+    }
+    // the first column in which both nodes' right-hand sides may be non-zero, rounded down to the Gram's column classes
+    int gram_c0(int64_t pair) const { return std::max(col[(size_t)row_a[pair]], col[(size_t)row_b[pair]]) / DC_GRAM * DC_GRAM; }
+};
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 // ---- serial host instantiation: the same block steps, the same block routines, scalar loops where the kernels use the fp64 MFMA (sums over k ascending, formed from zero
@@ -112,27 +181,27 @@ struct DcHost {
         for (int i = 0; i < DC_NB; ++i) for (int j = 0; j <= i; ++j) A[(size_t)(k0 + i) * n + k0 + j] = blk[(size_t)i * DC_LD + j];
     }
     void factor_first() { factor_block(0); }
+    // one row of the panel's substitution: row[0 .. 63] <- row L_kk^-T, by 16-wide sub-blocks (what one lane column of dc_panel_kernel computes)
+    static void substitute_row(const double* l, double* row) {
+        for (int j = 0; j < DC_NB / DC_SUB; ++j) {
+            double rr[DC_SUB];
+            for (int c = 0; c < DC_SUB; ++c) {
+                double acc = 0.0;
+                for (int kk = 0; kk < j * DC_SUB; ++kk) acc += l[(size_t)(j * DC_SUB + c) * DC_LD + kk] * row[kk];
+                rr[c] = row[j * DC_SUB + c] - acc;
+            }
+            for (int p = 0; p < DC_SUB; ++p) {
+                const double yp = rr[p] / l[(size_t)(j * DC_SUB + p) * DC_LD + j * DC_SUB + p];
+                rr[p] = yp;
+                for (int q = p + 1; q < DC_SUB; ++q) rr[q] = rr[q] - l[(size_t)(j * DC_SUB + q) * DC_LD + j * DC_SUB + p] * yp;
+            }
+            for (int c = 0; c < DC_SUB; ++c) row[j * DC_SUB + c] = rr[c];
+        }
+    }
     void panel(int k) {
         const int k0 = k * DC_NB;
         load_block(k0);
-        const double* l = blk.data();
-        for (int r = k0 + DC_NB; r < n; ++r) {
-            double* row = A + (size_t)r * n + k0;
-            for (int j = 0; j < DC_NB / DC_SUB; ++j) {
-                double rr[DC_SUB];
-                for (int c = 0; c < DC_SUB; ++c) {
-                    double acc = 0.0;
-                    for (int kk = 0; kk < j * DC_SUB; ++kk) acc += l[(size_t)(j * DC_SUB + c) * DC_LD + kk] * row[kk];
-                    rr[c] = row[j * DC_SUB + c] - acc;
-                }
-                for (int p = 0; p < DC_SUB; ++p) {
-                    const double yp = rr[p] / l[(size_t)(j * DC_SUB + p) * DC_LD + j * DC_SUB + p];
-                    rr[p] = yp;
-                    for (int q = p + 1; q < DC_SUB; ++q) rr[q] = rr[q] - l[(size_t)(j * DC_SUB + q) * DC_LD + j * DC_SUB + p] * yp;
-                }
-                for (int c = 0; c < DC_SUB; ++c) row[j * DC_SUB + c] = rr[c];
-            }
-        }
+        for (int r = k0 + DC_NB; r < n; ++r) substitute_row(blk.data(), A + (size_t)r * n + k0);
     }
     void update(int k) {
         const int k0 = k * DC_NB, k1 = k0 + DC_NB;
@@ -168,7 +237,45 @@ struct DcHost {
             yv[c] -= dc_sum4(part[0], part[1], part[2], part[3]);
         }
     }
+    // covariance: the right-hand sides W[m][n] on the factor in A
+    double* W = nullptr;
+    void cov_solve(int k, int rows) {
+        const int k0 = k * DC_NB;
+        load_block(k0);
+        for (int r = 0; r < rows * DC_NB; ++r) substitute_row(blk.data(), W + (size_t)r * n + k0);
+    }
+    void cov_update(int k, int rows) {
+        const int k0 = k * DC_NB;
+        for (int r = 0; r < rows * DC_NB; ++r)
+            for (int c = k0 + DC_NB; c < n; ++c) {
+                double acc = 0.0;
+                for (int kk = 0; kk < DC_NB; ++kk) acc += W[(size_t)r * n + k0 + kk] * A[(size_t)c * n + k0 + kk];
+                W[(size_t)r * n + c] -= acc;
+            }
+    }
 };
+
+// The 6 x 6 blocks (rows of node ia[k], columns of node ib[k]) of the inverse of the symmetric positive definite n x n matrix `a` (padded like dc_host_solve), n_pairs >= 1,
+// 0 <= ia, ib < n / 6.  Returns false — and leaves cov alone — when a pivot failed.
+inline bool dc_host_covariance(int n, const double* a, int64_t n_pairs, const int32_t* ia, const int32_t* ib, bool skip, double* cov) {
+    const int nc = (n + DC_NB - 1) / DC_NB * DC_NB;
+    std::vector<double> A((size_t)nc * nc, 0.0);
+    for (int i = 0; i < nc; ++i) {
+        if (i < n) { for (int j = 0; j < n; ++j) A[(size_t)i * nc + j] = a[(size_t)i * n + j]; }
+        else A[(size_t)i * nc + i] = 1.0;
+    }
+    DcHost H{nc, A.data(), nullptr, nullptr, nullptr};
+    dc_factor_steps(nc, H);
+    if (H.failed) return false;
+    const DcCovPlan Q(n_pairs, ia, ib);
+    std::vector<double> W((size_t)Q.m * nc, 0.0), part((size_t)6 * DC_GRAM);
+    for (int r = 0; r < Q.m; ++r) if (Q.col[(size_t)r] >= 0) W[(size_t)r * nc + Q.col[(size_t)r]] = 1.0;
+    H.W = W.data();
+    dc_cov_steps(nc, Q.mt, Q.start_tile.data(), skip, H);
+    for (int64_t k = 0; k < n_pairs; ++k)
+        dc_gram_block(DcSerial{}, W.data() + (size_t)Q.row_a[(size_t)k] * nc, W.data() + (size_t)Q.row_b[(size_t)k] * nc, (size_t)nc, nc, skip ? Q.gram_c0(k) : 0, part.data(), cov + 36 * k);
+    return true;
+}
 
 // Solves A x = b for the symmetric positive definite n x n matrix `a` (row-major, any n >= 1: padded to a multiple of 64 by an identity block).  Returns false — and leaves
 // x alone — when a pivot failed.

@@ -179,6 +179,7 @@ struct DenseState {
     DBuf<double> A;            // [n][n] row-major: the system, then its factor L on the lower triangle
     DBuf<double> scratch;      // the current panel, k-major (dense_scratch_doubles)
     DBuf<double> vec;          // w [n] (right-hand side, used up by the forward sweep) and y [n]
+    DBuf<double> cov; DBuf<int32_t> cov_idx;      // pgo_pose_covariance: right-hand sides, panel copy and blocks (dense_cov_doubles), index lists (dense_cov_ints); first call
     int n = 0;                 // 6 keyframes-of-the-handle, padded to a multiple of 64
     bool built = false;
 };
@@ -397,6 +398,15 @@ int dense_allocate(pgo_problem* p);      // build_graph: the buffers of this gra
 void dense_release(pgo_problem* p);      // build_graph for another solver
 int dense_step(pgo_problem* p, bool* ok, double* t_factored);      // lm_step: scatter, factor, failure flag, sweeps into C.x
 size_t dense_scratch_doubles(int n);
+// pgo_pose_covariance: the pairs' blocks of the inverse of the undamped reduced system at solve_begin's linearisation (every keyframe of a pair free)
+int dense_pose_covariance(pgo_problem* p, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* out, bool* ok);
+// ... and its launches on a factor (pgo_dense_spd_covariance runs exactly these): the request's plan, the buffers' sizes, the index upload, the launches, where the blocks land
+struct DcCovPlan;
+size_t dense_cov_doubles(int n, int m, int64_t n_pairs);
+size_t dense_cov_ints(int m, int64_t n_pairs);
+int dense_cov_upload(pgo_problem* p, const DcCovPlan& Q, std::vector<int32_t>& staging, int32_t* idx);
+int launch_dense_covariance(pgo_problem* p, const double* A, int n, const DcCovPlan& Q, double* work, const int32_t* idx);
+double* dense_cov_blocks(double* work, int n, int m);
 // the launches themselves (n a multiple of 64; pgo_dense_spd_solve runs exactly these)
 void launch_dense_scatter(const GraphDev& G, const CgDev& C, double* A, int n, double* w, hipStream_t st);
 void launch_dense_factor(double* A, int n, double* scratch, int32_t* fail, bool force_fail, hipStream_t st);

@@ -1,5 +1,5 @@
 // pgo_measure.hip — measurement helpers and test diagnostics of the C-ABI: HIP-event times and algorithmic bytes of the solver's kernels on the state of an open solve
-// (pgo_time_kernel), of K0 (pgo_time_vio_odometry_kernel), of the dense inverse (pgo_dense_spd_inverse) and of the dense Cholesky solve (pgo_dense_spd_solve), the sums of squares of a multigrid level's operators
+// (pgo_time_kernel), of K0 (pgo_time_vio_odometry_kernel), of the dense inverse (pgo_dense_spd_inverse), of the dense Cholesky solve (pgo_dense_spd_solve) and of its covariance blocks (pgo_dense_spd_covariance), the sums of squares of a multigrid level's operators
 // (pgo_mg_level_norms), a preconditioner applied to the caller's vectors (pgo_apply_preconditioner), the last PCG's iterate (pgo_get_linear_solution) and the installed
 // hierarchy's aggregates (pgo_mg_level_parents).  Nothing here runs inside a solve's own steps.
 #include <algorithm>
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "pgo_handle.hpp"
+#include "pgo_dense_math.hpp"
 
 namespace {
 
@@ -287,6 +288,46 @@ int pgo_dense_spd_solve(pgo_problem* p, int32_t n, const double* a, const double
     if (fail) { p->err = "matrix is not numerically positive definite"; return PGO_ERR_NUMERIC; }
     HIPCHK(p, hipMemcpy(hb.data(), d_x.p, hb.size() * sizeof(double), hipMemcpyDeviceToHost));
     std::memcpy(x, hb.data(), (size_t)n * sizeof(double));
+    return PGO_OK;
+}
+
+int pgo_dense_spd_covariance(pgo_problem* p, int32_t n, const double* a, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms) {
+    if (!p || n <= 0 || !a || n_pairs < 1 || !ia || !ib || !cov || launches < 1) return PGO_ERR_INVALID_ARG;
+    for (int64_t k = 0; k < n_pairs; ++k) if (ia[k] < 0 || ib[k] < 0 || ia[k] >= n / 6 || ib[k] >= n / 6) { p->err = "pgo_dense_spd_covariance: node index out of range (node i = rows 6 i .. 6 i + 5)"; return PGO_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    const int nc = (n + 63) / 64 * 64;
+    std::vector<double> h((size_t)nc * nc, 0.0);
+    for (int i = 0; i < nc; ++i) {
+        if (i < n) std::memcpy(&h[(size_t)i * nc], a + (size_t)i * n, (size_t)n * sizeof(double));
+        else h[(size_t)i * nc + i] = 1.0;
+    }
+    const DcCovPlan Q(n_pairs, ia, ib);
+    DBuf<double> d_a, d_scr, d_work; DBuf<int32_t> d_idx, d_fail;
+    HIPCHK(p, d_a.ensure((size_t)nc * nc)); HIPCHK(p, d_scr.ensure(dense_scratch_doubles(nc))); HIPCHK(p, d_work.ensure(dense_cov_doubles(nc, Q.m, n_pairs)));
+    HIPCHK(p, d_idx.ensure(dense_cov_ints(Q.m, n_pairs))); HIPCHK(p, d_fail.ensure(1));
+    std::vector<int32_t> staging;
+    if ((rc = dense_cov_upload(p, Q, staging, d_idx.p)) != PGO_OK) return rc;
+    EventPair ev;
+    HIPCHK(p, ev.create());
+    float total = 0;
+    int32_t fail = 0;
+    for (int l = 0; l < launches && !fail; ++l) {
+        HIPCHK(p, hipMemcpyAsync(d_a.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, p->st));
+        HIPCHK(p, hipMemsetAsync(d_fail.p, 0, sizeof(int32_t), p->st));
+        HIPCHK(p, hipEventRecord(ev.e0, p->st));
+        launch_dense_factor(d_a.p, nc, d_scr.p, d_fail.p, false, p->st);
+        if ((rc = launch_dense_covariance(p, d_a.p, nc, Q, d_work.p, d_idx.p)) != PGO_OK) return rc;      // (a failed factor: numbers nobody reads — inside their own buffers)
+        HIPCHK(p, hipEventRecord(ev.e1, p->st));
+        HIPCHK(p, hipMemcpyAsync(&fail, d_fail.p, sizeof(fail), hipMemcpyDeviceToHost, p->st));
+        HIPCHK(p, hipStreamSynchronize(p->st));
+        float ms = 0;
+        HIPCHK(p, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+        total += ms;
+    }
+    if (avg_ms) *avg_ms = (double)total / launches;
+    if (fail) { p->err = "matrix is not numerically positive definite"; return PGO_ERR_NUMERIC; }
+    HIPCHK(p, hipMemcpy(cov, dense_cov_blocks(d_work.p, nc, Q.m), (size_t)36 * n_pairs * sizeof(double), hipMemcpyDeviceToHost));
     return PGO_OK;
 }
 

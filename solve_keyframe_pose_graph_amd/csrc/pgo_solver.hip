@@ -733,6 +733,58 @@ int pgo_evaluate(pgo_problem* p, const double* q, const double* t, const double*
     return PGO_OK;
 }
 
+// Marginal covariances of keyframe poses (ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for pose blocks; the contract: include/pgo.h).  The handle is
+// linearised at the given point the way pgo_evaluate does it, and everything that carries over to the next solve is put back: the summary, the LM controller's state and
+// the two-level method's history across solves (solve_begin spends one solve of its back-off).
+int pgo_pose_covariance(pgo_problem* p, const double* q, const double* t, const double* sw, int64_t N, int64_t S, int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cov) {
+    if (!p) return PGO_ERR_INVALID_ARG;
+    if (n_pairs < 0 || (n_pairs > 0 && (!node_a || !node_b || !cov))) { p->err = "pgo_pose_covariance: null pair array or negative count"; return PGO_ERR_INVALID_ARG; }
+    if (p->in_solve) { p->err = "pgo_pose_covariance inside a solve (between pgo_solve_begin and pgo_solve_end)"; return PGO_ERR_STATE; }
+    if (p->comm || p->local_ids) { p->err = "pgo_pose_covariance: one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
+    if (p->opt.linear_solver == PGO_LINEAR_PCG_MATRIX_FREE) {
+        p->err = "pgo_pose_covariance: pgo_options.linear_solver = PGO_LINEAR_PCG_MATRIX_FREE keeps no block-CSR values to factor; select PGO_LINEAR_PCG_BLOCK_JACOBI or PGO_LINEAR_DENSE_CHOLESKY";
+        return PGO_ERR_STATE;
+    }
+    if (N > PGO_DENSE_MAX_KEYFRAMES) { p->err = "pgo_pose_covariance: more than PGO_DENSE_MAX_KEYFRAMES (" + std::to_string(PGO_DENSE_MAX_KEYFRAMES) + ") keyframes"; return PGO_ERR_INVALID_ARG; }
+    std::vector<uint8_t> referenced((size_t)std::max<int64_t>(N, 0), 0);
+    auto mark = [&](int32_t n) { if (n >= 0 && n < N) referenced[(size_t)n] = 1; };
+    for (const HostClass* H : {&p->rel, &p->swe}) for (int64_t e = 0; e < H->size(); ++e) { mark(H->c1[e]); mark(H->c2[e]); }
+    for (const PriorDev& pr : p->priors) mark(pr.node);
+    for (int64_t k = 0; k < n_pairs; ++k) for (int32_t n : {node_a[k], node_b[k]}) {
+        if (n < 0 || n >= N) { p->err = "pgo_pose_covariance: keyframe index out of range"; return PGO_ERR_INVALID_ARG; }
+        if (!referenced[(size_t)n]) { p->err = "pgo_pose_covariance: keyframe " + std::to_string(n) + " is referenced by no residual block: it has no covariance"; return PGO_ERR_INVALID_ARG; }
+    }
+    struct Restore {
+        pgo_problem* p; pgo_summary sum; double radius, decrease_factor, last_rho; bool reuse_diagonal, terminated, have_prev_step; int iteration, invalid;
+        int mode, retests, backoff, skip, keep_streak; bool skip_all; double drop_radius;
+        ~Restore() {
+            p->in_solve = false;
+            p->sum = sum; p->radius = radius; p->decrease_factor = decrease_factor; p->last_rho = last_rho; p->reuse_diagonal = reuse_diagonal; p->terminated = terminated;
+            p->have_prev_step = have_prev_step; p->iteration = iteration; p->invalid = invalid;
+            if (dense_mode(p)) return;      // (solve_begin leaves the history alone there, and a graph build for the exact solver resets it on purpose)
+            CoarseState& c = p->coarse;
+            c.mode = mode; c.retests = retests; c.backoff = backoff; c.skip = skip; c.keep_streak = keep_streak; c.skip_all = skip_all; c.drop_radius = drop_radius;
+        }
+    } restore{p, p->sum, p->radius, p->decrease_factor, p->last_rho, p->reuse_diagonal, p->terminated, p->have_prev_step, p->iteration, p->invalid,
+              p->coarse.mode, p->coarse.retests, p->coarse.backoff, p->coarse.skip, p->coarse.keep_streak, p->coarse.skip_all, p->coarse.drop_radius};
+    int rc = solve_begin(p, q, t, sw, N, S);   // upload + K1 + K2 at the given point (a changed graph is built here)
+    if (rc != PGO_OK) return rc;
+    if (!std::isfinite(p->x_cost)) { p->err = "pgo_pose_covariance: the cost at this point is not finite"; return PGO_ERR_NUMERIC; }
+    if (p->built_mf) { p->err = "pgo_pose_covariance: the graph was built matrix-free"; return PGO_ERR_STATE; }
+    // pairs with a constant keyframe: zero blocks (constant keyframes are not parameters); the others go to the device
+    std::vector<int32_t> ia, ib; std::vector<int64_t> where;
+    for (int64_t k = 0; k < n_pairs; ++k) if (p->h_node_free[(size_t)node_a[k]] && p->h_node_free[(size_t)node_b[k]]) { ia.push_back(node_a[k]); ib.push_back(node_b[k]); where.push_back(k); }
+    std::vector<double> blocks(ia.size() * 36);
+    if (!ia.empty()) {
+        bool ok = true;
+        if ((rc = dense_pose_covariance(p, (int64_t)ia.size(), ia.data(), ib.data(), blocks.data(), &ok)) != PGO_OK) { after_failure(p); return rc; }
+        if (!ok) { p->err = "pgo_pose_covariance: the undamped system is not numerically positive definite (is the gauge fixed: a regulariser or a constant keyframe?)"; return PGO_ERR_NUMERIC; }
+    }
+    std::fill(cov, cov + (size_t)n_pairs * 36, 0.0);
+    for (size_t u = 0; u < where.size(); ++u) std::memcpy(cov + (size_t)where[u] * 36, blocks.data() + u * 36, 36 * sizeof(double));
+    return PGO_OK;
+}
+
 int pgo_get_jacobian_blocks(pgo_problem* p, int32_t kind, int64_t first, int64_t count, double* J1, double* J2, double* dr_ds) {
     if (!p || kind < 0 || kind > 2 || first < 0 || count < 0) return PGO_ERR_INVALID_ARG;
     if (p->graph_dirty) { p->err = "no linearisation available"; return PGO_ERR_STATE; }
