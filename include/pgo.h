@@ -577,6 +577,20 @@ int pgo_apply_preconditioner(pgo_problem* p, int32_t which, double radius, int64
 int pgo_get_linear_solution(pgo_problem* p, double* x);
 int pgo_mg_level_parents(pgo_problem* p, int32_t level, int32_t* parent, int64_t capacity, int64_t* n);
 
+/* Test diagnostics of the matrix-free normal operator (tests/test_gpu_normal_operator.py; one GPU only: PGO_ERR_STATE with a communicator attached).
+ *
+ * pgo_get_matrix_free_tiles: host copies of the workgroup tiles the graph build uploaded for the matrix-free operator (the matvec, K2's per-keyframe sums and the
+ * record kernel walk the same tables), read back from the device arrays.  *n_tiles receives the number of tiles — 0 when this handle's operator is the assembled
+ * block-CSR one (pgo_options.linear_solver, or the fall-back for a keyframe with more than 256 edge sides or several regularisers).  Every array may be NULL (all
+ * NULL: size query); else capacity >= *n_tiles entries each, tile_node0 capacity + 1: tile t holds the keyframes tile_node0[t] .. tile_node0[t + 1] - 1, lanes[t]
+ * lanes of which the first pair_lanes[t] serve both sides of a relative-pose edge whose keyframes share the tile and those from first_switch_lane[t] on serve
+ * switchable sides, and sides[t] edge sides (contribution slots).  PGO_ERR_STATE before a graph is built (pgo_solve_begin / pgo_evaluate).
+ *
+ * pgo_apply_normal_operator_batch: Y[v] = (H_reduced + damping) X[v] for n_vec host vectors of 6 n_nodes doubles through the launch of pgo_apply_normal_operator,
+ * with the LM system built once at trust-region radius `radius` (<= 0: the current one; the radius is restored).  Needs an open solve. */
+int pgo_get_matrix_free_tiles(pgo_problem* p, int32_t* tile_node0, int32_t* lanes, int32_t* pair_lanes, int32_t* first_switch_lane, int32_t* sides, int64_t capacity, int64_t* n_tiles);
+int pgo_apply_normal_operator_batch(pgo_problem* p, double radius, int64_t n_vec, const double* X, double* Y);
+
 /* ------------------------------------------------------------------------------------------ */
 /* graph construction on the device from the raw VIO poses                   */
 /* ------------------------------------------------------------------------------------------ */

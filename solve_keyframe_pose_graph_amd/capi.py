@@ -85,7 +85,7 @@ EXPORTS = [
     "pgo_get_jacobian_blocks", "pgo_get_normal_blocks", "pgo_apply_normal_operator", "pgo_manifold_plus",
     "pgo_comm_get_unique_id", "pgo_comm_init", "pgo_comm_destroy", "pgo_comm_init_custom", "pgo_comm_set_exchange", "pgo_local_group_create", "pgo_local_group_abort", "pgo_local_group_destroy", "pgo_comm_init_local",
     "pgo_get_sharding_stats", "pgo_mg_level_norms", "pgo_partition_edges",
-    "pgo_apply_preconditioner", "pgo_get_linear_solution", "pgo_mg_level_parents",
+    "pgo_apply_preconditioner", "pgo_get_linear_solution", "pgo_mg_level_parents", "pgo_get_matrix_free_tiles", "pgo_apply_normal_operator_batch",
     "pgo_time_linearize_kernel", "pgo_time_kernel", "pgo_time_vio_odometry_kernel", "pgo_dense_spd_inverse", "pgo_dense_spd_solve", "pgo_dense_spd_covariance", "pgo_device_synchronize", "pgo_strerror", "pgo_last_error", "pgo_build_info",
 ]
 
@@ -480,6 +480,25 @@ class Problem:
         out = np.zeros(n.value, np.int32)
         self._check(self.lib.pgo_mg_level_parents(self.h, C.c_int32(level), _pi(out), C.c_int64(out.size), C.byref(n)))
         return out
+
+    def matrix_free_tiles(self):
+        """test diagnostic: the matrix-free operator's tile tables as the graph build uploaded them -> dict(n_tiles, node0 [n_tiles + 1], lanes, pair_lanes,
+        first_switch_lane, sides [n_tiles each]); n_tiles = 0: this handle's operator is the assembled block-CSR one"""
+        n = C.c_int64(0)
+        self._check(self.lib.pgo_get_matrix_free_tiles(self.h, None, None, None, None, None, C.c_int64(0), C.byref(n)))
+        node0 = np.zeros(n.value + 1, np.int32)
+        lanes, pairs, sw0, sides = (np.zeros(n.value, np.int32) for _ in range(4))
+        if n.value:
+            self._check(self.lib.pgo_get_matrix_free_tiles(self.h, _pi(node0), _pi(lanes), _pi(pairs), _pi(sw0), _pi(sides), C.c_int64(n.value), C.byref(n)))
+        return dict(n_tiles=int(n.value), node0=node0, lanes=lanes, pair_lanes=pairs, first_switch_lane=sw0, sides=sides)
+
+    def apply_normal_operator_batch(self, X, radius=0.0):
+        """test diagnostic: Y[v] = (H_reduced + damping) X[v] for the rows of X (n_vec x 6 n_nodes), the LM system built once at `radius` (<= 0: the current one)"""
+        X = _d(X)
+        n_vec = 1 if X.ndim == 1 else X.shape[0]
+        Y = np.zeros_like(X)
+        self._check(self.lib.pgo_apply_normal_operator_batch(self.h, C.c_double(radius), C.c_int64(n_vec), _pd(X), _pd(Y)))
+        return Y
 
     def comm_destroy(self):
         self._check(self.lib.pgo_comm_destroy(self.h))

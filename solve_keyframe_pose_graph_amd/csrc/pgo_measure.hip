@@ -1,7 +1,8 @@
 // pgo_measure.hip — measurement helpers and test diagnostics of the C-ABI: HIP-event times and algorithmic bytes of the solver's kernels on the state of an open solve
 // (pgo_time_kernel), of K0 (pgo_time_vio_odometry_kernel), of the dense inverse (pgo_dense_spd_inverse), of the dense Cholesky solve (pgo_dense_spd_solve) and of its covariance blocks (pgo_dense_spd_covariance), the sums of squares of a multigrid level's operators
-// (pgo_mg_level_norms), a preconditioner applied to the caller's vectors (pgo_apply_preconditioner), the last PCG's iterate (pgo_get_linear_solution) and the installed
-// hierarchy's aggregates (pgo_mg_level_parents).  Nothing here runs inside a solve's own steps.
+// (pgo_mg_level_norms), a preconditioner applied to the caller's vectors (pgo_apply_preconditioner), the last PCG's iterate (pgo_get_linear_solution), the installed
+// hierarchy's aggregates (pgo_mg_level_parents), the matrix-free operator's tile tables (pgo_get_matrix_free_tiles) and the normal operator applied to a batch of vectors
+// (pgo_apply_normal_operator_batch).  Nothing here runs inside a solve's own steps.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -457,6 +458,73 @@ int pgo_mg_level_parents(pgo_problem* p, int32_t level, int32_t* parent, int64_t
     const int32_t* src = level == 0 ? p->mg.M.agg0 : p->mg.levels[level - 1].parent;
     HIPCHK(p, hipStreamSynchronize(p->st));
     HIPCHK(p, hipMemcpy(parent, src, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return PGO_OK;
+}
+
+// Test diagnostic: the matrix-free operator's workgroup tiles as the graph build uploaded them (read back from the device arrays the matvec, K2 and the record kernel walk);
+// *n_tiles = 0: this handle's operator is the assembled block-CSR one
+int pgo_get_matrix_free_tiles(pgo_problem* p, int32_t* tile_node0, int32_t* lanes, int32_t* pair_lanes, int32_t* first_switch_lane, int32_t* sides, int64_t capacity, int64_t* n_tiles) {
+    if (!p || !n_tiles) return PGO_ERR_INVALID_ARG;
+    *n_tiles = 0;
+    if (p->comm || p->local_ids) { p->err = "pgo_get_matrix_free_tiles: one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
+    if (p->graph_dirty) { p->err = "pgo_get_matrix_free_tiles: no graph is built (pgo_solve_begin / pgo_evaluate build it)"; return PGO_ERR_STATE; }
+    if (!p->built_mf) return PGO_OK;
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    const int64_t tiles = p->F.tiles;
+    *n_tiles = tiles;
+    if (!tile_node0 && !lanes && !pair_lanes && !first_switch_lane && !sides) return PGO_OK;      // (size query)
+    if (capacity < tiles) { p->err = "pgo_get_matrix_free_tiles: the arrays are too short for this graph's tiles"; return PGO_ERR_INVALID_ARG; }
+    std::vector<int32_t> node0((size_t)tiles + 1), sw0((size_t)std::max<int64_t>(tiles, 1));
+    std::vector<int64_t> inc0((size_t)tiles + 1);
+    std::vector<ushort4> rng((size_t)std::max<int64_t>(p->N, 1));
+    HIPCHK(p, hipStreamSynchronize(p->st));
+    HIPCHK(p, hipMemcpy(node0.data(), p->F.tile_node0, node0.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(p, hipMemcpy(inc0.data(), p->F.tile_inc0, inc0.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (tiles > 0) HIPCHK(p, hipMemcpy(sw0.data(), p->F.tile_sw0, (size_t)tiles * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (p->N > 0) HIPCHK(p, hipMemcpy(rng.data(), p->F.node_rng, (size_t)p->N * sizeof(ushort4), hipMemcpyDeviceToHost));
+    for (int64_t t = 0; t < tiles; ++t) {
+        if (tile_node0) tile_node0[t] = node0[(size_t)t];
+        if (lanes) lanes[t] = (int32_t)(inc0[(size_t)t + 1] - inc0[(size_t)t]);
+        if (pair_lanes) pair_lanes[t] = (int32_t)((uint32_t)sw0[(size_t)t] >> 16);
+        if (first_switch_lane) first_switch_lane[t] = sw0[(size_t)t] & 0xffff;
+        // the slots of a tile are numbered through its keyframes' relative-pose sides, then their switchable sides: the last keyframe's switchable range ends at the tile's side count
+        const int32_t last = node0[(size_t)t + 1] - 1;
+        if (sides) sides[t] = last >= node0[(size_t)t] && last < p->N ? (int32_t)rng[(size_t)last].w : 0;
+    }
+    if (tile_node0) tile_node0[tiles] = node0[(size_t)tiles];
+    return PGO_OK;
+}
+
+// Test diagnostic: Y[v] = (H_reduced + damping) X[v] for a batch of host vectors, through the launch of pgo_apply_normal_operator, with the LM system built ONCE at `radius`
+// (<= 0: the current one).  One GPU only.
+int pgo_apply_normal_operator_batch(pgo_problem* p, double radius, int64_t n_vec, const double* X, double* Y) {
+    if (!p) return PGO_ERR_INVALID_ARG;
+    auto refuse = [&](const char* why) { p->err = std::string("pgo_apply_normal_operator_batch: ") + why; return PGO_ERR_STATE; };
+    if (p->comm || p->local_ids) return refuse("one GPU only: a communicator is attached");
+    if (!p->in_solve) return refuse("needs an open solve (pgo_solve_begin)");
+    if (n_vec < 1 || !X || !Y || !std::isfinite(radius)) return refuse("invalid argument: null array, no vector, or a radius that is not finite");
+    int rc;
+    if ((rc = set_device(p)) != PGO_OK) return rc;
+    struct Restore {      // (as pgo_apply_preconditioner: the radius and the two-level method's comparison state stay as they were found)
+        pgo_problem* p; double radius; int mode, retests;
+        ~Restore() { p->radius = radius; p->coarse.mode = mode; p->coarse.retests = retests; p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0; }
+    } restore{p, p->radius, p->coarse.mode, p->coarse.retests};
+    if (radius > 0.0) p->radius = radius;
+    if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);
+    bool ok = true;
+    if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
+    const int64_t n6 = p->N * 6;
+    if (n6 == 0) return PGO_OK;
+    DBuf<double> d_io;
+    HIPCHK(p, d_io.ensure((size_t)n6 * 2));
+    for (int64_t v = 0; v < n_vec; ++v) {
+        HIPCHK(p, hipMemcpyAsync(d_io.p, X + (size_t)v * n6, (size_t)n6 * sizeof(double), hipMemcpyHostToDevice, p->st));
+        if (p->built_mf) launch_mf_apply(p->G, p->F, p->Sc, p->C, d_io.p, d_io.p + n6, p->st);
+        else launch_apply_operator(p->G, p->C, d_io.p, d_io.p + n6, p->st);
+        HIPCHK(p, hipMemcpyAsync(Y + (size_t)v * n6, d_io.p + n6, (size_t)n6 * sizeof(double), hipMemcpyDeviceToHost, p->st));
+        HIPCHK(p, hipStreamSynchronize(p->st));
+    }
     return PGO_OK;
 }
 
