@@ -15,6 +15,7 @@
 
 #include "pgo.h"
 #include "pgo_internal.hpp"
+#include "pgo_mg_cycle.hpp"
 #include "pgo_comm.hpp"
 #include "pgo_mg_host.hpp"
 
@@ -42,7 +43,7 @@ inline bool debug_break_dense() { if (!debug_hooks_enabled()) return false; cons
 // PGO_DEBUG_NO_SPLIT_UPDATE=1 (read once per process): the multigrid PCG keeps the unsplit vector update (cg_update_mg_kernel<true>) where it would split it
 // (tests/test_gpu_split_update.py compares the two bit for bit).
 inline bool debug_no_split_update() { static const bool on = []() { const char* e = std::getenv("PGO_DEBUG_NO_SPLIT_UPDATE"); return debug_hooks_enabled() && e && e[0] == '1' && e[1] == 0; }(); return on; }
-// PGO_DEBUG_SPLIT_HOSTS=<a>,<b> (read once; for scans): the eligible launches of the cycle (mg_rider_hosts' order) that carry the split update's two riders, a <= b
+// PGO_DEBUG_SPLIT_HOSTS=<a>,<b> (read once; for scans): the rider-eligible launches of the cycle plan (pgo_mg_cycle.hpp), by ordinal, that carry the split update's two riders, a <= b
 // (a == b: one launch carries both); ignored unless both exist on the hierarchy at hand
 inline bool debug_split_hosts(int* a, int* b) {
     static const int v = []() {
@@ -424,6 +425,7 @@ int build_mg(pgo_problem* p);
 int mg_operators(pgo_problem* p, int32_t* fail, bool hoff_valid, bool kernels_only, double t_build0);
 bool mg_exchange_at(pgo_problem* p, int point, int lv, int* plan, double** v1, double** v2, const double** dinv);
 int mg_apply_ranks(pgo_problem* p, bool inside_iteration);
+int mg_cycle(pgo_problem* p, const CgDev& C, MgCycleArgs a);      // one cycle on the handle's hierarchy; `a`: what differs from the PCG start's cycle on C's vectors
 double mg_cs(const pgo_problem* p);
 double mg_scale(const pgo_problem* p);
 const MgLevelDev* mg_fine_view(const pgo_problem* p);

@@ -227,7 +227,7 @@ struct UpdRiderDev {
     const double* scal; const double* r; const float* Lf;
     double* z; double* p; double* x; double* part_rz;      // part_rz: the slots of the NEXT iteration's parity
 };
-// which two launches of the cycle carry the riders: ordinals among the cycle's eligible launches (mg_rider_hosts), -1: the unsplit kernel
+// which two launches of the cycle carry the riders: ordinals among the cycle plan's rider-eligible launches (pgo_mg_cycle.hpp), -1: the unsplit kernel
 struct UpdSplit { int host_a = -1, host_b = -1; bool on() const { return host_a >= 0; } };
 
 // ---- launchers (pgo_kernels.hip).  All asynchronous on `st`. ----
@@ -335,22 +335,28 @@ void launch_mg_transition_w(const MgLevelDev& A, hipStream_t st);               
 void launch_mg_transition_product(const MgLevelDev& A, const MgLevelDev& B, hipStream_t st);          // B = Ps^T W (several ranks: this rank's rows' part of it)
 void launch_mg_level_galerkin(const MgLevelDev& A, const MgLevelDev& B, hipStream_t st);              // B = P^T A P (plain transition)
 void launch_mg_dense_top(const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, hipStream_t st);
-// Several ranks: the cycle is cut into segments by the exchanges its kernels need (pgo_shard.hip issues them); launch_mg_apply calls the hook BEFORE the kernel that reads the
-// exchanged vectors.  point: 0 = down-sweep of `level` (1-based; n_levels = the dense solve) is about to read x (and r) of that level, 1 = the up-sweep of `level` is about to
-// read xt of that level (plain transition) or xf of level + 1 (explicit transfer operator), 2 = the prolongation to the keyframes is about to read xf of level 1.
+// The cycle's launches are described once, as a list of steps (pgo_mg_cycle.hpp: mg_cycle_plan); launch_mg_apply walks that list.  Several ranks: the cycle is cut into segments
+// by the exchanges its kernels need (pgo_multigrid.hip issues them) — exchange points are steps of the plan, placed BEFORE the kernel that reads the exchanged vectors, and
+// launch_mg_apply calls the hook there.  point: 0 = down-sweep of `level` (1-based; n_levels = the dense solve) is about to read x (and r) of that level, 1 = the up-sweep of
+// `level` is about to read xt of that level (plain transition) or xf of level + 1 (explicit transfer operator), 2 = the prolongation to the keyframes is about to read xf of level 1.
+// A hook that returns non-zero ends the cycle at that point; launch_mg_apply returns its code.
 struct MgExchangeHook { void* ctx; int (*fn)(void* ctx, int point, int level); };
-// z += scale P V(P^T r) (every coarse correction inside V scaled alike), r.z partials updated in place (cg_update's workgroup -> slot mapping)
-void launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, const double* r, double* z, double* part_rz, double scale, bool inside_iteration, hipStream_t st,
-                     bool restricted = false /* r_1 (and x_1) already formed by launch_cg_update_mg */, double prolong_scale = 0.0 /* c of the smoothed transitions */,
-                     const MgLevelDev* fine = nullptr /* smoothed keyframe transition: the keyframe level's transfer view (r_1 = Ps_0^T r and z += s Ps_0 x_1 by kernels of their own) */,
-                     const MgExchangeHook* hook = nullptr /* several ranks: called where the cycle needs rows of other ranks */, int* hook_rc = nullptr,
-                     const UpdSplit* split = nullptr /* after launch_cg_update_mg_crit: the launches that carry the rest of the update */, int parity = 0, int first = 0,
-                     int* n_hosts = nullptr /* out: the eligible launches this cycle made — mg_rider_hosts' count, or the two enumerations have drifted apart */);
-int mg_rider_hosts(const CgDev& C, const MgDev& M, const MgLevelDev* levels, int* tiles /*[2 MG_MAX_LEVELS]*/);      // launches of a restricted cycle that can carry riders (their own workgroups, launch order)
+struct MgCycleArgs {
+    const double* r = nullptr; double* z = nullptr; double* part_rz = nullptr;      // z += scale P V(P^T r), the r.z partials updated in place (cg_update's workgroup -> slot mapping)
+    double scale = 1.0;                    // every coarse correction inside V scaled alike
+    double prolong_scale = 0.0;            // c of the smoothed transitions
+    bool inside_iteration = false;         // the kernels stop with the PCG (C.flags)
+    bool restricted = false;               // r_1 (and x_1) already formed by launch_cg_update_mg*
+    const MgLevelDev* fine = nullptr;      // smoothed keyframe transition: the keyframe level's transfer view (r_1 = Ps_0^T r and z += s Ps_0 x_1 by kernels of their own)
+    const MgExchangeHook* hook = nullptr;  // several ranks: called where the cycle needs rows of other ranks
+    const UpdSplit* split = nullptr;       // after launch_cg_update_mg_crit: the plan's eligible launches that carry the rest of the update
+    int parity = 0, first = 0;             // ... and what their riders need of the iteration
+};
+int launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, const MgCycleArgs& a, hipStream_t st);
 // cg_update + r_1 = P_0^T r', x_1 = w D_1^-1 r_1 of the multigrid (M.blk_tab)
 void launch_cg_update_mg(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int n_pq_partials, hipStream_t st);
 void launch_cg_update_mg_sr(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int first, int n_pq_partials, hipStream_t st);      // single-reduction form (cg_update_kernel<true>) with the same restriction
-void launch_cg_update_mg_crit(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int first, int n_pq_partials, hipStream_t st);    // ... its critical half only (UpdRiderDev): launch_mg_apply(split) must follow
+void launch_cg_update_mg_crit(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int first, int n_pq_partials, hipStream_t st);    // ... its critical half only (UpdRiderDev): launch_mg_apply with MgCycleArgs::split must follow
 
 double k1_algorithmic_bytes(const GraphDev& G, bool want_jacobian);
 

@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "pgo_internal.hpp"
+#include "pgo_mg_cycle.hpp"
 
 namespace pgo {
 

@@ -71,7 +71,7 @@ int enqueue(pgo_problem* p, int which, int kk) {
         case 3: launch_k1(G, p->d_pose[p->cur ^ 1].p, p->d_swv[p->cur ^ 1].p, false, part(p, 5), &np, p->st); return PGO_OK;
         case 6: case 7: {
             if (p->local_ids) {      // several ranks (7 only): this rank's share of the cycle's kernels, no exchanges (what its GPU computes per cycle)
-                launch_mg_apply(G, p->C, p->mg.M, p->mg.levels, p->coarse.K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), nullptr);
+                mg_cycle(p, p->C, MgCycleArgs{});
                 return PGO_OK;
             }
             const PcgForm f = multigrid_form(p, which);
@@ -104,7 +104,7 @@ double cycle_bytes(const pgo_problem* p, bool split_update) {
     double cyc = N * (24.0 + 16.0 / 8.0 * 8.0) /* d0 + slot table (restriction) */ + N * (2.0 * 48.0 + 24.0 + 4.0 + 4.0) /* z read + write, d0, agg0, member list (prolongation) */;
     for (int l = 0; l + 1 < p->mg.M.n_levels; ++l) {
         const MgLevelDev& A = p->mg.levels[l];
-        if (A.smoothed && A.rt_valf)      // explicit transfer operator: the level's own blocks once (smoothing step), R and R^T once each, Dinv once, r / x / y / xf and the level above's r, x
+        if (mg_explicit(A))      // explicit transfer operator: the level's own blocks once (smoothing step), R and R^T once each, Dinv once, r / x / y / xf and the level above's r, x
             cyc += (double)A.nnzb * (144.0 + 4.0) + 2.0 * (double)A.n_w * (144.0 + 4.0) + (double)A.n * (288.0 + 24.0 + 8.0 * 48.0 + 16.0) + (double)A.n_next * (288.0 + 2.0 * 48.0 + 8.0);
         else
             cyc += (A.smoothed ? 4.0 : 2.0) * (double)A.nnzb * (144.0 + 4.0) + (double)A.n * ((A.smoothed ? 4.0 : 2.0) * 288.0 /* Dinv: smoothing steps */ + 24.0 + (A.smoothed ? 18.0 : 10.0) * 48.0 + 16.0);
@@ -371,7 +371,7 @@ int pgo_mg_level_norms(pgo_problem* p, int32_t level, double* out8) {
 
 // Test diagnostic: Z[v] = M^-1 R[v] with the asked-for preconditioner of the current LM system at `radius` (<= 0: the current one).  The system is built ONCE, the way
 // pgo_apply_normal_operator builds it; then the preconditioner's operators, whatever build_system's own rules would choose for this system; then every vector takes the
-// unfused start path of pcg_start: cg_init (r = R[v], z = D^-1 r) and launch_coarse_apply / launch_mg_apply as the PCG start launches them.  One GPU only.
+// unfused start path of pcg_start: cg_init (r = R[v], z = D^-1 r) and launch_coarse_apply / mg_cycle as the PCG start launches them.  One GPU only.
 int pgo_apply_preconditioner(pgo_problem* p, int32_t which, double radius, int64_t n_vec, const double* R, double* Z) {
     if (!p) return PGO_ERR_INVALID_ARG;
     auto refuse = [&](const char* why) { p->err = std::string("pgo_apply_preconditioner: ") + why; return PGO_ERR_STATE; };
@@ -418,7 +418,7 @@ int pgo_apply_preconditioner(pgo_problem* p, int32_t which, double radius, int64
         if (which == PGO_PRECOND_BLOCK_JACOBI) launch_cg_init(p->G, C, 0, 0.0, p->st);
         else {
             launch_cg_init_vectors(p->G, C, 0, p->st);
-            if (which == PGO_PRECOND_MULTIGRID) launch_mg_apply(p->G, C, p->mg.M, p->mg.levels, p->coarse.K, C.r, C.z, C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
+            if (which == PGO_PRECOND_MULTIGRID) mg_cycle(p, C, MgCycleArgs{});
             else launch_coarse_apply(p->G, C, p->coarse.K, C.r, C.z, C.part_rz, false, p->st);
         }
         double* out = Z + (size_t)v * n6;

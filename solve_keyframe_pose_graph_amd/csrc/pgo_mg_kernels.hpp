@@ -1410,134 +1410,99 @@ __global__ __launch_bounds__(CG_BLOCK, PGO_SR_CRIT_WAVES) void cg_update_mg_crit
                                                                                        int parity, int nparts_pq, int nparts, int first) {
     cg_update_mg_body<true, true>(G, C, M, r1_out, x1_out, Dinv1, parity, nparts_pq, nparts, first);
 }
-void launch_cg_update_mg(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int n_pq_partials, hipStream_t st) {
+// the three forms of the restricting update share one launch: r_1 (and x_1 = w D_1^-1 r_1) go to level 1, or to the dense level's residual when there is no sparse level
+template <typename Kernel>
+static void launch_update_mg(Kernel kernel, const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int first, int n_pq_partials, hipStream_t st) {
     const int g = cg_grid(G);
-    if (M.n_levels == 1) hipLaunchKernelGGL(cg_update_mg_kernel<false>, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, K.rc, (double*)nullptr, (const double*)nullptr, k & 1, n_pq_partials, g, 0);
-    else hipLaunchKernelGGL(cg_update_mg_kernel<false>, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, levels[0].r, levels[0].x, (const double*)levels[0].Dinv, k & 1, n_pq_partials, g, 0);
+    const MgTarget T = mg_target_above(M, levels, K, -1);
+    hipLaunchKernelGGL(kernel, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, T.r, T.x, T.Dinv, k & 1, n_pq_partials, g, first);
+}
+void launch_cg_update_mg(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int n_pq_partials, hipStream_t st) {
+    launch_update_mg(cg_update_mg_kernel<false>, G, C, M, levels, K, k, 0, n_pq_partials, st);
 }
 void launch_cg_update_mg_sr(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int first, int n_pq_partials, hipStream_t st) {
-    const int g = cg_grid(G);
-    if (M.n_levels == 1) hipLaunchKernelGGL(cg_update_mg_kernel<true>, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, K.rc, (double*)nullptr, (const double*)nullptr, k & 1, n_pq_partials, g, first);
-    else hipLaunchKernelGGL(cg_update_mg_kernel<true>, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, levels[0].r, levels[0].x, (const double*)levels[0].Dinv, k & 1, n_pq_partials, g, first);
+    launch_update_mg(cg_update_mg_kernel<true>, G, C, M, levels, K, k, first, n_pq_partials, st);
 }
 void launch_cg_update_mg_crit(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, int k, int first, int n_pq_partials, hipStream_t st) {
-    const int g = cg_grid(G);
-    if (M.n_levels == 1) hipLaunchKernelGGL(cg_update_mg_crit_kernel, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, K.rc, (double*)nullptr, (const double*)nullptr, k & 1, n_pq_partials, g, first);
-    else hipLaunchKernelGGL(cg_update_mg_crit_kernel, dim3(g), dim3(CG_BLOCK), 0, st, G, C, M, levels[0].r, levels[0].x, (const double*)levels[0].Dinv, k & 1, n_pq_partials, g, first);
+    launch_update_mg(cg_update_mg_crit_kernel, G, C, M, levels, K, k, first, n_pq_partials, st);
 }
-// The launches of a `restricted` cycle on one GPU that can carry riders of the split update, in launch order — the CG_BLOCK-sized sparse-level launches between the update and
-// the kernel that adds P_0 x_1 to z (launch_mg_apply counts the same launches in the same order): tiles[e] = the launch's own workgroups.  Returns their number.
-int mg_rider_hosts(const CgDev& C, const MgDev& M, const MgLevelDev* levels, int* tiles) {
+// One cycle: the steps of mg_cycle_plan (pgo_mg_cycle.hpp), each mapped to its kernel launch or to the exchange hook.  Returns the hook's code: a failing exchange ends the cycle there.
+int launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, const MgCycleArgs& a, hipStream_t st) {
+    const MgCyclePlan P = mg_cycle_plan(M, levels, K, C.extra_rz, cg_grid(G), a.restricted, a.fine);
+    const int32_t* stop = a.inside_iteration ? C.flags : nullptr;     // at PCG start the flag still belongs to the previous solve
     const int nl = M.n_levels;
-    const bool fused = C.extra_rz > 0;
-    int n = 0;
-    for (int l = 1; l < nl; ++l) {
-        const MgLevelDev& A = levels[l - 1];
-        if (A.smoothed && A.rt_valf) { if (A.tiles_own + A.rT_tiles > 0) tiles[n++] = A.tiles_own + A.rT_tiles; }
-        else if (A.tiles_own > 0) tiles[n++] = A.tiles_own;
-    }
-    for (int l = nl - 1; l >= 1; --l) {
-        const MgLevelDev& A = levels[l - 1];
-        if (A.tiles_own == 0 || (l == 1 && fused)) continue;
-        tiles[n++] = A.tiles_own;
-    }
-    return n;
-}
-void launch_mg_apply(const GraphDev& G, const CgDev& C, const MgDev& M, const MgLevelDev* levels, const CoarseDev& K, const double* r, double* z, double* part_rz, double scale, bool inside_iteration, hipStream_t st,
-                     bool restricted, double prolong_scale, const MgLevelDev* fine /* transfer view of the keyframe level: smoothed keyframe transition (never `restricted`, never fused) */,
-                     const MgExchangeHook* hook, int* hook_rc, const UpdSplit* split, int parity, int first, int* n_hosts) {
-    // the split update's riders: eligible launch number `e` (mg_rider_hosts' order) carries what the split assigns to it, as cg_grid more workgroups
+    const double* r = a.r; double* z = a.z; double* part_rz = a.part_rz;
+    const double scale = a.scale;
+    const dim3 block(CG_BLOCK);
     UpdRiderDev U0{}; U0.kind = 0;
-    int e_next = 0;
-    unsigned rider_wgs = 0;
-    auto rider = [&]() {
+    // the level a kernel prolongs into: with a smoothed transition it must receive the bare correction e = P x (xt = 0 + P x), smoothed afterwards; an explicit-transfer level's
+    // up-sweep reads x_next itself: nothing is prolonged into it
+    auto below_of = [&](int level) { MgLevelDev B = levels[level >= 2 ? level - 2 : 0]; if (level >= 2 && B.smoothed) B.x = const_cast<double*>(B.zero); return B; };
+    auto prolongs = [&](int level) { return level >= 2 && !mg_explicit(levels[level - 2]) ? 1 : 0; };
+    int e = 0;      // ordinal of the next rider-eligible launch
+    for (int i = 0; i < P.n; ++i) {
+        const MgCycleStep& s = P.steps[i];
+        const int l = s.level;
+        // the split update's riders: the eligible launch the split names carries them, as cg_grid more workgroups behind its own
         UpdRiderDev U = U0;
-        rider_wgs = 0;
-        if (split && split->on()) {
-            const int e = e_next;
-            U.kind = (e == split->host_a ? 1 : 0) | (e == split->host_b ? 2 : 0);
+        if (s.rider) {
+            if (a.split && a.split->on()) U.kind = (e == a.split->host_a ? 1 : 0) | (e == a.split->host_b ? 2 : 0);
             if (U.kind) {
-                U.riders = cg_grid(G); U.parity = parity; U.first = first; U.N = G.N;
+                U.riders = cg_grid(G); U.parity = a.parity; U.first = a.first; U.N = G.N;
                 U.scal = C.scal; U.r = r; U.Lf = C.Lf; U.z = z; U.p = C.p; U.x = C.x; U.part_rz = part_rz;
-                rider_wgs = (unsigned)U.riders;
             }
+            ++e;
         }
-        ++e_next;
-        return U;
-    };
-    const int32_t* stop = inside_iteration ? C.flags : nullptr;     // at PCG start the flag still belongs to the previous solve
-    const int nl = M.n_levels;
-    const unsigned g1 = (unsigned)((std::max(M.a1 - M.a0, 0) + MG_TILE_ROWS - 1) / MG_TILE_ROWS);      // (several ranks: the rank's own aggregates)
-    // several ranks: the exchange a kernel's reads need is issued right before it (pgo_solver.hip); a failing exchange ends the cycle (the caller sees *hook_rc)
-    bool hook_failed = false;
-    auto xchg = [&](int point, int level) { if (hook && !hook_failed) { const int rc = hook->fn(hook->ctx, point, level); if (rc != 0) { hook_failed = true; if (hook_rc) *hook_rc = rc; } } };
-    if (restricted) {}
-    else if (fine) {      // r_1 = Ps_0^T r (and x_1 = Dinv_1 r_1): the restriction half of mg_sdown_kernel on the keyframe level's transfer view, which has no tiles of its own
-        MgLevelDev T = *fine; T.tiles = 0; T.tiles_own = 0; T.r = const_cast<double*>(r);
-        if (nl == 1) hipLaunchKernelGGL(mg_sdown_kernel, dim3((unsigned)T.rT_tiles), dim3(CG_BLOCK), 0, st, T, K.rc, (double*)nullptr, (const double*)nullptr, stop, U0);
-        else hipLaunchKernelGGL(mg_sdown_kernel, dim3((unsigned)T.rT_tiles), dim3(CG_BLOCK), 0, st, T, levels[0].r, levels[0].x, (const double*)levels[0].Dinv, stop, U0);
-    }
-    else if (g1 == 0) {}
-    else if (nl == 1) hipLaunchKernelGGL(mg_restrict0_kernel, dim3(g1), dim3(CG_BLOCK), 0, st, M, r, K.rc, (double*)nullptr, (const double*)nullptr, stop);
-    else hipLaunchKernelGGL(mg_restrict0_kernel, dim3(g1), dim3(CG_BLOCK), 0, st, M, r, levels[0].r, levels[0].x, (const double*)levels[0].Dinv, stop);
-    for (int l = 1; l < nl; ++l) {                     // sparse level l -> level l+1
-        MgLevelDev A = levels[l - 1];
-        xchg(0, l);
-        if (hook_failed) return;
-        if (A.smoothed && A.rt_valf) {      // explicit transfer operator: smoothing step and restriction in one launch (two kinds of workgroups)
-            const unsigned g = (unsigned)(A.tiles_own + A.rT_tiles);
-            if (g == 0) continue;
-            const UpdRiderDev U = rider();
-            if (l + 1 == nl) hipLaunchKernelGGL(mg_sdown_kernel, dim3(g + rider_wgs), dim3(CG_BLOCK), 0, st, A, K.rc, (double*)nullptr, (const double*)nullptr, stop, U);
-            else hipLaunchKernelGGL(mg_sdown_kernel, dim3(g + rider_wgs), dim3(CG_BLOCK), 0, st, A, levels[l].r, levels[l].x, (const double*)levels[l].Dinv, stop, U);
-            continue;
-        }
-        if (A.tiles_own == 0) continue;
-        if (A.smoothed) {
-            // smoothed prolongator: t = r - A x_pre, u = c Dinv t; the restriction kernel then forms P^T (t - A u) = Ps^T t
-            hipLaunchKernelGGL(mg_smooth_step_kernel, dim3((unsigned)A.tiles_own), dim3(CG_BLOCK), 0, st, A, (const double*)A.r, (const double*)A.x, A.t, (const double*)nullptr, (const double*)nullptr, A.u, prolong_scale, stop);
-            A.r = A.t; A.x = A.u;
-        }
-        const UpdRiderDev U = rider();
-        if (l + 1 == nl) hipLaunchKernelGGL(mg_down_kernel, dim3((unsigned)A.tiles_own + rider_wgs), dim3(CG_BLOCK), 0, st, A, K.rc, (double*)nullptr, (const double*)nullptr, stop, U);
-        else hipLaunchKernelGGL(mg_down_kernel, dim3((unsigned)A.tiles_own + rider_wgs), dim3(CG_BLOCK), 0, st, A, levels[l].r, levels[l].x, (const double*)levels[l].Dinv, stop, U);
-    }
-    // the level below a kernel that prolongs: with a smoothed transition it must receive the bare correction e = P x (xt = 0 + P x), smoothed afterwards
-    auto below_of = [&](int idx) { MgLevelDev B = levels[idx]; if (B.smoothed) B.x = const_cast<double*>(B.zero); return B; };
-    auto expl_at = [&](int idx) { return idx >= 0 && levels[idx].smoothed && levels[idx].rt_valf != nullptr; };      // that level's up-sweep reads x_next itself: nothing is prolonged into it
-    xchg(0, nl);
-    if (hook_failed) return;
-    hipLaunchKernelGGL(mg_dense_solve_kernel, dim3((unsigned)K.n_agg), dim3(384), 0, st, K, nl >= 2 ? below_of(nl - 2) : levels[0], nl >= 2 && !expl_at(nl - 2) ? 1 : 0, scale, stop);
-    const bool fused = C.extra_rz > 0;     // level 1's kernel prolongs to the keyframes itself (the solver sets extra_rz = its tile count when that fits the partial-sum slots)
-    const unsigned g0 = (unsigned)cg_grid(G);
-    for (int l = nl - 1; l >= 1; --l) {
-        MgLevelDev A = levels[l - 1];
-        xchg(1, l);
-        if (hook_failed) return;
-        if (A.tiles_own == 0) continue;
-        if (expl_at(l - 1)) {      // x = v + s R^T x_next: prolongation and post-smoothing in one launch
-            const double* xn = l + 1 == nl ? (const double*)K.yc : (const double*)levels[l].xf;
-            if (l == 1 && fused) hipLaunchKernelGGL(mg_up_kernel<true>, dim3((unsigned)(A.tiles_own < MAX_PARTIALS ? A.tiles_own : MAX_PARTIALS)), dim3(CG_BLOCK), 0, st, A, A, 0, scale, stop, M, r, z, part_rz + g0, xn, U0);
-            else {
-                const UpdRiderDev U = rider();
-                hipLaunchKernelGGL(mg_up_kernel<false>, dim3((unsigned)A.tiles_own + rider_wgs), dim3(CG_BLOCK), 0, st, A, l >= 2 ? below_of(l - 2) : levels[0], l >= 2 && !expl_at(l - 2) ? 1 : 0, scale, stop, M, r, z, part_rz, xn, U);
-            }
-            continue;
-        }
-        if (A.smoothed) {
-            // y = x_pre + e - c Dinv (A e) = x_pre + Ps x_next ; the post-smoothing kernel then works on y
-            hipLaunchKernelGGL(mg_smooth_step_kernel, dim3((unsigned)A.tiles_own), dim3(CG_BLOCK), 0, st, A, (const double*)nullptr, (const double*)A.xt, (double*)nullptr, (const double*)A.x, (const double*)A.xt, A.y, prolong_scale, stop);
-            A.xt = A.y;
-        }
-        if (l == 1 && fused) hipLaunchKernelGGL(mg_up_kernel<true>, dim3((unsigned)(A.tiles_own < MAX_PARTIALS ? A.tiles_own : MAX_PARTIALS)), dim3(CG_BLOCK), 0, st, A, A, 0, scale, stop, M, r, z, part_rz + g0, (const double*)nullptr, U0);
-        else {
-            const UpdRiderDev U = rider();
-            hipLaunchKernelGGL(mg_up_kernel<false>, dim3((unsigned)A.tiles_own + rider_wgs), dim3(CG_BLOCK), 0, st, A, l >= 2 ? below_of(l - 2) : levels[0], l >= 2 && !expl_at(l - 2) ? 1 : 0, scale, stop, M, r, z, part_rz, (const double*)nullptr, U);
+        const dim3 grid(s.grid + (U.kind ? (unsigned)U.riders : 0u));
+        switch (s.kind) {
+            case MgStep::exchange:      // several ranks: the exchange a kernel's reads need is issued right before it (pgo_multigrid.hip)
+                if (a.hook) { const int rc = a.hook->fn(a.hook->ctx, s.point, l); if (rc != 0) return rc; }
+                break;
+            case MgStep::restrict0: {
+                const MgTarget T = mg_target_above(M, levels, K, -1);
+                hipLaunchKernelGGL(mg_restrict0_kernel, grid, block, 0, st, M, r, T.r, T.x, T.Dinv, stop);
+                break; }
+            case MgStep::restrict_fine: {      // r_1 = Ps_0^T r (and x_1 = Dinv_1 r_1): the restriction half of mg_sdown_kernel on the keyframe level's transfer view, which has no tiles of its own
+                MgLevelDev V = *a.fine; V.tiles = 0; V.tiles_own = 0; V.r = const_cast<double*>(r);
+                const MgTarget T = mg_target_above(M, levels, K, -1);
+                hipLaunchKernelGGL(mg_sdown_kernel, grid, block, 0, st, V, T.r, T.x, T.Dinv, stop, U0);
+                break; }
+            case MgStep::pre_smooth: {      // smoothed prolongator: t = r - A x_pre, u = c Dinv t; the restriction kernel then forms P^T (t - A u) = Ps^T t
+                const MgLevelDev& A = levels[l - 1];
+                hipLaunchKernelGGL(mg_smooth_step_kernel, grid, block, 0, st, A, (const double*)A.r, (const double*)A.x, A.t, (const double*)nullptr, (const double*)nullptr, A.u, a.prolong_scale, stop);
+                break; }
+            case MgStep::down: {
+                MgLevelDev A = levels[l - 1];
+                if (A.smoothed) { A.r = A.t; A.x = A.u; }      // (what pre_smooth left)
+                const MgTarget T = mg_target_above(M, levels, K, l - 1);
+                hipLaunchKernelGGL(mg_down_kernel, grid, block, 0, st, A, T.r, T.x, T.Dinv, stop, U);
+                break; }
+            case MgStep::sdown: {      // explicit transfer operator: smoothing step and restriction in one launch (two kinds of workgroups)
+                const MgTarget T = mg_target_above(M, levels, K, l - 1);
+                hipLaunchKernelGGL(mg_sdown_kernel, grid, block, 0, st, levels[l - 1], T.r, T.x, T.Dinv, stop, U);
+                break; }
+            case MgStep::dense_solve:
+                hipLaunchKernelGGL(mg_dense_solve_kernel, grid, dim3(384), 0, st, K, below_of(nl), prolongs(nl), scale, stop);
+                break;
+            case MgStep::post_smooth: {      // y = x_pre + e - c Dinv (A e) = x_pre + Ps x_next ; the post-smoothing kernel then works on y
+                const MgLevelDev& A = levels[l - 1];
+                hipLaunchKernelGGL(mg_smooth_step_kernel, grid, block, 0, st, A, (const double*)nullptr, (const double*)A.xt, (double*)nullptr, (const double*)A.x, (const double*)A.xt, A.y, a.prolong_scale, stop);
+                break; }
+            case MgStep::up: case MgStep::up_fused: {      // explicit operator: x = v + s R^T x_next, prolongation and post-smoothing in one launch
+                MgLevelDev A = levels[l - 1];
+                const double* xn = nullptr;
+                if (mg_explicit(A)) xn = l + 1 == nl ? (const double*)K.yc : (const double*)levels[l].xf;
+                else if (A.smoothed) A.xt = A.y;      // (what post_smooth left)
+                if (s.kind == MgStep::up_fused) hipLaunchKernelGGL(mg_up_kernel<true>, grid, block, 0, st, A, A, 0, scale, stop, M, r, z, part_rz + cg_grid(G), xn, U0);
+                else hipLaunchKernelGGL(mg_up_kernel<false>, grid, block, 0, st, A, below_of(l), prolongs(l), scale, stop, M, r, z, part_rz, xn, U);
+                break; }
+            case MgStep::prolong0:
+                hipLaunchKernelGGL(mg_prolong0_kernel, grid, block, 0, st, G, M, (const double*)(nl == 1 ? K.yc : levels[0].xf), r, z, part_rz, scale, stop);
+                break;
+            case MgStep::prolong_fine:
+                hipLaunchKernelGGL(mg_prolong0s_kernel, grid, block, 0, st, G, *a.fine, (const double*)(nl == 1 ? K.yc : levels[0].xf), r, z, part_rz, scale, stop);
+                break;
         }
     }
-    xchg(2, 1);
-    if (hook_failed) return;
-    if (fine) hipLaunchKernelGGL(mg_prolong0s_kernel, dim3(g0), dim3(CG_BLOCK), 0, st, G, *fine, (const double*)(nl == 1 ? K.yc : levels[0].xf), r, z, part_rz, scale, stop);
-    else if (!fused) hipLaunchKernelGGL(mg_prolong0_kernel, dim3(g0), dim3(CG_BLOCK), 0, st, G, M, (const double*)(nl == 1 ? K.yc : levels[0].xf), r, z, part_rz, scale, stop);
-    if (n_hosts) *n_hosts = e_next;
+    return 0;
 }

@@ -572,7 +572,7 @@ double mg_cs(const pgo_problem* p) {
     const double wp = p->opt.mg_prolongation_damping > 0.0 && p->opt.mg_prolongation_damping < 0.85 ? p->opt.mg_prolongation_damping : 0.6;
     return wp / mg_omega(p);
 }
-const MgLevelDev* mg_fine_view(const pgo_problem* p) { return p->mg.fine ? &p->mg.fineT : nullptr; }      // smoothed keyframe transition: what launch_mg_apply restricts and prolongs with
+const MgLevelDev* mg_fine_view(const pgo_problem* p) { return p->mg.fine ? &p->mg.fineT : nullptr; }      // smoothed keyframe transition: what the cycle restricts and prolongs with
 double mg_scale(const pgo_problem* p) { return p->opt.mg_correction_scale >= 1.0 && p->opt.mg_correction_scale <= 4.0 ? p->opt.mg_correction_scale : 1.0; }
 
 // Several ranks: which exchange the multigrid cycle needs at one of launch_mg_apply's hook points (pgo_internal.hpp: MgExchangeHook) — the plan (index of the level whose vectors
@@ -586,7 +586,7 @@ double mg_scale(const pgo_problem* p) { return p->opt.mg_correction_scale >= 1.0
 bool mg_exchange_at(pgo_problem* p, int point, int lv, int* plan, double** v1, double** v2, const double** dinv /* non-null result: only r (*v2) travels, x (*v1) = Dinv r is formed on receipt */) {
     const int nl = p->mg.M.n_levels;
     auto dist = [&](int level) { return level >= 1 && level < nl && (size_t)(level - 1) < p->mg.dist.size() && p->mg.dist[(size_t)level - 1] != 0; };
-    auto expl = [&](int level) { return level >= 1 && level < nl && p->mg.levels[level - 1].smoothed && p->mg.levels[level - 1].rt_valf != nullptr; };
+    auto expl = [&](int level) { return level >= 1 && level < nl && mg_explicit(p->mg.levels[level - 1]); };
     *v1 = nullptr; *v2 = nullptr; *plan = -1; *dinv = nullptr;
     if (p->world() <= 1 || p->mg.lvl_plan.empty()) return false;
     if (point == 0) {
@@ -616,9 +616,17 @@ static int mg_exchange_hook(void* ctx, int point, int level) {
 int mg_apply_ranks(pgo_problem* p, bool inside_iteration) {
     MgHookCtx hc{p, inside_iteration ? p->C.flags : nullptr};
     MgExchangeHook hook{&hc, mg_exchange_hook};
-    int hrc = PGO_OK;
-    launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->coarse.K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), inside_iteration, p->st, false, mg_cs(p), nullptr, &hook, &hrc);
-    return hrc;
+    MgCycleArgs a;
+    a.inside_iteration = inside_iteration; a.hook = &hook;
+    return mg_cycle(p, p->C, a);
+}
+// One cycle on the handle's hierarchy: what every caller would say alike — the correction scale, c of the smoothed transitions, the keyframe level's transfer view, z — is filled
+// in here; r and the r.z partials default to C's (the PCG start); `a` states what differs.  Returns the exchange hook's code.
+int mg_cycle(pgo_problem* p, const CgDev& C, MgCycleArgs a) {
+    if (!a.r) a.r = C.r;
+    if (!a.part_rz) a.part_rz = C.part_rz;
+    a.z = C.z; a.scale = mg_scale(p); a.prolong_scale = mg_cs(p); a.fine = mg_fine_view(p);
+    return launch_mg_apply(p->G, C, p->mg.M, p->mg.levels, p->coarse.K, a, p->st);
 }
 
 // Multigrid operators of the system just built: Galerkin products level by level, block-Jacobi inverses, dense inverse of the coarsest level.

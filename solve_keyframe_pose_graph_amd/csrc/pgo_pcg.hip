@@ -187,8 +187,10 @@ bool single_reduction(const pgo_problem* p) {
 static UpdSplit choose_split(const pgo_problem* p) {
     UpdSplit sp;
     if (debug_no_split_update() || mg_fine_view(p)) return sp;
-    int tiles[2 * MG_MAX_LEVELS];
-    const int n = mg_rider_hosts(p->C, p->mg.M, p->mg.levels, tiles);
+    const MgCyclePlan P = mg_cycle_plan(p->mg.M, p->mg.levels, p->coarse.K, p->C.extra_rz, cg_grid_size(p->G), true, nullptr);
+    uint32_t tiles[MgCyclePlan::CAPACITY];      // the eligible launches' own workgroups, by host ordinal
+    int n = 0;
+    for (int i = 0; i < P.n; ++i) if (P.steps[i].rider) tiles[n++] = P.steps[i].grid;
     if (n < 2) return sp;
     int a = 0;
     for (int e = 1; e < n; ++e) if (tiles[e] < tiles[a]) a = e;
@@ -253,14 +255,10 @@ int pcg_precond(pgo_problem* p, const PcgForm& f, int k) {
     if (f.fused_coarse()) launch_coarse_solve_dot(p->coarse.K, p->C.flags, part_rz + f.fused_parts, p->st);      // the dense solve: y and the coarse part of r.u
     else if (f.mg() && f.rec == PcgForm::ranks) return mg_apply_ranks(p, true);      // u = D^-1 r + P0 V(P0^T r)
     else if (f.mg()) {
-        const bool split = f.rec == PcgForm::sr && f.post == PcgForm::mg_restricted && f.split.on();
-        int hosts = 0;
-        launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->coarse.K, r, p->C.z, part_rz, mg_scale(p), true, p->st, f.post == PcgForm::mg_restricted, mg_cs(p), mg_fine_view(p), nullptr, nullptr,
-                        split ? &f.split : nullptr, k & 1, k == 0 ? 1 : 0, &hosts);
-        if (split) {      // the riders were assigned by ordinal: the cycle must have made exactly the launches the split was chosen on
-            int tiles[2 * MG_MAX_LEVELS];
-            if (hosts != mg_rider_hosts(p->C, p->mg.M, p->mg.levels, tiles) || f.split.host_b >= hosts) { p->err = "split update: the cycle's launches differ from mg_rider_hosts' list"; return PGO_ERR_STATE; }
-        }
+        MgCycleArgs a;
+        a.r = r; a.part_rz = part_rz; a.inside_iteration = true; a.restricted = f.post == PcgForm::mg_restricted;
+        if (f.rec == PcgForm::sr && a.restricted && f.split.on()) { a.split = &f.split; a.parity = k & 1; a.first = k == 0 ? 1 : 0; }      // (hosts chosen on the plan this cycle walks: choose_split)
+        return mg_cycle(p, p->C, a);
     }
     else if (f.post == PcgForm::two_level) launch_coarse_apply(p->G, p->C, p->coarse.K, r, p->C.z, part_rz, true, p->st);
     return PGO_OK;
@@ -288,7 +286,7 @@ int pcg_start(pgo_problem* p, const PcgForm& f, bool warm, double tol2) {
     } else {
         int g = launch_cg_init_vectors(p->G, p->C, warm ? 1 : 0, p->st);
         const int g_bb = g;      // the slots of part_pq that hold the partials of b.D^-1 b
-        if (f.mg()) launch_mg_apply(p->G, p->C, p->mg.M, p->mg.levels, p->coarse.K, p->C.r, p->C.z, p->C.part_rz, mg_scale(p), false, p->st, false, mg_cs(p), mg_fine_view(p));
+        if (f.mg()) mg_cycle(p, p->C, MgCycleArgs{});
         else launch_coarse_apply(p->G, p->C, p->coarse.K, p->C.r, p->C.z, p->C.part_rz, false, p->st);
         if (f.fused_coarse()) {    // z is complete here: the slots the fused kernels will use beyond the start-up kernels' stay zero for this parity
             HIPCHK(p, hipMemsetAsync(p->C.part_rz + g, 0, (size_t)(f.fused_parts + p->C.extra_rz - g) * sizeof(double), p->st));

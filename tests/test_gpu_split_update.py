@@ -8,6 +8,10 @@ with library defaults, under PGO_DEBUG_POISON=1 and with cg_use_graph=0 — all 
   deep_plain      9 000 keyframes, plain loops, chain-like, four levels
   shallow         6 000 keyframes, plain loops, the default dense level: level 2 (<= 512 nodes) is already the dense one, so fewer than two launches could carry a
                   rider and the unsplit kernel runs BY RULE, hook or no hook
+  explicit        640 keyframes (tests/precond_cases.py's multigrid graph), three levels, level 1 with an explicit transfer operator: its down-sweep is mg_sdown_kernel, and
+                  the eligible launches are that one and level 2's two (level 1's up-sweep is the fused one)
+  explicit_deep   the same graph with level 2 smoothed as well: the rule's pair is level 2's mg_sdown_kernel launch and its up-sweep, which reads the dense level's solution
+                  itself (xn) — riders carried by an explicit-transfer level
 Which path the HOST chose is read off pgo_time_kernel(6)'s byte count (the split iteration reads the residual once more, 48 B per keyframe): it witnesses the rule's decision
 only — that the riders then ran is what the digests show, since a rider that did not run leaves x, p and z stale.
 PGO_DEBUG_SPLIT_HOSTS (the scan hook behind DESIGN.md §9's host variants) is held to the same bits: both riders in ONE launch, and a pair other than the rule's.
@@ -22,6 +26,8 @@ import sys
 import numpy as np
 import pytest
 
+from tests.precond_cases import MG_BASE
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +37,8 @@ GRAPHS = {
     "deep_rejected": (dict(n=12000, loops=12000, odom_f_max=2, seed=3), True, dict(mg_smoothed_fine=0, mg_dense_max_nodes=64)),
     "deep_plain": (dict(n=9000, loops=900, odom_f_max=1, seed=2, outlier_frac=0.0), False, dict(mg_smoothed_fine=0, mg_dense_max_nodes=64)),
     "shallow": (dict(n=6000, loops=600, odom_f_max=1, seed=2, outlier_frac=0.0), False, dict(mg_smoothed_fine=0)),
+    "explicit": ("mg640", True, dict(MG_BASE, mg_smoothed_levels=1, mg_explicit_transfer=1, mg_passes=2, mg_dense_max_nodes=16)),
+    "explicit_deep": ("mg640", True, dict(MG_BASE, mg_smoothed_levels=2, mg_explicit_transfer=1, mg_passes=2, mg_dense_max_nodes=16)),
 }
 
 
@@ -38,8 +46,12 @@ def digest(name, **opt):
     from solve_keyframe_pose_graph_amd import capi, graphgen
     from tests import util
     spec, switchable, base = GRAPHS[name]
-    spec = dict(spec)
-    g = graphgen.generate(spec.pop("n"), spec.pop("loops"), **spec)
+    if isinstance(spec, str):
+        from tests import precond_cases
+        g = precond_cases.graph(spec)
+    else:
+        spec = dict(spec)
+        g = graphgen.generate(spec.pop("n"), spec.pop("loops"), **spec)
     q, t, s = util.initial_state(g, switchable)
     kw = dict(base); kw.update(opt)
     P = util.pgo_problem(g, switchable, **kw)
@@ -92,15 +104,25 @@ def test_split_and_unsplit_update_give_the_same_bits(name):
         assert any(rec[2] == 0 for rec in ref["log"]), "no rejected step: the graph no longer exercises pauses and resumes"
 
 
+def hosts_give_the_same_bits(name, hosts):
+    ref = digest_in_a_new_process(name, False)
+    d = digest_in_a_new_process(name, True, hosts=hosts)
+    assert d["iteration_bytes"] - ref["iteration_bytes"] == 48 * ref["keyframes"]
+    assert d["log"] == ref["log"], (d["log"], ref["log"])
+    assert d["sha256"] == ref["sha256"] and d["final_cost"] == ref["final_cost"] and d["cg_iterations"] == ref["cg_iterations"]
+
+
 @pytest.mark.parametrize("hosts", ["0,0", "0,1", "1,1"])
 def test_other_host_launches_give_the_same_bits(hosts):
     """Eligible launches of deep_rejected's cycle come in launch order, the down-sweeps first.  "0,0" / "1,1": one launch carries both riders (a lane rewrites the z
     entries it has read itself); "0,1": the level-1 and level-2 down-sweeps, not the rule's pair."""
-    ref = digest_in_a_new_process("deep_rejected", False)
-    d = digest_in_a_new_process("deep_rejected", True, hosts=hosts)
-    assert d["iteration_bytes"] - ref["iteration_bytes"] == 48 * ref["keyframes"]
-    assert d["log"] == ref["log"], (d["log"], ref["log"])
-    assert d["sha256"] == ref["sha256"] and d["final_cost"] == ref["final_cost"] and d["cg_iterations"] == ref["cg_iterations"]
+    hosts_give_the_same_bits("deep_rejected", hosts)
+
+
+def test_an_explicit_transfer_down_sweep_as_host_gives_the_same_bits():
+    """`explicit`'s first eligible launch is level 1's mg_sdown_kernel launch — the one with the most workgroups of its own, which the rule never picks: here it carries the
+    direction / solution rider, level 2's down-sweep the block-Jacobi one."""
+    hosts_give_the_same_bits("explicit", "0,1")
 
 
 if __name__ == "__main__":
