@@ -406,8 +406,7 @@ int build_graph(pgo_problem* p, int64_t N, int64_t S, const double* sw_now) {
     if (dense_mode(p)) {
         // no aggregates, and no memory of them: the two-level method's history across solves (kept / dropped, back-off) counts CONSECUTIVE solves that used it, and a graph built
         // for the exact solver ends every such run — a handle that goes back to a PCG afterwards starts where a fresh handle starts (solves before and after are bitwise equal)
-        CoarseState& c = p->coarse;
-        c.mode = 0; c.retests = 0; c.skip_all = false; c.drop_radius = 0.0; c.backoff = 0; c.skip = 0; c.keep_streak = 0;
+        p->coarse.hist = CoarseState::History{};
     }
     if (!p->mg.built && !dense_mode(p) && (rc = build_two_level_aggregates(p)) != PGO_OK) return rc;      // (a graph that got the multigrid never uses the two-level method: its dense operator would be built and uploaded for nothing)
     phase("two-level aggregates");

@@ -15,6 +15,7 @@
 
 #include "pgo.h"
 #include "pgo_internal.hpp"
+#include "pgo_lm.hpp"
 #include "pgo_mg_cycle.hpp"
 #include "pgo_comm.hpp"
 #include "pgo_mg_host.hpp"
@@ -168,10 +169,13 @@ struct CoarseState {
     DBuf<int32_t> d_cblk_ab, d_cagg_free, d_cinfo;
     CoarseDev K{};
     bool built = false, active = false;
-    int mode = 0;                    // per solve: 0 not yet compared with plain block-Jacobi, 1 keep, 2 dropped (it did not pay on this graph)
-    int retests = 0; bool skip_all = false; double drop_radius = 0.0;   // dropped at a small radius: one more comparison once the radius reaches coarse_min_radius
-    int backoff = 0, skip = 0;       // a handle that keeps dropping it (incremental triggers on the same kind of graph) retests ever more rarely
-    int keep_streak = 0;             // consecutive solves that kept it: the comparison is then repeated only every 4th solve
+    // the method's history on this handle, within a solve and across solves: plain values, saved and put back by copy
+    struct History {
+        int mode = 0;                    // per solve: 0 not yet compared with plain block-Jacobi, 1 keep, 2 dropped (it did not pay on this graph)
+        int retests = 0; bool skip_all = false; double drop_radius = 0.0;   // dropped at a small radius: one more comparison once the radius reaches coarse_min_radius
+        int backoff = 0, skip = 0;       // a handle that keeps dropping it (incremental triggers on the same kind of graph) retests ever more rarely
+        int keep_streak = 0;             // consecutive solves that kept it: the comparison is then repeated only every 4th solve
+    } hist;
     uint64_t geometry_epoch = 0;     // the linearisation (lin_epoch) the aggregates' centroids were computed at
 };
 
@@ -310,11 +314,9 @@ struct pgo_problem {
     ScaleDev Sc{};
     CgDev C{};
 
-    // LM state
-    bool in_solve = false, scale_ready = false, terminated = false, have_prev_step = false;
-    double radius = 0, decrease_factor = 2, x_cost = 0, x_norm = 0, gmax = 0;
-    bool reuse_diagonal = false;
-    int iteration = 0, invalid = 0;
+    // the open solve: the LM controller's state (pgo_lm.hpp), the scaling's and the clock's
+    bool in_solve = false, scale_ready = false;
+    LmState lm;
     double t_begin = 0, t_device0 = 0;
     pgo_summary sum;
 
@@ -325,7 +327,6 @@ struct pgo_problem {
 
     OwnedStream st;                      // (declared here: released after pcg, before everything above)
     PcgState pcg;                        // the PCG driver (pgo_pcg.hip)
-    double last_rho = 1.0;               // relative decrease of the last accepted step of this solve
 };
 
 
@@ -339,11 +340,6 @@ enum { S_COST = 0, S_PRIOR_COST = 1, S_MODEL = 2, S_SW_STEP2 = 3, S_SW_XNORM2 = 
 
 inline int set_device(pgo_problem* p) { HIPCHK(p, hipSetDevice(p->device)); return PGO_OK; }
 inline double* part(pgo_problem* p, int k) { return p->d_part.p + (size_t)k * p->n_part; }      // partial-sum scratch array k
-
-// "A rejection is in the air": the previous step was rejected (rejections come in streaks: the radius shrinks over several steps), or the last accepted step's relative decrease
-// fell below 0.8 — the quadratic model is losing its grip (C3's and C4's first rejected steps follow rho = 0.67 and 0.62; the accepted hard steps of both follow rho >= 0.89).
-// build_system defers the multigrid of a hard system by it, lm_step arms both pauses of the PCG by it (a deferred build waits for the first of them).
-inline bool rejection_likely(const pgo_problem* p) { return p->reuse_diagonal || p->last_rho < 0.8; }
 
 // ---- pgo_graph.hip: host edge lists -> device graph
 int add_edges(pgo_problem* p, HostClass& H, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, const int32_t* sw, double loss_enc = 0.0);
@@ -366,7 +362,7 @@ int build_two_level_aggregates(pgo_problem* p);
 void two_level_solve_begin(pgo_problem* p);
 void two_level_solve_end(pgo_problem* p);
 int build_coarse(pgo_problem* p, bool force = false);
-int build_system(pgo_problem* p, bool* ok);
+int build_lm_system(pgo_problem* p, bool* ok);      // the LM system at the current radius with its preconditioner; *ok false: a diagonal block is not positive definite
 bool single_reduction(const pgo_problem* p);
 // The form of a PCG iteration: its recurrence, and what follows the vector update.  Chosen once per PCG phase (choose_form), again where the in-flight switch installs the multigrid.
 struct PcgForm {

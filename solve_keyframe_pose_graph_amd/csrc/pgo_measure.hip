@@ -20,17 +20,18 @@ namespace {
 //   6  one multigrid-preconditioned PCG iteration;  7  the cycle's level kernels alone (several ranks: this rank's share, no exchanges)
 //   8  this rank's kernels of one multigrid set-up (operators of an LM system incl. the dense inverse), without the exchanges between them
 
-int build_lm_system(pgo_problem* p) {
-    const pgo_options& o = p->opt;
-    if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, o.min_lm_diagonal, o.max_lm_diagonal, p->st);
-    bool ok = true;
-    return build_system(p, &ok);
-}
+// What a diagnostic that builds an LM system of its own at `radius` (<= 0: the current one) leaves as it found it: the radius, and the two-level method's comparison state
+// (build_lm_system may spend a retest).  No preconditioner stays active behind it.
+struct ProbeRestore {
+    pgo_problem* p; double radius; int mode, retests;
+    ProbeRestore(pgo_problem* q, double r) : p(q), radius(q->lm.radius), mode(q->coarse.hist.mode), retests(q->coarse.hist.retests) { if (r > 0.0) p->lm.radius = r; }
+    ~ProbeRestore() { p->lm.radius = radius; p->coarse.hist.mode = mode; p->coarse.hist.retests = retests; p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0; }
+};
 
 // 2 / 4 / 5: a live block-Jacobi PCG state to iterate on (tolerance 0: never converges during the timed launches)
 int setup_block_jacobi(pgo_problem* p) {
-    int rc;
-    if ((rc = build_lm_system(p)) != PGO_OK) return rc;
+    int rc; bool ok = true;
+    if ((rc = build_lm_system(p, &ok)) != PGO_OK) return rc;
     p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0;   // the timed iteration is the plain block-Jacobi one: no partial-sum slots of a multigrid / two-level solve
     launch_cg_init(p->G, p->C, 0, 0.0, p->st);
     return PGO_OK;
@@ -39,8 +40,8 @@ int setup_block_jacobi(pgo_problem* p) {
 // 6 / 7 / 8: the multigrid operators of the current LM system and a live PCG state on them
 int setup_multigrid(pgo_problem* p, int which) {
     if (!p->mg.built || !p->built_mf || (p->local_ids && which == 6)) { p->err = "pgo_time_kernel: this graph has no multigrid hierarchy (mg_min_keyframes) / several ranks: only the level kernels (7) can be timed"; return PGO_ERR_STATE; }
-    int rc;
-    if ((rc = build_lm_system(p)) != PGO_OK) return rc;
+    int rc; bool ok = true;
+    if ((rc = build_lm_system(p, &ok)) != PGO_OK) return rc;
     if (!p->mg.active && (rc = build_mg(p)) != PGO_OK) return rc;
     if (!p->mg.active) { p->err = "pgo_time_kernel: the multigrid operators of this system are not positive definite"; return PGO_ERR_NUMERIC; }
     if (!p->local_ids) return pcg_start(p, choose_form(p), false, 0.0);      // (tolerance 0: never converges during the timed launches)
@@ -383,15 +384,9 @@ int pgo_apply_preconditioner(pgo_problem* p, int32_t which, double radius, int64
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
     if ((rc = mg_fresh_install(p)) != PGO_OK) return rc;      // a fresh graph's hierarchy decides which preconditioners this graph has
-    // what the call must leave as it found it: the radius, and the two-level method's comparison state (build_system may spend a retest)
-    struct Restore {
-        pgo_problem* p; double radius; int mode, retests;
-        ~Restore() { p->radius = radius; p->coarse.mode = mode; p->coarse.retests = retests; p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0; }
-    } restore{p, p->radius, p->coarse.mode, p->coarse.retests};
-    if (radius > 0.0) p->radius = radius;
-    if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);
+    ProbeRestore restore(p, radius);
     bool ok = true;
-    if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
+    if ((rc = build_lm_system(p, &ok)) != PGO_OK) return rc;
     if (!ok) return refuse("a diagonal block of the system is not positive definite at this radius");
     if (which == PGO_PRECOND_BLOCK_JACOBI) { p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0; }
     else if (which == PGO_PRECOND_TWO_LEVEL) {
@@ -434,7 +429,7 @@ int pgo_get_linear_solution(pgo_problem* p, double* x) {
     if (!p || !x) return PGO_ERR_INVALID_ARG;
     if (p->comm || p->local_ids) { p->err = "pgo_get_linear_solution: one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
     if (!p->in_solve) { p->err = "pgo_get_linear_solution needs an open solve (pgo_solve_begin)"; return PGO_ERR_STATE; }
-    if (p->iteration < 1) { p->err = "pgo_get_linear_solution: no PCG has run in this solve yet (pgo_lm_step)"; return PGO_ERR_STATE; }
+    if (p->lm.iteration < 1) { p->err = "pgo_get_linear_solution: no PCG has run in this solve yet (pgo_lm_step)"; return PGO_ERR_STATE; }
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
     return nodes_to_global(p, p->C.x, 6, x);
@@ -506,14 +501,9 @@ int pgo_apply_normal_operator_batch(pgo_problem* p, double radius, int64_t n_vec
     if (n_vec < 1 || !X || !Y || !std::isfinite(radius)) return refuse("invalid argument: null array, no vector, or a radius that is not finite");
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
-    struct Restore {      // (as pgo_apply_preconditioner: the radius and the two-level method's comparison state stay as they were found)
-        pgo_problem* p; double radius; int mode, retests;
-        ~Restore() { p->radius = radius; p->coarse.mode = mode; p->coarse.retests = retests; p->mg.active = false; p->coarse.active = false; p->C.extra_rz = 0; }
-    } restore{p, p->radius, p->coarse.mode, p->coarse.retests};
-    if (radius > 0.0) p->radius = radius;
-    if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);
+    ProbeRestore restore(p, radius);
     bool ok = true;
-    if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
+    if ((rc = build_lm_system(p, &ok)) != PGO_OK) return rc;
     const int64_t n6 = p->N * 6;
     if (n6 == 0) return PGO_OK;
     DBuf<double> d_io;

@@ -680,11 +680,11 @@ int regroup_if_moved(pgo_problem* p, const double* sv /* host: the caller's swit
 static bool regroup_allowed(const pgo_problem* p) {
     // (not during the first three LM iterations: the switches of outliers — and of inliers far from the odometry guess, which recover — are still falling then: measured on C3,
     // 17 % of the switchable edges have moved after the first step, and a regroup there is paid twice)
-    return p->opt.mg_regroup_fraction > 0.0 && p->mg.built && p->S > 0 && p->mg.regroups < 2 && p->iteration >= 3 && (int64_t)p->mg.sw_built.size() == p->swe.size();
+    return p->opt.mg_regroup_fraction > 0.0 && p->mg.built && p->S > 0 && p->mg.regroups < 2 && p->lm.iteration >= 3 && (int64_t)p->mg.sw_built.size() == p->swe.size();
 }
 // several ranks: the regroup happens where multigrid operators are about to be built, synchronously (its host half holds collectives) — every rank at the same LM step
 static int maybe_regroup(pgo_problem* p) {
-    if (!regroup_allowed(p) || p->iteration <= 3) return PGO_OK;
+    if (!regroup_allowed(p) || p->lm.iteration <= 3) return PGO_OK;
     std::vector<double> sv((size_t)p->S);
     HIPCHK(p, hipMemcpyAsync(sv.data(), p->d_swv[p->cur].p, sv.size() * sizeof(double), hipMemcpyDeviceToHost, p->st));
     HIPCHK(p, hipStreamSynchronize(p->st));
@@ -837,8 +837,8 @@ int build_mg(pgo_problem* p) {
     // (measured: 1 114 tiles on 1 024 workgroups — C4 — lose 3 % to the ragged second trip against the separate prolongation kernel; 3 907 tiles — C5 — gain 3.5 %)
     const int t1 = m.levels[0].tiles;
     p->C.extra_rz = (m.active && !p->local_ids && !m.fine && m.M.n_levels >= 2 && (t1 <= MAX_PARTIALS || t1 >= 2 * MAX_PARTIALS)) ? std::min<int>(t1, MAX_PARTIALS) : 0;
-    if (p->opt.verbosity > 0 && h != 0) std::fprintf(stderr, "[pgo] multigrid: a coarse block is not positive definite at radius %.1e -> off for this iteration\n", p->radius);
-    if (p->opt.verbosity > 1) std::fprintf(stderr, "[pgo] multigrid: operators of LM iteration %d built in %.2f ms\n", p->iteration, (now_s() - t_build0) * 1e3);
+    if (p->opt.verbosity > 0 && h != 0) std::fprintf(stderr, "[pgo] multigrid: a coarse block is not positive definite at radius %.1e -> off for this iteration\n", p->lm.radius);
+    if (p->opt.verbosity > 1) std::fprintf(stderr, "[pgo] multigrid: operators of LM iteration %d built in %.2f ms\n", p->lm.iteration, (now_s() - t_build0) * 1e3);
     return PGO_OK;
 }
 

@@ -79,13 +79,13 @@ int build_coarse(pgo_problem* p, bool force) {
     // ~64 x coarse_aggregates keyframes), otherwise only at large trust regions, where the slow modes are the long wavelengths
     // (measured: scripts/gpu_coarse_ab.py).
     if (!c.built || p->opt.coarse_aggregates <= 0) return PGO_OK;
-    if (!force && c.mode == 2) {
+    if (!force && c.hist.mode == 2) {
         // dropped at a smaller trust region: the long wavelengths it removes dominate more and more as the radius grows, so it gets another
         // comparison once the radius is 9x (two accepted steps) beyond the one it lost at — at most twice per solve
-        if (c.retests >= 2 || c.skip_all || !(p->radius >= 9.0 * c.drop_radius)) return PGO_OK;   // (eligibility by aggregate size / coarse_min_radius is checked below)
-        ++c.retests; c.mode = 0;
+        if (c.hist.retests >= 2 || c.hist.skip_all || !(p->lm.radius >= 9.0 * c.hist.drop_radius)) return PGO_OK;   // (eligibility by aggregate size / coarse_min_radius is checked below)
+        ++c.hist.retests; c.hist.mode = 0;
     }
-    if (!force && !(c.K.m <= 64 || (p->radius >= p->opt.coarse_min_radius && c.K.m <= 1024))) return PGO_OK;   // aggregates of thousands of keyframes are too coarse to help
+    if (!force && !(c.K.m <= 64 || (p->lm.radius >= p->opt.coarse_min_radius && c.K.m <= 1024))) return PGO_OK;   // aggregates of thousands of keyframes are too coarse to help
     if (c.geometry_epoch != p->lin_epoch) {          // the aggregates' centroids follow the poses of the current linearisation
         launch_coarse_geometry(p->G, c.K, p->d_pose[p->cur].p, p->st);
         c.geometry_epoch = p->lin_epoch;
@@ -100,30 +100,30 @@ int build_coarse(pgo_problem* p, bool force) {
     HIPCHK(p, hipStreamSynchronize(p->st));
     c.active = h == 0;
     if (p->opt.verbosity > 1) std::fprintf(stderr, "[pgo] coarse operator assembled and inverted in %.3f ms (since the start of build_coarse)\n", (now_s() - t_coarse0) * 1e3);
-    if (p->opt.verbosity > 0) std::fprintf(stderr, "[pgo] coarse space: %d aggregates of %d keyframes, %d blocks, radius %.1e: %s\n", c.K.n_agg, c.K.m, c.K.n_blk, p->radius, h == 0 ? "on" : "coarse operator not positive definite -> off");
+    if (p->opt.verbosity > 0) std::fprintf(stderr, "[pgo] coarse space: %d aggregates of %d keyframes, %d blocks, radius %.1e: %s\n", c.K.n_agg, c.K.m, c.K.n_blk, p->lm.radius, h == 0 ? "on" : "coarse operator not positive definite -> off");
     return PGO_OK;
 }
 // The back-off across solves.  At a solve's start: a handle in back-off skips the two-level method; one that kept it in the last solves uses it without the comparison.
 void two_level_solve_begin(pgo_problem* p) {
     CoarseState& c = p->coarse;
-    c.retests = 0; c.drop_radius = 0.0;
-    if (c.skip > 0) { c.mode = 2; c.skip_all = true; --c.skip; }
-    else { c.mode = (c.keep_streak % 4 != 0) ? 1 : 0; c.skip_all = false; }
+    c.hist.retests = 0; c.hist.drop_radius = 0.0;
+    if (c.hist.skip > 0) { c.hist.mode = 2; c.hist.skip_all = true; --c.hist.skip; }
+    else { c.hist.mode = (c.hist.keep_streak % 4 != 0) ? 1 : 0; c.hist.skip_all = false; }
 }
 // At its end — (a solve that kept it: the next three solves of this handle use it without the comparison)
 // a solve in which the coarse space lost every comparison: the following solves of this handle (incremental triggers on the same kind
 // of graph) skip it, 1, 3, 7, 15 solves at a time, before comparing again; one win resets the back-off
 void two_level_solve_end(pgo_problem* p) {
     CoarseState& c = p->coarse;
-    if (c.mode == 2 && !c.skip_all) { c.backoff = std::min(2 * c.backoff + 1, 15); c.skip = c.backoff; }
-    if (c.mode == 1) ++c.keep_streak; else if (c.mode == 2 && !c.skip_all) c.keep_streak = 0;
+    if (c.hist.mode == 2 && !c.hist.skip_all) { c.hist.backoff = std::min(2 * c.hist.backoff + 1, 15); c.hist.skip = c.hist.backoff; }
+    if (c.hist.mode == 1) ++c.hist.keep_streak; else if (c.hist.mode == 2 && !c.hist.skip_all) c.hist.keep_streak = 0;
 }
 
-int build_system(pgo_problem* p, bool* ok) {
+static int build_system(pgo_problem* p, bool* ok) {
     PcgState& s = p->pcg;
     int rc;
     HIPCHK(p, hipMemsetAsync(p->d_flags.p + 4, 0, sizeof(int32_t), p->st));
-    launch_build_rows(p->G, p->L, p->Sc, p->C, p->radius, 1 /*one GPU: this handle adds Hd, g and the damping; multi-GPU: the keyframe's owner (G.own)*/, p->built_mf ? p->d_lam.p : nullptr, p->st);
+    launch_build_rows(p->G, p->L, p->Sc, p->C, p->lm.radius, 1 /*one GPU: this handle adds Hd, g and the damping; multi-GPU: the keyframe's owner (G.own)*/, p->built_mf ? p->d_lam.p : nullptr, p->st);
     if ((rc = exchange_rows(p, p->C.Dtot, 36, p->C.b, 6)) != PGO_OK) return rc;   // reduced diagonal + rhs of shared keyframes
     launch_invert_rows(p->G, p->C, p->d_flags.p + 4, p->st);
     int32_t fail = 0;
@@ -137,7 +137,7 @@ int build_system(pgo_problem* p, bool* ok) {
     *ok = fail == 0;
     p->mg.active = false; s.mg_failed = false; p->C.extra_rz = 0; s.mg_start_deferred = false;
     // block-Jacobi-equivalent iterations this system is expected to need: those of the last fully solved system of this solve x sqrt(radius ratio); 0 = no prediction
-    s.cg_predicted = (s.cg_prev_radius > 0.0 && p->radius > 0.0) ? s.cg_prev_equiv * std::sqrt(p->radius / s.cg_prev_radius) : 0.0;
+    s.cg_predicted = (s.cg_prev_radius > 0.0 && p->lm.radius > 0.0) ? s.cg_prev_equiv * std::sqrt(p->lm.radius / s.cg_prev_radius) : 0.0;
     if (dense_mode(p)) { s.cg_predicted = 0.0; p->coarse.active = false; return PGO_OK; }      // the exact dense solver: no preconditioner to decide on
     if (*ok && p->mg.built) {
         // Which preconditioner the PCG of this LM system starts with.  Block-Jacobi iterations grow like sqrt(radius) from one accepted step
@@ -156,9 +156,9 @@ int build_system(pgo_problem* p, bool* ok) {
         // accepted one at a large radius, i.e. exactly the systems predicted hard, and block-Jacobi reaches the first pause (cg_early_tolerance, a few dozen iterations)
         // for a fraction of what the operators cost (C3, step 4: 32 ms for a step thrown away at 21 iterations).  Then the build waits for the pause (lm_step).
         const bool hard = p->opt.mg_switch_iterations <= 0 || predicted >= start_factor * (double)p->opt.mg_switch_iterations;
-        // ... and only where a rejection is in the air (rejection_likely, pgo_handle.hpp): elsewhere — the accepted hard steps of C3 and C4 follow rho >= 0.89 — a prelude is
+        // ... and only where a rejection is in the air (rejection_likely, pgo_lm.hpp): elsewhere — the accepted hard steps of C3 and C4 follow rho >= 0.89 — a prelude is
         // 74 block-Jacobi iterations the multigrid would not have needed: 3 ms x 5 on C3, 5 ms x 12 on C4
-        s.mg_start_deferred = hard && rejection_likely(p) && p->opt.mg_switch_iterations > 0 && p->opt.cg_early_tolerance > p->opt.cg_rel_tolerance;
+        s.mg_start_deferred = hard && rejection_likely(p->lm) && p->opt.mg_switch_iterations > 0 && p->opt.cg_early_tolerance > p->opt.cg_rel_tolerance;
         if (s.mg_start_deferred) {      // ... but not for long: a step that has not reached the pause within the prelude is a hard one that stays (late C3 systems need ~300 block-Jacobi iterations to 1e-2)
             const int prelude = 72;      // three chunks (measured on C3 / C4, 20 steps: 48 -> 0.392 / 1.500 s — C3's rejected step 4 needs 53 —, 72 -> 0.322 / 1.515 s, 96 -> 0.324 / 1.524 s)
             s.mg_switch_at = std::min(s.mg_switch_at, prelude);
@@ -167,6 +167,11 @@ int build_system(pgo_problem* p, bool* ok) {
     }
     else if (*ok && (rc = build_coarse(p)) != PGO_OK) return rc;
     return PGO_OK;
+}
+// The LM system at the current radius: the damping diagonal (a rejected or an invalid step keeps the one it had: reuse_diagonal), then the system and its preconditioner
+int build_lm_system(pgo_problem* p, bool* ok) {
+    if (!p->lm.reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);
+    return build_system(p, ok);
 }
 // One GPU, matrix-free matvec, tolerance not below 1e-11: the PCG runs in its single-reduction (Chronopoulos-Gear) form — matvec w = A u with the partials of u.w, then ONE
 // vector kernel whose head re-reduces u.w and r.u together (pgo_kernels.hip: sr_head).  Decided by the options alone, so every phase of a paused PCG runs the same form.
@@ -524,7 +529,7 @@ int finish_system(pgo_problem* p, CgResult* cg, bool evaluated, int* precond_use
     // many loose pieces), so once per solve — at the first full-accuracy step that used it — plain block-Jacobi gets the SAME
     // iteration budget on the same system: if it does not converge within it the coarse space stays for the rest of
     // the solve, otherwise it is dropped.  The test costs at most as many iterations as the coarse run took.
-    if (c.active && c.mode == 0 && !evaluated && !cg->breakdown && cg->converged) {
+    if (c.active && c.hist.mode == 0 && !evaluated && !cg->breakdown && cg->converged) {
         HIPCHK(p, p->d_tmp.ensure((size_t)p->N * 6));
         HIPCHK(p, hipMemcpyAsync(p->d_tmp.p, p->C.x, (size_t)p->N * 6 * sizeof(double), hipMemcpyDeviceToDevice, p->st));
         c.active = false;
@@ -535,11 +540,11 @@ int finish_system(pgo_problem* p, CgResult* cg, bool evaluated, int* precond_use
         if (plain.converged && !plain.breakdown) {      // block-Jacobi alone is at least as fast here
             // lost although it needed clearly fewer iterations: worth another comparison at a larger radius; lost without even that
             // (the aggregates' rigid modes are not this graph's slow modes): no more comparisons in this solve
-            if ((double)plain.iterations < 1.2 * (double)cg->iterations) c.retests = 2;
-            c.mode = 2; cg->iterations += plain.iterations; c.drop_radius = p->radius;
+            if ((double)plain.iterations < 1.2 * (double)cg->iterations) c.hist.retests = 2;
+            c.hist.mode = 2; cg->iterations += plain.iterations; c.hist.drop_radius = p->lm.radius;
         }
         else {
-            c.mode = 1; c.active = true; c.backoff = 0;
+            c.hist.mode = 1; c.active = true; c.hist.backoff = 0;
             HIPCHK(p, hipMemcpyAsync(p->C.x, p->d_tmp.p, (size_t)p->N * 6 * sizeof(double), hipMemcpyDeviceToDevice, p->st));
             cg->iterations += plain.iterations;
         }
@@ -551,7 +556,7 @@ int finish_system(pgo_problem* p, CgResult* cg, bool evaluated, int* precond_use
     *precond_used = p->mg.active ? PGO_PRECOND_MULTIGRID : (c.active ? PGO_PRECOND_TWO_LEVEL : PGO_PRECOND_BLOCK_JACOBI);
     if (cg->breakdown && (p->mg.active || c.active) && !evaluated) {
         if (o.verbosity > 0) std::fprintf(stderr, "[pgo] %s: PCG breakdown at radius %.1e after %d iterations (preconditioner not positive definite) -> block-Jacobi for this system\n",
-                                          p->mg.active ? "multigrid" : "two-level method", p->radius, cg->iterations);
+                                          p->mg.active ? "multigrid" : "two-level method", p->lm.radius, cg->iterations);
         if (p->mg.active) { p->mg.active = false; s.mg_failed = true; }
         c.active = false;      // (this system only: build_coarse decides again for the next one)
         p->C.extra_rz = 0;
@@ -566,7 +571,7 @@ int finish_system(pgo_problem* p, CgResult* cg, bool evaluated, int* precond_use
     // block-Jacobi-equivalent work of this system, for the next system's choice of preconditioner (build_system)
     if (!evaluated && !cg->breakdown) {
         const double equiv = p->mg.levels[0].smoothed ? 8.0 : 4.0;     // block-Jacobi iterations one multigrid iteration stands for on a hard system
-        s.cg_prev_equiv = (double)s.cg_extra + (p->mg.active ? equiv : 1.0) * (double)cg->iterations; s.cg_prev_radius = p->radius;
+        s.cg_prev_equiv = (double)s.cg_extra + (p->mg.active ? equiv : 1.0) * (double)cg->iterations; s.cg_prev_radius = p->lm.radius;
     }
     return PGO_OK;
 }

@@ -60,8 +60,8 @@ int linearize(pgo_problem* p, double* cost_out) {
     double h[S_N];
     if ((rc = read_scalars(p, h)) != PGO_OK) return rc;
     *cost_out = 0.5 * (h[S_COST] + h[S_PRIOR_COST]);
-    p->x_norm = std::sqrt(h[S_XNORM2] + h[S_SW_XNORM2]);
-    p->gmax = h[S_GMAX];
+    p->lm.x_norm = std::sqrt(h[S_XNORM2] + h[S_SW_XNORM2]);
+    p->lm.gmax = h[S_GMAX];
     return PGO_OK;
 }
 
@@ -78,7 +78,7 @@ void log_iter(pgo_problem* p, const pgo_iteration& it) {
 }
 
 void terminate(pgo_problem* p, int type, const char* msg) {
-    p->terminated = true;
+    p->lm.terminated = true;
     p->sum.termination_type = type;
     std::snprintf(p->sum.message, sizeof(p->sum.message), "%s", msg);
 }
@@ -121,192 +121,120 @@ int solve_begin(pgo_problem* p, const double* quat, const double* t, const doubl
     HIPCHK(p, hipStreamSynchronize(p->st));
     p->t_device0 = now_s();
     std::memset(&p->sum, 0, sizeof(p->sum));
-    p->in_solve = true; p->terminated = false; p->scale_ready = false; p->have_prev_step = false;
+    p->in_solve = true; p->scale_ready = false; p->lm = lm_begin(p->opt);
     p->st_exchanges = p->st_allreduces = p->st_pcg_iterations = 0; p->st_bytes_neighbour = p->st_bytes_allreduce = 0.0;
-    p->pcg.cg_prev_equiv = 0.0; p->pcg.cg_prev_radius = 0.0; p->mg.regroups = 0; p->last_rho = 1.0;
+    p->pcg.cg_prev_equiv = 0.0; p->pcg.cg_prev_radius = 0.0; p->mg.regroups = 0;
     if (!dense_mode(p)) two_level_solve_begin(p);      // (a dense solve leaves the two-level method's history across solves alone)
-    p->radius = p->opt.initial_trust_region_radius; p->decrease_factor = 2.0; p->reuse_diagonal = false; p->iteration = 0; p->invalid = 0;
     p->sum.termination_type = PGO_NO_CONVERGENCE;
-    if ((rc = linearize(p, &p->x_cost)) != PGO_OK) return rc;
-    p->sum.initial_cost = p->x_cost;
-    p->sum.final_cost = p->x_cost;
-    if (!std::isfinite(p->x_cost)) { terminate(p, PGO_FAILURE, "initial cost is not finite"); return PGO_OK; }
+    if ((rc = linearize(p, &p->lm.x_cost)) != PGO_OK) return rc;
+    p->sum.initial_cost = p->lm.x_cost;
+    p->sum.final_cost = p->lm.x_cost;
+    if (!std::isfinite(p->lm.x_cost)) { terminate(p, PGO_FAILURE, "initial cost is not finite"); return PGO_OK; }
     pgo_iteration it{};
-    it.iteration = 0; it.step_is_valid = 1; it.step_is_successful = 1; it.cost = p->x_cost; it.gradient_max_norm = p->gmax; it.trust_region_radius = p->radius;
+    it.iteration = 0; it.step_is_valid = 1; it.step_is_successful = 1; it.cost = p->lm.x_cost; it.gradient_max_norm = p->lm.gmax; it.trust_region_radius = p->lm.radius;
     it.seconds = now_s() - p->t_device0;
     log_iter(p, it);
     return PGO_OK;
 }
 
+// candidate point x (+) delta in the other state buffer: its cost, the model cost change and the step norm
+int evaluate_candidate(pgo_problem* p, LmCandidate* c) {
+    const int nxt = p->cur ^ 1;
+    int np = 0, np2 = 0, rc;
+    launch_model_change(p->G, p->L, p->Sc, p->C.x, p->d_delta_s.p, part(p, 4), &np, p->st);
+    launch_reduce(part(p, 4), np, 0, p->d_scal.p + S_MODEL, p->st);
+    launch_plus(p->G, p->d_pose[p->cur].p, p->d_swv[p->cur].p, p->C.x, p->d_delta_s.p, p->d_pose[nxt].p, p->d_swv[nxt].p, part(p, 1), part(p, 2), &np2, p->st);
+    launch_reduce(part(p, 1), np2, 0, p->d_scal.p + S_STEP2, p->st);
+    launch_reduce(part(p, 2), np2, 0, p->d_scal.p + S_SW_STEP2, p->st);
+    if ((rc = run_k1(p, nxt, false)) != PGO_OK) return rc;
+    HIPCHK(p, hipMemsetAsync(p->d_scal.p + S_SW_XNORM2, 0, 2 * sizeof(double), p->st));   // SW_XNORM2, GMAX unused here
+    HIPCHK(p, hipMemsetAsync(p->d_scal.p + S_XNORM2, 0, sizeof(double), p->st));
+    double h[S_N] = {0};
+    if ((rc = read_scalars(p, h)) != PGO_OK) return rc;
+    *c = LmCandidate{0.5 * (h[S_COST] + h[S_PRIOR_COST]), -h[S_MODEL], std::sqrt(h[S_STEP2] + h[S_SW_STEP2])};
+    return PGO_OK;
+}
+
+// One LM iteration: the controller's decisions (pgo_lm.hpp) around the device work — system, dense step or staged PCG, candidate, relinearisation
 int lm_step(pgo_problem* p, int ignore_termination, int* done) {
     if (!p->in_solve) { p->err = "pgo_lm_step before pgo_solve_begin"; return PGO_ERR_STATE; }
     const pgo_options& o = p->opt;
+    LmState& lm = p->lm;
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
-    if (p->terminated && !ignore_termination) { if (done) *done = 1; return PGO_OK; }
-    if (p->sum.termination_type == PGO_FAILURE && p->terminated) { if (done) *done = 1; return PGO_OK; }
-    // FinalizeIterationAndCheckIfMinimizerCanContinue
-    if (!ignore_termination) {
-        if (p->iteration >= o.max_num_iterations) { terminate(p, PGO_NO_CONVERGENCE, "Maximum number of iterations reached."); if (done) *done = 1; return PGO_OK; }
-        if (p->gmax <= o.gradient_tolerance) { terminate(p, PGO_CONVERGENCE, "Gradient tolerance reached."); if (done) *done = 1; return PGO_OK; }
-        if (p->radius < o.min_trust_region_radius) { terminate(p, PGO_CONVERGENCE, "Minimum trust region radius reached."); if (done) *done = 1; return PGO_OK; }
-    }
+    if (lm.terminated && (!ignore_termination || p->sum.termination_type == PGO_FAILURE)) { *done = 1; return PGO_OK; }
+    const LmStop before = lm_pre_step(lm, o, ignore_termination != 0);
+    if (before.message) { terminate(p, before.type, before.message); *done = 1; return PGO_OK; }
     const double t0 = now_s();
-    ++p->iteration;
+    ++lm.iteration;
     pgo_iteration it{};
-    it.iteration = p->iteration; it.trust_region_radius = p->radius;
-    if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, o.min_lm_diagonal, o.max_lm_diagonal, p->st);
+    it.iteration = lm.iteration; it.trust_region_radius = lm.radius;
     bool ok = true;
-    if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
+    if ((rc = build_lm_system(p, &ok)) != PGO_OK) return rc;
     double t_built = now_s();
     const bool dense = dense_mode(p);
-    int why_invalid = ok ? PGO_STEP_ACCEPTED : PGO_STEP_INVALID_FACTORIZATION;      // pgo_iteration.reason of an invalid step
+    int why_invalid = ok ? PGO_STEP_ACCEPTED : PGO_STEP_INVALID_FACTORIZATION;      // pgo_iteration.reason of an invalid step; PGO_STEP_ACCEPTED: the linear solve is valid
     int precond_used = dense ? PGO_PRECOND_DIRECT : PGO_PRECOND_BLOCK_JACOBI;
     CgResult cg{0, false, 0.0, false};
     p->pcg.cg_extra = 0;
-    const int nxt = p->cur ^ 1;
-    double h[S_N] = {0};
-    // candidate point x (+) delta, its cost, the model cost change and the step norms -> h[]
-    auto evaluate_candidate = [&]() -> int {
-        int np = 0, np2 = 0, r2;
-        launch_model_change(p->G, p->L, p->Sc, p->C.x, p->d_delta_s.p, part(p, 4), &np, p->st);
-        launch_reduce(part(p, 4), np, 0, p->d_scal.p + S_MODEL, p->st);
-        launch_plus(p->G, p->d_pose[p->cur].p, p->d_swv[p->cur].p, p->C.x, p->d_delta_s.p, p->d_pose[nxt].p, p->d_swv[nxt].p, part(p, 1), part(p, 2), &np2, p->st);
-        launch_reduce(part(p, 1), np2, 0, p->d_scal.p + S_STEP2, p->st);
-        launch_reduce(part(p, 2), np2, 0, p->d_scal.p + S_SW_STEP2, p->st);
-        if ((r2 = run_k1(p, nxt, false)) != PGO_OK) return r2;
-        HIPCHK(p, hipMemsetAsync(p->d_scal.p + S_SW_XNORM2, 0, 2 * sizeof(double), p->st));   // SW_XNORM2, GMAX unused here
-        HIPCHK(p, hipMemsetAsync(p->d_scal.p + S_XNORM2, 0, sizeof(double), p->st));
-        return read_scalars(p, h);
-    };
-    bool evaluated = false;
+    LmCandidate cand{};
+    bool evaluated = false;      // the step was rejected at a pause: `cand` is the candidate of that pause
     if (ok && dense) {
         // The exact solver: no PCG, no tolerance, no pause, no warm start.  Scatter + factorisation count as the system, the two sweeps as the solve; a failed pivot is
         // Ceres' linear-solver failure — the same invalid step a failed 6x6 block gives.
         if ((rc = dense_step(p, &ok, &t_built)) != PGO_OK) return rc;
-        p->have_prev_step = false;
+        lm.have_prev_step = false;
         if (!ok) why_invalid = PGO_STEP_INVALID_FACTORIZATION;
     } else if (ok) {
-        // The PCG pauses at up to two intermediate tolerances (cg_early_tolerance > cg_mid_tolerance > cg_rel_tolerance).  A rejected step
-        // only changes the trust-region radius (Ceres StepRejected), so a step that is already clearly bad at a pause
-        // (relative_decrease below the stage's threshold, and neither convergence test would fire) is rejected without paying for the
-        // remaining decades; otherwise the same PCG resumes towards the next tolerance.
-        struct Stage { double tol, reject_rho; };
-        Stage stages[2]; int n_stages = 0;
-        // A pause costs one candidate evaluation (~0.1 ms: eight small launches and a host sync) and pays only when a step is rejected on a system whose PCG is expensive.  The
-        // reference's own sessions (hundreds to a few thousand keyframes, steps accepted almost throughout, PCGs of 20-100 iterations at ~14 us) only pay: measured 20.8 -> 17.1 ms
-        // on a 400-keyframe trigger, 63.2 -> 60.3 ms at 3 000.  So below CG_PAUSE_MIN_KEYFRAMES the pauses are armed by the first rejected step of the solve (a rejection is
-        // usually followed by more: the radius shrinks in several steps) — a rule that depends on the solve's own history only.
-        constexpr int64_t CG_PAUSE_MIN_KEYFRAMES = 20000;
-        // ... and (round 5) in proportion to what they can save.  A pause costs ~0.25 ms (candidate evaluation, host round trips, the PCG's restart out of its hipGraph), and a
-        // system whose step is ACCEPTED pays it for nothing: 13 of C3's 20 steps, 2.8 % of its headline.
-        //   * both pauses where a rejection is in the air (rejection_likely, pgo_handle.hpp: the rule build_system defers the multigrid by);
-        //   * the FIRST pause alone, as cheap insurance, where the system is expensive enough for one wasted solve to outweigh dozens of pauses: predicted block-Jacobi-equivalent
-        //     iterations x keyframes >= 5.6e7, i.e. a solve of >= ~20 ms (a pause pair is 0.5 ms; a block-Jacobi iteration costs ~36 us per 100 000 keyframes).  rho does NOT
-        //     predict every rejection: C5's step 8 follows rho = 0.97 and is rejected with rho = -2.0 — 1.87 s of PCG thrown away against 0.25 s with the pause
-        //     (profiles/r05_pause_rule.txt); a system without a prediction counts as mg_switch_iterations iterations;
-        //   * none elsewhere.  The PCG's own iterates do not depend on where it pauses.
-        const double predicted_its = p->pcg.cg_predicted > 0.0 ? p->pcg.cg_predicted : (double)(o.mg_switch_iterations > 0 ? o.mg_switch_iterations : 400);
-        const bool expensive = predicted_its * (double)p->N_global >= 5.6e7;
-        const bool armed = p->N_global >= CG_PAUSE_MIN_KEYFRAMES || p->sum.num_unsuccessful_steps > 0;
-        const bool pauses = armed && (rejection_likely(p) || p->opt.cg_pause_always != 0);
-        const bool early_only = armed && !pauses && expensive;
-        if ((pauses || early_only) && o.cg_early_tolerance > o.cg_rel_tolerance) stages[n_stages++] = Stage{o.cg_early_tolerance, o.cg_early_reject_rho};
-        if (pauses && o.cg_mid_tolerance > o.cg_rel_tolerance && (n_stages == 0 || o.cg_mid_tolerance < stages[0].tol)) stages[n_stages++] = Stage{o.cg_mid_tolerance, o.cg_mid_reject_rho};
-        const bool warm = o.cg_warm_start != 0 && p->have_prev_step && p->reuse_diagonal;
-        if ((rc = run_pcg(p, &cg, PcgPhase{n_stages ? stages[0].tol : o.cg_rel_tolerance, -1, warm})) != PGO_OK) return rc;
-        for (int sidx = 0; sidx < n_stages && !cg.breakdown && !evaluated; ++sidx) {
-            if ((rc = evaluate_candidate()) != PGO_OK) return rc;
-            const double mc = -h[S_MODEL];
-            const double cand = 0.5 * (h[S_COST] + h[S_PRIOR_COST]);
-            const double dc = p->x_cost - cand;
-            const double sn = std::sqrt(h[S_STEP2] + h[S_SW_STEP2]);
-            const bool clear_reject = mc > 0.0 && std::isfinite(mc) && std::isfinite(cand) && dc / mc < stages[sidx].reject_rho &&
-                                      sn > o.parameter_tolerance * (p->x_norm + o.parameter_tolerance) && std::fabs(dc) > o.function_tolerance * p->x_cost;
-            if (clear_reject) evaluated = true;
+        // the PCG, paused where lm_pause_plan says: at a pause the candidate is evaluated, and the same PCG resumes towards the next tolerance unless the step is clearly bad
+        const LmPausePlan plan = lm_pause_plan(lm, o, p->N_global, p->pcg.cg_predicted, p->sum.num_unsuccessful_steps);
+        auto tol_of = [&](int stage) { return stage < plan.n ? plan.stage[stage].tol : o.cg_rel_tolerance; };
+        const bool warm = o.cg_warm_start != 0 && lm.have_prev_step && lm.reuse_diagonal;
+        if ((rc = run_pcg(p, &cg, PcgPhase{tol_of(0), -1, warm})) != PGO_OK) return rc;
+        for (int sidx = 0; sidx < plan.n && !cg.breakdown && !evaluated; ++sidx) {
+            if ((rc = evaluate_candidate(p, &cand)) != PGO_OK) return rc;
+            if (lm_clear_reject(lm, o, cand, plan.stage[sidx].reject_rho)) evaluated = true;
             else {
                 const bool to_mg = p->pcg.mg_start_deferred && !p->mg.active;
                 p->pcg.mg_start_deferred = false;
-                if ((rc = run_pcg(p, &cg, PcgPhase{sidx + 1 < n_stages ? stages[sidx + 1].tol : o.cg_rel_tolerance, cg.iterations, false, to_mg})) != PGO_OK) return rc;
+                if ((rc = run_pcg(p, &cg, PcgPhase{tol_of(sidx + 1), cg.iterations, false, to_mg})) != PGO_OK) return rc;
             }
         }
         if ((rc = finish_system(p, &cg, evaluated, &precond_used)) != PGO_OK) return rc;
-        p->have_prev_step = !cg.breakdown;
+        lm.have_prev_step = !cg.breakdown;
         if (cg.breakdown) { ok = false; why_invalid = PGO_STEP_INVALID_BREAKDOWN; }
     }
     it.cg_iterations = cg.iterations + p->pcg.cg_extra; it.cg_residual = cg.rel_residual;
     const double t_solved = now_s();
     it.seconds_system = t_built - t0; it.seconds_pcg = t_solved - t_built;
     it.cg_iterations_multigrid = p->mg.active ? cg.iterations : 0; it.single_reduction = ok && single_reduction(p) ? 1 : 0;
-    if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d PCG: %d iterations%s after %d with block-Jacobi; system + preconditioner %.3f ms, PCG %.3f ms\n", p->iteration, cg.iterations, p->mg.active ? " with the multigrid" : "", p->pcg.cg_extra, (t_built - t0) * 1e3, (t_solved - t_built) * 1e3);
+    if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d PCG: %d iterations%s after %d with block-Jacobi; system + preconditioner %.3f ms, PCG %.3f ms\n", lm.iteration, cg.iterations, p->mg.active ? " with the multigrid" : "", p->pcg.cg_extra, (t_built - t0) * 1e3, (t_solved - t_built) * 1e3);
     p->sum.cg_iterations += cg.iterations + p->pcg.cg_extra;
     if (p->mg.active) p->sum.cg_iterations_multigrid += cg.iterations;     // iterations before an in-flight switch (cg_extra) ran with block-Jacobi
     if (ok) {
-        if (!evaluated && (rc = evaluate_candidate()) != PGO_OK) return rc;
+        if (!evaluated && (rc = evaluate_candidate(p, &cand)) != PGO_OK) return rc;
         it.seconds_evaluate = now_s() - t_solved;
-        if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d candidate evaluated in %.3f ms\n", p->iteration, it.seconds_evaluate * 1e3);
-        it.model_cost_change = -h[S_MODEL];
-        if (!(it.model_cost_change > 0.0) || !std::isfinite(it.model_cost_change)) { ok = false; why_invalid = PGO_STEP_INVALID_MODEL; }
+        if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d candidate evaluated in %.3f ms\n", lm.iteration, it.seconds_evaluate * 1e3);
     }
     it.preconditioner = precond_used;
-    if (!ok) {
-        // HandleInvalidStep
-        it.step_is_valid = 0; it.cost = p->x_cost; it.gradient_max_norm = p->gmax; it.reason = why_invalid;
-        ++p->invalid; ++p->sum.num_unsuccessful_steps;
-        if (p->invalid >= o.max_num_consecutive_invalid_steps && !ignore_termination) {
-            terminate(p, PGO_FAILURE, "Number of consecutive invalid steps more than max_num_consecutive_invalid_steps.");
-            it.seconds = now_s() - t0; log_iter(p, it);
-            if (done) *done = 1;
-            return PGO_OK;
-        }
-        p->radius *= 0.5; p->reuse_diagonal = true;   // LevenbergMarquardtStrategy::StepIsInvalid
-        it.seconds = now_s() - t0; log_iter(p, it);
-        if (done) *done = 0;
-        return PGO_OK;
-    }
-    p->invalid = 0;
-    it.step_is_valid = 1;
-    const double cand_cost = 0.5 * (h[S_COST] + h[S_PRIOR_COST]);
-    it.step_norm = std::sqrt(h[S_STEP2] + h[S_SW_STEP2]);
-    it.cost_change = p->x_cost - cand_cost;
-    it.relative_decrease = it.cost_change / it.model_cost_change;
-    bool stop = false;
-    if (!ignore_termination) {
-        if (it.step_norm <= o.parameter_tolerance * (p->x_norm + o.parameter_tolerance)) { terminate(p, PGO_CONVERGENCE, "Parameter tolerance reached."); stop = true; }
-        else if (std::fabs(it.cost_change) <= o.function_tolerance * p->x_cost) { terminate(p, PGO_CONVERGENCE, "Function tolerance reached."); stop = true; }
-    }
-    if (stop) {
-        it.reason = PGO_STEP_CONVERGED;
-        it.cost = p->x_cost; it.gradient_max_norm = p->gmax; it.seconds = now_s() - t0; log_iter(p, it);
-        if (done) *done = 1;
-        return PGO_OK;
-    }
-    if (std::isfinite(cand_cost) && it.relative_decrease > o.min_relative_decrease) {
-        // HandleSuccessfulStep
-        p->cur = nxt;
-        double c = 0;
+    const LmOutcome out = lm_step_outcome(lm, o, ignore_termination != 0, why_invalid, evaluated, cand, &it);
+    double new_cost = lm.x_cost;
+    if (out == LmOutcome::accepted) {      // HandleSuccessfulStep: the candidate becomes the state, linearised anew
+        p->cur ^= 1;
         const double t_lin = now_s();
-        if ((rc = linearize(p, &c)) != PGO_OK) return rc;
+        if ((rc = linearize(p, &new_cost)) != PGO_OK) return rc;
         it.seconds_linearize = now_s() - t_lin;
-        if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d linearised in %.3f ms\n", p->iteration, it.seconds_linearize * 1e3);
-        p->x_cost = c;
-        it.step_is_successful = 1;
-        p->radius = p->radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * it.relative_decrease - 1.0, 3));   // StepAccepted
-        p->radius = std::min(o.max_trust_region_radius, p->radius);
-        p->decrease_factor = 2.0; p->reuse_diagonal = false;
-        p->last_rho = it.relative_decrease;
-        it.reason = PGO_STEP_ACCEPTED;
-        ++p->sum.num_successful_steps;
-        if ((rc = regroup_start(p)) != PGO_OK) return rc;     // the switches have moved: does the hierarchy above level 1 still fit them?
-    } else {
-        p->radius = p->radius / p->decrease_factor; p->decrease_factor *= 2.0; p->reuse_diagonal = true;   // StepRejected
-        it.reason = evaluated ? PGO_STEP_REJECTED_AT_PAUSE : PGO_STEP_REJECTED_RHO;
-        ++p->sum.num_unsuccessful_steps;
+        if (o.verbosity > 1) std::fprintf(stderr, "[pgo] it %3d linearised in %.3f ms\n", lm.iteration, it.seconds_linearize * 1e3);
     }
-    it.cost = p->x_cost; it.gradient_max_norm = p->gmax; it.seconds = now_s() - t0;
+    lm_finish_step(lm, o, out, it.relative_decrease, new_cost);
+    if (out == LmOutcome::accepted) ++p->sum.num_successful_steps; else if (!it.step_is_valid || out == LmOutcome::rejected) ++p->sum.num_unsuccessful_steps;
+    if (out == LmOutcome::accepted && (rc = regroup_start(p)) != PGO_OK) return rc;     // the switches have moved: does the hierarchy above level 1 still fit them?
+    const LmStop after = lm_outcome_stop(out);
+    if (after.message) terminate(p, after.type, after.message);
+    it.cost = lm.x_cost; it.gradient_max_norm = lm.gmax; it.seconds = now_s() - t0;
     log_iter(p, it);
-    p->sum.final_cost = p->x_cost;
-    if (done) *done = 0;
+    p->sum.final_cost = lm.x_cost;
+    *done = after.message ? 1 : 0;
     return PGO_OK;
 }
 
@@ -315,8 +243,8 @@ int solve_end(pgo_problem* p, double* quat, double* t, double* sw, pgo_summary* 
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
     const double t_dev = now_s();
-    p->sum.num_iterations = p->iteration;
-    p->sum.final_cost = p->x_cost;
+    p->sum.num_iterations = p->lm.iteration;
+    p->sum.final_cost = p->lm.x_cost;
     p->sum.seconds_device = t_dev - p->t_device0;
     if (p->sum.termination_type != PGO_FAILURE && quat && t) {
         // single write-back at the very end (reference relies on this: src/PoseGraphSLAM.cpp:1894-1903)
@@ -691,7 +619,7 @@ int pgo_solve(pgo_problem* p, double* q, double* t, double* sw, int64_t N, int64
     if (!p) return PGO_ERR_INVALID_ARG;
     int rc = solve_begin(p, q, t, sw, N, S);
     if (rc != PGO_OK) return rc;
-    int done = p->terminated ? 1 : 0;
+    int done = p->lm.terminated ? 1 : 0;
     while (!done) { rc = lm_step(p, 0, &done); if (rc != PGO_OK) { after_failure(p); p->in_solve = false; return rc; } }
     rc = solve_end(p, q, t, sw, s);
     if (rc != PGO_OK) { after_failure(p); p->in_solve = false; }
@@ -704,7 +632,7 @@ int pgo_evaluate(pgo_problem* p, const double* q, const double* t, const double*
     int rc = solve_begin(p, q, t, sw, N, S);   // upload + K1 + K2 + norms at the given point
     if (rc != PGO_OK) return rc;
     p->in_solve = false;
-    if (cost) *cost = p->x_cost;
+    if (cost) *cost = p->lm.x_cost;
     const int64_t Er = p->G.rel.E, Es = p->G.sw.E, Eg = p->G.n_prior;
     if (residuals) {
         const int64_t total = 6 * Er + 7 * Es + 6 * Eg;
@@ -754,22 +682,13 @@ int pgo_pose_covariance(pgo_problem* p, const double* q, const double* t, const 
         if (n < 0 || n >= N) { p->err = "pgo_pose_covariance: keyframe index out of range"; return PGO_ERR_INVALID_ARG; }
         if (!referenced[(size_t)n]) { p->err = "pgo_pose_covariance: keyframe " + std::to_string(n) + " is referenced by no residual block: it has no covariance"; return PGO_ERR_INVALID_ARG; }
     }
-    struct Restore {
-        pgo_problem* p; pgo_summary sum; double radius, decrease_factor, last_rho; bool reuse_diagonal, terminated, have_prev_step; int iteration, invalid;
-        int mode, retests, backoff, skip, keep_streak; bool skip_all; double drop_radius;
-        ~Restore() {
-            p->in_solve = false;
-            p->sum = sum; p->radius = radius; p->decrease_factor = decrease_factor; p->last_rho = last_rho; p->reuse_diagonal = reuse_diagonal; p->terminated = terminated;
-            p->have_prev_step = have_prev_step; p->iteration = iteration; p->invalid = invalid;
-            if (dense_mode(p)) return;      // (solve_begin leaves the history alone there, and a graph build for the exact solver resets it on purpose)
-            CoarseState& c = p->coarse;
-            c.mode = mode; c.retests = retests; c.backoff = backoff; c.skip = skip; c.keep_streak = keep_streak; c.skip_all = skip_all; c.drop_radius = drop_radius;
-        }
-    } restore{p, p->sum, p->radius, p->decrease_factor, p->last_rho, p->reuse_diagonal, p->terminated, p->have_prev_step, p->iteration, p->invalid,
-              p->coarse.mode, p->coarse.retests, p->coarse.backoff, p->coarse.skip, p->coarse.keep_streak, p->coarse.skip_all, p->coarse.drop_radius};
+    struct Restore {      // (dense mode: solve_begin leaves the history alone, and a graph build for the exact solver resets it on purpose)
+        pgo_problem* p; pgo_summary sum; LmState lm; CoarseState::History hist;
+        ~Restore() { p->in_solve = false; p->sum = sum; p->lm = lm; if (!dense_mode(p)) p->coarse.hist = hist; }
+    } restore{p, p->sum, p->lm, p->coarse.hist};
     int rc = solve_begin(p, q, t, sw, N, S);   // upload + K1 + K2 at the given point (a changed graph is built here)
     if (rc != PGO_OK) return rc;
-    if (!std::isfinite(p->x_cost)) { p->err = "pgo_pose_covariance: the cost at this point is not finite"; return PGO_ERR_NUMERIC; }
+    if (!std::isfinite(p->lm.x_cost)) { p->err = "pgo_pose_covariance: the cost at this point is not finite"; return PGO_ERR_NUMERIC; }
     if (p->built_mf) { p->err = "pgo_pose_covariance: the graph was built matrix-free"; return PGO_ERR_STATE; }
     // pairs with a constant keyframe: zero blocks (constant keyframes are not parameters); the others go to the device
     std::vector<int32_t> ia, ib; std::vector<int64_t> where;
@@ -851,10 +770,8 @@ int pgo_apply_normal_operator(pgo_problem* p, const double* x, double* y) {
     if (!p->in_solve) { p->err = "pgo_apply_normal_operator needs an open solve (pgo_solve_begin)"; return PGO_ERR_STATE; }
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
-    const pgo_options& o = p->opt;
-    if (!p->reuse_diagonal) launch_lm_diag(p->G, p->L, p->Sc, o.min_lm_diagonal, o.max_lm_diagonal, p->st);
     bool ok = true;
-    if ((rc = build_system(p, &ok)) != PGO_OK) return rc;
+    if ((rc = build_lm_system(p, &ok)) != PGO_OK) return rc;
     // x and y are arrays over ALL keyframes (multi-GPU: this rank applies its part to its keyframes, shared rows are summed)
     HIPCHK(p, p->d_io.ensure((size_t)p->N * 12));
     double* xin = p->d_io.p; double* yout = p->d_io.p + (size_t)p->N * 6;
