@@ -442,6 +442,31 @@ int pgo_pose_covariance(pgo_problem* p, const double* quat_xyzw, const double* t
                         int64_t n_nodes, int64_t n_switch,
                         int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cov /* n_pairs x 36, row-major */);
 
+/* Covariance blocks of pose AND switch parameter blocks = `ceres::Covariance::Compute(pairs, &problem)` + `GetCovarianceBlockInTangentSpace` for any pair of the problem's
+ * parameter blocks, on a handle of ANY pgo_options.linear_solver.  A block id follows the tangent layout documented at the top: id < n_nodes is keyframe id (size 6),
+ * n_nodes <= id < n_nodes + n_switch is the caller's switch index id - n_nodes (size 1).  The linearisation point, "no damping, no scaling" and the corrected blocks of
+ * robust edges are pgo_pose_covariance's.
+ *   cov[k]   (HOST) has a fixed stride of 36 doubles: the d_a x d_b block (rows of block_a[k], columns of block_b[k]) of H^-1 over all free parameters, row-major in the
+ *            leading d_a d_b entries, the rest 0.  Pose-pose blocks are the bits of pgo_pose_covariance on a handle that call accepts.  With H = [H_pp C; C^T diag(h)] and S the
+ *            undamped Schur complement the factor is of: Sigma_pp = S^-1, Sigma_p,e = S^-1 v_e, Sigma_e,f = delta_ef / h_e + v_e^T S^-1 v_f with v_e = -c_e / h_e (DESIGN.md
+ *            section 3.4).  cov(b, a) is the exact transpose of cov(a, b) for every combination of sizes; a repeated pair and two calls give the same bits (no atomics,
+ *            every sum in a fixed order).
+ *   A constant keyframe is not a parameter: every pair with one gets a zero block.  A switch whose edge has one constant keyframe drops that side of c_e; with both constant
+ *   its variance is 1 / h_e and its cross blocks are zero.  PGO_ERR_INVALID_ARG, nothing written: an id outside [0, n_nodes + n_switch), a keyframe no residual block
+ *   references, a switch index no switchable edge uses.
+ * Handle state and limits as pgo_pose_covariance: not inside an open solve and not with a communicator attached (PGO_ERR_STATE), at most PGO_DENSE_MAX_KEYFRAMES
+ * keyframes (PGO_ERR_INVALID_ARG); summary, trust-region state and the two-level method's history are put back, a solve after the call runs as if it had not happened.
+ * All three linear_solver values are accepted.  A graph with block-CSR values (0, 2) is scattered from them as for pgo_pose_covariance.  A matrix-free graph (1, the default)
+ * is NOT rebuilt and stays matrix-free: S is assembled on the device from the normal blocks of the linearisation (pgo_get_normal_blocks' numbers: the diagonal blocks, J1^T J2
+ * per edge — formed for the call —, the switch couplings), each lower-triangle block written once as a sum in edge order.  Either way the handle gets the dense buffers at
+ * the first call and keeps them until its next graph build; memory as pgo_pose_covariance, with one more row of n doubles per distinct requested switch.
+ * PGO_ERR_NUMERIC: a pivot of the factorisation was not > 0 (or NaN), or a requested switch's h_e is not > 0 or not finite; cov is untouched and the handle stays usable.
+ * Launches: the right-hand sides, the matrix (build_rows + scatter, or J1^T J2 + one scatter), the factorisation (2 nt - 1), the substitutions from the first requested
+ * row's block column on, one Gram launch.  Times: profiles/param_covariance_times.txt. */
+int pgo_covariance(pgo_problem* p, const double* quat_xyzw, const double* t, const double* sw,
+                   int64_t n_nodes, int64_t n_switch,
+                   int64_t n_pairs, const int32_t* block_a, const int32_t* block_b, double* cov /* n_pairs x 36 */);
+
 /* Parity hook for the Jacobian blocks K1 produced at the last pgo_evaluate / pgo_solve_begin point.
  * For edge kind k (0 relpose, 1 switchable, 2 regulariser) copies, for edges [first, first+count):
  *   J1[count*36], J2[count*36]  row-major (rows = residual 0..5, cols = [dtheta(3), dt(3)] of c1 / c2;
@@ -674,6 +699,15 @@ int pgo_dense_spd_solve(pgo_problem* p, int32_t n, const double* a, const double
  * times; the matrix is padded like pgo_dense_spd_solve's.  cov: n_pairs x 36 (host), n_pairs >= 1; *avg_ms (may be NULL): the HIP-event average of one factorisation +
  * covariance.  PGO_ERR_NUMERIC when a pivot is not positive (cov is then left alone). */
 int pgo_dense_spd_covariance(pgo_problem* p, int32_t n, const double* a, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms);
+/* pgo_covariance's kernels on their own (test and measurement hook): blocks of the inverse of H = [a C; C^T diag(h)] from the factor of the caller's symmetric positive
+ * definite matrix `a` (n x n, padded like pgo_dense_spd_solve's) — `a` plays the Schur complement, so H's pose part is a + C diag(h)^-1 C^T — with the right-hand-side,
+ * factor, substitution and Gram launches of pgo_covariance, `launches` times.  The n_sw sparse switch columns of C, in block form: sw_node[2 s], sw_node[2 s + 1] the two
+ * distinct nodes column s has entries in (node i = rows 6 i .. 6 i + 5, i < n / 6; -1: no entries on that side), sw_c[12 s + 6 side + k] the six values on each side,
+ * sw_h[s] the diagonal entry.  Block ids ia, ib: a node, or n / 6 + s for switch s.  cov: n_pairs x 36 (host) in pgo_covariance's layout, n_pairs >= 1; *avg_ms (may be
+ * NULL): the HIP-event average of one right-hand sides + factorisation + covariance.  PGO_ERR_NUMERIC when a pivot is not positive or a requested switch's h is not a
+ * positive finite number (cov is then left alone). */
+int pgo_dense_spd_param_covariance(pgo_problem* p, int32_t n, const double* a, int32_t n_sw, const int32_t* sw_node, const double* sw_c, const double* sw_h,
+                                   int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms);
 
 /* Waits for everything the handle has in flight: its stream and — after a pgo_solve_begin that (re)built the device graph — the worker thread that prepares the multigrid
  * hierarchy's host half beside the build (otherwise installed where the solve first needs it).  bench.py calls it before its timed region starts. */

@@ -81,12 +81,12 @@ EXPORTS = [
     "pgo_add_relpose_edges", "pgo_add_relpose_edges_robust", "pgo_get_relpose_edge_loss", "pgo_add_switchable_edges", "pgo_set_node_regularizers", "pgo_set_nodes_constant",
     "pgo_num_relpose_edges", "pgo_num_switchable_edges", "pgo_num_regularizers",
     "pgo_set_vio_poses", "pgo_num_vio_poses", "pgo_add_odometry_edges_from_vio", "pgo_initial_guess_from_vio", "pgo_get_relpose_edge_records",
-    "pgo_solve", "pgo_solve_begin", "pgo_lm_step", "pgo_solve_end", "pgo_evaluate", "pgo_pose_covariance",
+    "pgo_solve", "pgo_solve_begin", "pgo_lm_step", "pgo_solve_end", "pgo_evaluate", "pgo_pose_covariance", "pgo_covariance",
     "pgo_get_jacobian_blocks", "pgo_get_normal_blocks", "pgo_apply_normal_operator", "pgo_manifold_plus",
     "pgo_comm_get_unique_id", "pgo_comm_init", "pgo_comm_destroy", "pgo_comm_init_custom", "pgo_comm_set_exchange", "pgo_local_group_create", "pgo_local_group_abort", "pgo_local_group_destroy", "pgo_comm_init_local",
     "pgo_get_sharding_stats", "pgo_mg_level_norms", "pgo_partition_edges",
     "pgo_apply_preconditioner", "pgo_get_linear_solution", "pgo_mg_level_parents", "pgo_get_matrix_free_tiles", "pgo_apply_normal_operator_batch",
-    "pgo_time_linearize_kernel", "pgo_time_kernel", "pgo_time_vio_odometry_kernel", "pgo_dense_spd_inverse", "pgo_dense_spd_solve", "pgo_dense_spd_covariance", "pgo_device_synchronize", "pgo_strerror", "pgo_last_error", "pgo_build_info",
+    "pgo_time_linearize_kernel", "pgo_time_kernel", "pgo_time_vio_odometry_kernel", "pgo_dense_spd_inverse", "pgo_dense_spd_solve", "pgo_dense_spd_covariance", "pgo_dense_spd_param_covariance", "pgo_device_synchronize", "pgo_strerror", "pgo_last_error", "pgo_build_info",
 ]
 
 _lib = None
@@ -327,6 +327,19 @@ class Problem:
         self._shape = (N, S)
         return cov
 
+    def covariance(self, quat, t, sw, pairs):
+        """= ceres::Covariance for any pair of parameter blocks, on a handle of any linear_solver: pairs = [(a, b), ...] of block ids — id < n_nodes keyframe id (6
+        tangent entries [dtheta, dt]), n_nodes + i the caller's switch index i (1 entry).  Returns a list of (d_a, d_b) arrays.  Raises PgoError on failure."""
+        q, tt, s = self._state(quat, t, sw)
+        N, S = q.size // 4, s.size
+        pr = _i(pairs).reshape(-1, 2)
+        a, b = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        cov = np.zeros((len(pr), 36))
+        self._check(self.lib.pgo_covariance(self.h, _pd(q), _pd(tt), _pd(s) if S else None, C.c_int64(N), C.c_int64(S), C.c_int64(len(pr)), _pi(a), _pi(b), _pd(cov)))
+        self._shape = (N, S)
+        dim = lambda i: 6 if i < N else 1
+        return [cov[k, :dim(x) * dim(y)].reshape(dim(x), dim(y)).copy() for k, (x, y) in enumerate(pr)]
+
     def jacobian_blocks(self, kind, first=0, count=None):
         n = [self.n_rel, self.n_sw, self.n_reg][kind]
         count = n - first if count is None else count
@@ -395,6 +408,23 @@ class Problem:
         cov = np.zeros((len(pr), 6, 6)); ms = C.c_double(0)
         self._check(self.lib.pgo_dense_spd_covariance(self.h, C.c_int32(n), _pd(a), C.c_int64(len(pr)), _pi(ia), _pi(ib), _pd(cov), C.c_int32(launches), C.byref(ms)))
         return cov, ms.value
+
+    def dense_spd_param_covariance(self, a, sw_node, sw_c, sw_h, pairs, launches=1):
+        """pgo_covariance's right-hand-side, factor, substitution and Gram launches on a symmetric positive definite matrix `a` (the Schur complement) plus sparse switch
+        columns in block form: sw_node (n_sw, 2) the two nodes of each column (-1: none), sw_c (n_sw, 12) its values, sw_h (n_sw,) the diagonal.  Block ids: node i, or
+        n // 6 + s.  Returns (list of (d_a, d_b) blocks, average milliseconds)."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        n = a.shape[0]
+        assert a.shape == (n, n)
+        nd, cc, hh = _i(sw_node).reshape(-1, 2), _d(sw_c).reshape(-1, 12), _d(sw_h).reshape(-1)
+        assert len(nd) == len(cc) == len(hh)
+        pr = _i(pairs).reshape(-1, 2)
+        ia, ib = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        cov = np.zeros((len(pr), 36)); ms = C.c_double(0)
+        self._check(self.lib.pgo_dense_spd_param_covariance(self.h, C.c_int32(n), _pd(a), C.c_int32(len(hh)), _pi(nd), _pd(cc), _pd(hh), C.c_int64(len(pr)), _pi(ia), _pi(ib), _pd(cov),
+                                                            C.c_int32(launches), C.byref(ms)))
+        dim = lambda i: 6 if i < n // 6 else 1
+        return [cov[k, :dim(x) * dim(y)].reshape(dim(x), dim(y)).copy() for k, (x, y) in enumerate(pr)], ms.value
 
     def synchronize(self):
         self._check(self.lib.pgo_device_synchronize(self.h))

@@ -8,6 +8,10 @@
 //
 // Covariance blocks (pgo_pose_covariance, after scatter and factor): 1 (the right-hand sides) + 2 (nt - k0) - 1 (solve, update from the first requested keyframe's block
 // column k0 on) + 1 (Gram) launches, under the same rules.
+//
+// Pose and switch blocks (pgo_covariance): the same chain with switch rows -c_e / h_e among the right-hand sides (dcp_rhs_kernel, ahead of the factor) and Gram products of
+// 6- and 1-row blocks (dcp_gram_kernel); on a matrix-free graph the matrix comes from the normal blocks in one scatter launch (dcm_scatter_kernel) instead of build_rows +
+// dc_scatter_kernel.
 #include <algorithm>
 #include <cstdlib>
 #include <limits>
@@ -321,6 +325,50 @@ __global__ __launch_bounds__(DC_THREADS) void dcv_gram_kernel(const double* __re
     dc_gram_block(DcTeam{}, W + (size_t)rows[2 * pair] * n, W + (size_t)rows[2 * pair + 1] * n, (size_t)n, n, c0[pair], part, cov + 36 * pair);
 }
 
+// ---- pgo_covariance: pose and switch blocks (the algebra and the plans: pgo_dense_math.hpp).  The substitution launches are dcv_solve_kernel / dcv_update_kernel.
+
+// the right-hand sides into the zeroed W, one thread per row: a unit row's one, a switch row's -c_side / h (dc_param_rhs_row); a requested switch whose h cannot divide
+// raises the failure flag
+__global__ __launch_bounds__(DC_THREADS) void dcp_rhs_kernel(double* __restrict__ W, int n, int m, const int32_t* __restrict__ col, const int32_t* __restrict__ sw_node,
+                                                             const double* __restrict__ sw_c, const double* __restrict__ sw_h, int32_t* __restrict__ fail) {
+    const int r = (int)blockIdx.x * DC_THREADS + (int)threadIdx.x;
+    if (r >= m) return;
+    if (dc_param_rhs_row(W + (size_t)r * n, col[r], sw_node, sw_c, sw_h)) *fail = 1;
+}
+
+// One workgroup per requested pair (dc_param_gram): pr[5 pair ..]: the first rows of W of the two blocks, the Gram's first column, the sizes (d_a | d_b << 8), and the
+// switch index when the pair is a switch with itself (1 / h is added), else -1.  Writes all 36 entries of the pair.
+__global__ __launch_bounds__(DC_THREADS) void dcp_gram_kernel(const double* __restrict__ W, int n, const int32_t* __restrict__ pr, const double* __restrict__ sw_h, double* __restrict__ cov) {
+    __shared__ double part[6 * DC_GRAM];
+    const size_t pair = blockIdx.x;
+    const int32_t* q = pr + 5 * pair;
+    const int32_t s = q[4];
+    dc_param_gram(DcTeam{}, W + (size_t)q[0] * n, q[3] & 255, W + (size_t)q[1] * n, q[3] >> 8, (size_t)n, n, q[2], s >= 0, s >= 0 ? 1.0 / sw_h[s] : 0.0, part, cov + 36 * pair);
+}
+
+// The undamped Schur complement of a matrix-free handle -> the zeroed dense matrix, from the normal blocks (DcMfPlan; dc_mf_diag_entry, dc_mf_offdiag_entry).  One thread per
+// entry: the 36 of every keyframe's diagonal block (identity where it is not free), the padding's ones, the 36 of every lower-triangle off-diagonal block.  Each
+// address has one writer.
+struct DcMfDev { const int32_t* seg_ptr; const int32_t* seg_hi; const int32_t* seg_lo; const int32_t* ent; const int32_t* side_ptr; const int32_t* side; int64_t segments; };
+__global__ __launch_bounds__(DC_THREADS) void dcm_scatter_kernel(int64_t N, const uint8_t* __restrict__ node_free, DcMfDev M, const double* __restrict__ Hd, const double* __restrict__ hoff_rel,
+                                                                 const double* __restrict__ hoff_sw, const double* __restrict__ sw_c, const double* __restrict__ sw_h, double* __restrict__ A, int n) {
+    const int64_t gid = (int64_t)blockIdx.x * DC_THREADS + threadIdx.x;
+    const int64_t n36 = N * 36, pad = (int64_t)n - N * 6;
+    if (gid < n36) {
+        const int64_t node = gid / 36;
+        const int e = (int)(gid - node * 36), a = e / 6, c = e - a * 6;
+        const size_t row = (size_t)node * 6 + a;
+        if (node_free[node]) A[row * n + (size_t)node * 6 + c] = dc_mf_diag_entry(Hd + (size_t)node * 36, M.side, M.side_ptr[node], M.side_ptr[node + 1], a, c, sw_c, sw_h);
+        else if (a == c) A[row * n + row] = 1.0;
+        return;
+    }
+    if (gid < n36 + pad) { const size_t i = (size_t)(N * 6 + (gid - n36)); A[i * n + i] = 1.0; return; }
+    const int64_t t = gid - n36 - pad, s = t / 36;
+    if (s >= M.segments) return;
+    const int e = (int)(t - s * 36), a = e / 6, c = e - a * 6;
+    A[((size_t)M.seg_hi[s] * 6 + a) * n + (size_t)M.seg_lo[s] * 6 + c] = dc_mf_offdiag_entry(M.ent, M.seg_ptr[s], M.seg_ptr[s + 1], a, c, hoff_rel, hoff_sw, sw_c, sw_h);
+}
+
 struct DcLaunch {
     double* A; int n, ldu; double* LT; int32_t* fail; int force_fail; double* w; double* yv; double* x; int n_out; hipStream_t st;
     int nt() const { return n / DC_NB; }
@@ -376,6 +424,34 @@ int launch_dense_covariance(pgo_problem* p, const double* A, int n, const DcCovP
     dc_cov_steps(n, Q.mt, Q.start_tile.data(), true, D);
     hipLaunchKernelGGL(dcv_gram_kernel, dim3((unsigned)np), dim3(DC_THREADS), 0, p->st, (const double*)work, n, idx + m, idx + m + 2 * np, dense_cov_blocks(work, n, m));
     return PGO_OK;
+}
+
+// ---- pose and switch blocks (pgo_covariance, pgo_dense_spd_param_covariance).  work: dense_cov_doubles(n, Q.m, pairs), laid out as above; idx: dense_param_ints(Q.m, pairs,
+// switches) — the rows' columns, five numbers per pair (dcp_gram_kernel), the switches' two nodes.  sw_c [12 per switch], sw_h: device arrays.
+size_t dense_param_ints(int m, int64_t n_pairs, int64_t n_sw) { return (size_t)m + (size_t)5 * n_pairs + (size_t)2 * n_sw; }
+int dense_param_upload(pgo_problem* p, const DcParamPlan& Q, int64_t n_sw, const int32_t* sw_node, std::vector<int32_t>& staging, int32_t* idx) {
+    const size_t np = Q.row_a.size();
+    staging.assign(Q.col.begin(), Q.col.end());
+    for (size_t k = 0; k < np; ++k) for (int32_t v : {Q.row_a[k], Q.row_b[k], (int32_t)Q.gram_c0((int64_t)k), Q.dim_a[k] | (Q.dim_b[k] << 8), Q.self_switch[k]}) staging.push_back(v);
+    staging.insert(staging.end(), sw_node, sw_node + 2 * n_sw);
+    HIPCHK(p, hipMemcpyAsync(idx, staging.data(), staging.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->st));      // (staging outlives the caller's next synchronize)
+    return PGO_OK;
+}
+// the right-hand sides: needs no factor, so it runs ahead of the factorisation and shares its failure flag and its one synchronisation
+int launch_dense_param_rhs(pgo_problem* p, int n, const DcParamPlan& Q, double* work, const int32_t* idx, const double* sw_c, const double* sw_h, int32_t* fail) {
+    const int m = Q.m;
+    const int64_t np = (int64_t)Q.row_a.size();
+    HIPCHK(p, hipMemsetAsync(work, 0, (size_t)m * n * sizeof(double), p->st));
+    hipLaunchKernelGGL(dcp_rhs_kernel, dim3((unsigned)((m + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, p->st, work, n, m, idx, idx + m + 5 * np, sw_c, sw_h, fail);
+    return PGO_OK;
+}
+// the substitutions and the Gram products, on the factor in A
+void launch_dense_param_covariance(pgo_problem* p, const double* A, int n, const DcParamPlan& Q, double* work, const int32_t* idx, const double* sw_h) {
+    const int m = Q.m;
+    const int64_t np = (int64_t)Q.row_a.size();
+    DcCovLaunch D{A, n, work, m + 16, work + (size_t)m * n, p->st};
+    dc_cov_steps(n, Q.mt, Q.start_tile.data(), true, D);
+    hipLaunchKernelGGL(dcp_gram_kernel, dim3((unsigned)np), dim3(DC_THREADS), 0, p->st, (const double*)work, n, idx + m, sw_h, dense_cov_blocks(work, n, m));
 }
 
 // ---- the handle's side
@@ -444,6 +520,55 @@ int dense_pose_covariance(pgo_problem* p, int64_t n_pairs, const int32_t* ia, co
     *ok = h == 0;
     if (!*ok) return PGO_OK;
     if ((rc = launch_dense_covariance(p, d.A.p, n, Q, d.cov.p, d.cov_idx.p)) != PGO_OK) return rc;
+    HIPCHK(p, hipMemcpyAsync(out, dense_cov_blocks(d.cov.p, n, Q.m), (size_t)36 * n_pairs * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    HIPCHK(p, hipStreamSynchronize(p->st));
+    return PGO_OK;
+}
+
+// The blocks of pgo_covariance on the linearisation solve_begin has left.  Block ids: a free keyframe, or N + the internal index of a switchable edge; sw_node: per
+// switchable edge its two keyframes, -1 where one is constant.  The matrix is dense_pose_covariance's on a graph with block-CSR values; on a matrix-free graph it is
+// assembled from the normal blocks (J1^T J2 per edge formed here, as pgo_get_normal_blocks does), the graph stays what it is.  *ok = false: a pivot failed or a
+// requested switch's h cannot divide, out untouched.
+int dense_param_covariance(pgo_problem* p, const std::vector<int32_t>& sw_node, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* out, bool* ok) {
+    DenseState& d = p->dense;
+    int rc;
+    if (!d.built && (rc = dense_allocate(p)) != PGO_OK) return rc;      // (until the handle's next graph build)
+    const int n = d.n;
+    const int64_t Es = p->G.sw.E;
+    const DcParamPlan Q(n, (int32_t)p->N, sw_node.data(), n_pairs, ia, ib);
+    HIPCHK(p, d.cov.ensure(dense_cov_doubles(n, Q.m, n_pairs))); HIPCHK(p, d.cov_idx.ensure(dense_param_ints(Q.m, n_pairs, Es)));
+    std::vector<int32_t> staging, mf_staging;
+    DBuf<int32_t> d_mf;
+    if ((rc = dense_param_upload(p, Q, Es, sw_node.data(), staging, d.cov_idx.p)) != PGO_OK) return rc;
+    int32_t* fail = p->d_flags.p + 4;
+    HIPCHK(p, hipMemsetAsync(fail, 0, sizeof(int32_t), p->st));
+    if ((rc = launch_dense_param_rhs(p, n, Q, d.cov.p, d.cov_idx.p, p->L.c, p->L.hss, fail)) != PGO_OK) return rc;
+    HIPCHK(p, hipMemsetAsync(d.A.p, 0, (size_t)n * n * sizeof(double), p->st));
+    if (p->built_mf) {
+        HIPCHK(p, p->d_Hoff.ensure((size_t)(p->G.rel.Epad + p->G.sw.Epad) * 36));
+        p->L.Hoff = p->d_Hoff.p;
+        launch_k2_offdiag(p->G, p->L, p->st);
+        const DcMfPlan M(p->N, p->h_node_free.data(), p->rel.size(), p->rel.c1.data(), p->rel.c2.data(), p->swe.size(), p->swe.c1.data(), p->swe.c2.data());
+        size_t at[6], total = 0;
+        const std::vector<int32_t>* parts[6] = {&M.seg_ptr, &M.seg_hi, &M.seg_lo, &M.ent, &M.side_ptr, &M.side};
+        for (int k = 0; k < 6; ++k) { at[k] = total; mf_staging.insert(mf_staging.end(), parts[k]->begin(), parts[k]->end()); total = mf_staging.size(); }
+        HIPCHK(p, d_mf.upload(mf_staging, p->st));
+        const DcMfDev Md{d_mf.p + at[0], d_mf.p + at[1], d_mf.p + at[2], d_mf.p + at[3], d_mf.p + at[4], d_mf.p + at[5], M.segments()};
+        const int64_t threads = p->N * 36 + ((int64_t)n - p->N * 6) + M.segments() * 36;
+        hipLaunchKernelGGL(dcm_scatter_kernel, dim3((unsigned)((threads + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, p->st, (int64_t)p->N, p->G.node_free, Md, (const double*)p->L.Hd,
+                           (const double*)p->L.Hoff, (const double*)(p->L.Hoff + (size_t)p->G.rel.Epad * 36), (const double*)p->L.c, (const double*)p->L.hss, d.A.p, n);
+    } else {
+        launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);      // (finite numbers for build_rows' division, whatever the buffers held)
+        launch_build_rows(p->G, p->L, p->Sc, p->C, std::numeric_limits<double>::infinity(), 1, nullptr, p->st);
+        launch_dense_scatter(p->G, p->C, d.A.p, n, d.vec.p, p->st);
+    }
+    launch_dense_factor(d.A.p, n, d.scratch.p, fail, debug_break_dense(), p->st);
+    int32_t h = 0;
+    HIPCHK(p, hipMemcpyAsync(&h, fail, sizeof(int32_t), hipMemcpyDeviceToHost, p->st));
+    HIPCHK(p, hipStreamSynchronize(p->st));      // (the staging vectors and the plan's device copy are done with their uploads here; d_mf is read by nothing launched later)
+    *ok = h == 0;
+    if (!*ok) return PGO_OK;
+    launch_dense_param_covariance(p, d.A.p, n, Q, d.cov.p, d.cov_idx.p, p->L.hss);
     HIPCHK(p, hipMemcpyAsync(out, dense_cov_blocks(d.cov.p, n, Q.m), (size_t)36 * n_pairs * sizeof(double), hipMemcpyDeviceToHost, p->st));
     HIPCHK(p, hipStreamSynchronize(p->st));
     return PGO_OK;

@@ -404,6 +404,16 @@ size_t dense_cov_ints(int m, int64_t n_pairs);
 int dense_cov_upload(pgo_problem* p, const DcCovPlan& Q, std::vector<int32_t>& staging, int32_t* idx);
 int launch_dense_covariance(pgo_problem* p, const double* A, int n, const DcCovPlan& Q, double* work, const int32_t* idx);
 double* dense_cov_blocks(double* work, int n, int m);
+// pgo_covariance: pose and switch blocks on a block-CSR or a matrix-free graph (block ids: a free keyframe, or N + the internal index of a switchable edge; sw_node: per
+// switchable edge its two keyframes, -1 for a constant one) ...
+int dense_param_covariance(pgo_problem* p, const std::vector<int32_t>& sw_node, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* out, bool* ok);
+// ... and its launches (pgo_dense_spd_param_covariance runs exactly these): index upload, the right-hand sides (before the factor: they share its failure flag), the
+// substitutions and Gram products on the factor.  Buffers: dense_cov_doubles / dense_param_ints; the blocks land at dense_cov_blocks.
+struct DcParamPlan;
+size_t dense_param_ints(int m, int64_t n_pairs, int64_t n_sw);
+int dense_param_upload(pgo_problem* p, const DcParamPlan& Q, int64_t n_sw, const int32_t* sw_node, std::vector<int32_t>& staging, int32_t* idx);
+int launch_dense_param_rhs(pgo_problem* p, int n, const DcParamPlan& Q, double* work, const int32_t* idx, const double* sw_c, const double* sw_h, int32_t* fail);
+void launch_dense_param_covariance(pgo_problem* p, const double* A, int n, const DcParamPlan& Q, double* work, const int32_t* idx, const double* sw_h);
 // the launches themselves (n a multiple of 64; pgo_dense_spd_solve runs exactly these)
 void launch_dense_scatter(const GraphDev& G, const CgDev& C, double* A, int n, double* w, hipStream_t st);
 void launch_dense_factor(double* A, int n, double* scratch, int32_t* fail, bool force_fail, hipStream_t st);
