@@ -347,8 +347,8 @@ int pgo_add_relpose_edges(pgo_problem* p, int64_t n, const int32_t* c1, const in
  * (r already carries the edge weight) and b = a^2:
  *   PGO_LOSS_HUBER   rho = s for s <= b, 2 a sqrt(s) - b beyond        PGO_LOSS_CAUCHY   rho = b log(1 + s / b)
  * The block costs 0.5 rho(s); residual and Jacobian blocks are scaled by sqrt(rho'(s)) (Ceres' Corrector; rho'' <= 0 for both losses, so
- * there is no second-order term).  Out of scope: a loss on switchable edges (the reference combines the two only in a routine this library
- * does not replace, :803) and losses with rho'' > 0 (ceres::TolerantLoss). */
+ * there is no second-order term).  Switchable edges take the same losses (pgo_add_switchable_edges_robust).  Out of scope: losses with
+ * rho'' > 0 (ceres::TolerantLoss) and a loss on regularisers. */
 enum { PGO_LOSS_TRIVIAL = 0, PGO_LOSS_HUBER = 1, PGO_LOSS_CAUCHY = 2 };
 /* pgo_add_relpose_edges with `AddResidualBlock(SixDOFError::Create(..), new ceres::HuberLoss(a) / CauchyLoss(a), ...)`
  * — reference src/PoseGraphSLAM.cpp:793-796 with :401-402.  PGO_LOSS_TRIVIAL is exactly pgo_add_relpose_edges (loss_a ignored); an unknown
@@ -370,6 +370,20 @@ int pgo_get_relpose_edge_loss(const pgo_problem* p, int64_t first, int64_t n, in
  * it may be NULL.  Each switch index must be used by at most one edge (reference: switch e <-> loop edge e). */
 int pgo_add_switchable_edges(pgo_problem* p, int64_t n, const int32_t* c1, const int32_t* c2,
                              const double* c1_T_c2, const double* weight, const int32_t* switch_idx);
+
+/* pgo_add_switchable_edges with `AddResidualBlock(SixDOFErrorWithSwitchingConstraints::Create(..), robust_norm, ...)` — reference
+ * src/PoseGraphSLAM.cpp:800-807, the active branch of the batch routine's loop closures, with robust_norm = HuberLoss(0.1) (:401-402).
+ * s = |r|^2 is taken over all SEVEN rows of the block, r = [ s r6 ; s (1 - s) ]; the Corrector scales r and all five Jacobian blocks, the
+ * switch column dr/ds included, by sqrt(rho'(s)).  The contract is that of pgo_add_relpose_edges_robust: PGO_LOSS_TRIVIAL is exactly
+ * pgo_add_switchable_edges (loss_a ignored); an unknown `loss`, or a `loss_a` that is not finite or <= 0 for a non-trivial loss, returns
+ * PGO_ERR_INVALID_ARG and adds nothing.  Robust and plain switchable edges share one add order and one index space.  The parity hooks follow
+ * Problem::Evaluate with apply_loss_function = true: pgo_evaluate returns the corrected 7-row residuals, the cost with 0.5 rho(s) for these
+ * blocks and the gradient of the robust objective, switch entries included; pgo_get_jacobian_blocks(kind 1) the corrected J1, J2 and dr_ds;
+ * pgo_get_normal_blocks the corrected offdiag, sw_c, sw_hss and sw_gs. */
+int pgo_add_switchable_edges_robust(pgo_problem* p, int64_t n, const int32_t* c1, const int32_t* c2, const double* c1_T_c2,
+                                    const double* weight, const int32_t* switch_idx, int32_t loss, double loss_a);
+/* The loss of switchable edges [first, first+n): loss[k] = PGO_LOSS_*, loss_a[k] = its parameter (0 for a trivial edge).  Either output may be NULL. */
+int pgo_get_switchable_edge_loss(const pgo_problem* p, int64_t first, int64_t n, int32_t* loss, double* loss_a);
 
 /* REPLACES the current regulariser set: `RemoveResidualBlock` of all previous ones followed by
  * n x `AddResidualBlock(NodePoseRegularization::Create(target, weight), NULL, q[node], t[node])`

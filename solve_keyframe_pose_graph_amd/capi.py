@@ -78,7 +78,7 @@ class ShardingStats(C.Structure):
 ABI_VERSION = 7      # PGO_ABI_VERSION of the include/pgo.h this view mirrors
 EXPORTS = [
     "pgo_abi_version", "pgo_abi_sizeof", "pgo_options_init", "pgo_create", "pgo_destroy", "pgo_set_options", "pgo_reserve",
-    "pgo_add_relpose_edges", "pgo_add_relpose_edges_robust", "pgo_get_relpose_edge_loss", "pgo_add_switchable_edges", "pgo_set_node_regularizers", "pgo_set_nodes_constant",
+    "pgo_add_relpose_edges", "pgo_add_relpose_edges_robust", "pgo_get_relpose_edge_loss", "pgo_add_switchable_edges", "pgo_add_switchable_edges_robust", "pgo_get_switchable_edge_loss", "pgo_set_node_regularizers", "pgo_set_nodes_constant",
     "pgo_num_relpose_edges", "pgo_num_switchable_edges", "pgo_num_regularizers",
     "pgo_set_vio_poses", "pgo_num_vio_poses", "pgo_add_odometry_edges_from_vio", "pgo_initial_guess_from_vio", "pgo_get_relpose_edge_records",
     "pgo_solve", "pgo_solve_begin", "pgo_lm_step", "pgo_solve_end", "pgo_evaluate", "pgo_pose_covariance", "pgo_covariance",
@@ -224,13 +224,32 @@ class Problem:
         self._check(self.lib.pgo_num_relpose_edges(self.h, C.byref(n)))
         return n.value
 
-    def add_switchable_edges(self, c1, c2, c1_T_c2, weight, switch_idx):
+    def add_switchable_edges(self, c1, c2, c1_T_c2, weight, switch_idx, loss=None):
+        """loss: as in add_relpose_edges, here on the 7-row switchable block (`AddResidualBlock(SixDOFErrorWithSwitchingConstraints::Create(..), robust_norm, ..)`,
+        reference src/PoseGraphSLAM.cpp:800-807)"""
         c1, c2, T, s = _i(c1), _i(c2), _d(c1_T_c2), _i(switch_idx)
         n = len(c1)
         w = _d(weight) if weight is not None else None
         assert len(c2) == n and T.size == 16 * n and len(s) == n
-        self._check(self.lib.pgo_add_switchable_edges(self.h, C.c_int64(n), _pi(c1), _pi(c2), _pd(T), _pd(w), _pi(s)))
+        if loss is None:
+            self._check(self.lib.pgo_add_switchable_edges(self.h, C.c_int64(n), _pi(c1), _pi(c2), _pd(T), _pd(w), _pi(s)))
+        else:
+            kind, a = loss
+            kind = LOSS_NAMES[kind] if isinstance(kind, str) else int(kind)
+            self._check(self.lib.pgo_add_switchable_edges_robust(self.h, C.c_int64(n), _pi(c1), _pi(c2), _pd(T), _pd(w), _pi(s), C.c_int32(kind), C.c_double(a)))
         self.n_sw += n
+
+    def switchable_edge_loss(self, first=0, n=None):
+        """(PGO_LOSS_* kind, parameter a) of switchable edges [first, first + n) in add order; a = 0 for plain edges"""
+        n = self.num_switchable_edges() - first if n is None else n
+        kind = np.zeros(n, np.int32); a = np.zeros(n)
+        self._check(self.lib.pgo_get_switchable_edge_loss(self.h, C.c_int64(first), C.c_int64(n), _pi(kind), _pd(a)))
+        return kind, a
+
+    def num_switchable_edges(self):
+        n = C.c_int64()
+        self._check(self.lib.pgo_num_switchable_edges(self.h, C.byref(n)))
+        return n.value
 
     def set_node_regularizers(self, node, target, weight):
         node, T, w = _i(node), _d(target), _d(weight)
@@ -570,9 +589,7 @@ def problem_from_graph(g, switchable=True, options=None, edge_slice=None, loop_l
     """Builds a Problem from a graphgen.PoseGraph the way the reference's trigger adds residual blocks
     (odometry -> SixDOFError, loop closures -> switchable / plain, regularisers).  `edge_slice(kind, n)`
     optionally returns the index subset this rank owns (edge sharding).  loop_loss = ("huber", a) / ("cauchy", a):
-    the robust loss of the loop closures when they are plain relative-pose edges (switchable=False)."""
-    if loop_loss is not None and switchable:
-        raise ValueError("a robust loss on switchable edges is not supported: pass switchable=False")
+    the robust loss of the loop closures, switchable (the reference's batch routine, src/PoseGraphSLAM.cpp:800-807) or plain."""
     P = Problem(options, **opt_kw)
     sel = (lambda kind, n: np.arange(n)) if edge_slice is None else edge_slice
     io = sel("odom", g.n_odom)
@@ -581,7 +598,7 @@ def problem_from_graph(g, switchable=True, options=None, edge_slice=None, loop_l
     il = sel("loop", g.n_loops)
     if len(il):
         if switchable:
-            P.add_switchable_edges(g.loop_c1[il], g.loop_c2[il], g.loop_T[il], g.loop_w[il], il.astype(np.int32))
+            P.add_switchable_edges(g.loop_c1[il], g.loop_c2[il], g.loop_T[il], g.loop_w[il], il.astype(np.int32), loss=loop_loss)
         else:
             P.add_relpose_edges(g.loop_c1[il], g.loop_c2[il], g.loop_T[il], g.loop_w[il], loss=loop_loss)
     ir = sel("reg", len(g.reg_node))

@@ -180,7 +180,7 @@ bool PoseGraphSLAM::reinit_ceres_problem_onnewloopedge_optimize6DOF_once() {
         pending.push_back({b, a, weight, e});
     }
     if (!c1.empty()) {
-        last_rc_ = pgo_add_switchable_edges(problem_, (int64_t)c1.size(), c1.data(), c2.data(), T.data(), w.data(), sw.data());
+        last_rc_ = pgo_add_switchable_edges_robust(problem_, (int64_t)c1.size(), c1.data(), c2.data(), T.data(), w.data(), sw.data(), loop_loss_kind_, loop_loss_a_);      // (trivial: pgo_add_switchable_edges)
         if (last_rc_ != PGO_OK) return failed();
     }
     added_edges_.insert(added_edges_.end(), pending.begin(), pending.end());
@@ -417,6 +417,16 @@ void VectorGraphSource::getWorld2SetIDMap(std::map<int, int>& out) const {
     for (int w = 0; w < n; ++w) out[w] = set_of_[w];
 }
 
+bool PoseGraphSLAM::set_loop_edge_loss(int kind, double a) {
+    if (kind != PGO_LOSS_TRIVIAL && kind != PGO_LOSS_HUBER && kind != PGO_LOSS_CAUCHY) return false;
+    if (kind != PGO_LOSS_TRIVIAL && !(std::isfinite(a) && a > 0.0)) return false;
+    loop_loss_kind_ = kind; loop_loss_a_ = kind == PGO_LOSS_TRIVIAL ? 0.0 : a;
+    return true;
+}
+bool PoseGraphSLAM::get_loop_edge_loss(int64_t first, int64_t n, int32_t* kind, double* a) const {
+    return pgo_get_switchable_edge_loss(problem_, first, n, kind, a) == PGO_OK;
+}
+
 }  // namespace pgo_host
 
 // ================================================================================================
@@ -511,6 +521,9 @@ void pgo_host_add_loop_edge(pgo_host_session* s, int a, int b, const double* bTa
 void pgo_host_set_kidnapped(pgo_host_session* s, int k) { s->src.set_kidnapped(k != 0); }
 void pgo_host_set_device_graph_construction(pgo_host_session* s, int on) { s->slam->set_device_graph_construction(on != 0); }
 int pgo_host_load_state(pgo_host_session* s, int as_constants) { return (s->slam && s->slam->load_state(as_constants != 0)) ? 1 : 0; }
+int pgo_host_set_loop_edge_loss(pgo_host_session* s, int kind, double a) { return (s->slam && s->slam->set_loop_edge_loss(kind, a)) ? 1 : 0; }
+int pgo_host_n_added_edges_switchable(pgo_host_session* s) { int n = 0; for (const AddedEdge& e : s->slam->added_edges()) n += e.switch_idx >= 0 ? 1 : 0; return n; }
+int pgo_host_get_loop_edge_loss(pgo_host_session* s, int64_t first, int64_t n, int32_t* kind, double* a) { return (s->slam && s->slam->get_loop_edge_loss(first, n, kind, a)) ? 1 : 0; }
 int pgo_host_trigger(pgo_host_session* s) { return s->slam->reinit_ceres_problem_onnewloopedge_optimize6DOF_once() ? 1 : 0; }
 int pgo_host_n_nodes(pgo_host_session* s) { return s->slam->nNodes(); }
 int pgo_host_solved_until(pgo_host_session* s) { return s->slam->solvedUntil(); }

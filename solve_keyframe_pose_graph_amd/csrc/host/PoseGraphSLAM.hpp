@@ -73,6 +73,12 @@ public:
     // Steps -3-/-4- (odometry measurements, yaw weights, VIO-derived initial guesses) run as device kernels from the resident raw VIO
     // poses by default; `false` computes them on the host thread like the reference — kept for the parity tests.
     void set_device_graph_construction(bool on) { device_graph_construction_ = on; }
+    // The loss of the loop edges the trigger adds FROM NOW ON — the reference's `robust_norm` member (PoseGraphSLAM.h:200), which its batch routine hands to the switchable loop
+    // blocks (src/PoseGraphSLAM.cpp:800-807).  kind = PGO_LOSS_*; the default is PGO_LOSS_TRIVIAL, the trigger's own `NULL`.  False (and no change) for an unknown kind or
+    // a parameter that is not finite and positive.
+    bool set_loop_edge_loss(int kind, double a);
+    // the loss of the switchable blocks [first, first + n) the library holds (pgo_get_switchable_edge_loss)
+    bool get_loop_edge_loss(int64_t first, int64_t n, int32_t* kind, double* a) const;
 
     // PoseGraphSLAM::load_state (reference src/PoseGraphSLAM.cpp:30-165): the keyframes the data source holds beyond the current
     // optimisation variables are a previously solved map (e.g. from solved_posegraph.json).  Each becomes an optimisation variable at
@@ -121,6 +127,7 @@ private:
     int odom_until_ = 0;                 // odometry residues exist for every keyframe below this index
     int status_ = -1, last_rc_ = 0;
     bool device_graph_construction_ = true;
+    int loop_loss_kind_ = PGO_LOSS_TRIVIAL; double loop_loss_a_ = 0.0;
     std::map<int, std::tuple<int, int>> changes_to_setid_on_set_union;
     std::vector<AddedEdge> added_edges_;
     std::vector<AddedRegularizer> regs_;

@@ -509,7 +509,7 @@ int dense_pose_covariance(pgo_problem* p, int64_t n_pairs, const int32_t* ia, co
     if ((rc = dense_cov_upload(p, Q, staging, d.cov_idx.p)) != PGO_OK) return rc;
     int32_t* fail = p->d_flags.p + 4;
     launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);      // (finite numbers for the division below, whatever the buffers held)
-    launch_build_rows(p->G, p->L, p->Sc, p->C, std::numeric_limits<double>::infinity(), 1, nullptr, p->st);
+    launch_build_rows(p->G, p->L, p->Sc, p->C, std::numeric_limits<double>::infinity(), 1, nullptr, p->ScMf.a_inv, p->st);
     HIPCHK(p, hipMemsetAsync(d.A.p, 0, (size_t)n * n * sizeof(double), p->st));
     HIPCHK(p, hipMemsetAsync(fail, 0, sizeof(int32_t), p->st));
     launch_dense_scatter(p->G, p->C, d.A.p, n, d.vec.p, p->st);
@@ -559,7 +559,7 @@ int dense_param_covariance(pgo_problem* p, const std::vector<int32_t>& sw_node, 
                            (const double*)p->L.Hoff, (const double*)(p->L.Hoff + (size_t)p->G.rel.Epad * 36), (const double*)p->L.c, (const double*)p->L.hss, d.A.p, n);
     } else {
         launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);      // (finite numbers for build_rows' division, whatever the buffers held)
-        launch_build_rows(p->G, p->L, p->Sc, p->C, std::numeric_limits<double>::infinity(), 1, nullptr, p->st);
+        launch_build_rows(p->G, p->L, p->Sc, p->C, std::numeric_limits<double>::infinity(), 1, nullptr, p->ScMf.a_inv, p->st);
         launch_dense_scatter(p->G, p->C, d.A.p, n, d.vec.p, p->st);
     }
     launch_dense_factor(d.A.p, n, d.scratch.p, fail, debug_break_dense(), p->st);

@@ -278,6 +278,37 @@ PGO_HD void switch_residual(const Pose& c1, const Pose& c2, const Meas& m, doubl
     }
 }
 
+// The switchable block under the loss `enc` (SixDOFErrorWithSwitchingConstraints WITH robust_norm, src/PoseGraphSLAM.cpp:800-807).  s_hat = |r|^2 over all SEVEN rows, and the
+// Corrector scales every row of r and of all five Jacobian blocks, dr/ds included, by c = sqrt(rho'(s_hat)):
+//   r = c [ s r6 ; s (1 - s) ]   J1 = c s A1, J2 = c s A2   dr/ds = c [ r6 ; 1 - 2 s ]          returns rho(s_hat); the block costs 0.5 rho, not 0.5 c^2 s_hat
+// r6 is evaluated once without Jacobians for s_hat and then, with A1 and A2, once more: no Jacobian entry is live while the loss (sqrt / log) is evaluated.  A1 and A2 are scaled
+// by the ONE product c s; enc = 0 gives c = 1 and the bits of switch_residual.
+template <bool WANT_J>
+PGO_HD double switch_residual_robust(const Pose& c1, const Pose& c2, const Meas& m, double s, double enc, double* r7, double* J1, double* J2, double* Js7, double& c) {
+    double r0[6];
+    relpose_residual<false>(c1, c2, m, 1.0, r0, nullptr, nullptr);
+    const double p = s * (1.0 - s);
+    double sh = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) { const double v = s * r0[i]; sh += v * v; }
+    sh += p * p;
+    const double rho = robust_loss(enc, sh, c);
+    double r6[6];
+    relpose_residual<WANT_J>(c1, c2, m, 1.0, r6, J1, J2);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) r7[i] = c * (s * r6[i]);
+    r7[6] = c * p;
+    if (WANT_J) {
+        const double cs = c * s;
+#pragma unroll
+        for (int i = 0; i < 36; ++i) { J1[i] *= cs; J2[i] *= cs; }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) Js7[i] = c * r6[i];
+        Js7[6] = c * (1.0 - 2.0 * s);
+    }
+    return rho;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Node regulariser (NodePoseRegularization) with target f = (R_f, t_f) given as a rigid Matrix4d and
 // q_f = Eigen quaternion of R_f:   delta = f^-1 [R(q1) p1; 0 1]
@@ -373,7 +404,8 @@ PGO_HD void edge_compact(const Pose& c1, const Pose& c2, const Meas& m, double w
     rec[15] = 0.0;
 }
 
-// side 0: own = c1, other = c2.  side 1: own = c2, other = c1.  kscale = sqrt(a_inv) for switchable edges, 0 otherwise.
+// side 0: own = c1, other = c2.  side 1: own = c2, other = c1.  kscale = sqrt(a_inv) for switchable edges, 0 otherwise (c sqrt(a_inv) under a robust loss: the record's r6 is
+// unscaled and its ws = s c, so the caller hands the matvec c^2 a_inv — see sw_prepare_loss_kernel).
 // Neither R2 nor M is formed: rotations act through the quaternion (v' = v + w t + t x qv, t = 2 v x qv for R2^T; mirrored for R2) and
 // M = d I - av bv^T - bv av^T + [c]x through its three vectors — 18 fewer live doubles than holding two 3x3 matrices.  Measured on MI355X
 // (C3): the same 28 us per matvec as the matrix form at 4 wavefronts/SIMD; forcing 5 or 6 (amdgpu_waves_per_eu) still spills 36 / 108 B

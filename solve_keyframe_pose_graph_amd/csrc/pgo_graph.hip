@@ -251,16 +251,18 @@ const char* pack_mf_tiles(const IncidentLists& I, const HostClass& rel, const Ho
 
 // ---- uploads.  Each waits for its copies: the host struct may go when it returns.
 int upload_class(pgo_problem* p, const PackedClass& P, DBuf<int32_t>& dc1, DBuf<int32_t>& dc2, DBuf<int32_t>* dsw, DBuf<double>& dmeas, DBuf<int4>& dwin, EdgeClassDev& out) {
-    const bool robust = !dsw && !P.loss.empty();      // (the relative-pose class of a handle with a robust edge)
+    const bool robust = !P.loss.empty();      // (a class with a robust edge)
+    DBuf<double>& dloss = dsw ? p->d_sloss : p->d_rloss;
+    DBuf<double>& dlossc = dsw ? p->d_slossc : p->d_rlossc;
     if (P.Epad > 0) {
         HIPCHK(p, dc1.upload(P.c1, p->st)); HIPCHK(p, dc2.upload(P.c2, p->st)); HIPCHK(p, dmeas.upload(P.meas, p->st)); HIPCHK(p, dwin.upload(P.win, p->st));
         if (dsw) HIPCHK(p, dsw->upload(P.sw, p->st));
-        if (robust) { HIPCHK(p, p->d_rloss.upload(P.loss, p->st)); HIPCHK(p, p->d_rlossc.ensure((size_t)P.Epad)); }
+        if (robust) { HIPCHK(p, dloss.upload(P.loss, p->st)); HIPCHK(p, dlossc.ensure((size_t)P.Epad)); }
         HIPCHK(p, hipStreamSynchronize(p->st));
     }
     out.c1 = dc1.p; out.c2 = dc2.p; out.meas = dmeas.p; out.swidx = dsw ? dsw->p : nullptr; out.win = dwin.p;
     out.E = P.E; out.Epad = P.Epad; out.tiles = P.tiles(); out.J = nullptr;
-    out.loss = robust ? p->d_rloss.p : nullptr; out.lossc = robust ? p->d_rlossc.p : nullptr;
+    out.loss = robust ? dloss.p : nullptr; out.lossc = robust ? dlossc.p : nullptr;
     return PGO_OK;
 }
 
@@ -299,6 +301,7 @@ int allocate_work_buffers(pgo_problem* p) {
     HIPCHK(p, p->d_c.ensure(std::max<int64_t>(Es * 12, 1))); HIPCHK(p, p->d_hss.ensure(std::max<int64_t>(Es, 1))); HIPCHK(p, p->d_gs.ensure(std::max<int64_t>(Es, 1)));
     HIPCHK(p, p->d_scale_p.ensure(std::max<int64_t>(N * 6, 1))); HIPCHK(p, p->d_diag_p.ensure(std::max<int64_t>(N * 6, 1)));
     HIPCHK(p, p->d_scale_s.ensure(std::max<int64_t>(Es, 1))); HIPCHK(p, p->d_diag_s.ensure(std::max<int64_t>(Es, 1))); HIPCHK(p, p->d_a_inv.ensure(std::max<int64_t>(Es, 1)));
+    if (G.sw.lossc) HIPCHK(p, p->d_a_inv_mf.ensure(std::max<int64_t>(Es, 1)));
     HIPCHK(p, p->d_val.ensure(mf ? 1 : std::max<int64_t>(p->nnzb * 36, 1))); HIPCHK(p, p->d_Lf.ensure(std::max<int64_t>(N * 24 + 64 * 24, 1))); HIPCHK(p, p->d_Dtot_b.ensure(std::max<int64_t>(N * 42, 1)));
     HIPCHK(p, p->d_cgvec.ensure(std::max<int64_t>(N * 42, 1)));
     p->n_part = std::max<int64_t>(MAX_PARTIALS, (G.rel.tiles + G.sw.tiles + 3) / 4 + 1);
@@ -318,6 +321,8 @@ void bind_descriptors(pgo_problem* p) {
     G.bsr_rowptr = p->d_bsr_rowptr.p; G.bsr_col = p->d_bsr_col.p; G.nnzb = p->nnzb;
     p->L = LinDev{p->d_Hd_g.p, p->d_Hd_g.p + (size_t)N * 36, p->d_Hoff.p, p->d_c.p, p->d_hss.p, p->d_gs.p};
     p->Sc = ScaleDev{p->d_scale_p.p, p->d_scale_s.p, p->d_diag_p.p, p->d_diag_s.p, p->d_a_inv.p};
+    p->ScMf = p->Sc;
+    if (G.sw.lossc) p->ScMf.a_inv = p->d_a_inv_mf.p;
     CgDev& C = p->C;
     C.val = p->d_val.p; C.Lf = p->d_Lf.p; C.Dtot = p->d_Dtot_b.p; C.b = p->d_Dtot_b.p + (size_t)N * 36;
     double* v = p->d_cgvec.p; const size_t n6 = (size_t)N * 6;

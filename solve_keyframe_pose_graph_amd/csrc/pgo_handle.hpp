@@ -107,7 +107,7 @@ struct EventPair {
 struct HostClass {
     std::vector<int32_t> c1, c2, sw;
     std::vector<double> meas;   // 8 per edge: q_obs(4) t_obs(3) w
-    std::vector<double> loss;   // relative-pose class only: the encoded robust loss (+a Huber, -a Cauchy, 0 trivial) of edges [0, loss.size()); the edges beyond it — and all
+    std::vector<double> loss;   // the encoded robust loss (+a Huber, -a Cauchy, 0 trivial) of edges [0, loss.size()); the edges beyond it — and all
                                 // of them while it is empty (no robust edge was ever added) — are trivial
     int64_t size() const { return (int64_t)c1.size(); }
 };
@@ -268,6 +268,8 @@ struct pgo_problem {
     DBuf<int32_t> d_rc1, d_rc2, d_sc1, d_sc2, d_sidx, d_bsr_col;
     DBuf<double> d_rmeas, d_smeas;
     DBuf<double> d_rloss, d_rlossc;   // robust loss plane of the relative-pose class and K1's corrector scales (allocated only for a handle with a robust edge)
+    DBuf<double> d_sloss, d_slossc;   // ... of the switchable class (allocated only for a handle with a robust switchable edge)
+    DBuf<double> d_a_inv_mf;          // [Es] c^2 a_inv, the matrix-free matvec's Schur scale on such a handle (sw_prepare_loss_kernel); ScMf.a_inv points at it
     DBuf<int4> d_rwin, d_swin;
     DBuf<PriorDev> d_prior;
     DBuf<int64_t> d_inc_rowptr, d_inc, d_bsr_rowptr;
@@ -312,6 +314,7 @@ struct pgo_problem {
     GraphDev G{};
     LinDev L{};
     ScaleDev Sc{};
+    ScaleDev ScMf{};                       // what the matrix-free matvec launches receive: Sc, but on a handle with a robust switchable edge a_inv = d_a_inv_mf
     CgDev C{};
 
     // the open solve: the LM controller's state (pgo_lm.hpp), the scaling's and the clock's

@@ -7,7 +7,7 @@
 //   sw      [S]               switch variables
 //   edge inputs per class (relpose / switchable), SoA planes padded to a multiple of 64:
 //     c1,c2 [Epad] int32      endpoint keyframes           meas [8][Epad]  q_obs(4) t_obs(3) weight
-//     loss  [Epad]            (relpose only, optional) encoded robust loss per edge; lossc [Epad] its corrector scale at the last linearisation
+//     loss  [Epad]            (optional) encoded robust loss per edge; lossc [Epad] its corrector scale at the last linearisation
 //     swidx [Epad] int32      (switchable only)            win  [tiles] int4 {lo1,n1,lo2,n2} pose windows for LDS staging
 //   K1 output per tile, AoSoA [tile][k/2][lane][2] so every store is 16 B/lane, 1 KiB/wave-instruction:
 //     relpose   78 doubles/edge: r[6]  J1[36] J2[36]                (row-major 6x6, cols [dtheta, dt])
@@ -73,7 +73,7 @@ struct EdgeClassDev {
     double* J;              // tiles x DOUBLES x 64
     int64_t E, Epad;
     int32_t tiles;
-    // robust loss (relative-pose class only; both null when the handle has no robust edge: K1 and the compaction then run their plain instantiations)
+    // robust loss (both null when the class has no robust edge: K1 and the compaction then run the instantiations without it)
     const double* loss;     // [Epad] +a Huber(a), -a Cauchy(a), 0 trivial (robust_loss, pgo_device_math.hpp)
     double* lossc;          // [Epad] c = sqrt(rho') of every edge at the last linearisation, written by K1 with Jacobians, read by the matrix-free compaction
 };
@@ -236,7 +236,8 @@ void launch_prior(const GraphDev& G, const double* pose8, bool want_jacobian, do
 void launch_k2(const GraphDev& G, const LinDev& L, bool want_offdiag, hipStream_t st, const MfDev* F = nullptr /* matrix-free tiles: the per-keyframe sums run on them */);
 void launch_scale_init(const GraphDev& G, const LinDev& L, const ScaleDev& Sc, int jacobi_scaling, hipStream_t st);
 void launch_lm_diag(const GraphDev& G, const LinDev& L, const ScaleDev& Sc, double min_diag, double max_diag, hipStream_t st);
-void launch_build_rows(const GraphDev& G, const LinDev& L, const ScaleDev& Sc, const CgDev& C, double radius, int add_lambda, double* lam_out /*null: write BSR blocks*/, hipStream_t st);
+void launch_build_rows(const GraphDev& G, const LinDev& L, const ScaleDev& Sc, const CgDev& C, double radius, int add_lambda, double* lam_out /*null: write BSR blocks*/,
+                       double* a_inv_mf /*c^2 a_inv for the matrix-free matvec, written when G.sw.lossc is set*/, hipStream_t st);
 void launch_mf_compact(const GraphDev& G, const MfDev& F, const double* pose8, const double* sw, hipStream_t st);
 void launch_mf_spmv(const GraphDev& G, const MfDev& F, const ScaleDev& Sc, const CgDev& C, int k, double tol2, hipStream_t st);
 void launch_mf_apply(const GraphDev& G, const MfDev& F, const ScaleDev& Sc, const CgDev& C, const double* x, double* y, hipStream_t st);

@@ -184,7 +184,9 @@ __device__ __forceinline__ void k1_store(double2* p, double a, double b) {
 }
 
 // LOSS: some relative-pose edge carries a robust loss (rel.loss / rel.lossc non-null; launch_k1 picks it by that alone, so a handle without one runs the plain code)
-template <bool WANT_J, bool NT, bool LOSS = false>
+// SWLOSS: some switchable edge carries one (sw.loss / sw.lossc non-null).  These instantiations serve the relative-pose class either way, looking at rel.loss at run time (a
+// null plane is the encoding 0, whose block has the plain block's bits), so LOSS is false in them and the forms stay nine, not twelve.
+template <bool WANT_J, bool NT, bool LOSS = false, bool SWLOSS = false>
 __global__ __launch_bounds__(K1_WAVES * 64) void k1_edges_kernel(EdgeClassDev rel, EdgeClassDev sw, const double* __restrict__ pose8,
                                                                   const double* __restrict__ swv, double* __restrict__ partials) {
     __shared__ __attribute__((aligned(16))) char lds_win[K1_WAVES * 2 * WIN_MAX * WIN_STRIDE];
@@ -223,6 +225,13 @@ __global__ __launch_bounds__(K1_WAVES * 64) void k1_edges_kernel(EdgeClassDev re
                     cost += rho;
                     if (WANT_J) rel.lossc[e] = c;
                 }
+            } else if (SWLOSS) {
+                double c;
+                const double rho = relpose_residual_robust<WANT_J>(P1, P2, M, rel.loss ? rel.loss[e] : 0.0, r, J1, J2, c);
+                if (valid) {
+                    cost += rho;
+                    if (WANT_J && rel.lossc) rel.lossc[e] = c;
+                }
             } else {
                 relpose_residual<WANT_J>(P1, P2, M, M.w, r, J1, J2);
                 if (valid) {
@@ -250,13 +259,25 @@ __global__ __launch_bounds__(K1_WAVES * 64) void k1_edges_kernel(EdgeClassDev re
         } else {
             const double s = valid ? swv[C.swidx[e]] : 0.0;
             double r[7], Js[7], J1[36], J2[36];
-            switch_residual<WANT_J>(P1, P2, M, s, r, J1, J2, Js);
-            if (valid) {
+            if (SWLOSS) {      // all seven rows of r and all five Jacobian blocks scaled by c; the block costs rho(|r|^2) — in the cost-only form too
+                double c;
+                const double rho = switch_residual_robust<WANT_J>(P1, P2, M, s, sw.loss[e], r, J1, J2, Js, c);
+                if (valid) {
+                    cost += rho;
+                    if (WANT_J) sw.lossc[e] = c;
+                } else {
 #pragma unroll
-                for (int i = 0; i < 7; ++i) cost += r[i] * r[i];
+                    for (int i = 0; i < 7; ++i) { r[i] = 0.0; Js[i] = 0.0; }
+                }
             } else {
+                switch_residual<WANT_J>(P1, P2, M, s, r, J1, J2, Js);
+                if (valid) {
 #pragma unroll
-                for (int i = 0; i < 7; ++i) { r[i] = 0.0; Js[i] = 0.0; }
+                    for (int i = 0; i < 7; ++i) cost += r[i] * r[i];
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 7; ++i) { r[i] = 0.0; Js[i] = 0.0; }
+                }
             }
             double2* out = reinterpret_cast<double2*>(C.J) + (size_t)tile * (SW_DOUBLES / 2 * TILE) + lane;
             if (WANT_J) {
@@ -306,6 +327,12 @@ void launch_k1(const GraphDev& G, const double* pose8, const double* sw, bool wa
     if (grid == 0) return;
     const double out_bytes = 8.0 * TILE * ((double)G.rel.tiles * REL_DOUBLES + (double)G.sw.tiles * SW_DOUBLES);
     const bool nt = out_bytes > 224.0e6;   // beyond what the Infinity Cache absorbs (see k1_store)
+    if (G.sw.loss) {
+        if (!want_jacobian) hipLaunchKernelGGL((k1_edges_kernel<false, false, false, true>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
+        else if (nt) hipLaunchKernelGGL((k1_edges_kernel<true, true, false, true>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
+        else hipLaunchKernelGGL((k1_edges_kernel<true, false, false, true>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
+        return;
+    }
     if (G.rel.loss) {
         if (!want_jacobian) hipLaunchKernelGGL((k1_edges_kernel<false, false, true>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
         else if (nt) hipLaunchKernelGGL((k1_edges_kernel<true, true, true>), dim3(grid), dim3(K1_WAVES * 64), 0, st, G.rel, G.sw, pose8, sw, partials);
@@ -327,6 +354,7 @@ double k1_algorithmic_bytes(const GraphDev& G, bool want_jacobian) {
     double b = 56.0 * N + 8.0 * Es + 72.0 * (Er + Es) + 68.0 * Eg;
     if (want_jacobian) b += 624.0 * Er + 688.0 * Es + 336.0 * Eg;
     if (G.rel.loss) b += (want_jacobian ? 16.0 : 8.0) * Er;      // the loss plane in, the corrector scales out
+    if (G.sw.loss) b += (want_jacobian ? 16.0 : 8.0) * Es;       // the same for the switchable class
     return b;
 }
 
@@ -615,6 +643,18 @@ __global__ void sw_prepare_kernel(GraphDev G, LinDev L, ScaleDev Sc, double radi
     Sc.a_inv[e] = 1.0 / (L.hss[e] + Sc.diag_s[e] / (radius * s * s));
 }
 
+// ... on a handle with a robust switchable edge: a_inv as above for the readers that pair it with K2's couplings (L.c carries c^2 already: build_rows_kernel, the switch
+// back-substitution, the coarse assembly) and c^2 a_inv for the matrix-free matvec, which pairs it with the record's UNSCALED r6: its k = r6 sqrt(c^2 a_inv) = c r6 sqrt(a_inv)
+__global__ void sw_prepare_loss_kernel(GraphDev G, LinDev L, ScaleDev Sc, double radius, double* __restrict__ a_inv_mf) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= G.sw.E) return;
+    const double s = Sc.scale_s[e];
+    const double ai = 1.0 / (L.hss[e] + Sc.diag_s[e] / (radius * s * s));
+    const double c = G.sw.lossc[e];
+    Sc.a_inv[e] = ai;
+    a_inv_mf[e] = c * c * ai;
+}
+
 __global__ __launch_bounds__(256) void build_rows_kernel(GraphDev G, LinDev L, ScaleDev Sc, CgDev C, double radius, int add_lambda, double* __restrict__ lam_out) {
     const bool write_val = lam_out == nullptr;
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -802,8 +842,9 @@ __device__ __forceinline__ double2 lf_apply_pair(const float* __restrict__ Lf, c
     return j == 0 ? make_double2(zz[0], zz[1]) : j == 1 ? make_double2(zz[2], zz[3]) : make_double2(zz[4], zz[5]);
 }
 
-void launch_build_rows(const GraphDev& G, const LinDev& L, const ScaleDev& Sc, const CgDev& C, double radius, int add_lambda, double* lam_out, hipStream_t st) {
-    if (G.sw.E > 0) hipLaunchKernelGGL(sw_prepare_kernel, dim3((unsigned)((G.sw.E + 255) / 256)), dim3(256), 0, st, G, L, Sc, radius);
+void launch_build_rows(const GraphDev& G, const LinDev& L, const ScaleDev& Sc, const CgDev& C, double radius, int add_lambda, double* lam_out, double* a_inv_mf, hipStream_t st) {
+    if (G.sw.E > 0 && G.sw.lossc && a_inv_mf) hipLaunchKernelGGL(sw_prepare_loss_kernel, dim3((unsigned)((G.sw.E + 255) / 256)), dim3(256), 0, st, G, L, Sc, radius, a_inv_mf);
+    else if (G.sw.E > 0) hipLaunchKernelGGL(sw_prepare_kernel, dim3((unsigned)((G.sw.E + 255) / 256)), dim3(256), 0, st, G, L, Sc, radius);
     if (G.N > 0) hipLaunchKernelGGL(build_rows_kernel, dim3((unsigned)((G.N + 255) / 256)), dim3(256), 0, st, G, L, Sc, C, radius, add_lambda, lam_out);
 }
 void launch_invert_rows(const GraphDev& G, const CgDev& C, int32_t* fail_flag, hipStream_t st) {
@@ -1296,7 +1337,8 @@ void launch_apply_operator(const GraphDev& G, const CgDev& C, const double* x, d
 //   phase A  one lane per edge-side of the workgroup's keyframes: y_e = J_side^T (I - k k^T)(J1 p1 + J2 p2)  -> LDS
 //   phase B  one lane per (keyframe, row): sum of the keyframe's edge-sides in list order (deterministic) + damping + regulariser
 // ------------------------------------------------------------------------------------------------
-template <bool LOSS>      // LOSS: the record's weight of a relative-pose edge is w c, c = K1's corrector scale at this linearisation (G.rel.lossc) — the bits K1's own blocks carry
+// SWLOSS: ... and that of a switchable side is s c (G.sw.lossc); its r6 planes stay unscaled, the matvec's Schur scale carries the c (sw_prepare_loss_kernel)
+template <bool LOSS, bool SWLOSS = false>      // LOSS: the record's weight of a relative-pose edge is w c, c = K1's corrector scale at this linearisation (G.rel.lossc) — the bits K1's own blocks carry
 __global__ __launch_bounds__(256) void mf_compact_kernel(GraphDev G, MfDev F, const double* __restrict__ pose8, const double* __restrict__ swv) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= F.ninc) return;
@@ -1309,7 +1351,7 @@ __global__ __launch_bounds__(256) void mf_compact_kernel(GraphDev G, MfDev F, co
     const double* mp = C.meas + e;
     const size_t ep = (size_t)C.Epad;
     const Meas M{mp[0], mp[ep], mp[2 * ep], mp[3 * ep], mp[4 * ep], mp[5 * ep], mp[6 * ep], mp[7 * ep]};
-    const double ws = is_sw ? swv[C.swidx[e]] : LOSS ? M.w * G.rel.lossc[e] : M.w;
+    const double ws = is_sw ? (SWLOSS ? swv[C.swidx[e]] * G.sw.lossc[e] : swv[C.swidx[e]]) : LOSS ? M.w * G.rel.lossc[e] : M.w;
     double rec[COMPACT_DOUBLES];
     edge_compact(P1, P2, M, ws, is_sw, rec);
     for (int pl = 0; pl < MF_PLANES; ++pl) F.rec[(size_t)pl * F.ninc_pad + i] = make_double2(rec[2 * pl], rec[2 * pl + 1]);
@@ -1561,7 +1603,9 @@ static inline int mf_grid(const MfDev& F) { const int g = F.tiles < MF_MAX_GRID 
 int mf_grid_size(const MfDev& F) { return mf_grid(F); }
 void launch_mf_compact(const GraphDev& G, const MfDev& F, const double* pose8, const double* sw, hipStream_t st) {
     if (F.ninc <= 0) return;
-    if (G.rel.lossc) hipLaunchKernelGGL(mf_compact_kernel<true>, dim3((unsigned)((F.ninc + 255) / 256)), dim3(256), 0, st, G, F, pose8, sw);
+    if (G.sw.lossc && G.rel.lossc) hipLaunchKernelGGL((mf_compact_kernel<true, true>), dim3((unsigned)((F.ninc + 255) / 256)), dim3(256), 0, st, G, F, pose8, sw);
+    else if (G.sw.lossc) hipLaunchKernelGGL((mf_compact_kernel<false, true>), dim3((unsigned)((F.ninc + 255) / 256)), dim3(256), 0, st, G, F, pose8, sw);
+    else if (G.rel.lossc) hipLaunchKernelGGL(mf_compact_kernel<true>, dim3((unsigned)((F.ninc + 255) / 256)), dim3(256), 0, st, G, F, pose8, sw);
     else hipLaunchKernelGGL(mf_compact_kernel<false>, dim3((unsigned)((F.ninc + 255) / 256)), dim3(256), 0, st, G, F, pose8, sw);
 }
 void launch_mf_spmv(const GraphDev& G, const MfDev& F, const ScaleDev& Sc, const CgDev& C, int k, double tol2, hipStream_t st) {

@@ -562,7 +562,7 @@ int pgo_apply_normal_operator_batch(pgo_problem* p, double radius, int64_t n_vec
     HIPCHK(p, d_io.ensure((size_t)n6 * 2));
     for (int64_t v = 0; v < n_vec; ++v) {
         HIPCHK(p, hipMemcpyAsync(d_io.p, X + (size_t)v * n6, (size_t)n6 * sizeof(double), hipMemcpyHostToDevice, p->st));
-        if (p->built_mf) launch_mf_apply(p->G, p->F, p->Sc, p->C, d_io.p, d_io.p + n6, p->st);
+        if (p->built_mf) launch_mf_apply(p->G, p->F, p->ScMf, p->C, d_io.p, d_io.p + n6, p->st);
         else launch_apply_operator(p->G, p->C, d_io.p, d_io.p + n6, p->st);
         HIPCHK(p, hipMemcpyAsync(Y + (size_t)v * n6, d_io.p + n6, (size_t)n6 * sizeof(double), hipMemcpyDeviceToHost, p->st));
         HIPCHK(p, hipStreamSynchronize(p->st));

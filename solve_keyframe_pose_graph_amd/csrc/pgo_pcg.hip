@@ -123,7 +123,7 @@ static int build_system(pgo_problem* p, bool* ok) {
     PcgState& s = p->pcg;
     int rc;
     HIPCHK(p, hipMemsetAsync(p->d_flags.p + 4, 0, sizeof(int32_t), p->st));
-    launch_build_rows(p->G, p->L, p->Sc, p->C, p->lm.radius, 1 /*one GPU: this handle adds Hd, g and the damping; multi-GPU: the keyframe's owner (G.own)*/, p->built_mf ? p->d_lam.p : nullptr, p->st);
+    launch_build_rows(p->G, p->L, p->Sc, p->C, p->lm.radius, 1 /*one GPU: this handle adds Hd, g and the damping; multi-GPU: the keyframe's owner (G.own)*/, p->built_mf ? p->d_lam.p : nullptr, p->ScMf.a_inv, p->st);
     if ((rc = exchange_rows(p, p->C.Dtot, 36, p->C.b, 6)) != PGO_OK) return rc;   // reduced diagonal + rhs of shared keyframes
     launch_invert_rows(p->G, p->C, p->d_flags.p + 4, p->st);
     int32_t fail = 0;
@@ -223,12 +223,12 @@ PcgForm choose_form(const pgo_problem* p, bool this_rank_only) {
 }
 // w = A u (with the partials of u.w; the classic forms: the new direction first, and the convergence test against tol2; the fused two-level method: the prolongation inside)
 void pcg_matvec(pgo_problem* p, const PcgForm& f, int k, double tol2) {
-    if (f.rec == PcgForm::ranks && p->built_mf) launch_mf_apply_dot(p->G, p->F, p->Sc, p->C, p->C.z, p->C.q, p->st);   // w = A_r u and the partials of u.w in one kernel
+    if (f.rec == PcgForm::ranks && p->built_mf) launch_mf_apply_dot(p->G, p->F, p->ScMf, p->C, p->C.z, p->C.q, p->st);   // w = A_r u and the partials of u.w in one kernel
     else if (f.rec == PcgForm::ranks) { launch_apply_operator(p->G, p->C, p->C.z, p->C.q, p->st); launch_cgcg_dots(p->G, p->C, p->st); }
-    else if (f.rec == PcgForm::sr) launch_mf_apply_dot_live(p->G, p->F, p->Sc, p->C, p->st);      // (no head: it only asks whether the PCG has stopped)
-    else if (f.rec == PcgForm::sr_coarse) launch_mf_apply_dot_live_coarse(p->G, p->F, p->Sc, p->C, p->coarse.K, k > 0 ? 1 : 0, p->st);      // w = A (z_bj + P y) (iteration 0: the PCG start has left the complete u in C.z)
-    else if (f.rec == PcgForm::classic_coarse) launch_mf_spmv_coarse(p->G, p->F, p->Sc, p->C, p->coarse.K, k, tol2, f.fused_parts, k > 0 ? 1 : 0, p->st);
-    else if (f.rec == PcgForm::classic_mf) launch_mf_spmv(p->G, p->F, p->Sc, p->C, k, tol2, p->st);
+    else if (f.rec == PcgForm::sr) launch_mf_apply_dot_live(p->G, p->F, p->ScMf, p->C, p->st);      // (no head: it only asks whether the PCG has stopped)
+    else if (f.rec == PcgForm::sr_coarse) launch_mf_apply_dot_live_coarse(p->G, p->F, p->ScMf, p->C, p->coarse.K, k > 0 ? 1 : 0, p->st);      // w = A (z_bj + P y) (iteration 0: the PCG start has left the complete u in C.z)
+    else if (f.rec == PcgForm::classic_coarse) launch_mf_spmv_coarse(p->G, p->F, p->ScMf, p->C, p->coarse.K, k, tol2, f.fused_parts, k > 0 ? 1 : 0, p->st);
+    else if (f.rec == PcgForm::classic_mf) launch_mf_spmv(p->G, p->F, p->ScMf, p->C, k, tol2, p->st);
     else launch_cg_spmv(p->G, p->C, k, tol2, p->st);
 }
 // the vector update (the single-reduction forms: with the iteration's one reduction point; `first`: also when a PCG that stopped before its first update is resumed — p = s = 0 still)
@@ -275,7 +275,7 @@ int pcg_precond(pgo_problem* p, const PcgForm& f, int k) {
 int pcg_start(pgo_problem* p, const PcgForm& f, bool warm, double tol2) {
     int rc;
     if (warm) {
-        if (p->built_mf) launch_mf_apply(p->G, p->F, p->Sc, p->C, p->C.x, p->C.q, p->st);
+        if (p->built_mf) launch_mf_apply(p->G, p->F, p->ScMf, p->C, p->C.x, p->C.q, p->st);
         else launch_apply_operator(p->G, p->C, p->C.x, p->C.q, p->st);
         if ((rc = exchange_rows(p, p->C.q, 6, nullptr, 0)) != PGO_OK) return rc;
     }

@@ -469,6 +469,22 @@ int pgo_add_switchable_edges(pgo_problem* p, int64_t n, const int32_t* c1, const
     if (n > 0 && !sw) { p->err = "switch index array required"; return PGO_ERR_INVALID_ARG; }
     return add_edges(p, p->swe, n, c1, c2, T, w, sw);
 }
+int pgo_add_switchable_edges_robust(pgo_problem* p, int64_t n, const int32_t* c1, const int32_t* c2, const double* T, const double* w, const int32_t* sw, int32_t loss, double loss_a) {
+    if (!p) return PGO_ERR_INVALID_ARG;
+    if (loss != PGO_LOSS_TRIVIAL && loss != PGO_LOSS_HUBER && loss != PGO_LOSS_CAUCHY) { p->err = "unknown robust loss"; return PGO_ERR_INVALID_ARG; }
+    if (loss != PGO_LOSS_TRIVIAL && !(std::isfinite(loss_a) && loss_a > 0.0)) { p->err = "the robust loss parameter must be finite and positive"; return PGO_ERR_INVALID_ARG; }
+    if (n > 0 && !sw) { p->err = "switch index array required"; return PGO_ERR_INVALID_ARG; }
+    return add_edges(p, p->swe, n, c1, c2, T, w, sw, loss == PGO_LOSS_HUBER ? loss_a : loss == PGO_LOSS_CAUCHY ? -loss_a : 0.0);
+}
+int pgo_get_switchable_edge_loss(const pgo_problem* p, int64_t first, int64_t n, int32_t* loss, double* loss_a) {
+    if (!p || first < 0 || n < 0 || first + n > p->swe.size()) return PGO_ERR_INVALID_ARG;
+    for (int64_t k = 0; k < n; ++k) {
+        const double enc = first + k < (int64_t)p->swe.loss.size() ? p->swe.loss[first + k] : 0.0;
+        if (loss) loss[k] = enc > 0.0 ? PGO_LOSS_HUBER : enc < 0.0 ? PGO_LOSS_CAUCHY : PGO_LOSS_TRIVIAL;
+        if (loss_a) loss_a[k] = std::fabs(enc);
+    }
+    return PGO_OK;
+}
 int pgo_set_node_regularizers(pgo_problem* p, int64_t n, const int32_t* node, const double* target, const double* weight) {
     if (!p || n < 0 || (n > 0 && (!node || !target || !weight))) return PGO_ERR_INVALID_ARG;
     std::vector<PriorDev> v((size_t)n);
@@ -827,7 +843,7 @@ int pgo_apply_normal_operator(pgo_problem* p, const double* x, double* y) {
     HIPCHK(p, p->d_io.ensure((size_t)p->N * 12));
     double* xin = p->d_io.p; double* yout = p->d_io.p + (size_t)p->N * 6;
     if ((rc = nodes_from_global(p, x, 6, xin)) != PGO_OK) return rc;
-    if (p->built_mf) launch_mf_apply(p->G, p->F, p->Sc, p->C, xin, yout, p->st);
+    if (p->built_mf) launch_mf_apply(p->G, p->F, p->ScMf, p->C, xin, yout, p->st);
     else launch_apply_operator(p->G, p->C, xin, yout, p->st);
     if ((rc = exchange_rows(p, yout, 6, nullptr, 0)) != PGO_OK) return rc;
     return nodes_to_global(p, yout, 6, y);

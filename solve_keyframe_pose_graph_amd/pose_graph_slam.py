@@ -162,6 +162,21 @@ class PoseGraphSLAM:
         """Steps -3-/-4- of the trigger (odometry measurements, yaw weights, VIO-derived guesses) as device kernels (default) or on the host."""
         self.lib.pgo_host_set_device_graph_construction(self.h, C.c_int(1 if on else 0))
 
+    def set_loop_edge_loss(self, kind, a=0.0):
+        """The robust loss of the loop edges the trigger adds from now on: the reference's `robust_norm` member (PoseGraphSLAM.h:200) on its switchable loop blocks
+        (src/PoseGraphSLAM.cpp:800-807).  kind: "trivial" (the default), "huber", "cauchy" or the PGO_LOSS_* number."""
+        kind = capi.LOSS_NAMES[kind] if isinstance(kind, str) else int(kind)
+        if not self.lib.pgo_host_set_loop_edge_loss(self.h, C.c_int(kind), C.c_double(a)):
+            raise ValueError("set_loop_edge_loss: unknown loss, or a parameter that is not finite and positive")
+
+    def loop_edge_loss(self, first=0, n=None):
+        """(PGO_LOSS_* kind, parameter a) of the switchable blocks [first, first + n) the trigger has added"""
+        n = self.lib.pgo_host_n_added_edges_switchable(self.h) - first if n is None else n
+        kind = np.zeros(n, np.int32); a = np.zeros(n)
+        if not self.lib.pgo_host_get_loop_edge_loss(self.h, C.c_int64(first), C.c_int64(n), kind.ctypes.data_as(C.POINTER(C.c_int32)), a.ctypes.data_as(_dp)):
+            raise ValueError("loop_edge_loss: range outside the switchable blocks added so far")
+        return kind, a
+
     # ---- PoseGraphSLAM interface ----
     def load_state(self, optimization_variable_as_constants=True):
         """PoseGraphSLAM::load_state: the keyframes already in the data source are a previously solved map (kept constant)."""
