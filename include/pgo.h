@@ -450,8 +450,9 @@ int pgo_evaluate(pgo_problem* p, const double* quat_xyzw, const double* t, const
  * PGO_ERR_NUMERIC: a pivot of the factorisation was not > 0 (or NaN); cov is untouched and the handle stays usable.  That catches a breakdown and nothing more: a graph
  * whose gauge is not fixed (no regulariser, no constant keyframe) is singular, and rounding may still let it factor with a tiny pivot — the blocks are then meaningless
  * large numbers.  Fixing the gauge is the caller's job, as with Ceres' sparse covariance algorithms.
- * Launches: scatter, the factorisation (2 nt - 1, nt = n / 64), the right-hand sides, 2 (nt - k0) - 1 for the substitutions from the block column k0 of the first
- * requested keyframe on, one Gram launch.  Times: profiles/dense_covariance_times.txt. */
+ * Launches (pgo_covariance's, one device path): the right-hand sides, the matrix (build_rows + scatter), the factorisation (2 nt - 1, nt = n / 64), 2 (nt - k0) - 1 for
+ * the substitutions from the block column k0 of the first requested keyframe on, one Gram launch.  Times: profiles/dense_covariance_times.txt,
+ * profiles/one_covariance_path_times.txt. */
 int pgo_pose_covariance(pgo_problem* p, const double* quat_xyzw, const double* t, const double* sw,
                         int64_t n_nodes, int64_t n_switch,
                         int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cov /* n_pairs x 36, row-major */);
@@ -461,7 +462,7 @@ int pgo_pose_covariance(pgo_problem* p, const double* quat_xyzw, const double* t
  * n_nodes <= id < n_nodes + n_switch is the caller's switch index id - n_nodes (size 1).  The linearisation point, "no damping, no scaling" and the corrected blocks of
  * robust edges are pgo_pose_covariance's.
  *   cov[k]   (HOST) has a fixed stride of 36 doubles: the d_a x d_b block (rows of block_a[k], columns of block_b[k]) of H^-1 over all free parameters, row-major in the
- *            leading d_a d_b entries, the rest 0.  Pose-pose blocks are the bits of pgo_pose_covariance on a handle that call accepts.  With H = [H_pp C; C^T diag(h)] and S the
+ *            leading d_a d_b entries, the rest 0.  pgo_pose_covariance is this call restricted to keyframe ids on a handle with block-CSR values: one device path, so the pose-pose blocks of the two are the same bits.  With H = [H_pp C; C^T diag(h)] and S the
  *            undamped Schur complement the factor is of: Sigma_pp = S^-1, Sigma_p,e = S^-1 v_e, Sigma_e,f = delta_ef / h_e + v_e^T S^-1 v_f with v_e = -c_e / h_e (DESIGN.md
  *            section 3.4).  cov(b, a) is the exact transpose of cov(a, b) for every combination of sizes; a repeated pair and two calls give the same bits (no atomics,
  *            every sum in a fixed order).
@@ -709,11 +710,12 @@ int pgo_dense_spd_inverse(pgo_problem* p, int32_t n, const double* a, double* a_
  * the factorisation reports a pivot that is not positive (x is then left alone). */
 int pgo_dense_spd_solve(pgo_problem* p, int32_t n, const double* a, const double* b, double* x, int32_t launches, double* avg_ms);
 /* pgo_pose_covariance's kernels on their own (test and measurement hook): the 6 x 6 blocks (rows of "node" ia[k], columns of node ib[k]; node i = rows 6 i .. 6 i + 5,
- * i < n / 6) of the inverse of the caller's symmetric positive definite matrix, with exactly the factor, substitution and Gram launches of pgo_pose_covariance, `launches`
- * times; the matrix is padded like pgo_dense_spd_solve's.  cov: n_pairs x 36 (host), n_pairs >= 1; *avg_ms (may be NULL): the HIP-event average of one factorisation +
- * covariance.  PGO_ERR_NUMERIC when a pivot is not positive (cov is then left alone). */
+ * i < n / 6; an index outside: PGO_ERR_INVALID_ARG) of the inverse of the caller's symmetric positive definite matrix: pgo_dense_spd_param_covariance below without
+ * switch columns — the same right-hand-side, factor, substitution and Gram launches, `launches` times; the matrix is padded like pgo_dense_spd_solve's.  cov: n_pairs x 36
+ * (host), n_pairs >= 1; *avg_ms (may be NULL): the HIP-event average of one right-hand sides + factorisation + covariance.  PGO_ERR_NUMERIC when a pivot is not positive
+ * (cov is then left alone). */
 int pgo_dense_spd_covariance(pgo_problem* p, int32_t n, const double* a, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms);
-/* pgo_covariance's kernels on their own (test and measurement hook): blocks of the inverse of H = [a C; C^T diag(h)] from the factor of the caller's symmetric positive
+/* The kernels of pgo_covariance and pgo_pose_covariance on their own (test and measurement hook): blocks of the inverse of H = [a C; C^T diag(h)] from the factor of the caller's symmetric positive
  * definite matrix `a` (n x n, padded like pgo_dense_spd_solve's) — `a` plays the Schur complement, so H's pose part is a + C diag(h)^-1 C^T — with the right-hand-side,
  * factor, substitution and Gram launches of pgo_covariance, `launches` times.  The n_sw sparse switch columns of C, in block form: sw_node[2 s], sw_node[2 s + 1] the two
  * distinct nodes column s has entries in (node i = rows 6 i .. 6 i + 5, i < n / 6; -1: no entries on that side), sw_c[12 s + 6 side + k] the six values on each side,

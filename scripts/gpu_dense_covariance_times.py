@@ -2,8 +2,8 @@
     python scripts/gpu_dense_covariance_times.py > profiles/dense_covariance_times.txt
   * session-structured graphs (those of scripts/gpu_dense_cholesky_times.py) of 200, 600 and 1024 keyframes at their initial state; requests: the last keyframe's block
     alone, and the diagonal blocks of all keyframes;
-  * kernels: pgo_dense_spd_covariance's avg_ms (HIP events around the factorisation, the substitutions and the Gram launch — exactly pgo_pose_covariance's launches after
-    the scatter) on the handle's own undamped reduced matrix, average of 3 after one untimed call; next to it pgo_dense_spd_solve's avg_ms on the same matrix (the
+  * kernels: pgo_dense_spd_covariance's avg_ms (HIP events around the right-hand sides, the factorisation, the substitutions and the Gram launch — exactly
+    pgo_pose_covariance's launches but for the matrix's build and scatter) on the handle's own undamped reduced matrix, average of 3 after one untimed call; next to it pgo_dense_spd_solve's avg_ms on the same matrix (the
     factorisation and the two sweeps of one dense LM step);
   * call: wall-clock of pgo_pose_covariance itself (linearisation, system build, scatter, factor, covariance, read-back), the fastest of 3 after one untimed call.
 Nothing here is a pass/fail number."""
@@ -19,7 +19,7 @@ from tests import dense_cov_ref as ref      # noqa: E402
 from tests import util      # noqa: E402
 
 print("library: %s" % capi.build_info()[0])
-print("milliseconds; kernels = factor + substitutions + Gram (HIP events), call = pgo_pose_covariance (wall clock), factor + sweeps = pgo_dense_spd_solve on the same matrix")
+print("milliseconds; kernels = right-hand sides + factor + substitutions + Gram (HIP events), call = pgo_pose_covariance (wall clock), factor + sweeps = pgo_dense_spd_solve on the same matrix")
 print("%-6s %6s %9s | %-14s %6s %9s %10s %10s | %14s" % ("graph", "n", "launches", "request", "pairs", "rhs rows", "kernels", "call", "factor+sweeps"))
 for N in (200, 600, 1024):
     g = graphgen.generate(N, N // 5, odom_f_max=5, apply_yaw_weight=1, seed=5, **dict(graphgen._SMALL, turn_deg_per_keyframe=2.0))

@@ -4,9 +4,9 @@
     state; requests: (a) the last keyframe's block alone, (b) the diagonal blocks of all keyframes, (c) the variances of all switches;
   * kernels: pgo_dense_spd_param_covariance's avg_ms (HIP events around the right-hand sides, the FACTORISATION, the substitutions and the Gram launch — pgo_covariance's
     launches after the matrix is in place) on the handle's own undamped reduced matrix and switch columns, average of 3 after one untimed call; beside it
-    pgo_dense_spd_covariance's avg_ms (pgo_pose_covariance's launches) for (a) and (b);
+    pgo_dense_spd_covariance's avg_ms (the same launches through the pose-only hook: a second measurement of the same thing) for (a) and (b);
   * call: wall clock of pgo_covariance itself (linearisation, the matrix, factor, covariance, read-back), the fastest of 3 after one untimed call, on a block-CSR handle
-    (linear_solver = 0: build_rows + scatter) and on a matrix-free handle (the default: J1^T J2 per edge, host plan, one scatter); beside it pgo_pose_covariance on the
+    (linear_solver = 0: build_rows + scatter) and on a matrix-free handle (the default: J1^T J2 per edge, host plan, one scatter); beside it pgo_pose_covariance (the same routine through its own entry point) on the
     block-CSR handle for (a) and (b).  The difference of the two pgo_covariance columns is what the matrix-free assembly costs more (or less) than build_rows + scatter.
 Nothing here is a pass/fail number."""
 import os
@@ -40,7 +40,7 @@ def main(out_path):
         lines.append(s)
 
     emit("library: %s" % capi.build_info()[0])
-    emit("milliseconds; kernels = right-hand sides + factor + substitutions + Gram (HIP events; pose: pgo_pose_covariance's launches on the same matrix), call = wall clock of the entry point")
+    emit("milliseconds; kernels = right-hand sides + factor + substitutions + Gram (HIP events; pose: the same launches through pgo_dense_spd_covariance), call = wall clock of the entry point")
     emit("%-6s %6s %5s | %-14s %6s %9s | %9s %9s | %12s %12s %12s" % ("graph", "n", "sw", "request", "pairs", "rhs rows", "kernels", "pose", "call csr", "call mf", "pose call"))
     for N in (200, 600, 1024):
         g = graphgen.generate(N, N // 5, odom_f_max=5, apply_yaw_weight=1, seed=5, **dict(graphgen._SMALL, turn_deg_per_keyframe=2.0))

@@ -417,7 +417,7 @@ class Problem:
         return out, ms.value
 
     def dense_spd_covariance(self, a, pairs, launches=1):
-        """pgo_pose_covariance's factor, substitution and Gram launches on a symmetric positive definite matrix ("node" i = rows 6 i .. 6 i + 5); returns (blocks
+        """pgo_pose_covariance's right-hand-side, factor, substitution and Gram launches (dense_spd_param_covariance without switches) on a symmetric positive definite matrix ("node" i = rows 6 i .. 6 i + 5); returns (blocks
         (n_pairs, 6, 6), average milliseconds)."""
         a = np.ascontiguousarray(a, dtype=np.float64)
         n = a.shape[0]

@@ -6,11 +6,9 @@
 // inside a launch, there are no atomics, and every sum has a fixed order.  All fp64; the panel's and the update's products run on v_mfma_f64_16x16x4_f64 (operand maps: the
 // comment above gj_block_inverse in pgo_kernels.hip).
 //
-// Covariance blocks (pgo_pose_covariance, after scatter and factor): 1 (the right-hand sides) + 2 (nt - k0) - 1 (solve, update from the first requested keyframe's block
-// column k0 on) + 1 (Gram) launches, under the same rules.
-//
-// Pose and switch blocks (pgo_covariance): the same chain with switch rows -c_e / h_e among the right-hand sides (dcp_rhs_kernel, ahead of the factor) and Gram products of
-// 6- and 1-row blocks (dcp_gram_kernel); on a matrix-free graph the matrix comes from the normal blocks in one scatter launch (dcm_scatter_kernel) instead of build_rows +
+// Covariance blocks (pgo_pose_covariance and pgo_covariance, one path): 1 (the right-hand sides: a keyframe's six unit rows, a switch's row -c_e / h_e; dcp_rhs_kernel,
+// ahead of the factor) + 2 (nt - k0) - 1 (solve, update from the first requested block column k0 on) + 1 (Gram products of 6- and 1-row blocks, dcp_gram_kernel)
+// launches, under the same rules.  On a matrix-free graph the matrix comes from the normal blocks in one scatter launch (dcm_scatter_kernel) instead of build_rows +
 // dc_scatter_kernel.
 #include <algorithm>
 #include <cstdlib>
@@ -225,12 +223,6 @@ __global__ __launch_bounds__(DC_THREADS) void dc_scatter_kernel(GraphDev G, CgDe
 
 // ---- covariance blocks: forward substitution with many right-hand sides (the rows of W[m][n]), then one Gram product per requested pair
 
-// the ones of the right-hand sides into the zeroed W (col < 0: a padding row)
-__global__ __launch_bounds__(DC_THREADS) void dcv_rhs_kernel(double* __restrict__ W, int n, int m, const int32_t* __restrict__ col) {
-    const int r = (int)blockIdx.x * DC_THREADS + (int)threadIdx.x;
-    if (r < m && col[r] >= 0) W[(size_t)r * n + col[r]] = 1.0;
-}
-
 // Solve of step k: dc_panel_kernel's substitution on the tile rows of W instead of the tile rows of A below the diagonal (a copy, so that the factor's kernel keeps its
 // machine code): one workgroup per tile row that has started, one wavefront per 16 right-hand sides, Y = W_.k L_kk^-T over W_.k and, k-major, into YT[64][ldm].
 __global__ __launch_bounds__(DC_THREADS) void dcv_solve_kernel(const double* __restrict__ A, int n, int k, double* __restrict__ W, int ldm, double* __restrict__ YT) {
@@ -317,15 +309,7 @@ __global__ __launch_bounds__(DC_THREADS) void dcv_update_kernel(const double* __
                 W[(size_t)(i0 + s * 16 + lk + 4 * reg) * n + bi * DC_NB + j0 + t * 16 + lr] = old[s][t][reg] - acc[s][t][reg];
 }
 
-// One workgroup per requested pair: cov[pair] = W_a W_b^T (dc_gram_block).  rows[2 pair], rows[2 pair + 1]: the first of the six rows of W of the two keyframes; c0[pair]:
-// the first column class neither of them is still zero in.
-__global__ __launch_bounds__(DC_THREADS) void dcv_gram_kernel(const double* __restrict__ W, int n, const int32_t* __restrict__ rows, const int32_t* __restrict__ c0, double* __restrict__ cov) {
-    __shared__ double part[6 * DC_GRAM];
-    const size_t pair = blockIdx.x;
-    dc_gram_block(DcTeam{}, W + (size_t)rows[2 * pair] * n, W + (size_t)rows[2 * pair + 1] * n, (size_t)n, n, c0[pair], part, cov + 36 * pair);
-}
-
-// ---- pgo_covariance: pose and switch blocks (the algebra and the plans: pgo_dense_math.hpp).  The substitution launches are dcv_solve_kernel / dcv_update_kernel.
+// ---- the right-hand sides and the Gram products of pose and switch blocks (the algebra and the plan: pgo_dense_math.hpp)
 
 // the right-hand sides into the zeroed W, one thread per row: a unit row's one, a switch row's -c_side / h (dc_param_rhs_row); a requested switch whose h cannot divide
 // raises the failure flag
@@ -402,32 +386,11 @@ void launch_dense_scatter(const GraphDev& G, const CgDev& C, double* A, int n, d
     hipLaunchKernelGGL(dc_scatter_kernel, dim3((unsigned)((threads + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, st, G, C, A, n, w);
 }
 
-// ---- covariance blocks from the factor in A.  work: dense_cov_doubles(n, Q.m, pairs) doubles — W, the k-major copy of a solved block column, the blocks; idx:
-// dense_cov_ints(Q.m, pairs) — the right-hand sides' columns, then per pair the two row indices, then per pair the Gram's first column.
+// ---- covariance blocks of pose and switch parameters (pgo_pose_covariance, pgo_covariance, the two pgo_dense_spd_*covariance hooks).  work: dense_cov_doubles(n, Q.m,
+// pairs) doubles — W, the k-major copy of a solved block column, the blocks; idx: dense_param_ints(Q.m, pairs, switches) — the rows' columns, five numbers per pair
+// (dcp_gram_kernel), the switches' two nodes.  sw_c [12 per switch], sw_h: device arrays.
 size_t dense_cov_doubles(int n, int m, int64_t n_pairs) { return (size_t)m * n + (size_t)DC_NB * (m + 16) + (size_t)36 * n_pairs; }
-size_t dense_cov_ints(int m, int64_t n_pairs) { return (size_t)m + (size_t)3 * n_pairs; }
-int dense_cov_upload(pgo_problem* p, const DcCovPlan& Q, std::vector<int32_t>& staging, int32_t* idx) {
-    const size_t np = Q.row_a.size();
-    staging.assign(Q.col.begin(), Q.col.end());
-    for (size_t k = 0; k < np; ++k) { staging.push_back(Q.row_a[k]); staging.push_back(Q.row_b[k]); }
-    for (size_t k = 0; k < np; ++k) staging.push_back(Q.gram_c0((int64_t)k));
-    HIPCHK(p, hipMemcpyAsync(idx, staging.data(), staging.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->st));      // (staging outlives the caller's next synchronize)
-    return PGO_OK;
-}
 double* dense_cov_blocks(double* work, int n, int m) { return work + (size_t)m * n + (size_t)DC_NB * (m + 16); }
-int launch_dense_covariance(pgo_problem* p, const double* A, int n, const DcCovPlan& Q, double* work, const int32_t* idx) {
-    const int m = Q.m;
-    const int64_t np = (int64_t)Q.row_a.size();
-    HIPCHK(p, hipMemsetAsync(work, 0, (size_t)m * n * sizeof(double), p->st));
-    hipLaunchKernelGGL(dcv_rhs_kernel, dim3((unsigned)((m + DC_THREADS - 1) / DC_THREADS)), dim3(DC_THREADS), 0, p->st, work, n, m, idx);
-    DcCovLaunch D{A, n, work, m + 16, work + (size_t)m * n, p->st};
-    dc_cov_steps(n, Q.mt, Q.start_tile.data(), true, D);
-    hipLaunchKernelGGL(dcv_gram_kernel, dim3((unsigned)np), dim3(DC_THREADS), 0, p->st, (const double*)work, n, idx + m, idx + m + 2 * np, dense_cov_blocks(work, n, m));
-    return PGO_OK;
-}
-
-// ---- pose and switch blocks (pgo_covariance, pgo_dense_spd_param_covariance).  work: dense_cov_doubles(n, Q.m, pairs), laid out as above; idx: dense_param_ints(Q.m, pairs,
-// switches) — the rows' columns, five numbers per pair (dcp_gram_kernel), the switches' two nodes.  sw_c [12 per switch], sw_h: device arrays.
 size_t dense_param_ints(int m, int64_t n_pairs, int64_t n_sw) { return (size_t)m + (size_t)5 * n_pairs + (size_t)2 * n_sw; }
 int dense_param_upload(pgo_problem* p, const DcParamPlan& Q, int64_t n_sw, const int32_t* sw_node, std::vector<int32_t>& staging, int32_t* idx) {
     const size_t np = Q.row_a.size();
@@ -494,41 +457,12 @@ int dense_step(pgo_problem* p, bool* ok, double* t_factored) {
     return PGO_OK;
 }
 
-// The covariance blocks of pgo_pose_covariance on the linearisation solve_begin has left: the undamped reduced system (the damping is diag / (radius s^2): exactly zero
-// at radius = +inf, in the pose rows and in the switches' Schur terms alike) in build_rows' block-CSR values, scattered, factored, then the substitutions and the Gram
-// products of the pairs whose two keyframes are free (ia, ib: those pairs, n_pairs >= 1).  The system build_rows writes is in the tangent coordinates themselves — the
-// Jacobi scaling only shapes the damping — so there is no scaling to undo on the way out.  *ok = false: a pivot failed, out untouched.
-int dense_pose_covariance(pgo_problem* p, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* out, bool* ok) {
-    DenseState& d = p->dense;
-    int rc;
-    if (!d.built && (rc = dense_allocate(p)) != PGO_OK) return rc;      // (a graph built for the block-CSR PCG: until its next graph build)
-    const int n = d.n;
-    const DcCovPlan Q(n_pairs, ia, ib);
-    HIPCHK(p, d.cov.ensure(dense_cov_doubles(n, Q.m, n_pairs))); HIPCHK(p, d.cov_idx.ensure(dense_cov_ints(Q.m, n_pairs)));
-    std::vector<int32_t> staging;
-    if ((rc = dense_cov_upload(p, Q, staging, d.cov_idx.p)) != PGO_OK) return rc;
-    int32_t* fail = p->d_flags.p + 4;
-    launch_lm_diag(p->G, p->L, p->Sc, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->st);      // (finite numbers for the division below, whatever the buffers held)
-    launch_build_rows(p->G, p->L, p->Sc, p->C, std::numeric_limits<double>::infinity(), 1, nullptr, p->ScMf.a_inv, p->st);
-    HIPCHK(p, hipMemsetAsync(d.A.p, 0, (size_t)n * n * sizeof(double), p->st));
-    HIPCHK(p, hipMemsetAsync(fail, 0, sizeof(int32_t), p->st));
-    launch_dense_scatter(p->G, p->C, d.A.p, n, d.vec.p, p->st);
-    launch_dense_factor(d.A.p, n, d.scratch.p, fail, debug_break_dense(), p->st);
-    int32_t h = 0;
-    HIPCHK(p, hipMemcpyAsync(&h, fail, sizeof(int32_t), hipMemcpyDeviceToHost, p->st));
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    *ok = h == 0;
-    if (!*ok) return PGO_OK;
-    if ((rc = launch_dense_covariance(p, d.A.p, n, Q, d.cov.p, d.cov_idx.p)) != PGO_OK) return rc;
-    HIPCHK(p, hipMemcpyAsync(out, dense_cov_blocks(d.cov.p, n, Q.m), (size_t)36 * n_pairs * sizeof(double), hipMemcpyDeviceToHost, p->st));
-    HIPCHK(p, hipStreamSynchronize(p->st));
-    return PGO_OK;
-}
-
-// The blocks of pgo_covariance on the linearisation solve_begin has left.  Block ids: a free keyframe, or N + the internal index of a switchable edge; sw_node: per
-// switchable edge its two keyframes, -1 where one is constant.  The matrix is dense_pose_covariance's on a graph with block-CSR values; on a matrix-free graph it is
-// assembled from the normal blocks (J1^T J2 per edge formed here, as pgo_get_normal_blocks does), the graph stays what it is.  *ok = false: a pivot failed or a
-// requested switch's h cannot divide, out untouched.
+// The blocks of pgo_pose_covariance and pgo_covariance on the linearisation solve_begin has left (ia, ib: the pairs whose keyframes are all free, n_pairs >= 1).  Block
+// ids: a free keyframe, or N + the internal index of a switchable edge; sw_node: per switchable edge its two keyframes, -1 where one is constant.  On a graph with
+// block-CSR values the matrix is the undamped reduced system (the damping is diag / (radius s^2): exactly zero at radius = +inf, in the pose rows and in the switches'
+// Schur terms alike) in build_rows' values, scattered; the system build_rows writes is in the tangent coordinates themselves — the Jacobi scaling only shapes the
+// damping — so there is no scaling to undo on the way out.  On a matrix-free graph it is assembled from the normal blocks (J1^T J2 per edge formed here, as
+// pgo_get_normal_blocks does), the graph stays what it is.  *ok = false: a pivot failed or a requested switch's h cannot divide, out untouched.
 int dense_param_covariance(pgo_problem* p, const std::vector<int32_t>& sw_node, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* out, bool* ok) {
     DenseState& d = p->dense;
     int rc;

@@ -10,12 +10,12 @@
 // Solve: L y = b by block columns (y_k = L_kk^-1 w_k, then w_i -= L_ik y_k for i > k), L^T x = y by block rows from the bottom (x_k = L_kk^-T y_k, then
 // y_j -= L_kj^T x_k for j < k).  Every sum has a fixed order: two runs give the same bits.
 //
-// Covariance blocks (pgo_pose_covariance): Sigma = (L L^T)^-1 = L^-T L^-1, so the 6 x 6 block of keyframes (a, b) is (L^-1 E_a)^T (L^-1 E_b) with E_c the 6 unit columns of
+// Covariance blocks (pgo_pose_covariance, pgo_covariance): Sigma = (L L^T)^-1 = L^-T L^-1, so the 6 x 6 block of keyframes (a, b) is (L^-1 E_a)^T (L^-1 E_b) with E_c the 6 unit columns of
 // keyframe c: forward substitutions only.  The right-hand sides are the ROWS of W (m x n row-major, m a multiple of 64, sorted by the column of their one), solved in place
 // by block columns k:   solve  Y = W_.k L_kk^-T for every 64-row tile of W (the panel's substitution);   update  W_.i -= Y L_ik^T for i > k.
 // A unit column is zero before its one, so a tile row of W whose first right-hand side starts in tile k0 has nothing but zeros to solve and to subtract in the steps k < k0:
 // they are skipped (dc_cov_steps), and since every skipped operation would have produced or subtracted +0 the result has the same bits with and without the skipping.
-// Then   gram  Sigma_ab = W_a W_b^T over the n columns (dc_gram_block): 256 column classes (column mod 256) summed ascending, then a fixed binary tree over the classes —
+// Then   gram  Sigma_ab = W_a W_b^T over the n columns (dc_param_gram_block): 256 column classes (column mod 256) summed ascending, then a fixed binary tree over the classes —
 // the same operations whatever the size of the team, and the same for (a, b) and (b, a) with the factors of every product swapped: the block of (b, a) is the exact transpose.
 // Switch parameters (pgo_covariance) add one right-hand-side row each and Gram products of 6- and 1-row blocks; a matrix-free handle's matrix is assembled from its normal
 // blocks: both further down, with their plans.
@@ -96,29 +96,8 @@ PGO_DC_HD void dc_backward_block(const Team& T, const double* a, double* v, doub
 // the four partial sums of a 64-term product (terms 16 q .. 16 q + 15 each, ascending) in the order the sweeps add them
 PGO_DC_HD double dc_sum4(double p0, double p1, double p2, double p3) { return (p0 + p1) + (p2 + p3); }
 
-// One 6 x 6 covariance block: out[i * 6 + j] = sum over the columns c0 <= c < n of wa[i * ld + c] * wb[j * ld + c] (wa, wb: 6 consecutive rows of W; c0 a multiple of
-// DC_GRAM: the columns before it hold zeros in one of the two).  part[6 * DC_GRAM] is shared by the team.  Team size: 1, or a divisor of DC_GRAM.  The caller syncs before.
+// the Gram products' column classes (dc_param_gram_block)
 constexpr int DC_GRAM = 256;
-template <class Team>
-PGO_DC_HD void dc_gram_block(const Team& T, const double* wa, const double* wb, size_t ld, int n, int c0, double* part, double* out) {
-    for (int i = 0; i < 6; ++i) {
-        for (int cls = T.rank(); cls < DC_GRAM; cls += T.size()) {
-            double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            for (int c = c0 + cls; c < n; c += DC_GRAM) {
-                const double a = wa[(size_t)i * ld + c];
-                for (int j = 0; j < 6; ++j) acc[j] = acc[j] + a * wb[(size_t)j * ld + c];
-            }
-            for (int j = 0; j < 6; ++j) part[j * DC_GRAM + cls] = acc[j];
-        }
-        T.sync();
-        for (int s = DC_GRAM / 2; s >= 1; s >>= 1) {
-            for (int e = T.rank(); e < 6 * s; e += T.size()) { const int j = e / s, cls = e - j * s; part[j * DC_GRAM + cls] = part[j * DC_GRAM + cls] + part[j * DC_GRAM + cls + s]; }
-            T.sync();
-        }
-        if (T.rank() == 0) for (int j = 0; j < 6; ++j) out[i * 6 + j] = part[j * DC_GRAM];
-        T.sync();
-    }
-}
 
 // ---- the order of the block steps: what the launcher (one or two launches per call) and the host instantiation both run
 template <class Ops>
@@ -147,29 +126,6 @@ inline void dc_cov_steps(int n, int mt, const int32_t* start_tile, bool skip, Op
     }
 }
 
-// What the host prepares of a covariance request (pgo_dense.hip runs it for the kernels, dc_host_covariance below for the host instantiation): the requested "nodes"
-// (node i = rows 6 i .. 6 i + 5) deduplicated and sorted, six right-hand sides each, padded to whole tile rows.
-struct DcCovPlan {
-    int m = 0, mt = 0;                     // rows of W (a multiple of 64), its tile rows
-    std::vector<int32_t> col;              // [m] the column of the one of every right-hand side; -1: a padding row (all zeros)
-    std::vector<int32_t> start_tile;       // [mt]
-    std::vector<int32_t> row_a, row_b;     // per pair: the first of the six rows of W of node a / node b
-    DcCovPlan(int64_t n_pairs, const int32_t* ia, const int32_t* ib) {
-        std::vector<int32_t> uniq(ia, ia + n_pairs);
-        uniq.insert(uniq.end(), ib, ib + n_pairs);
-        std::sort(uniq.begin(), uniq.end());
-        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-        m = (int)((uniq.size() * 6 + DC_NB - 1) / DC_NB * DC_NB); mt = m / DC_NB;
-        col.assign((size_t)m, -1);
-        for (size_t u = 0; u < uniq.size(); ++u) for (int a = 0; a < 6; ++a) col[u * 6 + a] = uniq[u] * 6 + a;
-        for (int R = 0; R < mt; ++R) start_tile.push_back(col[(size_t)R * DC_NB] / DC_NB);
-        auto row_of = [&](int32_t node) { return (int32_t)(6 * (std::lower_bound(uniq.begin(), uniq.end(), node) - uniq.begin())); };
-        for (int64_t k = 0; k < n_pairs; ++k) { row_a.push_back(row_of(ia[k])); row_b.push_back(row_of(ib[k])); }
-    }
-    // the first column in which both nodes' right-hand sides may be non-zero, rounded down to the Gram's column classes
-    int gram_c0(int64_t pair) const { return std::max(col[(size_t)row_a[pair]], col[(size_t)row_b[pair]]) / DC_GRAM * DC_GRAM; }
-};
-
 // ---- covariance blocks of pose AND switch parameters (pgo_covariance).  With H = [H_pp C; C^T diag(h)] over the keyframes' tangent entries and one entry per switch, and
 // S = H_pp - C diag(h)^-1 C^T the Schur complement the factor is of, v_e = -c_e / h_e (twelve non-zeros: the rows of the edge's two keyframes) gives
 //   Sigma_pp = S^-1,   Sigma_p,e = S^-1 v_e,   Sigma_e,f = delta_ef / h_e + v_e^T S^-1 v_f:
@@ -196,8 +152,10 @@ PGO_DC_HD bool dc_param_rhs_row(double* wrow, int32_t col, const int32_t* sw_nod
     return false;
 }
 
-// One DA x DB block (DA, DB: 6 or 1), row-major in the leading DA DB entries of out[36], the rest 0: dc_gram_block's sums — column classes ascending, then the binary tree —
-// over DA rows of wa and DB rows of wb; <6, 6> is dc_gram_block operation for operation.  add: delta_ef / h_e of a switch paired with itself (else 0, not added).
+// One DA x DB block (DA, DB: 6 or 1), row-major in the leading DA DB entries of out[36], the rest 0: out[i * DB + j] = sum over the columns c0 <= c < n of
+// wa[i * ld + c] * wb[j * ld + c] — column classes ascending, then the binary tree — over DA rows of wa and DB rows of wb (consecutive rows of W; c0 a multiple of DC_GRAM:
+// the columns before it hold zeros in one of the two).  add: delta_ef / h_e of a switch paired with itself (else 0, not added).  part[6 * DC_GRAM] is shared by the team.
+// Team size: 1, or a divisor of DC_GRAM.  The caller syncs before.
 template <int DA, int DB, class Team>
 PGO_DC_HD void dc_param_gram_block(const Team& T, const double* wa, const double* wb, size_t ld, int n, int c0, bool with_add, double add, double* part, double* out) {
     for (int i = 0; i < DA; ++i) {
@@ -232,7 +190,7 @@ PGO_DC_HD void dc_param_gram(const Team& T, const double* wa, int da, const doub
 // What the host prepares of a pgo_covariance request: the requested block ids deduplicated, six unit rows per node and one row per switch, ordered by the first non-zero
 // column — the switch rows whose lower node is i, which start at column 6 i, then node i's own six rows, 6 i .. 6 i + 5; a switch without a node (both keyframes
 // constant: an all-zero row, its variance is 1 / h alone) after everything — so that each tile row's first non-zero column ascends and dc_cov_steps' "started rows are a
-// prefix" holds; padded to whole tile rows.  n: the order of the (padded) matrix.
+// prefix" holds; padded to whole tile rows.  n: the order of the (padded) matrix.  sw_node is read for ids >= n_nodes only: a request of nodes alone may pass nullptr.
 struct DcParamPlan {
     int m = 0, mt = 0;
     std::vector<int32_t> col;              // [m] as dc_param_rhs_row reads it
@@ -276,7 +234,7 @@ struct DcParamPlan {
             self_switch.push_back(ia[k] >= n_nodes && ia[k] == ib[k] ? ia[k] - n_nodes : -1);
         }
     }
-    // the first column in which both blocks' right-hand sides may be non-zero, rounded down to the Gram's column classes (a node's rows: that of its first row, as DcCovPlan)
+    // the first column in which both blocks' right-hand sides may be non-zero, rounded down to the Gram's column classes (a node's rows: that of its first row)
     int gram_c0(int64_t pair) const { return std::max(first_col[(size_t)row_a[(size_t)pair]], first_col[(size_t)row_b[(size_t)pair]]) / DC_GRAM * DC_GRAM; }
 };
 
@@ -433,28 +391,6 @@ struct DcHost {
             }
     }
 };
-
-// The 6 x 6 blocks (rows of node ia[k], columns of node ib[k]) of the inverse of the symmetric positive definite n x n matrix `a` (padded like dc_host_solve), n_pairs >= 1,
-// 0 <= ia, ib < n / 6.  Returns false — and leaves cov alone — when a pivot failed.
-inline bool dc_host_covariance(int n, const double* a, int64_t n_pairs, const int32_t* ia, const int32_t* ib, bool skip, double* cov) {
-    const int nc = (n + DC_NB - 1) / DC_NB * DC_NB;
-    std::vector<double> A((size_t)nc * nc, 0.0);
-    for (int i = 0; i < nc; ++i) {
-        if (i < n) { for (int j = 0; j < n; ++j) A[(size_t)i * nc + j] = a[(size_t)i * n + j]; }
-        else A[(size_t)i * nc + i] = 1.0;
-    }
-    DcHost H{nc, A.data(), nullptr, nullptr, nullptr};
-    dc_factor_steps(nc, H);
-    if (H.failed) return false;
-    const DcCovPlan Q(n_pairs, ia, ib);
-    std::vector<double> W((size_t)Q.m * nc, 0.0), part((size_t)6 * DC_GRAM);
-    for (int r = 0; r < Q.m; ++r) if (Q.col[(size_t)r] >= 0) W[(size_t)r * nc + Q.col[(size_t)r]] = 1.0;
-    H.W = W.data();
-    dc_cov_steps(nc, Q.mt, Q.start_tile.data(), skip, H);
-    for (int64_t k = 0; k < n_pairs; ++k)
-        dc_gram_block(DcSerial{}, W.data() + (size_t)Q.row_a[(size_t)k] * nc, W.data() + (size_t)Q.row_b[(size_t)k] * nc, (size_t)nc, nc, skip ? Q.gram_c0(k) : 0, part.data(), cov + 36 * k);
-    return true;
-}
 
 // pgo_covariance's blocks on the host: `a` is S (n x n, padded like dc_host_solve; node i = rows 6 i .. 6 i + 5, n / 6 nodes), the n_sw switches as DcParamPlan takes
 // them; block ids ia, ib in [0, n / 6 + n_sw).  cov: n_pairs x 36.  Returns false — and leaves cov alone — when a pivot failed or a requested switch's h is unusable.

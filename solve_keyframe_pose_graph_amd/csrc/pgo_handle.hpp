@@ -184,7 +184,7 @@ struct DenseState {
     DBuf<double> A;            // [n][n] row-major: the system, then its factor L on the lower triangle
     DBuf<double> scratch;      // the current panel, k-major (dense_scratch_doubles)
     DBuf<double> vec;          // w [n] (right-hand side, used up by the forward sweep) and y [n]
-    DBuf<double> cov; DBuf<int32_t> cov_idx;      // pgo_pose_covariance: right-hand sides, panel copy and blocks (dense_cov_doubles), index lists (dense_cov_ints); first call
+    DBuf<double> cov; DBuf<int32_t> cov_idx;      // pgo_pose_covariance, pgo_covariance: right-hand sides, panel copy and blocks (dense_cov_doubles), index lists (dense_param_ints); first call
     int n = 0;                 // 6 keyframes-of-the-handle, padded to a multiple of 64
     bool built = false;
 };
@@ -398,21 +398,14 @@ int dense_allocate(pgo_problem* p);      // build_graph: the buffers of this gra
 void dense_release(pgo_problem* p);      // build_graph for another solver
 int dense_step(pgo_problem* p, bool* ok, double* t_factored);      // lm_step: scatter, factor, failure flag, sweeps into C.x
 size_t dense_scratch_doubles(int n);
-// pgo_pose_covariance: the pairs' blocks of the inverse of the undamped reduced system at solve_begin's linearisation (every keyframe of a pair free)
-int dense_pose_covariance(pgo_problem* p, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* out, bool* ok);
-// ... and its launches on a factor (pgo_dense_spd_covariance runs exactly these): the request's plan, the buffers' sizes, the index upload, the launches, where the blocks land
-struct DcCovPlan;
-size_t dense_cov_doubles(int n, int m, int64_t n_pairs);
-size_t dense_cov_ints(int m, int64_t n_pairs);
-int dense_cov_upload(pgo_problem* p, const DcCovPlan& Q, std::vector<int32_t>& staging, int32_t* idx);
-int launch_dense_covariance(pgo_problem* p, const double* A, int n, const DcCovPlan& Q, double* work, const int32_t* idx);
-double* dense_cov_blocks(double* work, int n, int m);
-// pgo_covariance: pose and switch blocks on a block-CSR or a matrix-free graph (block ids: a free keyframe, or N + the internal index of a switchable edge; sw_node: per
-// switchable edge its two keyframes, -1 for a constant one) ...
+// pgo_pose_covariance, pgo_covariance: the pairs' blocks of the inverse of the undamped system at solve_begin's linearisation, pose and switch blocks, on a block-CSR or a
+// matrix-free graph (block ids: a free keyframe, or N + the internal index of a switchable edge; sw_node: per switchable edge its two keyframes, -1 for a constant one) ...
 int dense_param_covariance(pgo_problem* p, const std::vector<int32_t>& sw_node, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* out, bool* ok);
-// ... and its launches (pgo_dense_spd_param_covariance runs exactly these): index upload, the right-hand sides (before the factor: they share its failure flag), the
-// substitutions and Gram products on the factor.  Buffers: dense_cov_doubles / dense_param_ints; the blocks land at dense_cov_blocks.
+// ... and its launches (the two pgo_dense_spd_*covariance hooks run exactly these): index upload, the right-hand sides (before the factor: they share its failure flag),
+// the substitutions and Gram products on the factor.  Buffers: dense_cov_doubles / dense_param_ints; the blocks land at dense_cov_blocks.
 struct DcParamPlan;
+size_t dense_cov_doubles(int n, int m, int64_t n_pairs);
+double* dense_cov_blocks(double* work, int n, int m);
 size_t dense_param_ints(int m, int64_t n_pairs, int64_t n_sw);
 int dense_param_upload(pgo_problem* p, const DcParamPlan& Q, int64_t n_sw, const int32_t* sw_node, std::vector<int32_t>& staging, int32_t* idx);
 int launch_dense_param_rhs(pgo_problem* p, int n, const DcParamPlan& Q, double* work, const int32_t* idx, const double* sw_c, const double* sw_h, int32_t* fail);

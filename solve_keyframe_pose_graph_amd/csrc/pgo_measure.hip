@@ -293,9 +293,10 @@ int pgo_dense_spd_solve(pgo_problem* p, int32_t n, const double* a, const double
     return PGO_OK;
 }
 
-int pgo_dense_spd_covariance(pgo_problem* p, int32_t n, const double* a, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms) {
-    if (!p || n <= 0 || !a || n_pairs < 1 || !ia || !ib || !cov || launches < 1) return PGO_ERR_INVALID_ARG;
-    for (int64_t k = 0; k < n_pairs; ++k) if (ia[k] < 0 || ib[k] < 0 || ia[k] >= n / 6 || ib[k] >= n / 6) { p->err = "pgo_dense_spd_covariance: node index out of range (node i = rows 6 i .. 6 i + 5)"; return PGO_ERR_INVALID_ARG; }
+// The covariance launches on a symmetric positive definite matrix and n_sw >= 0 switch columns, arguments checked by the two hooks below: the right-hand sides, the
+// factorisation, the substitutions and the Gram products between one pair of events, `launches` times
+static int dense_spd_covariance_launches(pgo_problem* p, int32_t n, const double* a, int32_t n_sw, const int32_t* sw_node, const double* sw_c, const double* sw_h,
+                                         int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms) {
     int rc;
     if ((rc = set_device(p)) != PGO_OK) return rc;
     const int nc = (n + 63) / 64 * 64;
@@ -304,53 +305,7 @@ int pgo_dense_spd_covariance(pgo_problem* p, int32_t n, const double* a, int64_t
         if (i < n) std::memcpy(&h[(size_t)i * nc], a + (size_t)i * n, (size_t)n * sizeof(double));
         else h[(size_t)i * nc + i] = 1.0;
     }
-    const DcCovPlan Q(n_pairs, ia, ib);
-    DBuf<double> d_a, d_scr, d_work; DBuf<int32_t> d_idx, d_fail;
-    HIPCHK(p, d_a.ensure((size_t)nc * nc)); HIPCHK(p, d_scr.ensure(dense_scratch_doubles(nc))); HIPCHK(p, d_work.ensure(dense_cov_doubles(nc, Q.m, n_pairs)));
-    HIPCHK(p, d_idx.ensure(dense_cov_ints(Q.m, n_pairs))); HIPCHK(p, d_fail.ensure(1));
-    std::vector<int32_t> staging;
-    if ((rc = dense_cov_upload(p, Q, staging, d_idx.p)) != PGO_OK) return rc;
-    EventPair ev;
-    HIPCHK(p, ev.create());
-    float total = 0;
-    int32_t fail = 0;
-    for (int l = 0; l < launches && !fail; ++l) {
-        HIPCHK(p, hipMemcpyAsync(d_a.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, p->st));
-        HIPCHK(p, hipMemsetAsync(d_fail.p, 0, sizeof(int32_t), p->st));
-        HIPCHK(p, hipEventRecord(ev.e0, p->st));
-        launch_dense_factor(d_a.p, nc, d_scr.p, d_fail.p, false, p->st);
-        if ((rc = launch_dense_covariance(p, d_a.p, nc, Q, d_work.p, d_idx.p)) != PGO_OK) return rc;      // (a failed factor: numbers nobody reads — inside their own buffers)
-        HIPCHK(p, hipEventRecord(ev.e1, p->st));
-        HIPCHK(p, hipMemcpyAsync(&fail, d_fail.p, sizeof(fail), hipMemcpyDeviceToHost, p->st));
-        HIPCHK(p, hipStreamSynchronize(p->st));
-        float ms = 0;
-        HIPCHK(p, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-        total += ms;
-    }
-    if (avg_ms) *avg_ms = (double)total / launches;
-    if (fail) { p->err = "matrix is not numerically positive definite"; return PGO_ERR_NUMERIC; }
-    HIPCHK(p, hipMemcpy(cov, dense_cov_blocks(d_work.p, nc, Q.m), (size_t)36 * n_pairs * sizeof(double), hipMemcpyDeviceToHost));
-    return PGO_OK;
-}
-
-int pgo_dense_spd_param_covariance(pgo_problem* p, int32_t n, const double* a, int32_t n_sw, const int32_t* sw_node, const double* sw_c, const double* sw_h,
-                                   int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms) {
-    if (!p || n <= 0 || !a || n_sw < 0 || (n_sw > 0 && (!sw_node || !sw_c || !sw_h)) || n_pairs < 1 || !ia || !ib || !cov || launches < 1) return PGO_ERR_INVALID_ARG;
-    const int32_t nodes = n / 6;
-    for (int64_t k = 0; k < n_pairs; ++k) if (ia[k] < 0 || ib[k] < 0 || ia[k] >= nodes + n_sw || ib[k] >= nodes + n_sw) { p->err = "pgo_dense_spd_param_covariance: block id out of range (node i = rows 6 i .. 6 i + 5, then n / 6 + switch)"; return PGO_ERR_INVALID_ARG; }
-    for (int32_t s = 0; s < n_sw; ++s) {
-        const int32_t u = sw_node[2 * s], v = sw_node[2 * s + 1];
-        if (u < -1 || v < -1 || u >= nodes || v >= nodes || (u >= 0 && u == v)) { p->err = "pgo_dense_spd_param_covariance: a switch column's nodes must be distinct, below n / 6, or -1"; return PGO_ERR_INVALID_ARG; }
-    }
-    int rc;
-    if ((rc = set_device(p)) != PGO_OK) return rc;
-    const int nc = (n + 63) / 64 * 64;
-    std::vector<double> h((size_t)nc * nc, 0.0);
-    for (int i = 0; i < nc; ++i) {
-        if (i < n) std::memcpy(&h[(size_t)i * nc], a + (size_t)i * n, (size_t)n * sizeof(double));
-        else h[(size_t)i * nc + i] = 1.0;
-    }
-    const DcParamPlan Q(nc, nodes, sw_node, n_pairs, ia, ib);
+    const DcParamPlan Q(nc, n / 6, sw_node, n_pairs, ia, ib);
     DBuf<double> d_a, d_scr, d_work, d_c, d_h; DBuf<int32_t> d_idx, d_fail;
     HIPCHK(p, d_a.ensure((size_t)nc * nc)); HIPCHK(p, d_scr.ensure(dense_scratch_doubles(nc))); HIPCHK(p, d_work.ensure(dense_cov_doubles(nc, Q.m, n_pairs)));
     HIPCHK(p, d_idx.ensure(dense_param_ints(Q.m, n_pairs, n_sw))); HIPCHK(p, d_fail.ensure(1));
@@ -380,9 +335,27 @@ int pgo_dense_spd_param_covariance(pgo_problem* p, int32_t n, const double* a, i
         total += ms;
     }
     if (avg_ms) *avg_ms = (double)total / launches;
-    if (fail) { p->err = "matrix is not numerically positive definite, or a requested switch's h is not a positive finite number"; return PGO_ERR_NUMERIC; }
+    if (fail) { p->err = std::string("matrix is not numerically positive definite") + (n_sw ? ", or a requested switch's h is not a positive finite number" : ""); return PGO_ERR_NUMERIC; }
     HIPCHK(p, hipMemcpy(cov, dense_cov_blocks(d_work.p, nc, Q.m), (size_t)36 * n_pairs * sizeof(double), hipMemcpyDeviceToHost));
     return PGO_OK;
+}
+
+int pgo_dense_spd_covariance(pgo_problem* p, int32_t n, const double* a, int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms) {
+    if (!p || n <= 0 || !a || n_pairs < 1 || !ia || !ib || !cov || launches < 1) return PGO_ERR_INVALID_ARG;
+    for (int64_t k = 0; k < n_pairs; ++k) if (ia[k] < 0 || ib[k] < 0 || ia[k] >= n / 6 || ib[k] >= n / 6) { p->err = "pgo_dense_spd_covariance: node index out of range (node i = rows 6 i .. 6 i + 5)"; return PGO_ERR_INVALID_ARG; }
+    return dense_spd_covariance_launches(p, n, a, 0, nullptr, nullptr, nullptr, n_pairs, ia, ib, cov, launches, avg_ms);
+}
+
+int pgo_dense_spd_param_covariance(pgo_problem* p, int32_t n, const double* a, int32_t n_sw, const int32_t* sw_node, const double* sw_c, const double* sw_h,
+                                   int64_t n_pairs, const int32_t* ia, const int32_t* ib, double* cov, int32_t launches, double* avg_ms) {
+    if (!p || n <= 0 || !a || n_sw < 0 || (n_sw > 0 && (!sw_node || !sw_c || !sw_h)) || n_pairs < 1 || !ia || !ib || !cov || launches < 1) return PGO_ERR_INVALID_ARG;
+    const int32_t nodes = n / 6;
+    for (int64_t k = 0; k < n_pairs; ++k) if (ia[k] < 0 || ib[k] < 0 || ia[k] >= nodes + n_sw || ib[k] >= nodes + n_sw) { p->err = "pgo_dense_spd_param_covariance: block id out of range (node i = rows 6 i .. 6 i + 5, then n / 6 + switch)"; return PGO_ERR_INVALID_ARG; }
+    for (int32_t s = 0; s < n_sw; ++s) {
+        const int32_t u = sw_node[2 * s], v = sw_node[2 * s + 1];
+        if (u < -1 || v < -1 || u >= nodes || v >= nodes || (u >= 0 && u == v)) { p->err = "pgo_dense_spd_param_covariance: a switch column's nodes must be distinct, below n / 6, or -1"; return PGO_ERR_INVALID_ARG; }
+    }
+    return dense_spd_covariance_launches(p, n, a, n_sw, sw_node, sw_c, sw_h, n_pairs, ia, ib, cov, launches, avg_ms);
 }
 
 // Diagnostic (tests): sums of squares of what this rank's cycle kernels read of level `level` (1-based) — the same whichever way the set-up ran (pgo_options.mg_dist_setup)

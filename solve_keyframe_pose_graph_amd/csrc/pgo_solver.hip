@@ -677,58 +677,23 @@ int pgo_evaluate(pgo_problem* p, const double* q, const double* t, const double*
     return PGO_OK;
 }
 
-// Marginal covariances of keyframe poses (ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for pose blocks; the contract: include/pgo.h).  The handle is
-// linearised at the given point the way pgo_evaluate does it, and everything that carries over to the next solve is put back: the summary, the LM controller's state and
-// the two-level method's history across solves (solve_begin spends one solve of its back-off).
-int pgo_pose_covariance(pgo_problem* p, const double* q, const double* t, const double* sw, int64_t N, int64_t S, int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cov) {
+// The covariance blocks of pgo_pose_covariance and pgo_covariance (the contracts: include/pgo.h; the algebra: csrc/pgo_dense_math.hpp).  The handle is linearised at the
+// given point the way pgo_evaluate does it, and everything that carries over to the next solve is put back: the summary, the LM controller's state and the two-level
+// method's history across solves (solve_begin spends one solve of its back-off).  name: the entry point, for its messages.  pose_only (pgo_pose_covariance): ids at or
+// above N are out of range, and a handle without block-CSR values is refused — by its option before the graph is looked at, by its graph build after solve_begin.
+static int covariance_blocks(pgo_problem* p, const char* name, bool pose_only, const double* q, const double* t, const double* sw, int64_t N, int64_t S, int64_t n_pairs,
+                             const int32_t* block_a, const int32_t* block_b, double* cov) {
     if (!p) return PGO_ERR_INVALID_ARG;
-    if (n_pairs < 0 || (n_pairs > 0 && (!node_a || !node_b || !cov))) { p->err = "pgo_pose_covariance: null pair array or negative count"; return PGO_ERR_INVALID_ARG; }
-    if (p->in_solve) { p->err = "pgo_pose_covariance inside a solve (between pgo_solve_begin and pgo_solve_end)"; return PGO_ERR_STATE; }
-    if (p->comm || p->local_ids) { p->err = "pgo_pose_covariance: one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
-    if (p->opt.linear_solver == PGO_LINEAR_PCG_MATRIX_FREE) {
-        p->err = "pgo_pose_covariance: pgo_options.linear_solver = PGO_LINEAR_PCG_MATRIX_FREE keeps no block-CSR values to factor; select PGO_LINEAR_PCG_BLOCK_JACOBI or PGO_LINEAR_DENSE_CHOLESKY";
+    const std::string who = name;
+    if (n_pairs < 0 || (n_pairs > 0 && (!block_a || !block_b || !cov))) { p->err = who + ": null pair array or negative count"; return PGO_ERR_INVALID_ARG; }
+    if (p->in_solve) { p->err = who + " inside a solve (between pgo_solve_begin and pgo_solve_end)"; return PGO_ERR_STATE; }
+    if (p->comm || p->local_ids) { p->err = who + ": one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
+    if (pose_only && p->opt.linear_solver == PGO_LINEAR_PCG_MATRIX_FREE) {
+        p->err = who + ": pgo_options.linear_solver = PGO_LINEAR_PCG_MATRIX_FREE keeps no block-CSR values to factor; select PGO_LINEAR_PCG_BLOCK_JACOBI or PGO_LINEAR_DENSE_CHOLESKY";
         return PGO_ERR_STATE;
     }
-    if (N > PGO_DENSE_MAX_KEYFRAMES) { p->err = "pgo_pose_covariance: more than PGO_DENSE_MAX_KEYFRAMES (" + std::to_string(PGO_DENSE_MAX_KEYFRAMES) + ") keyframes"; return PGO_ERR_INVALID_ARG; }
-    std::vector<uint8_t> referenced((size_t)std::max<int64_t>(N, 0), 0);
-    auto mark = [&](int32_t n) { if (n >= 0 && n < N) referenced[(size_t)n] = 1; };
-    for (const HostClass* H : {&p->rel, &p->swe}) for (int64_t e = 0; e < H->size(); ++e) { mark(H->c1[e]); mark(H->c2[e]); }
-    for (const PriorDev& pr : p->priors) mark(pr.node);
-    for (int64_t k = 0; k < n_pairs; ++k) for (int32_t n : {node_a[k], node_b[k]}) {
-        if (n < 0 || n >= N) { p->err = "pgo_pose_covariance: keyframe index out of range"; return PGO_ERR_INVALID_ARG; }
-        if (!referenced[(size_t)n]) { p->err = "pgo_pose_covariance: keyframe " + std::to_string(n) + " is referenced by no residual block: it has no covariance"; return PGO_ERR_INVALID_ARG; }
-    }
-    struct Restore {      // (dense mode: solve_begin leaves the history alone, and a graph build for the exact solver resets it on purpose)
-        pgo_problem* p; pgo_summary sum; LmState lm; CoarseState::History hist;
-        ~Restore() { p->in_solve = false; p->sum = sum; p->lm = lm; if (!dense_mode(p)) p->coarse.hist = hist; }
-    } restore{p, p->sum, p->lm, p->coarse.hist};
-    int rc = solve_begin(p, q, t, sw, N, S);   // upload + K1 + K2 at the given point (a changed graph is built here)
-    if (rc != PGO_OK) return rc;
-    if (!std::isfinite(p->lm.x_cost)) { p->err = "pgo_pose_covariance: the cost at this point is not finite"; return PGO_ERR_NUMERIC; }
-    if (p->built_mf) { p->err = "pgo_pose_covariance: the graph was built matrix-free"; return PGO_ERR_STATE; }
-    // pairs with a constant keyframe: zero blocks (constant keyframes are not parameters); the others go to the device
-    std::vector<int32_t> ia, ib; std::vector<int64_t> where;
-    for (int64_t k = 0; k < n_pairs; ++k) if (p->h_node_free[(size_t)node_a[k]] && p->h_node_free[(size_t)node_b[k]]) { ia.push_back(node_a[k]); ib.push_back(node_b[k]); where.push_back(k); }
-    std::vector<double> blocks(ia.size() * 36);
-    if (!ia.empty()) {
-        bool ok = true;
-        if ((rc = dense_pose_covariance(p, (int64_t)ia.size(), ia.data(), ib.data(), blocks.data(), &ok)) != PGO_OK) { after_failure(p); return rc; }
-        if (!ok) { p->err = "pgo_pose_covariance: the undamped system is not numerically positive definite (is the gauge fixed: a regulariser or a constant keyframe?)"; return PGO_ERR_NUMERIC; }
-    }
-    std::fill(cov, cov + (size_t)n_pairs * 36, 0.0);
-    for (size_t u = 0; u < where.size(); ++u) std::memcpy(cov + (size_t)where[u] * 36, blocks.data() + u * 36, 36 * sizeof(double));
-    return PGO_OK;
-}
-
-// Covariance blocks of pose AND switch parameter blocks, on every kind of graph build (the contract: include/pgo.h; the algebra: csrc/pgo_dense_math.hpp).  The handle's
-// side is pgo_pose_covariance's: linearised as pgo_evaluate does it, everything that carries over to the next solve put back.
-int pgo_covariance(pgo_problem* p, const double* q, const double* t, const double* sw, int64_t N, int64_t S, int64_t n_pairs, const int32_t* block_a, const int32_t* block_b, double* cov) {
-    if (!p) return PGO_ERR_INVALID_ARG;
-    if (n_pairs < 0 || (n_pairs > 0 && (!block_a || !block_b || !cov))) { p->err = "pgo_covariance: null pair array or negative count"; return PGO_ERR_INVALID_ARG; }
-    if (p->in_solve) { p->err = "pgo_covariance inside a solve (between pgo_solve_begin and pgo_solve_end)"; return PGO_ERR_STATE; }
-    if (p->comm || p->local_ids) { p->err = "pgo_covariance: one GPU only: a communicator is attached"; return PGO_ERR_STATE; }
-    if (N > PGO_DENSE_MAX_KEYFRAMES) { p->err = "pgo_covariance: more than PGO_DENSE_MAX_KEYFRAMES (" + std::to_string(PGO_DENSE_MAX_KEYFRAMES) + ") keyframes"; return PGO_ERR_INVALID_ARG; }
-    if (N < 0 || S < 0) { p->err = "pgo_covariance: negative count"; return PGO_ERR_INVALID_ARG; }
+    if (N > PGO_DENSE_MAX_KEYFRAMES) { p->err = who + ": more than PGO_DENSE_MAX_KEYFRAMES (" + std::to_string(PGO_DENSE_MAX_KEYFRAMES) + ") keyframes"; return PGO_ERR_INVALID_ARG; }
+    if (N < 0 || S < 0) { p->err = who + ": negative count"; return PGO_ERR_INVALID_ARG; }
     std::vector<uint8_t> referenced((size_t)N, 0);
     auto mark = [&](int32_t n) { if (n >= 0 && n < N) referenced[(size_t)n] = 1; };
     for (const HostClass* H : {&p->rel, &p->swe}) for (int64_t e = 0; e < H->size(); ++e) { mark(H->c1[e]); mark(H->c2[e]); }
@@ -736,18 +701,23 @@ int pgo_covariance(pgo_problem* p, const double* q, const double* t, const doubl
     std::vector<int32_t> edge_of((size_t)S, -1);      // caller's switch index -> internal index of the switchable edge that uses it
     for (int64_t e = 0; e < p->swe.size(); ++e) if (p->swe.sw[e] >= 0 && p->swe.sw[e] < S) edge_of[(size_t)p->swe.sw[e]] = (int32_t)e;
     for (int64_t k = 0; k < n_pairs; ++k) for (int32_t id : {block_a[k], block_b[k]}) {
-        if (id < 0 || id >= N + S) { p->err = "pgo_covariance: block id out of range (keyframes 0 .. n_nodes - 1, then n_nodes + switch index)"; return PGO_ERR_INVALID_ARG; }
-        if (id < N && !referenced[(size_t)id]) { p->err = "pgo_covariance: keyframe " + std::to_string(id) + " is referenced by no residual block: it has no covariance"; return PGO_ERR_INVALID_ARG; }
-        if (id >= N && edge_of[(size_t)(id - N)] < 0) { p->err = "pgo_covariance: switch " + std::to_string(id - N) + " is used by no switchable edge: it has no covariance"; return PGO_ERR_INVALID_ARG; }
+        if (id < 0 || id >= (pose_only ? N : N + S)) {
+            p->err = who + (pose_only ? ": keyframe index out of range" : ": block id out of range (keyframes 0 .. n_nodes - 1, then n_nodes + switch index)");
+            return PGO_ERR_INVALID_ARG;
+        }
+        if (id < N && !referenced[(size_t)id]) { p->err = who + ": keyframe " + std::to_string(id) + " is referenced by no residual block: it has no covariance"; return PGO_ERR_INVALID_ARG; }
+        if (id >= N && edge_of[(size_t)(id - N)] < 0) { p->err = who + ": switch " + std::to_string(id - N) + " is used by no switchable edge: it has no covariance"; return PGO_ERR_INVALID_ARG; }
     }
-    struct Restore {      // (as in pgo_pose_covariance)
+    struct Restore {      // (dense mode: solve_begin leaves the history alone, and a graph build for the exact solver resets it on purpose)
         pgo_problem* p; pgo_summary sum; LmState lm; CoarseState::History hist;
         ~Restore() { p->in_solve = false; p->sum = sum; p->lm = lm; if (!dense_mode(p)) p->coarse.hist = hist; }
     } restore{p, p->sum, p->lm, p->coarse.hist};
     int rc = solve_begin(p, q, t, sw, N, S);   // upload + K1 + K2 at the given point (a changed graph is built here, for the handle's own linear solver)
     if (rc != PGO_OK) return rc;
-    if (!std::isfinite(p->lm.x_cost)) { p->err = "pgo_covariance: the cost at this point is not finite"; return PGO_ERR_NUMERIC; }
-    // pairs with a constant keyframe: zero blocks, filled in here; the others go to the device with keyframe ids as they are and switch ids by internal edge index
+    if (!std::isfinite(p->lm.x_cost)) { p->err = who + ": the cost at this point is not finite"; return PGO_ERR_NUMERIC; }
+    if (pose_only && p->built_mf) { p->err = who + ": the graph was built matrix-free"; return PGO_ERR_STATE; }
+    // pairs with a constant keyframe: zero blocks (constant keyframes are not parameters), filled in here; the others go to the device with keyframe ids as they are and
+    // switch ids by internal edge index
     auto is_free = [&](int32_t n) { return p->h_node_free[(size_t)n] != 0; };
     std::vector<int32_t> ia, ib; std::vector<int64_t> where;
     for (int64_t k = 0; k < n_pairs; ++k) {
@@ -762,13 +732,24 @@ int pgo_covariance(pgo_problem* p, const double* q, const double* t, const doubl
         bool ok = true;
         if ((rc = dense_param_covariance(p, sw_node, (int64_t)ia.size(), ia.data(), ib.data(), blocks.data(), &ok)) != PGO_OK) { after_failure(p); return rc; }
         if (!ok) {
-            p->err = "pgo_covariance: the undamped system is not numerically positive definite (is the gauge fixed: a regulariser or a constant keyframe?), or a requested switch's J_s^T J_s is not a positive finite number";
+            p->err = who + ": the undamped system is not numerically positive definite (is the gauge fixed: a regulariser or a constant keyframe?)" +
+                     (pose_only ? "" : ", or a requested switch's J_s^T J_s is not a positive finite number");
             return PGO_ERR_NUMERIC;
         }
     }
     std::fill(cov, cov + (size_t)n_pairs * 36, 0.0);
     for (size_t u = 0; u < where.size(); ++u) std::memcpy(cov + (size_t)where[u] * 36, blocks.data() + u * 36, 36 * sizeof(double));
     return PGO_OK;
+}
+
+// Marginal covariances of keyframe poses (ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for pose blocks), on a handle that keeps block-CSR values
+int pgo_pose_covariance(pgo_problem* p, const double* q, const double* t, const double* sw, int64_t N, int64_t S, int64_t n_pairs, const int32_t* node_a, const int32_t* node_b, double* cov) {
+    return covariance_blocks(p, "pgo_pose_covariance", true, q, t, sw, N, S, n_pairs, node_a, node_b, cov);
+}
+
+// Covariance blocks of pose AND switch parameter blocks, on every kind of graph build
+int pgo_covariance(pgo_problem* p, const double* q, const double* t, const double* sw, int64_t N, int64_t S, int64_t n_pairs, const int32_t* block_a, const int32_t* block_b, double* cov) {
+    return covariance_blocks(p, "pgo_covariance", false, q, t, sw, N, S, n_pairs, block_a, block_b, cov);
 }
 
 int pgo_get_jacobian_blocks(pgo_problem* p, int32_t kind, int64_t first, int64_t count, double* J1, double* J2, double* dr_ds) {

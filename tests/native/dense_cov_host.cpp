@@ -5,9 +5,9 @@
 #include "pgo_dense_math.hpp"
 
 extern "C" {
-// 1: computed; 0: a pivot was not positive (cov untouched).  cov: n_pairs x 36
+// 1: computed; 0: a pivot was not positive (cov untouched).  cov: n_pairs x 36.  Node blocks only (0 <= ia, ib < n / 6): a request without switches
 int dcv_covariance(int n, const double* a, long long n_pairs, const int* ia, const int* ib, int skip, double* cov) {
-    return pgo::dc_host_covariance(n, a, n_pairs, ia, ib, skip != 0, cov) ? 1 : 0;
+    return pgo::dc_host_param_covariance(n, a, nullptr, nullptr, nullptr, n_pairs, ia, ib, skip != 0, cov) ? 1 : 0;
 }
 }
 

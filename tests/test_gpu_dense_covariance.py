@@ -2,7 +2,7 @@
 
   1. the kernels alone against the refined reference;  2. through the handle, the reference formed from the handle's own normal blocks (the same H);  3. against the CPU
   checker's H, with the first-order term for the difference of the two matrices;  4. constant and unreferenced keyframes;  5. robust edges;  6. the contract;  7. no
-  footprint on the handle's next solve.
+  footprint on the handle's next solve;  8. the recorded bits.
 
 Reference, error measure e and the bound 8 x e_np: tests/dense_cov_ref.py.  Every test prints its figures (`DENSECOV ...`) before it asserts;
 profiles/dense_covariance_check.txt records them.
@@ -22,6 +22,7 @@ import pytest
 
 from solve_keyframe_pose_graph_amd import capi, graphgen
 from tests import dense_cov_ref as ref
+from tests import pose_cov_cases
 from tests import precond_cases as pc
 from tests import util
 
@@ -287,3 +288,22 @@ def test_the_call_leaves_no_footprint_on_the_next_solve():
     for x, y in zip(second_a[:3], second_b[:3]):
         assert np.array_equal(x, y)
     assert second_a[3].cg_iterations == second_b[3].cg_iterations and second_a[3].termination_type == second_b[3].termination_type
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+# 8. the recorded bits
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", pose_cov_cases.CASES)
+def test_the_blocks_are_the_recorded_bits(name):
+    """tests/golden/pose_covariance_bits.json holds what the pose-only launches returned before pgo_pose_covariance moved onto pgo_covariance's device path
+    (scripts/record_pose_covariance_bits.py; the cases: tests/pose_cov_cases.py).  Equal bits, no tolerance; covariance() on the same pose pairs returns them too."""
+    with open(os.path.join(ROOT, "tests", "golden", "pose_covariance_bits.json")) as f:
+        rec = json.load(f)["cases"][name]
+    want = np.array([[float.fromhex(v) for v in blk] for blk in rec]).reshape(-1, 6, 6)
+    got = pose_cov_cases.run(name)
+    differ = int((got["pose"] != want).sum()) if got["pose"].shape == want.shape else -1
+    print("DENSECOV recorded %-16s %4d blocks  %d entries differ  max |difference| %.3e" % (name, len(want), differ, np.abs(got["pose"] - want).max() if differ >= 0 else np.nan))
+    assert np.isfinite(want).all() and all(np.any(blk != 0.0) for blk in want)
+    assert np.array_equal(got["pose"], want)
+    if name.startswith("loops24"):
+        assert np.array_equal(got["covariance"], want)

@@ -95,22 +95,26 @@ def test_the_transposed_pair_is_the_exact_transpose_for_every_combination_of_siz
 
 
 def test_pose_pose_blocks_are_the_bits_of_the_pose_only_routine(shim):
-    """the rows of W do not interact: the switch rows beside them change no bit of the keyframes' blocks (tests/native/dense_cov_host.cpp: the routine of pgo_pose_covariance)"""
+    """the rows of W do not interact: the switch rows beside them change no bit of the keyframes' blocks — requested alone with the switch columns known, and through
+    tests/native/dense_cov_host.cpp, the request of pgo_pose_covariance: no switches at all.  One tile; padding and node 10 across the tile edge; three tiles."""
     so = os.path.join(HERE, "native", "libdense_cov_host.so")
     src = os.path.join(HERE, "native", "dense_cov_host.cpp")
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(os.path.join(INC, "pgo_dense_math.hpp"))):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I", INC, "-o", so, src])
-    old = C.CDLL(so)
-    n = 192
-    S, nodes, c, h = pref.spd_case(n)
-    N = n // 6
-    pp = [(0, 0), (31, 31), (10, 10), (0, 31), (1, 30), (30, 1)]
-    pairs = pp + [(N + s, N + s) for s in range(len(h))] + [(7, N + 3)]
-    _, cov = host_covariance(shim, S, nodes, c, h, pairs)
-    ia, ib = I32([a for a, _ in pp]), I32([b for _, b in pp])
-    want = np.zeros((len(pp), 36))
-    assert old.dcv_covariance(C.c_int(n), F64(S).ctypes.data_as(dp), C.c_longlong(len(pp)), ia.ctypes.data_as(ip), ib.ctypes.data_as(ip), C.c_int(1), want.ctypes.data_as(dp)) == 1
-    assert np.array_equal(cov[:len(pp)], want)
+    pose_only = C.CDLL(so)
+    for n in (64, 66, 192):
+        S, nodes, c, h = pref.spd_case(n)
+        N = n // 6
+        last, mid = N - 1, min(10, N - 1)
+        pp = [(0, 0), (last, last), (mid, mid), (0, last), (1, last - 1), (last - 1, 1)]
+        pairs = pp + [(N + s, N + s) for s in range(len(h))] + [(7, N + 3)]
+        _, cov = host_covariance(shim, S, nodes, c, h, pairs)
+        ok, alone = host_covariance(shim, S, nodes, c, h, pp)
+        ia, ib = I32([a for a, _ in pp]), I32([b for _, b in pp])
+        want = np.zeros((len(pp), 36))
+        assert pose_only.dcv_covariance(C.c_int(n), F64(S).ctypes.data_as(dp), C.c_longlong(len(pp)), ia.ctypes.data_as(ip), ib.ctypes.data_as(ip), C.c_int(1), want.ctypes.data_as(dp)) == 1
+        assert ok and np.isfinite(want).all() and np.all(want[:3, 0] > 0.0), n      # (the first three pairs: variances)
+        assert np.array_equal(cov[:len(pp)], alone) and np.array_equal(cov[:len(pp)], want), n
 
 
 def test_a_bad_h_and_an_indefinite_matrix_are_reported_and_nothing_is_written(shim):
