@@ -1,0 +1,89 @@
+/* pgo_sparse.h — C-ABI of libpgo_sparse.so: a tile-sparse exact Cholesky factorisation on the GPU (gfx950, fp64) for pose-graph systems above
+ * PGO_DENSE_MAX_KEYFRAMES, and covariance blocks from it.  A companion of libpgo.so, not a part of it: it links no libpgo.so, takes no pgo_problem and has no
+ * option in pgo_options.  A caller carries a handle's system across with pgo_get_normal_blocks (every handle has it, matrix-free ones too) and
+ * pgo_sparse_reduce_normal_blocks below.  Error codes are pgo.h's PGO_ERR_*.
+ *
+ * The matrix: n = 6 n_nodes rows padded to a multiple of 64, the keyframes in a permuted order (natural or reverse Cuthill-McKee), identity on the rows of
+ * keyframes outside the system and on the padding; only the 64 x 64 tiles of the lower triangle in which the factor L can be non-zero are stored (tile-level
+ * symbolic Cholesky).  With nt = n / 64 tile columns and s_k the tile rows below the diagonal of column k of L:
+ *
+ *   launches of one factorisation:  1 (diagonal tile 0) + per column k < nt - 1: panel (|s_k| workgroups) + update (|s_k| (|s_k| + 1) / 2 workgroups), and one
+ *                                   more for the diagonal tile k + 1 when k + 1 is not in s_k; an empty s_k: that one alone.  (info8[5])
+ *   launches of one pair of sweeps: 2 nt, whatever the number of right-hand sides: a workgroup handles one right-hand side, grid.y = n_rhs.  (info8[6])
+ *
+ * Nothing waits on another workgroup inside a launch, there are no atomics, every sum has a fixed order: two calls give the same bits.  In natural order the
+ * numbers are those of pgo_dense_spd_solve on the same matrix.  All arrays are host arrays; every call returns after its work is done.
+ * device_id: a HIP device, or -1 for the current one (pgo_options.device_id's convention); an object stays on the device it was created on. */
+#ifndef PGO_SPARSE_H
+#define PGO_SPARSE_H
+#include <stdint.h>
+
+#include "pgo.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define PGO_SPARSE_MAX_RHS 65535      /* right-hand sides of one pgo_sparse_chol_solve: the sweeps put them on grid.y */
+#define PGO_SPARSE_MAX_GROUPS 64      /* row groups of one pgo_sparse_chol_inverse_blocks */
+
+/* sc_plan_graph's `ordering` */
+enum { PGO_SPARSE_ORDER_AUTO = -1, PGO_SPARSE_ORDER_NATURAL = 0, PGO_SPARSE_ORDER_RCM = 1 };
+
+typedef struct pgo_sparse_chol pgo_sparse_chol;
+
+/* Solves a x = b for the symmetric positive definite n x n row-major matrix `a` with the tile-sparse kernels; row i at position pos[i] (a permutation of
+ * 0 .. n - 1; NULL: where it is).  The tile pattern is that of the exact non-zeros of the lower triangle.  info8 (may be NULL): nt, tiles of the matrix,
+ * tiles of L, 0, bytes of the tile storage, launches of one factorisation, of one pair of sweeps, tile updates.  The factor and the sweeps run `launches`
+ * (>= 1) times between HIP events; *avg_ms (may be NULL): their average.  Launches per run: info8[5] + info8[6].
+ * PGO_ERR_NUMERIC: a pivot was not > 0 (or NaN); x is left alone. */
+int pgo_sparse_spd_solve(int32_t device_id, int32_t n, const double* a, const double* b, const int32_t* pos, double* x, int64_t* info8, int32_t launches, double* avg_ms);
+
+/* Symbolic phase.  n_nodes keyframes; in_system[i] = 0: a constant or unreferenced keyframe (identity rows).  The n_pairs off-diagonal blocks of the system:
+ * pair_hi[k], pair_lo[k] — two distinct keyframes of the system (any of the two may be the higher), every pair once, else PGO_ERR_INVALID_ARG.
+ * ordering: PGO_SPARSE_ORDER_*.  Allocates the plan's device tables, the tile storage and the panel scratch on device_id.  No launch. */
+int pgo_sparse_chol_create(int32_t device_id, int64_t n_nodes, const uint8_t* in_system, int64_t n_pairs, const int32_t* pair_hi, const int32_t* pair_lo, int32_t ordering, pgo_sparse_chol** out);
+void pgo_sparse_chol_destroy(pgo_sparse_chol* h);
+
+/* info8: as pgo_sparse_spd_solve's, the ordering used (0 natural, 1 reverse Cuthill-McKee) in slot 3.  order (may be NULL) [n_nodes]: the keyframe at every
+ * position.  No launch. */
+int pgo_sparse_chol_info(const pgo_sparse_chol* h, int64_t* info8, int32_t* order);
+
+/* Numeric phase.  diag [n_nodes][36]: the diagonal blocks, row-major (those of keyframes outside the system are not read); pair_blocks [n_pairs][36]: the
+ * block of pair k, rows of pair_hi[k], columns of pair_lo[k].  Launches: 1 (fill: pure copies into the zeroed tiles) + info8[5].
+ * PGO_ERR_NUMERIC: a pivot was not > 0 (or NaN); the object has no factor then and takes another pgo_sparse_chol_factor. */
+int pgo_sparse_chol_factor(pgo_sparse_chol* h, const double* diag, const double* pair_blocks);
+
+/* X = A^-1 B for n_rhs right-hand sides, 1 <= n_rhs <= PGO_SPARSE_MAX_RHS; rows of B and X: 6 n_nodes doubles in the caller's keyframe order.  Entries of
+ * keyframes outside the system are not read and come back exactly 0.  Launches: info8[6] = 2 nt.  Right-hand side r gets the bits it gets alone. */
+int pgo_sparse_chol_solve(pgo_sparse_chol* h, int64_t n_rhs, const double* B, double* X);
+
+/* Blocks of the inverse between sparse rows.  n_groups (1 .. PGO_SPARSE_MAX_GROUPS) groups of 1 or 6 rows: group g = rows group_ptr[g] .. group_ptr[g + 1] - 1;
+ * row r = entries row_ptr[r] .. row_ptr[r + 1] - 1 of (col, val), col ascending, over the 6 n_nodes coordinates of the caller's keyframe order, on keyframes
+ * of the system only.  out[36 k] = V_ga[k] A^-1 V_gb[k]^T, a d_a x d_b block row-major in the leading entries of its 36, the rest 0 (pgo_covariance's
+ * layout).  Launches: 1 (the right-hand sides P v, copies) + nt - k0 (forward sweep only, all rows at once, from the first tile k0 that holds a non-zero
+ * of any row: the skipped steps would write +0) + 1 (Gram products, dc_param_gram_block).  out of (b, a) is the exact transpose of out of (a, b).
+ * For a handful of blocks: one workgroup per right-hand side per tile. */
+int pgo_sparse_chol_inverse_blocks(pgo_sparse_chol* h, int64_t n_groups, const int64_t* group_ptr, const int64_t* row_ptr, const int32_t* col, const double* val,
+                                   int64_t n_pairs, const int32_t* ga, const int32_t* gb, double* out);
+
+/* Host only: the undamped Schur complement S of a handle's last linearisation as blocks, from pgo_get_normal_blocks' arrays (diag [n_nodes][36], offdiag
+ * [n_rel + n_sw][36]: J1^T J2 per edge, relative-pose then switchable, internal order; sw_c [n_sw][12]; sw_hss [n_sw]), the edges' endpoints in the same
+ * order and node_free [n_nodes] (0: constant).  Per free keyframe H_ii - sum c c^T / h over its switch sides; per pair of free keyframes the sum in edge order
+ * of J1^T J2 (transposed where c1 is the lower keyframe) minus c_hi c_lo^T / h for switchable edges.  Writes *n_pairs (<= n_rel + n_sw: the room pair_hi,
+ * pair_lo and s_blocks [.][36] must have), pairs sorted by (higher, lower) keyframe, pair_hi > pair_lo; s_diag [n_nodes][36], zero where not free. */
+int pgo_sparse_reduce_normal_blocks(int64_t n_nodes, const uint8_t* node_free, const double* diag, const double* offdiag, const double* sw_c, const double* sw_hss,
+                                    int64_t n_rel, const int32_t* rel_c1, const int32_t* rel_c2, int64_t n_sw, const int32_t* swe_c1, const int32_t* swe_c2,
+                                    int64_t* n_pairs, int32_t* pair_hi, int32_t* pair_lo, double* s_diag, double* s_blocks);
+
+/* HIP-event milliseconds of the launches of the object's last pgo_sparse_chol_factor (fill included), _solve or _inverse_blocks */
+double pgo_sparse_chol_last_ms(const pgo_sparse_chol* h);
+
+const char* pgo_sparse_strerror(int code);
+/* the text of the last error of this object; h = NULL: of the calling thread's last call that had no object (pgo_sparse_spd_solve, pgo_sparse_chol_create, ...) */
+const char* pgo_sparse_last_error(const pgo_sparse_chol* h);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

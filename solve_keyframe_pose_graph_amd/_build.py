@@ -87,6 +87,37 @@ def build_libpgo(force=False, verbose=False):
     return LIBPGO
 
 
+LIBSPARSE = os.path.join(_HERE, "libpgo_sparse.so")
+SPARSE_SOURCE = "pgo_sparse.hip"
+SPARSE_HEADERS = ["pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_math.hpp"]
+SPARSE_OBJ_DIR = os.path.join(_ROOT, "build", "obj_sparse")
+# every symbol include/pgo_sparse.h declares
+SPARSE_EXPORTS = ["pgo_sparse_spd_solve", "pgo_sparse_chol_create", "pgo_sparse_chol_destroy", "pgo_sparse_chol_info", "pgo_sparse_chol_factor", "pgo_sparse_chol_solve",
+                  "pgo_sparse_chol_inverse_blocks", "pgo_sparse_reduce_normal_blocks", "pgo_sparse_chol_last_ms", "pgo_sparse_strerror", "pgo_sparse_last_error"]
+
+
+def compile_libpgo_sparse(target, verbose=False, obj_dir=None):
+    """libpgo_sparse.so (csrc/pgo_sparse.hip, include/pgo_sparse.h): the tile-sparse Cholesky companion library.  One translation unit, compile_libpgo's reproducibility
+    flags, objects in a directory of their own; it does not link libpgo.so.  verbose: the kernels' resource usage on stderr."""
+    obj_dir = obj_dir or SPARSE_OBJ_DIR
+    os.makedirs(obj_dir, exist_ok=True)
+    stem = os.path.splitext(SPARSE_SOURCE)[0]
+    obj = os.path.join(obj_dir, stem + ".o")
+    cmd = [hipcc_path()] + HIP_FLAGS + ["-ffile-prefix-map=%s=." % _ROOT, "-cuid=" + stem, "-I", INCLUDE, "-I", CSRC, "-x", "hip", "-c", os.path.join(CSRC, SPARSE_SOURCE), "-o", obj]
+    if verbose:
+        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
+    subprocess.check_call(cmd)
+    subprocess.check_call([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", obj, "-o", target, "-Wl,--build-id=none"])
+    return target
+
+
+def build_libpgo_sparse(force=False, verbose=False):
+    deps = [os.path.join(CSRC, f) for f in [SPARSE_SOURCE] + SPARSE_HEADERS] + [os.path.join(INCLUDE, "pgo_sparse.h"), os.path.join(INCLUDE, "pgo.h")]
+    if force or _stale(LIBSPARSE, deps):
+        compile_libpgo_sparse(LIBSPARSE, verbose=verbose)
+    return LIBSPARSE
+
+
 LIBHOST = os.path.join(_HERE, "libpgo_host.so")
 
 
@@ -129,6 +160,7 @@ def build_example_ranks(force=False):
 def build_all(force=False):
     build_graphgen(force)
     build_libpgo(force)
+    build_libpgo_sparse(force)
     build_host(force)
     build_examples(force)
     build_example_ranks(force)

@@ -1,0 +1,605 @@
+// pgo_sparse.hip — libpgo_sparse.so (include/pgo_sparse.h): the tile-sparse exact Cholesky solver on the device.  The six kernels of pgo_dense.hip with the matrix
+// addressed through an ScPlan (pgo_sparse_math.hpp): tile storage `tiles` x 4096 doubles, the plan's tables on the device as int32.  The arithmetic of the diagonal
+// tile, the panel, the update and the two sweeps is COPIED from dc_first_block_kernel, dc_panel_kernel, dc_update_kernel, dc_forward_kernel and dc_backward_kernel —
+// the same MFMA operand maps (the comment above dc_panel_kernel), the same summation order, the block routines of pgo_dense_math.hpp — on purpose: the originals live in
+// an anonymous namespace of a translation unit of libpgo.so, which this library neither links nor changes.  In natural order the results are the dense solver's as numbers.
+//
+// Nothing waits on another workgroup inside a launch, there are no atomics, every sum has a fixed order.  The step order is sc_factor_steps / sc_solve_steps, nowhere
+// else.  The update finds its target tile by ScPlan::find's binary search in row_col, in device code (sc_find): no per-step pair table.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "pgo_sparse.h"
+#include "pgo_sparse_blocks.hpp"
+
+namespace pgo {
+
+namespace {
+
+typedef double sc_d4 __attribute__((ext_vector_type(4)));
+constexpr int SC_THREADS = 256;
+
+struct ScTeam {
+    __device__ __forceinline__ int rank() const { return (int)threadIdx.x; }
+    __device__ __forceinline__ int size() const { return SC_THREADS; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+};
+
+// the plan's tables on the device
+struct ScDev { const int32_t* row_ptr; const int32_t* row_col; const int32_t* col_ptr; const int32_t* col_row; const int32_t* col_tile; const int32_t* ahead; };
+
+// ScPlan::find: the id of tile (i, j), j <= i; -1: not in the pattern
+__device__ __forceinline__ int sc_find(const ScDev& P, int i, int j) {
+    int lo = P.row_ptr[i];
+    const int end = P.row_ptr[i + 1];
+    int hi = end;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (P.row_col[mid] < j) lo = mid + 1; else hi = mid; }
+    return lo < end && P.row_col[lo] == j ? lo : -1;
+}
+
+// a stored tile -> LDS, all of it (the part above the diagonal of a diagonal tile is never read)
+__device__ __forceinline__ void sc_load_tile(const double* __restrict__ t, double* __restrict__ l) {
+    for (int idx = threadIdx.x; idx < DC_NB * DC_NB; idx += SC_THREADS) l[(idx >> 6) * DC_LD + (idx & 63)] = t[idx];
+}
+// the factored tile's lower triangle -> its storage
+__device__ __forceinline__ void sc_store_lower(double* __restrict__ t, const double* __restrict__ l) {
+    for (int idx = threadIdx.x; idx < DC_NB * DC_NB; idx += SC_THREADS) {
+        const int r = idx >> 6, c = idx & 63;
+        if (c <= r) t[idx] = l[r * DC_LD + c];
+    }
+}
+
+// diag: the diagonal tile of step 0, and every later one that no update factors one step ahead (an empty s_k, or k + 1 not in s_k)
+__global__ __launch_bounds__(SC_THREADS) void sc_diag_kernel(double* __restrict__ T, int tile, int32_t* __restrict__ fail) {
+    __shared__ double l[DC_NB * DC_LD];
+    double* __restrict__ t = T + (size_t)tile * SC_TILE;
+    sc_load_tile(t, l);
+    __syncthreads();
+    const bool bad = dc_factor_block(ScTeam{}, l);
+    sc_store_lower(t, l);
+    if (threadIdx.x == 0 && bad) *fail = 1;
+}
+
+// panel(k): one workgroup per tile of s_k (dc_panel_kernel's substitution, one wavefront per 16 rows).  Writes L_ik in place and, k-major, into LT[64][ldu] at the
+// columns 64 e .. 64 e + 63 of the tile's POSITION e in s_k: the scratch is as wide as the longest s_k, not as the matrix.
+__global__ __launch_bounds__(SC_THREADS) void sc_panel_kernel(double* __restrict__ T, ScDev P, int k, int ldu, double* __restrict__ LT) {
+    __shared__ double l[DC_NB * DC_LD];
+    sc_load_tile(T + (size_t)(P.row_ptr[k + 1] - 1) * SC_TILE, l);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int e = (int)blockIdx.x;                                         // < |s_k|: the grid
+    const int x0 = e * DC_NB + wave * DC_SUB;
+    double* __restrict__ arow = T + (size_t)P.col_tile[P.col_ptr[k] + e] * SC_TILE + (size_t)(wave * DC_SUB + lr) * DC_NB;
+    sc_d4 Y[DC_NB / DC_SUB];
+#pragma unroll
+    for (int j = 0; j < DC_NB / DC_SUB; ++j) {
+        double r[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = arow[j * DC_SUB + lk + 4 * reg];
+        sc_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int m = 0; m < j; ++m)
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(j * DC_SUB + lr) * DC_LD + m * DC_SUB + 4 * kk + lk], Y[m][kk], acc, 0, 0, 0);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = r[reg] - acc[reg];
+#pragma unroll
+        for (int p = 0; p < DC_SUB; ++p) {
+            const double yp = __shfl(r[p >> 2], (p & 3) * 16 + lr) / l[(j * DC_SUB + p) * DC_LD + j * DC_SUB + p];
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int q = lk + 4 * reg;
+                const double lqp = l[(j * DC_SUB + (q > p ? q : p)) * DC_LD + j * DC_SUB + p];      // (q <= p: the diagonal entry, unused)
+                r[reg] = q == p ? yp : (q > p ? r[reg] - lqp * yp : r[reg]);
+            }
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            Y[j][reg] = r[reg];
+            arow[j * DC_SUB + lk + 4 * reg] = r[reg];
+            LT[(size_t)(j * DC_SUB + lk + 4 * reg) * ldu + x0 + lr] = r[reg];
+        }
+    }
+}
+
+// update(k): one workgroup per pair a >= b of positions in s_k, decoded from the 1-D block index p = a (a + 1) / 2 + b; the tile (s_k[a], s_k[b]) -= L_a L_b^T as
+// dc_update_kernel computes it, operands from the k-major copy.  Pair (0, 0) is tile (k + 1, k + 1) when ahead[k]: that workgroup keeps the tile in LDS and factors it.
+__global__ __launch_bounds__(SC_THREADS) void sc_update_kernel(double* __restrict__ T, ScDev P, int k, int ldu, const double* __restrict__ LT, int32_t* __restrict__ fail) {
+    __shared__ double a[DC_NB * DC_LD];
+    const int p = (int)blockIdx.x;                                         // < |s_k| (|s_k| + 1) / 2: the grid
+    int pa = (int)((sqrt(8.0 * (double)p + 1.0) - 1.0) * 0.5);
+    while (pa * (pa + 1) / 2 > p) --pa;
+    while ((pa + 1) * (pa + 2) / 2 <= p) ++pa;
+    const int pb = p - pa * (pa + 1) / 2;
+    const int c0 = P.col_ptr[k];
+    const int id = sc_find(P, P.col_row[c0 + pa], P.col_row[c0 + pb]);      // in the pattern by construction of the symbolic factorisation
+    if (id < 0) return;
+    double* __restrict__ t = T + (size_t)id * SC_TILE;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int i0 = wr * 32, j0 = wc * 32;                                  // inside the tile
+    const int ia = pa * DC_NB + i0, jb = pb * DC_NB + j0;                  // columns of the k-major copy
+    const bool ahead = p == 0 && P.ahead[k] != 0;                          // this workgroup owns the next diagonal tile
+    if (!(pa == pb && wr == 0 && wc == 1)) {                               // (that quadrant lies above the diagonal)
+        sc_d4 acc[2][2];
+        double old[2][2][4];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                acc[s][u] = sc_d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) old[s][u][reg] = t[(i0 + s * 16 + lk + 4 * reg) * DC_NB + j0 + u * 16 + lr];
+            }
+#pragma unroll
+        for (int kk = 0; kk < DC_NB / 4; ++kk) {
+            const size_t row = (size_t)(kk * 4 + lk) * ldu;
+            const double a0 = LT[row + ia + lr], a1 = LT[row + ia + 16 + lr], b0 = LT[row + jb + lr], b1 = LT[row + jb + 16 + lr];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const int i = i0 + s * 16 + lk + 4 * reg, j = j0 + u * 16 + lr;
+                    const double v = old[s][u][reg] - acc[s][u][reg];
+                    if (ahead) a[i * DC_LD + j] = v;      // (written to the tile once, as the factor)
+                    else t[i * DC_NB + j] = v;
+                }
+    }
+    if (!ahead) return;
+    __syncthreads();
+    const bool bad = dc_factor_block(ScTeam{}, a);
+    sc_store_lower(t, a);
+    if (threadIdx.x == 0 && bad) *fail = 1;
+}
+
+// forward(k), grid (1 + |s_k|, n_rhs): every workgroup solves L_kk y_k = w_k of its right-hand side in LDS; the first writes y_k, the one of position e takes
+// L_ik y_k off the 64 rows i = s_k[e] of w
+__global__ __launch_bounds__(SC_THREADS) void sc_forward_kernel(const double* __restrict__ T, ScDev P, int k, int nc, double* __restrict__ W, double* __restrict__ Yv) {
+    __shared__ double l[DC_NB * DC_LD];
+    __shared__ double v[DC_NB], y[DC_NB], part[DC_NB * 4];
+    const int k0 = k * DC_NB, tid = threadIdx.x;
+    double* __restrict__ w = W + (size_t)blockIdx.y * nc;
+    double* __restrict__ yv = Yv + (size_t)blockIdx.y * nc;
+    sc_load_tile(T + (size_t)(P.row_ptr[k + 1] - 1) * SC_TILE, l);
+    if (tid < DC_NB) v[tid] = w[k0 + tid];
+    __syncthreads();
+    dc_forward_block(ScTeam{}, l, v, y);
+    if (blockIdx.x == 0) { if (tid < DC_NB) yv[k0 + tid] = y[tid]; return; }
+    const int e = P.col_ptr[k] + (int)blockIdx.x - 1;
+    const int i0 = P.col_row[e] * DC_NB;
+    const int r = tid >> 2, q = tid & 3;
+    const double* __restrict__ arow = T + (size_t)P.col_tile[e] * SC_TILE + (size_t)r * DC_NB;
+    double s = 0.0;
+#pragma unroll
+    for (int c = 16 * q; c < 16 * q + 16; ++c) s += arow[c] * y[c];
+    part[r * 4 + q] = s;
+    __syncthreads();
+    if (tid < DC_NB) w[i0 + tid] -= dc_sum4(part[tid * 4], part[tid * 4 + 1], part[tid * 4 + 2], part[tid * 4 + 3]);
+}
+
+// backward(k), grid (tiles of tile row k, n_rhs): every workgroup solves L_kk^T x_k = y_k; the one of the diagonal tile writes x_k, the one of tile (k, j) takes
+// L_kj^T x_k off the 64 entries j of y
+__global__ __launch_bounds__(SC_THREADS) void sc_backward_kernel(const double* __restrict__ T, ScDev P, int k, int nc, double* __restrict__ Yv, double* __restrict__ X) {
+    __shared__ double l[DC_NB * DC_LD];
+    __shared__ double v[DC_NB], xs[DC_NB], part[DC_NB * 4];
+    const int k0 = k * DC_NB, tid = threadIdx.x;
+    double* __restrict__ yv = Yv + (size_t)blockIdx.y * nc;
+    const int diag = P.row_ptr[k + 1] - 1, id = P.row_ptr[k] + (int)blockIdx.x;      // <= diag: the grid
+    sc_load_tile(T + (size_t)diag * SC_TILE, l);
+    if (tid < DC_NB) v[tid] = yv[k0 + tid];
+    __syncthreads();
+    dc_backward_block(ScTeam{}, l, v, xs);
+    if (id == diag) { if (tid < DC_NB) X[(size_t)blockIdx.y * nc + k0 + tid] = xs[tid]; return; }
+    const int j0 = P.row_col[id] * DC_NB;
+    const double* __restrict__ t = T + (size_t)id * SC_TILE;
+    const int c = tid & 63, q = tid >> 6;
+    double s = 0.0;
+#pragma unroll
+    for (int r = 16 * q; r < 16 * q + 16; ++r) s += t[r * DC_NB + c] * xs[r];
+    part[c * 4 + q] = s;
+    __syncthreads();
+    if (tid < DC_NB) yv[j0 + tid] -= dc_sum4(part[tid * 4], part[tid * 4 + 1], part[tid * 4 + 2], part[tid * 4 + 3]);
+}
+
+// fill: the caller's blocks into the zeroed tiles under the permutation (sc_block_entry), ones on the diagonal of the rows outside the system and of the padding.  One
+// thread per entry: 36 per keyframe, the padding, 36 per pair.  Pure copies, one writer per address.
+__global__ __launch_bounds__(SC_THREADS) void sc_fill_kernel(double* __restrict__ T, ScDev P, int64_t N, int nc, const uint8_t* __restrict__ in_system, const int32_t* __restrict__ pos,
+                                                             const double* __restrict__ diag, int64_t n_pairs, const int32_t* __restrict__ hi, const int32_t* __restrict__ lo, const double* __restrict__ blocks) {
+    const int64_t gid = (int64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+    const int64_t n36 = N * 36, pad = (int64_t)nc - N * 6;
+    int row, col;
+    double v;
+    if (gid < n36) {
+        const int64_t node = gid / 36;
+        const int e = (int)(gid - node * 36), a = e / 6, c = e - a * 6;
+        if (!sc_block_entry(pos[node], pos[node], a, c, &row, &col)) return;
+        if (in_system[node]) v = diag[gid];
+        else if (a == c) v = 1.0;
+        else return;
+    } else if (gid < n36 + pad) {
+        row = col = (int)(N * 6 + (gid - n36));
+        v = 1.0;
+    } else {
+        const int64_t u = gid - n36 - pad, k = u / 36;
+        if (k >= n_pairs) return;
+        const int e = (int)(u - k * 36), a = e / 6, c = e - a * 6;
+        sc_block_entry(pos[hi[k]], pos[lo[k]], a, c, &row, &col);
+        v = blocks[u];
+    }
+    const int id = sc_find(P, row / DC_NB, col / DC_NB);
+    if (id < 0) return;                                                    // (the pattern was made from these very pairs)
+    T[(size_t)id * SC_TILE + (size_t)(row % DC_NB) * DC_NB + col % DC_NB] = v;
+}
+
+// the right-hand sides of the inverse blocks: every non-zero of P v into the zeroed W (the host checked that no two meet)
+__global__ __launch_bounds__(SC_THREADS) void sc_rhs_kernel(double* __restrict__ W, int64_t nnz, const int64_t* __restrict__ at, const double* __restrict__ val) {
+    const int64_t gid = (int64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+    if (gid < nnz) W[at[gid]] = val[gid];
+}
+
+// gram: one workgroup per requested pair, pr[3 pair ..]: the first rows of Y of the two groups and their sizes (d_a | d_b << 8); dc_param_gram_block over the columns from c0 on
+__global__ __launch_bounds__(SC_THREADS) void sc_gram_kernel(const double* __restrict__ Y, int nc, int c0, const int32_t* __restrict__ pr, double* __restrict__ out) {
+    __shared__ double part[6 * DC_GRAM];
+    const size_t pair = blockIdx.x;
+    const int32_t* q = pr + 3 * pair;
+    dc_param_gram(ScTeam{}, Y + (size_t)q[0] * nc, q[2] & 255, Y + (size_t)q[1] * nc, q[2] >> 8, (size_t)nc, nc, c0, false, 0.0, part, out + 36 * pair);
+}
+
+// ---- host side
+thread_local std::string g_err;      // the last error of a call without an object
+
+struct DevBuf {
+    void* p = nullptr; size_t bytes = 0;
+    hipError_t ensure(size_t b) {
+        if (b <= bytes && p) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr; bytes = 0;
+        const hipError_t e = hipMalloc(&p, b ? b : 8);
+        if (e == hipSuccess) bytes = b ? b : 8; else p = nullptr;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    template <class V> V* as() const { return static_cast<V*>(p); }
+};
+
+#define SCHIP(err, call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) { (err) = std::string(#call) + ": " + hipGetErrorString(e_); return e_ == hipErrorOutOfMemory ? PGO_ERR_OUT_OF_MEMORY : PGO_ERR_HIP; } } while (0)
+
+// the launches, walked by sc_factor_steps and sc_solve_steps.  first_forward: the forward steps before it are skipped (they would solve and subtract +0); with_backward
+// = false: the forward sweep alone
+struct ScLaunch {
+    double* T; ScDev D; const ScPlan* P; double* LT; int32_t* fail; int nc; unsigned n_rhs; double* w; double* yv; double* x; int first_forward; bool with_backward; hipStream_t st;
+    void factor_diag(int k, bool) { hipLaunchKernelGGL(sc_diag_kernel, dim3(1), dim3(SC_THREADS), 0, st, T, P->diag(k), fail); }
+    void panel(int k) { hipLaunchKernelGGL(sc_panel_kernel, dim3((unsigned)P->s_size(k)), dim3(SC_THREADS), 0, st, T, D, k, P->ldu(), LT); }
+    void update(int k) { const unsigned m = (unsigned)P->s_size(k); hipLaunchKernelGGL(sc_update_kernel, dim3(m * (m + 1) / 2), dim3(SC_THREADS), 0, st, T, D, k, P->ldu(), (const double*)LT, fail); }
+    void forward(int k) { if (k >= first_forward) hipLaunchKernelGGL(sc_forward_kernel, dim3((unsigned)(1 + P->s_size(k)), n_rhs), dim3(SC_THREADS), 0, st, (const double*)T, D, k, nc, w, yv); }
+    void backward(int k) {
+        if (with_backward) hipLaunchKernelGGL(sc_backward_kernel, dim3((unsigned)(P->row_ptr[(size_t)k + 1] - P->row_ptr[(size_t)k]), n_rhs), dim3(SC_THREADS), 0, st, (const double*)T, D, k, nc, yv, x);
+    }
+};
+
+// a device, a stream, a plan with its tables, tile storage and panel scratch
+struct ScCore {
+    int device = -1; hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+    ScPlan P; ScDev D{}; DevBuf tables, T, LT, vec, fail;
+    std::string err;
+    double last_ms = 0.0;
+    int nc() const { return P.nt * DC_NB; }
+    int open(int device_id) {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count < 1) { err = "no HIP device"; return PGO_ERR_NO_DEVICE; }
+        if (device_id == -1 && hipGetDevice(&device_id) != hipSuccess) { err = "no current HIP device"; return PGO_ERR_NO_DEVICE; }      // (pgo_options.device_id's convention)
+        if (device_id < 0 || device_id >= count) { err = "no such HIP device"; return PGO_ERR_NO_DEVICE; }
+        SCHIP(err, hipSetDevice(device_id));
+        device = device_id;
+        SCHIP(err, hipStreamCreate(&st));
+        SCHIP(err, hipEventCreate(&e0)); SCHIP(err, hipEventCreate(&e1));
+        return PGO_OK;
+    }
+    int use() { SCHIP(err, hipSetDevice(device)); return PGO_OK; }
+    // the plan's six tables as int32, one upload; tile storage, scratch, failure flag
+    int upload_plan() {
+        std::vector<int32_t> h;
+        size_t at[6];
+        const std::vector<int32_t> ahead(P.ahead.begin(), P.ahead.end());
+        const std::vector<int32_t>* parts[6] = {&P.row_ptr, &P.row_col, &P.col_ptr, &P.col_row, &P.col_tile, &ahead};
+        for (int k = 0; k < 6; ++k) { at[k] = h.size(); h.insert(h.end(), parts[k]->begin(), parts[k]->end()); }
+        SCHIP(err, tables.ensure(h.size() * sizeof(int32_t)));
+        SCHIP(err, hipMemcpy(tables.p, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        const int32_t* d = tables.as<int32_t>();
+        D = ScDev{d + at[0], d + at[1], d + at[2], d + at[3], d + at[4], d + at[5]};
+        SCHIP(err, T.ensure((size_t)P.tiles() * SC_TILE * sizeof(double)));
+        SCHIP(err, LT.ensure(P.scratch_doubles() * sizeof(double)));
+        SCHIP(err, fail.ensure(sizeof(int32_t)));
+        return PGO_OK;
+    }
+    ScLaunch launcher(unsigned n_rhs, double* w, double* yv, double* x, int first_forward, bool with_backward) {
+        return ScLaunch{T.as<double>(), D, &P, LT.as<double>(), fail.as<int32_t>(), nc(), n_rhs, w, yv, x, first_forward, with_backward, st};
+    }
+    // after a run of launches between e0 and e1: the stream's end, the launches' errors, the events' time
+    int finish() {
+        SCHIP(err, hipStreamSynchronize(st));
+        SCHIP(err, hipGetLastError());
+        float ms = 0;
+        SCHIP(err, hipEventElapsedTime(&ms, e0, e1));
+        last_ms = ms;
+        return PGO_OK;
+    }
+    void close() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        if (st) (void)hipStreamSynchronize(st);
+        for (DevBuf* b : {&tables, &T, &LT, &vec, &fail}) b->release();
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        if (st) (void)hipStreamDestroy(st);
+        st = nullptr; e0 = e1 = nullptr; device = -1;
+    }
+};
+
+void plan_info(const ScPlan& P, int used, int64_t* info8) {
+    const int64_t v[8] = {P.nt, P.a_tiles, P.tiles(), used, (int64_t)(P.tiles() * (int64_t)SC_TILE * 8), P.factor_launches(), P.solve_launches(), P.tile_updates()};
+    std::copy(v, v + 8, info8);
+}
+
+}  // namespace
+
+}  // namespace pgo
+
+using namespace pgo;
+
+struct pgo_sparse_chol {
+    ScCore c;
+    int64_t N = 0, n_pairs = 0;
+    int used = 0;
+    bool factored = false;
+    std::vector<uint8_t> in_system;
+    std::vector<int32_t> order, pos;
+    DevBuf d_in, d_pos, d_hi, d_lo, d_diag, d_blocks, d_at, d_val, d_pr, d_out;
+    void release() {
+        if (c.device >= 0) (void)hipSetDevice(c.device);
+        if (c.st) (void)hipStreamSynchronize(c.st);
+        for (DevBuf* b : {&d_in, &d_pos, &d_hi, &d_lo, &d_diag, &d_blocks, &d_at, &d_val, &d_pr, &d_out}) b->release();
+        c.close();
+    }
+};
+
+extern "C" {
+
+const char* pgo_sparse_strerror(int code) {
+    switch (code) {
+        case PGO_OK: return "ok";
+        case PGO_ERR_INVALID_ARG: return "invalid argument";
+        case PGO_ERR_NO_DEVICE: return "no HIP device";
+        case PGO_ERR_HIP: return "a HIP call failed";
+        case PGO_ERR_OUT_OF_MEMORY: return "out of device memory";
+        case PGO_ERR_STATE: return "call order violated";
+        case PGO_ERR_NUMERIC: return "the matrix is not numerically positive definite";
+        default: return "unknown error";
+    }
+}
+const char* pgo_sparse_last_error(const pgo_sparse_chol* h) { return h ? h->c.err.c_str() : g_err.c_str(); }
+
+int pgo_sparse_spd_solve(int32_t device_id, int32_t n, const double* a, const double* b, const int32_t* pos, double* x, int64_t* info8, int32_t launches, double* avg_ms) {
+    g_err.clear();
+    if (n <= 0 || n > (1 << 30) || !a || !b || !x || launches < 1) { g_err = "pgo_sparse_spd_solve: null pointer, n <= 0 or launches < 1"; return PGO_ERR_INVALID_ARG; }
+    if (pos) {
+        std::vector<uint8_t> seen((size_t)n, 0);
+        for (int i = 0; i < n; ++i) { if (pos[i] < 0 || pos[i] >= n || seen[(size_t)pos[i]]) { g_err = "pgo_sparse_spd_solve: pos is not a permutation of 0 .. n - 1"; return PGO_ERR_INVALID_ARG; } seen[(size_t)pos[i]] = 1; }
+    }
+    ScCore c;
+    struct Closer { ScCore& c; ~Closer() { g_err = c.err; c.close(); } } closer{c};
+    int rc;
+    if ((rc = c.open(device_id)) != PGO_OK) return rc;
+    c.P = sc_plan_matrix(n, a, pos);
+    if (info8) plan_info(c.P, 0, info8);
+    if ((rc = c.upload_plan()) != PGO_OK) return rc;
+    const int nc = c.nc();
+    std::vector<double> hT((size_t)c.P.tiles() * SC_TILE, 0.0), hw((size_t)nc, 0.0);
+    sc_fill_tiles(c.P, n, a, pos, hT.data());
+    for (int i = 0; i < n; ++i) hw[(size_t)(pos ? pos[i] : i)] = b[i];
+    SCHIP(c.err, c.vec.ensure((size_t)3 * nc * sizeof(double)));
+    double* w = c.vec.as<double>();
+    ScLaunch L = c.launcher(1, w, w + nc, w + 2 * (size_t)nc, 0, true);
+    double total = 0.0;
+    int32_t fail = 0;
+    for (int l = 0; l < launches && !fail; ++l) {
+        SCHIP(c.err, hipMemcpyAsync(c.T.p, hT.data(), hT.size() * sizeof(double), hipMemcpyHostToDevice, c.st));
+        SCHIP(c.err, hipMemcpyAsync(w, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice, c.st));
+        SCHIP(c.err, hipMemsetAsync(c.fail.p, 0, sizeof(int32_t), c.st));
+        SCHIP(c.err, hipEventRecord(c.e0, c.st));
+        sc_factor_steps(c.P, L);
+        sc_solve_steps(c.P, L);      // (a failed factor: the sweeps run on numbers nobody reads — every address comes from the plan, none from the numbers)
+        SCHIP(c.err, hipEventRecord(c.e1, c.st));
+        SCHIP(c.err, hipMemcpyAsync(&fail, c.fail.p, sizeof(fail), hipMemcpyDeviceToHost, c.st));
+        if ((rc = c.finish()) != PGO_OK) return rc;
+        total += c.last_ms;
+    }
+    if (avg_ms) *avg_ms = total / launches;
+    if (fail) { c.err = "pgo_sparse_spd_solve: the matrix is not numerically positive definite"; return PGO_ERR_NUMERIC; }
+    SCHIP(c.err, hipMemcpy(hw.data(), w + 2 * (size_t)nc, hw.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) x[i] = hw[(size_t)(pos ? pos[i] : i)];
+    return PGO_OK;
+}
+
+int pgo_sparse_chol_create(int32_t device_id, int64_t n_nodes, const uint8_t* in_system, int64_t n_pairs, const int32_t* pair_hi, const int32_t* pair_lo, int32_t ordering, pgo_sparse_chol** out) {
+    g_err.clear();
+    if (!out) { g_err = "pgo_sparse_chol_create: null pointer"; return PGO_ERR_INVALID_ARG; }
+    *out = nullptr;
+    if (n_nodes < 1 || n_nodes > (int64_t)300000000 || !in_system || n_pairs < 0 || (n_pairs > 0 && (!pair_hi || !pair_lo)) || ordering < -1 || ordering > 1) {
+        g_err = "pgo_sparse_chol_create: null pointer, count out of range or unknown ordering"; return PGO_ERR_INVALID_ARG;
+    }
+    if (const char* what = sc_check_pairs(n_nodes, in_system, n_pairs, pair_hi, pair_lo)) { g_err = std::string("pgo_sparse_chol_create: ") + what; return PGO_ERR_INVALID_ARG; }
+    pgo_sparse_chol* h = new pgo_sparse_chol;
+    struct Guard { pgo_sparse_chol* h; ~Guard() { if (h) { g_err = h->c.err; h->release(); delete h; } } } guard{h};
+    int rc;
+    if ((rc = h->c.open(device_id)) != PGO_OK) return rc;
+    h->N = n_nodes; h->n_pairs = n_pairs;
+    h->in_system.assign(in_system, in_system + n_nodes);
+    std::vector<int64_t> adj_ptr; std::vector<int32_t> adj;
+    sc_pair_adjacency(n_nodes, n_pairs, pair_hi, pair_lo, adj_ptr, adj);
+    h->c.P = sc_plan_graph(n_nodes, adj_ptr.data(), adj.data(), in_system, ordering, h->order, &h->used);
+    h->pos.assign((size_t)n_nodes, 0);
+    for (int64_t q = 0; q < n_nodes; ++q) h->pos[(size_t)h->order[(size_t)q]] = (int32_t)q;
+    if ((rc = h->c.upload_plan()) != PGO_OK) return rc;
+    ScCore& c = h->c;
+    SCHIP(c.err, h->d_in.ensure((size_t)n_nodes)); SCHIP(c.err, h->d_pos.ensure((size_t)n_nodes * sizeof(int32_t)));
+    SCHIP(c.err, h->d_hi.ensure((size_t)n_pairs * sizeof(int32_t))); SCHIP(c.err, h->d_lo.ensure((size_t)n_pairs * sizeof(int32_t)));
+    SCHIP(c.err, h->d_diag.ensure((size_t)n_nodes * 36 * sizeof(double))); SCHIP(c.err, h->d_blocks.ensure((size_t)n_pairs * 36 * sizeof(double)));
+    SCHIP(c.err, hipMemcpy(h->d_in.p, in_system, (size_t)n_nodes, hipMemcpyHostToDevice));
+    SCHIP(c.err, hipMemcpy(h->d_pos.p, h->pos.data(), (size_t)n_nodes * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (n_pairs) {
+        SCHIP(c.err, hipMemcpy(h->d_hi.p, pair_hi, (size_t)n_pairs * sizeof(int32_t), hipMemcpyHostToDevice));
+        SCHIP(c.err, hipMemcpy(h->d_lo.p, pair_lo, (size_t)n_pairs * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    guard.h = nullptr;
+    *out = h;
+    return PGO_OK;
+}
+
+void pgo_sparse_chol_destroy(pgo_sparse_chol* h) {
+    if (!h) return;
+    h->release();
+    delete h;
+}
+
+int pgo_sparse_chol_info(const pgo_sparse_chol* h, int64_t* info8, int32_t* order) {
+    if (!h) return PGO_ERR_INVALID_ARG;
+    if (info8) plan_info(h->c.P, h->used, info8);
+    if (order) std::copy(h->order.begin(), h->order.end(), order);
+    return PGO_OK;
+}
+
+double pgo_sparse_chol_last_ms(const pgo_sparse_chol* h) { return h ? h->c.last_ms : 0.0; }
+
+int pgo_sparse_chol_factor(pgo_sparse_chol* h, const double* diag, const double* pair_blocks) {
+    if (!h) return PGO_ERR_INVALID_ARG;
+    ScCore& c = h->c;
+    c.err.clear();
+    if (!diag || (h->n_pairs > 0 && !pair_blocks)) { c.err = "pgo_sparse_chol_factor: null pointer"; return PGO_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = c.use()) != PGO_OK) return rc;
+    h->factored = false;
+    const int nc = c.nc();
+    SCHIP(c.err, hipMemcpyAsync(h->d_diag.p, diag, (size_t)h->N * 36 * sizeof(double), hipMemcpyHostToDevice, c.st));
+    if (h->n_pairs) SCHIP(c.err, hipMemcpyAsync(h->d_blocks.p, pair_blocks, (size_t)h->n_pairs * 36 * sizeof(double), hipMemcpyHostToDevice, c.st));
+    SCHIP(c.err, hipMemsetAsync(c.fail.p, 0, sizeof(int32_t), c.st));
+    SCHIP(c.err, hipEventRecord(c.e0, c.st));
+    SCHIP(c.err, hipMemsetAsync(c.T.p, 0, (size_t)c.P.tiles() * SC_TILE * sizeof(double), c.st));
+    const int64_t threads = h->N * 36 + ((int64_t)nc - h->N * 6) + h->n_pairs * 36;
+    hipLaunchKernelGGL(sc_fill_kernel, dim3((unsigned)((threads + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, c.st, c.T.as<double>(), c.D, h->N, nc, h->d_in.as<const uint8_t>(),
+                       h->d_pos.as<const int32_t>(), h->d_diag.as<const double>(), h->n_pairs, h->d_hi.as<const int32_t>(), h->d_lo.as<const int32_t>(), h->d_blocks.as<const double>());
+    ScLaunch L = c.launcher(1, nullptr, nullptr, nullptr, 0, false);
+    sc_factor_steps(c.P, L);
+    SCHIP(c.err, hipEventRecord(c.e1, c.st));
+    int32_t fail = 1;
+    SCHIP(c.err, hipMemcpyAsync(&fail, c.fail.p, sizeof(fail), hipMemcpyDeviceToHost, c.st));
+    if ((rc = c.finish()) != PGO_OK) return rc;
+    if (fail) { c.err = "pgo_sparse_chol_factor: the matrix is not numerically positive definite"; return PGO_ERR_NUMERIC; }
+    h->factored = true;
+    return PGO_OK;
+}
+
+int pgo_sparse_chol_solve(pgo_sparse_chol* h, int64_t n_rhs, const double* B, double* X) {
+    if (!h) return PGO_ERR_INVALID_ARG;
+    ScCore& c = h->c;
+    c.err.clear();
+    if (n_rhs < 1 || n_rhs > PGO_SPARSE_MAX_RHS || !B || !X) { c.err = "pgo_sparse_chol_solve: null pointer, or n_rhs outside 1 .. PGO_SPARSE_MAX_RHS"; return PGO_ERR_INVALID_ARG; }
+    if (!h->factored) { c.err = "pgo_sparse_chol_solve: no factor (pgo_sparse_chol_factor has not succeeded)"; return PGO_ERR_STATE; }
+    int rc;
+    if ((rc = c.use()) != PGO_OK) return rc;
+    const size_t nc = (size_t)c.nc(), n6 = (size_t)h->N * 6, total = (size_t)n_rhs * nc;
+    std::vector<double> hw(total, 0.0);
+    for (int64_t r = 0; r < n_rhs; ++r)
+        for (int64_t i = 0; i < h->N; ++i)
+            if (h->in_system[(size_t)i]) std::memcpy(&hw[(size_t)r * nc + (size_t)h->pos[(size_t)i] * 6], B + (size_t)r * n6 + (size_t)i * 6, 6 * sizeof(double));
+    SCHIP(c.err, c.vec.ensure(3 * total * sizeof(double)));
+    double* w = c.vec.as<double>();
+    SCHIP(c.err, hipMemcpyAsync(w, hw.data(), total * sizeof(double), hipMemcpyHostToDevice, c.st));
+    ScLaunch L = c.launcher((unsigned)n_rhs, w, w + total, w + 2 * total, 0, true);
+    SCHIP(c.err, hipEventRecord(c.e0, c.st));
+    sc_solve_steps(c.P, L);
+    SCHIP(c.err, hipEventRecord(c.e1, c.st));
+    SCHIP(c.err, hipMemcpyAsync(hw.data(), w + 2 * total, total * sizeof(double), hipMemcpyDeviceToHost, c.st));
+    if ((rc = c.finish()) != PGO_OK) return rc;
+    for (int64_t r = 0; r < n_rhs; ++r)
+        for (int64_t i = 0; i < h->N; ++i) {
+            double* xo = X + (size_t)r * n6 + (size_t)i * 6;
+            if (h->in_system[(size_t)i]) std::memcpy(xo, &hw[(size_t)r * nc + (size_t)h->pos[(size_t)i] * 6], 6 * sizeof(double));
+            else std::fill(xo, xo + 6, 0.0);
+        }
+    return PGO_OK;
+}
+
+int pgo_sparse_chol_inverse_blocks(pgo_sparse_chol* h, int64_t n_groups, const int64_t* group_ptr, const int64_t* row_ptr, const int32_t* col, const double* val,
+                                   int64_t n_pairs, const int32_t* ga, const int32_t* gb, double* out) {
+    if (!h) return PGO_ERR_INVALID_ARG;
+    ScCore& c = h->c;
+    c.err.clear();
+    if (n_groups < 1 || n_groups > PGO_SPARSE_MAX_GROUPS) { c.err = "pgo_sparse_chol_inverse_blocks: the number of groups is outside 1 .. PGO_SPARSE_MAX_GROUPS"; return PGO_ERR_INVALID_ARG; }
+    if (!group_ptr || !row_ptr || n_pairs < 0 || (n_pairs > 0 && (!ga || !gb || !out))) { c.err = "pgo_sparse_chol_inverse_blocks: null pointer or negative count"; return PGO_ERR_INVALID_ARG; }
+    for (int64_t k = 0; k < n_pairs; ++k) if (ga[k] < 0 || ga[k] >= n_groups || gb[k] < 0 || gb[k] >= n_groups) { c.err = "pgo_sparse_chol_inverse_blocks: a pair names a group out of range"; return PGO_ERR_INVALID_ARG; }
+    if (!h->factored) { c.err = "pgo_sparse_chol_inverse_blocks: no factor (pgo_sparse_chol_factor has not succeeded)"; return PGO_ERR_STATE; }
+    const int nc = c.nc();
+    const ScRows R(h->N, h->in_system.data(), h->pos.data(), nc, n_groups, group_ptr, row_ptr, col, val);
+    if (R.error) { c.err = std::string("pgo_sparse_chol_inverse_blocks: ") + R.error; return PGO_ERR_INVALID_ARG; }
+    if (n_pairs == 0) return PGO_OK;
+    int rc;
+    if ((rc = c.use()) != PGO_OK) return rc;
+    const size_t total = (size_t)R.rows * nc, nnz = R.at.size();
+    std::vector<int32_t> pr;
+    for (int64_t k = 0; k < n_pairs; ++k) for (int32_t v : {R.first_row[(size_t)ga[k]], R.first_row[(size_t)gb[k]], R.dim[(size_t)ga[k]] | (R.dim[(size_t)gb[k]] << 8)}) pr.push_back(v);
+    SCHIP(c.err, c.vec.ensure(2 * total * sizeof(double)));
+    SCHIP(c.err, h->d_at.ensure(nnz * sizeof(int64_t))); SCHIP(c.err, h->d_val.ensure(nnz * sizeof(double)));
+    SCHIP(c.err, h->d_pr.ensure(pr.size() * sizeof(int32_t))); SCHIP(c.err, h->d_out.ensure((size_t)n_pairs * 36 * sizeof(double)));
+    double* w = c.vec.as<double>();
+    double* yv = w + total;
+    if (nnz) {
+        SCHIP(c.err, hipMemcpyAsync(h->d_at.p, R.at.data(), nnz * sizeof(int64_t), hipMemcpyHostToDevice, c.st));
+        SCHIP(c.err, hipMemcpyAsync(h->d_val.p, R.val.data(), nnz * sizeof(double), hipMemcpyHostToDevice, c.st));
+    }
+    SCHIP(c.err, hipMemcpyAsync(h->d_pr.p, pr.data(), pr.size() * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
+    SCHIP(c.err, hipEventRecord(c.e0, c.st));
+    SCHIP(c.err, hipMemsetAsync(w, 0, 2 * total * sizeof(double), c.st));      // (y of the skipped steps: the zeros the Gram products read as such)
+    if (nnz) hipLaunchKernelGGL(sc_rhs_kernel, dim3((unsigned)((nnz + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, c.st, w, (int64_t)nnz, h->d_at.as<const int64_t>(), h->d_val.as<const double>());
+    ScLaunch L = c.launcher((unsigned)R.rows, w, yv, nullptr, R.first_tile, false);
+    sc_solve_steps(c.P, L);
+    const int c0 = std::min(R.first_tile * DC_NB, nc) / DC_GRAM * DC_GRAM;      // every column before it holds zeros in every row
+    hipLaunchKernelGGL(sc_gram_kernel, dim3((unsigned)n_pairs), dim3(SC_THREADS), 0, c.st, (const double*)yv, nc, c0, h->d_pr.as<const int32_t>(), h->d_out.as<double>());
+    SCHIP(c.err, hipEventRecord(c.e1, c.st));
+    std::vector<double> blocks((size_t)n_pairs * 36);
+    SCHIP(c.err, hipMemcpyAsync(blocks.data(), h->d_out.p, blocks.size() * sizeof(double), hipMemcpyDeviceToHost, c.st));
+    if ((rc = c.finish()) != PGO_OK) return rc;
+    std::copy(blocks.begin(), blocks.end(), out);
+    return PGO_OK;
+}
+
+int pgo_sparse_reduce_normal_blocks(int64_t n_nodes, const uint8_t* node_free, const double* diag, const double* offdiag, const double* sw_c, const double* sw_hss,
+                                    int64_t n_rel, const int32_t* rel_c1, const int32_t* rel_c2, int64_t n_sw, const int32_t* swe_c1, const int32_t* swe_c2,
+                                    int64_t* n_pairs, int32_t* pair_hi, int32_t* pair_lo, double* s_diag, double* s_blocks) {
+    g_err.clear();
+    const int64_t E = n_rel + n_sw;
+    if (n_nodes < 1 || n_rel < 0 || n_sw < 0 || !node_free || !diag || !n_pairs || !s_diag || (E > 0 && (!offdiag || !pair_hi || !pair_lo || !s_blocks)) ||
+        (n_rel > 0 && (!rel_c1 || !rel_c2)) || (n_sw > 0 && (!swe_c1 || !swe_c2 || !sw_c || !sw_hss))) {
+        g_err = "pgo_sparse_reduce_normal_blocks: null pointer or negative count"; return PGO_ERR_INVALID_ARG;
+    }
+    const ScReduced R = sc_reduce_normal_blocks(n_nodes, node_free, diag, offdiag, sw_c, sw_hss, n_rel, rel_c1, rel_c2, n_sw, swe_c1, swe_c2);
+    *n_pairs = (int64_t)R.pair_hi.size();
+    std::copy(R.pair_hi.begin(), R.pair_hi.end(), pair_hi);
+    std::copy(R.pair_lo.begin(), R.pair_lo.end(), pair_lo);
+    std::copy(R.diag.begin(), R.diag.end(), s_diag);
+    std::copy(R.blocks.begin(), R.blocks.end(), s_blocks);
+    return PGO_OK;
+}
+
+}  // extern "C"

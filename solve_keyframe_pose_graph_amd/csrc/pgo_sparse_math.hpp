@@ -1,8 +1,8 @@
 // pgo_sparse_math.hpp — the host side of a tile-sparse exact Cholesky solver for graphs above the dense solver's limit (pgo_dense.hip stops at PGO_DENSE_MAX_KEYFRAMES
 // because it stores all n^2 entries): the ordering of the keyframes, the tile pattern of the system, the symbolic factorisation, the order of the block steps and a serial
 // host instantiation of the whole factor and solve (tests/native/sparse_chol_host.cpp).  The arithmetic is pgo_dense_math.hpp's: the same 64 x 64 block routines, the same
-// panel substitution, the same update.  HOST ONLY so far: no kernel, no option of pgo_options and no entry point of the C-ABI uses it yet (DESIGN.md section 3.4 says why);
-// libpgo.so does not include this header.
+// panel substitution, the same update.  libpgo.so does not include this header and no option of pgo_options uses it (DESIGN.md section 3.4 says why); the kernels that run
+// this plan and this step order are the companion library's, libpgo_sparse.so (pgo_sparse.hip, include/pgo_sparse.h).
 //
 // The matrix is the dense solver's — n = 6 N padded to a multiple of 64, identity on the padding and on the rows of keyframes outside the system — with its rows and
 // columns in a permuted order of the keyframes, and only the 64 x 64 tiles of the lower triangle that the factor L can be non-zero in are stored: `tiles` x 4096 doubles,

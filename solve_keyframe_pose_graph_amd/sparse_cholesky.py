@@ -1,0 +1,256 @@
+"""ctypes binding of libpgo_sparse.so (include/pgo_sparse.h): the tile-sparse exact Cholesky solver on the GPU, for systems above capi.DENSE_MAX_KEYFRAMES, and
+covariance blocks from it.
+
+The library is a companion of libpgo.so: it takes no Problem.  covariance() below carries a Problem's system across with Problem.normal_blocks() — every handle has
+them, matrix-free ones too — and returns what Problem.covariance returns where that runs.  As capi: no CPU fallback, a missing library or device is an error."""
+import ctypes as C
+import dataclasses
+
+import numpy as np
+
+from . import _build
+from .capi import PgoError
+
+ORDER_AUTO, ORDER_NATURAL, ORDER_RCM = -1, 0, 1      # PGO_SPARSE_ORDER_*
+MAX_RHS, MAX_GROUPS = 65535, 64                      # PGO_SPARSE_MAX_RHS, PGO_SPARSE_MAX_GROUPS
+ERR_INVALID_ARG, ERR_STATE, ERR_NUMERIC = -1, -5, -7
+# what info() and spd_solve() report of a plan
+INFO = ("nt", "a_tiles", "l_tiles", "ordering", "bytes", "factor_launches", "solve_launches", "tile_updates")
+
+_dp, _ip, _lp, _bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+_lib = None
+
+
+def load(build=True):
+    global _lib
+    if _lib is not None:
+        return _lib
+    path = _build.build_libpgo_sparse() if build else _build.LIBSPARSE
+    lib = C.CDLL(path)
+    for f in _build.SPARSE_EXPORTS:
+        if not hasattr(lib, f):
+            raise RuntimeError("libpgo_sparse.so does not export %s" % f)
+    lib.pgo_sparse_strerror.restype = C.c_char_p
+    lib.pgo_sparse_strerror.argtypes = [C.c_int]
+    lib.pgo_sparse_last_error.restype = C.c_char_p
+    lib.pgo_sparse_last_error.argtypes = [C.c_void_p]
+    lib.pgo_sparse_chol_last_ms.restype = C.c_double
+    lib.pgo_sparse_chol_last_ms.argtypes = [C.c_void_p]
+    lib.pgo_sparse_chol_destroy.restype = None
+    lib.pgo_sparse_chol_destroy.argtypes = [C.c_void_p]
+    lib.pgo_sparse_spd_solve.argtypes = [C.c_int32, C.c_int32, _dp, _dp, _ip, _dp, _lp, C.c_int32, C.POINTER(C.c_double)]
+    lib.pgo_sparse_chol_create.argtypes = [C.c_int32, C.c_int64, _bp, C.c_int64, _ip, _ip, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.pgo_sparse_chol_info.argtypes = [C.c_void_p, _lp, _ip]
+    lib.pgo_sparse_chol_factor.argtypes = [C.c_void_p, _dp, _dp]
+    lib.pgo_sparse_chol_solve.argtypes = [C.c_void_p, C.c_int64, _dp, _dp]
+    lib.pgo_sparse_chol_inverse_blocks.argtypes = [C.c_void_p, C.c_int64, _lp, _lp, _ip, _dp, C.c_int64, _ip, _ip, _dp]
+    lib.pgo_sparse_reduce_normal_blocks.argtypes = [C.c_int64, _bp, _dp, _dp, _dp, _dp, C.c_int64, _ip, _ip, C.c_int64, _ip, _ip, _lp, _ip, _ip, _dp, _dp]
+    _lib = lib
+    return lib
+
+
+def _d(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _p(a, t):
+    return a.ctypes.data_as(t) if a is not None and a.size else None
+
+
+def _check(rc, h=None):
+    if rc != 0:
+        lib = load()
+        raise PgoError(rc, "%s — %s" % (lib.pgo_sparse_strerror(rc).decode(), lib.pgo_sparse_last_error(h).decode()))
+
+
+def spd_solve(a, b, pos=None, launches=1, device_id=0):
+    """the tile-sparse factor and sweep launches on a symmetric positive definite matrix, row i at position pos[i]; returns (solution, plan figures, average
+    milliseconds).  In natural order the solution equals capi.Problem.dense_spd_solve's as numbers."""
+    a, b = _d(a), _d(b)
+    n = a.shape[0]
+    assert a.shape == (n, n) and b.shape == (n,)
+    p = None if pos is None else _i(pos)
+    assert p is None or p.shape == (n,)
+    x, info, ms = np.empty(n), np.zeros(8, np.int64), C.c_double(0)
+    _check(load().pgo_sparse_spd_solve(device_id, n, _p(a, _dp), _p(b, _dp), None if p is None else p.ctypes.data_as(_ip), x.ctypes.data_as(_dp), info.ctypes.data_as(_lp), launches, C.byref(ms)))
+    return x, dict(zip(INFO, [int(v) for v in info])), ms.value
+
+
+def reduce_normal_blocks(n_nodes, node_free, diag, offdiag, sw_c, sw_hss, rel_c1, rel_c2, swe_c1, swe_c2):
+    """host only: the undamped Schur complement of Problem.normal_blocks()' arrays as blocks -> (pair_hi, pair_lo, s_diag (n_nodes, 6, 6), s_blocks (n_pairs, 6, 6))"""
+    free = np.ascontiguousarray(node_free, dtype=np.uint8)
+    rc1, rc2, sc1, sc2 = _i(rel_c1), _i(rel_c2), _i(swe_c1), _i(swe_c2)
+    diag, offdiag, sw_c, sw_hss = _d(diag), _d(offdiag), _d(sw_c), _d(sw_hss)
+    E = len(rc1) + len(sc1)
+    assert free.shape == (n_nodes,) and diag.size == 36 * n_nodes and offdiag.size == 36 * E and sw_c.size == 12 * len(sc1) and sw_hss.size == len(sc1) and len(rc2) == len(rc1) and len(sc2) == len(sc1)
+    n = C.c_int64(0)
+    hi, lo, sd, sb = np.zeros(E, np.int32), np.zeros(E, np.int32), np.zeros((n_nodes, 6, 6)), np.zeros((E, 6, 6))
+    _check(load().pgo_sparse_reduce_normal_blocks(n_nodes, _p(free, _bp), _p(diag, _dp), _p(offdiag, _dp), _p(sw_c, _dp), _p(sw_hss, _dp), len(rc1), _p(rc1, _ip), _p(rc2, _ip),
+                                                  len(sc1), _p(sc1, _ip), _p(sc2, _ip), C.byref(n), _p(hi, _ip), _p(lo, _ip), _p(sd, _dp), _p(sb, _dp)))
+    return hi[:n.value].copy(), lo[:n.value].copy(), sd, sb[:n.value].copy()
+
+
+class SparseCholesky:
+    """pgo_sparse_chol: the symbolic phase at construction (the keyframes of the system and the pairs that share a block), then factor / solve / inverse_blocks"""
+
+    def __init__(self, n_nodes, in_system, pair_hi, pair_lo, ordering=ORDER_AUTO, device_id=0):
+        self.lib = load()
+        self.h = C.c_void_p()
+        self.n_nodes = int(n_nodes)
+        ins = np.ascontiguousarray(in_system, dtype=np.uint8)
+        hi, lo = _i(pair_hi), _i(pair_lo)
+        assert ins.shape == (self.n_nodes,) and hi.shape == lo.shape
+        self.n_pairs = len(hi)
+        _check(self.lib.pgo_sparse_chol_create(device_id, self.n_nodes, _p(ins, _bp), self.n_pairs, _p(hi, _ip), _p(lo, _ip), ordering, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.pgo_sparse_chol_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """(plan figures, order): order[q] = the keyframe at position q"""
+        info, order = np.zeros(8, np.int64), np.zeros(self.n_nodes, np.int32)
+        _check(self.lib.pgo_sparse_chol_info(self.h, info.ctypes.data_as(_lp), order.ctypes.data_as(_ip)), self.h)
+        return dict(zip(INFO, [int(v) for v in info])), order
+
+    def last_ms(self):
+        """HIP-event milliseconds of the launches of the last factor, solve or inverse_blocks"""
+        return self.lib.pgo_sparse_chol_last_ms(self.h)
+
+    def factor(self, diag, pair_blocks):
+        diag, blocks = _d(diag), _d(pair_blocks)
+        assert diag.size == 36 * self.n_nodes and blocks.size == 36 * self.n_pairs
+        _check(self.lib.pgo_sparse_chol_factor(self.h, _p(diag, _dp), _p(blocks, _dp)), self.h)
+
+    def solve(self, B):
+        """A^-1 B for the rows of B (n_rhs x 6 n_nodes, or one vector), keyframes in the caller's order"""
+        B = _d(B)
+        rows = B.reshape(1, -1) if B.ndim == 1 else B
+        assert rows.shape[1] == 6 * self.n_nodes
+        X = np.empty_like(rows)
+        _check(self.lib.pgo_sparse_chol_solve(self.h, rows.shape[0], rows.ctypes.data_as(_dp), X.ctypes.data_as(_dp)), self.h)
+        return X.reshape(B.shape)
+
+    def inverse_blocks(self, groups, pairs):
+        """groups: a list of groups, each a list of 1 or 6 sparse rows (cols, vals) over the 6 n_nodes coordinates; pairs: [(group a, group b), ...].
+        Returns the list of V_a A^-1 V_b^T, (d_a, d_b) arrays."""
+        group_ptr, row_ptr, col, val = [0], [0], [], []
+        for g in groups:
+            for cols, vals in g:
+                col.extend(int(c) for c in cols); val.extend(float(v) for v in vals)
+                row_ptr.append(len(col))
+            group_ptr.append(len(row_ptr) - 1)
+        gp, rp, cc, vv = np.asarray(group_ptr, np.int64), np.asarray(row_ptr, np.int64), np.asarray(col, np.int32), np.asarray(val, np.float64)
+        pr = _i(pairs).reshape(-1, 2)
+        ga, gb = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        out = np.zeros((len(pr), 36))
+        _check(self.lib.pgo_sparse_chol_inverse_blocks(self.h, len(groups), gp.ctypes.data_as(_lp), rp.ctypes.data_as(_lp), _p(cc, _ip), _p(vv, _dp), len(pr), _p(ga, _ip), _p(gb, _ip), _p(out, _dp)), self.h)
+        dim = lambda g: len(groups[g])
+        return [out[k, :dim(a) * dim(b)].reshape(dim(a), dim(b)).copy() for k, (a, b) in enumerate(pr)]
+
+
+@dataclasses.dataclass
+class Edges:
+    """what covariance() has to know of a Problem's residual blocks, in the order they were added: the relative-pose edges' endpoints, the switchable edges' endpoints and
+    switch indices, the keyframes with a regulariser, the constant keyframes"""
+    rel_c1: np.ndarray
+    rel_c2: np.ndarray
+    sw_c1: np.ndarray
+    sw_c2: np.ndarray
+    sw_idx: np.ndarray
+    constant: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.int32))
+    reg_node: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(0, np.int32))
+
+    @classmethod
+    def from_graph(cls, g, switchable=True, constant=()):
+        """of capi.problem_from_graph(g, switchable)"""
+        none = np.zeros(0, np.int32)
+        if switchable:
+            return cls(_i(g.odom_c1), _i(g.odom_c2), _i(g.loop_c1), _i(g.loop_c2), np.arange(g.n_loops, dtype=np.int32), _i(constant), _i(g.reg_node))
+        return cls(_i(np.concatenate([g.odom_c1, g.loop_c1])), _i(np.concatenate([g.odom_c2, g.loop_c2])), none, none, none, _i(constant), _i(g.reg_node))
+
+
+def covariance(P, edges, quat, t, sw, pairs, ordering=ORDER_AUTO, device_id=None, timings=None):
+    """Problem.covariance for graphs of any size: pairs = [(a, b), ...] of block ids — below n_nodes a keyframe (6 tangent entries), n_nodes + i the switch index i (1
+    entry) — at the given point; a list of (d_a, d_b) arrays.  P: a capi.Problem on one GPU whose residual blocks `edges` describes.  The system is the undamped Schur
+    complement of P's normal blocks, factored by SparseCholesky; a keyframe is six unit rows, switch e the row -c_e / h_e, and 1 / h_e is added to a switch's variance.
+    Pairs with a constant keyframe: zero blocks.  ValueError: an unreferenced keyframe or an unused switch.  PgoError(PGO_ERR_NUMERIC): the system is not positive
+    definite (is the gauge fixed?) or a requested switch's h is not a positive finite number.  timings (a dict): HIP-event milliseconds of the factor and the blocks."""
+    q = np.asarray(quat, dtype=np.float64).reshape(-1, 4)
+    N = len(q)
+    S = 0 if sw is None else int(np.asarray(sw).size)
+    pr = _i(pairs).reshape(-1, 2)
+    free = np.ones(N, np.uint8); free[np.asarray(edges.constant, dtype=np.int64)] = 0
+    referenced = np.zeros(N, bool)
+    for c in (edges.rel_c1, edges.rel_c2, edges.sw_c1, edges.sw_c2, edges.reg_node):
+        referenced[np.asarray(c, dtype=np.int64)] = True
+    edge_of = {int(s): e for e, s in enumerate(edges.sw_idx)}      # switch index -> the (last) switchable edge that uses it
+    for i in np.unique(pr):
+        if i < 0 or i >= N + S:
+            raise ValueError("block id %d out of range (keyframes 0 .. n_nodes - 1, then n_nodes + switch index)" % i)
+        if i < N and not referenced[i]:
+            raise ValueError("keyframe %d is referenced by no residual block: it has no covariance" % i)
+        if i >= N and int(i) - N not in edge_of:
+            raise ValueError("switch %d is used by no switchable edge: it has no covariance" % (i - N))
+    P.evaluate(quat, t, sw, want_residuals=False, want_gradient=True)
+    diag, _, off, c, hss, _ = P.normal_blocks()
+    dim = lambda i: 6 if i < N else 1
+    is_const = lambda i: i < N and not free[i]
+    live = [k for k, (a, b) in enumerate(pr) if not is_const(a) and not is_const(b)]
+    out = [np.zeros((dim(a), dim(b))) for a, b in pr]
+    if not live:
+        return out
+    ids = sorted({int(i) for k in live for i in pr[k]})
+    for i in ids:
+        if i >= N:
+            h = hss[edge_of[i - N]]
+            if not (h > 0.0 and np.isfinite(h)):
+                raise PgoError(ERR_NUMERIC, "switch %d: J_s^T J_s = %r is not a positive finite number" % (i - N, h))
+    in_system = (free != 0) & referenced
+    hi, lo, sd, sb = reduce_normal_blocks(N, free, diag, off, c, hss, edges.rel_c1, edges.rel_c2, edges.sw_c1, edges.sw_c2)
+
+    def rows_of(i):
+        if i < N:
+            return [([6 * i + a], [1.0]) for a in range(6)]
+        e = edge_of[i - N]
+        ends = sorted((int(n), side) for side, n in enumerate((edges.sw_c1[e], edges.sw_c2[e])) if free[n])      # (columns ascending; a constant end has no row in the system)
+        return [([6 * n + a for n, _ in ends for a in range(6)], [-c[e, 6 * side + a] / hss[e] for _, side in ends for a in range(6)])]
+
+    F = SparseCholesky(N, in_system, hi, lo, ordering, P.options.device_id if device_id is None else device_id)
+    try:
+        F.factor(sd, sb)
+        if timings is not None:
+            timings["factor_ms"] = F.last_ms(); timings["blocks_ms"] = 0.0; timings["info"] = F.info()[0]
+        # at most MAX_GROUPS groups per call: pairs are served by the call that holds both their ids; the ids are dealt out in runs of MAX_GROUPS / 2
+        half = MAX_GROUPS // 2
+        runs = [ids[s:s + half] for s in range(0, len(ids), half)]
+        run_of = {i: r for r, run in enumerate(runs) for i in run}
+        todo = {}
+        for k in live:
+            a, b = int(pr[k][0]), int(pr[k][1])
+            todo.setdefault(tuple(sorted({run_of[a], run_of[b]})), []).append(k)
+        for key in sorted(todo):
+            members = [i for r in key for i in runs[r]]
+            at = {i: g for g, i in enumerate(members)}
+            blocks = F.inverse_blocks([rows_of(i) for i in members], [(at[int(pr[k][0])], at[int(pr[k][1])]) for k in todo[key]])
+            if timings is not None:
+                timings["blocks_ms"] += F.last_ms()
+            for k, blk in zip(todo[key], blocks):
+                a, b = int(pr[k][0]), int(pr[k][1])
+                if a >= N and a == b:
+                    blk = blk + 1.0 / hss[edge_of[a - N]]
+                out[k] = blk
+    finally:
+        F.close()
+    return out
