@@ -67,6 +67,27 @@ int pgo_sparse_chol_solve(pgo_sparse_chol* h, int64_t n_rhs, const double* B, do
 int pgo_sparse_chol_inverse_blocks(pgo_sparse_chol* h, int64_t n_groups, const int64_t* group_ptr, const int64_t* row_ptr, const int32_t* col, const double* val,
                                    int64_t n_pairs, const int32_t* ga, const int32_t* gb, double* out);
 
+/* The selected inverse: every entry of A^-1 that lies in the tile pattern of L — all diagonal blocks and the block of every pair given to pgo_sparse_chol_create —
+ * by Takahashi's recurrence on the factor's tiles, one backward pass over the block columns (sc_selinv_steps).  For many blocks: every keyframe's marginal covariance,
+ * every edge's joint covariance; no right-hand sides, no dense array.
+ *   launches: 1 (L_kk^-T L_kk^-1 of every diagonal tile, nt workgroups: it reads L alone) + per column k with a non-empty s_k three, a chain: G = L_sk L_kk^-1
+ *             (|s_k| workgroups), Z_sk = -Z_ss G (|s_k| workgroups), Z_kk -= G^T Z_sk (1 workgroup): info4[0].  Tile products (64 x 64 x 64, fp64 MFMA):
+ *             |s_k|^2 + |s_k| per column, info4[1].
+ *   memory:   a second tile array of info8[4] bytes (info4[2]), allocated by the first call and kept; G lives in the panel scratch.  The factor is only read:
+ *             pgo_sparse_chol_solve and _inverse_blocks give afterwards the bits they gave before.
+ * PGO_ERR_STATE: no factor.  A later pgo_sparse_chol_factor, successful or not, invalidates the selected inverse. */
+int pgo_sparse_chol_selected_inverse(pgo_sparse_chol* h);
+/* info4: launches of one pgo_sparse_chol_selected_inverse, its tile products, bytes of its tile array, 1 if a selected inverse of the present factor exists else 0.
+ * No launch. */
+int pgo_sparse_chol_selected_info(const pgo_sparse_chol* h, int64_t* info4);
+/* Blocks of A^-1 from the selected inverse: out[36 k] = the 6 x 6 block, row-major, with the rows of keyframe node_a[k] and the columns of keyframe node_b[k] (the
+ * caller's keyframe order; node_a[k] = node_b[k]: a marginal).  One launch, one thread per entry.  out of (b, a) is the exact transpose of out of (a, b), a diagonal
+ * block is exactly symmetric.  A pair with a keyframe outside the system: a zero block (pgo_covariance's rule for constant keyframes).  A block of which any tile is
+ * not in the pattern — two keyframes that share no block of the system and lie in tiles the factor does not fill — is reported, not guessed: zeros and
+ * in_pattern[k] = 0 (else 1); with in_pattern = NULL it is PGO_ERR_INVALID_ARG, the pair named in the error text, and out is left alone.
+ * PGO_ERR_STATE: no selected inverse of the present factor. */
+int pgo_sparse_chol_selected_blocks(pgo_sparse_chol* h, int64_t n_blocks, const int32_t* node_a, const int32_t* node_b, double* out /*[n_blocks][36]*/, uint8_t* in_pattern /*[n_blocks], may be NULL*/);
+
 /* Host only: the undamped Schur complement S of a handle's last linearisation as blocks, from pgo_get_normal_blocks' arrays (diag [n_nodes][36], offdiag
  * [n_rel + n_sw][36]: J1^T J2 per edge, relative-pose then switchable, internal order; sw_c [n_sw][12]; sw_hss [n_sw]), the edges' endpoints in the same
  * order and node_free [n_nodes] (0: constant).  Per free keyframe H_ii - sum c c^T / h over its switch sides; per pair of free keyframes the sum in edge order
@@ -76,7 +97,7 @@ int pgo_sparse_reduce_normal_blocks(int64_t n_nodes, const uint8_t* node_free, c
                                     int64_t n_rel, const int32_t* rel_c1, const int32_t* rel_c2, int64_t n_sw, const int32_t* swe_c1, const int32_t* swe_c2,
                                     int64_t* n_pairs, int32_t* pair_hi, int32_t* pair_lo, double* s_diag, double* s_blocks);
 
-/* HIP-event milliseconds of the launches of the object's last pgo_sparse_chol_factor (fill included), _solve or _inverse_blocks */
+/* HIP-event milliseconds of the launches of the object's last pgo_sparse_chol_factor (fill included), _solve, _inverse_blocks, _selected_inverse or _selected_blocks */
 double pgo_sparse_chol_last_ms(const pgo_sparse_chol* h);
 
 const char* pgo_sparse_strerror(int code);

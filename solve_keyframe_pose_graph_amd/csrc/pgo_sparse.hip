@@ -6,6 +6,9 @@
 //
 // Nothing waits on another workgroup inside a launch, there are no atomics, every sum has a fixed order.  The step order is sc_factor_steps / sc_solve_steps, nowhere
 // else.  The update finds its target tile by ScPlan::find's binary search in row_col, in device code (sc_find): no per-step pair table.
+//
+// The selected inverse (sc_selinv_steps: sc_sel_inverses_kernel, sc_sel_ginv_kernel, sc_sel_column_kernel, sc_sel_diag_kernel, then sc_sel_gather_kernel for 6 x 6 blocks)
+// has no counterpart in pgo_dense.hip: Takahashi's recurrence on the tiles of L into a second tile array, under the same rules.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -256,8 +259,183 @@ __global__ __launch_bounds__(SC_THREADS) void sc_gram_kernel(const double* __res
     dc_param_gram(ScTeam{}, Y + (size_t)q[0] * nc, q[2] & 255, Y + (size_t)q[1] * nc, q[2] >> 8, (size_t)nc, nc, c0, false, 0.0, part, out + 36 * pair);
 }
 
+// ---- the selected inverse (sc_selinv_steps): Z, a second tile array with the ids of L's tiles; T is only read.  G: the tiles G_e = L_{s[e],k} L_kk^-1 of one step,
+// row-major, compact by position e in s_k — the major order both column(k) (B operand: rows of G) and diag(k) (A operand: G^T) read with consecutive lanes.
+
+// ginv(k): one workgroup per tile of s_k.  g L_kk = l per row, one wavefront per 16 rows: sc_panel_kernel's scheme run backwards — the 16-wide block columns from the
+// last to the first, MFMA products with the block columns already solved (m = 3 .. j + 1), substitution inside the diagonal sub-block from its last column to its first.
+// Operand map: A[i][k] = L[16 m + k][16 j + i], B[k][n] = G[row n][16 m + k], D[i][n] = (G_m L_mj)[row n][16 j + i]; a lane holds row lr, columns lk + 4 reg.
+__global__ __launch_bounds__(SC_THREADS) void sc_sel_ginv_kernel(const double* __restrict__ T, ScDev P, int k, double* __restrict__ G) {
+    __shared__ double l[DC_NB * DC_LD];
+    sc_load_tile(T + (size_t)(P.row_ptr[k + 1] - 1) * SC_TILE, l);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int e = (int)blockIdx.x;                                         // < |s_k|: the grid
+    const double* __restrict__ arow = T + (size_t)P.col_tile[P.col_ptr[k] + e] * SC_TILE + (size_t)(wave * DC_SUB + lr) * DC_NB;
+    double* __restrict__ grow = G + (size_t)e * SC_TILE + (size_t)(wave * DC_SUB + lr) * DC_NB;
+    sc_d4 Y[DC_NB / DC_SUB];
+#pragma unroll
+    for (int j = DC_NB / DC_SUB - 1; j >= 0; --j) {
+        double r[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = arow[j * DC_SUB + lk + 4 * reg];
+        sc_d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int m = DC_NB / DC_SUB - 1; m > j; --m)
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(m * DC_SUB + 4 * kk + lk) * DC_LD + j * DC_SUB + lr], Y[m][kk], acc, 0, 0, 0);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = r[reg] - acc[reg];
+#pragma unroll
+        for (int p = DC_SUB - 1; p >= 0; --p) {
+            const double gp = __shfl(r[p >> 2], (p & 3) * 16 + lr) / l[(j * DC_SUB + p) * DC_LD + j * DC_SUB + p];
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int q = lk + 4 * reg;
+                const double lpq = l[(j * DC_SUB + p) * DC_LD + j * DC_SUB + (q < p ? q : p)];      // (q >= p: the diagonal entry, unused)
+                r[reg] = q == p ? gp : (q < p ? r[reg] - lpq * gp : r[reg]);
+            }
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            Y[j][reg] = r[reg];
+            grow[j * DC_SUB + lk + 4 * reg] = r[reg];
+        }
+    }
+}
+
+// column(k): one workgroup per position a; Z_{s[a],k} = - sum_b Z(s[a], s[b]) G_b.  2 x 2 MFMA tiles per wavefront over K = 64 (sc_update_kernel's layout), the
+// accumulators carried in registers over b ascending.  The tile Z(s[a], s[b]) goes through LDS: stored as (s[a], s[b]) where a >= b, as (s[b], s[a]) — read transposed —
+// where a < b; the stride of 65 makes both walks conflict-free.
+__global__ __launch_bounds__(SC_THREADS) void sc_sel_column_kernel(double* __restrict__ Z, ScDev P, int k, const double* __restrict__ G) {
+    __shared__ double z[DC_NB * DC_LD];
+    const int a = (int)blockIdx.x;                                         // < |s_k|: the grid
+    const int c0 = P.col_ptr[k], m = P.col_ptr[k + 1] - c0, ra = P.col_row[c0 + a];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int i0 = (wave >> 1) * 32, j0 = (wave & 1) * 32;                 // inside the tile
+    sc_d4 acc[2][2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) acc[s][u] = sc_d4{0.0, 0.0, 0.0, 0.0};
+    for (int b = 0; b < m; ++b) {
+        const int rb = P.col_row[c0 + b];
+        const bool tr = a < b;
+        const int id = tr ? sc_find(P, rb, ra) : sc_find(P, ra, rb);      // in the pattern by construction of the symbolic factorisation
+        if (id < 0) return;                                                // (the same for every thread of the workgroup)
+        __syncthreads();                                                   // the products of the tile before are done with z
+        sc_load_tile(Z + (size_t)id * SC_TILE, z);
+        __syncthreads();
+        const int si = tr ? 1 : DC_LD, sk = tr ? DC_LD : 1;
+        const double* __restrict__ g = G + (size_t)b * SC_TILE;
+#pragma unroll
+        for (int kk = 0; kk < DC_NB / 4; ++kk) {
+            const int kx = kk * 4 + lk;
+            const double a0 = z[(i0 + lr) * si + kx * sk], a1 = z[(i0 + 16 + lr) * si + kx * sk], b0 = g[kx * DC_NB + j0 + lr], b1 = g[kx * DC_NB + j0 + 16 + lr];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    double* __restrict__ t = Z + (size_t)P.col_tile[c0 + a] * SC_TILE;      // a tile of column k: none of those read above
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) t[(i0 + s * 16 + lk + 4 * reg) * DC_NB + j0 + u * 16 + lr] = -acc[s][u][reg];
+}
+
+// inverses: one workgroup per diagonal tile k (the grid: nt), Z_kk = L_kk^-T L_kk^-1 in LDS from the 64 unit right-hand sides, thread c substituting column c in place
+// (dc_forward_block, dc_backward_block); the entries i >= j, stored mirrored.  It reads L alone: one launch ahead of the chain of dependent steps.
+__global__ __launch_bounds__(SC_THREADS) void sc_sel_inverses_kernel(const double* __restrict__ T, double* __restrict__ Z, ScDev P) {
+    __shared__ double l[DC_NB * DC_LD];
+    __shared__ double x[DC_NB * DC_LD];
+    const int diag = P.row_ptr[blockIdx.x + 1] - 1;
+    sc_load_tile(T + (size_t)diag * SC_TILE, l);
+    for (int idx = threadIdx.x; idx < DC_NB * DC_NB; idx += SC_THREADS) x[(idx >> 6) * DC_LD + (idx & 63)] = (idx >> 6) == (idx & 63) ? 1.0 : 0.0;
+    __syncthreads();
+    if (threadIdx.x < DC_NB) {
+        double* v = x + threadIdx.x * DC_LD;                               // column c of the inverse, entry p at v[p]
+        dc_forward_block(DcSerial{}, l, v, v);
+        dc_backward_block(DcSerial{}, l, v, v);
+    }
+    __syncthreads();
+    double* __restrict__ t = Z + (size_t)diag * SC_TILE;
+    for (int idx = threadIdx.x; idx < DC_NB * DC_NB; idx += SC_THREADS) {
+        const int r = idx >> 6, c = idx & 63;
+        t[idx] = c <= r ? x[c * DC_LD + r] : x[r * DC_LD + c];              // entry (i, j), i >= j: entry i of column j
+    }
+}
+
+// diag(k): one workgroup.  Z_kk -= sum_a G_a^T Z_{s[a],k}, a ascending, 2 x 2 MFMA tiles per wavefront in the three quadrants on or below the diagonal; the entries
+// i >= j, each written to both triangles by the one lane that holds it.
+__global__ __launch_bounds__(SC_THREADS) void sc_sel_diag_kernel(double* __restrict__ Z, ScDev P, int k, const double* __restrict__ G) {
+    const int c0 = P.col_ptr[k], m = P.col_ptr[k + 1] - c0;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int i0 = (wave >> 1) * 32, j0 = (wave & 1) * 32;
+    if (i0 == 0 && j0 == 32) return;                                       // (that quadrant lies above the diagonal)
+    sc_d4 acc[2][2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) acc[s][u] = sc_d4{0.0, 0.0, 0.0, 0.0};
+    for (int a = 0; a < m; ++a) {
+        const double* __restrict__ g = G + (size_t)a * SC_TILE;
+        const double* __restrict__ zt = Z + (size_t)P.col_tile[c0 + a] * SC_TILE;
+#pragma unroll
+        for (int kk = 0; kk < DC_NB / 4; ++kk) {
+            const int kx = (kk * 4 + lk) * DC_NB;
+            const double a0 = g[kx + i0 + lr], a1 = g[kx + i0 + 16 + lr], b0 = zt[kx + j0 + lr], b1 = zt[kx + j0 + 16 + lr];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    double* t = Z + (size_t)(P.row_ptr[k + 1] - 1) * SC_TILE;              // the diagonal tile: none of those read above
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int i = i0 + s * 16 + lk + 4 * reg, j = j0 + u * 16 + lr;
+                if (i >= j) {
+                    const double v = t[i * DC_NB + j] - acc[s][u][reg];
+                    t[i * DC_NB + j] = v;
+                    t[j * DC_NB + i] = v;
+                }
+            }
+}
+
+// gather: one thread per entry of a requested 6 x 6 block of the inverse, rows of keyframe na, columns of keyframe nb in the caller's order (sc_selected_block_host).
+// flag[block]: 1, or 0 where one of the (up to four) tiles the block touches is not in the pattern — that block comes back zero, not guessed.
+__global__ __launch_bounds__(SC_THREADS) void sc_sel_gather_kernel(const double* __restrict__ Z, ScDev P, int64_t n_blocks, const int32_t* __restrict__ na, const int32_t* __restrict__ nb,
+                                                                   const uint8_t* __restrict__ in_system, const int32_t* __restrict__ pos, double* __restrict__ out, uint8_t* __restrict__ flag) {
+    const int64_t gid = (int64_t)blockIdx.x * SC_THREADS + threadIdx.x, blk = gid / 36;
+    if (blk >= n_blocks) return;
+    const int e = (int)(gid - blk * 36), i = e / 6, j = e - i * 6;
+    const int32_t a = na[blk], b = nb[blk];                                // both in 0 .. N - 1: the host checked
+    bool in = true, zero = !in_system[a] || !in_system[b];
+    int row, col;
+    if (!zero) {
+        for (int ci = 0; ci < 6; ci += 5)
+            for (int cj = 0; cj < 6; cj += 5) { sc_sigma_entry(pos[a], pos[b], ci, cj, &row, &col); if (sc_find(P, row / DC_NB, col / DC_NB) < 0) in = false; }
+    }
+    if (e == 0) flag[blk] = in ? 1 : 0;
+    double v = 0.0;
+    if (!zero && in) {
+        sc_sigma_entry(pos[a], pos[b], i, j, &row, &col);
+        v = Z[(size_t)sc_find(P, row / DC_NB, col / DC_NB) * SC_TILE + (size_t)(row % DC_NB) * DC_NB + col % DC_NB];
+    }
+    out[gid] = v;
+}
+
 // ---- host side
-thread_local std::string g_err;      // the last error of a call without an object
+thread_local std::string g_err;     // the last error of a call without an object
 
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
@@ -286,6 +464,15 @@ struct ScLaunch {
     void backward(int k) {
         if (with_backward) hipLaunchKernelGGL(sc_backward_kernel, dim3((unsigned)(P->row_ptr[(size_t)k + 1] - P->row_ptr[(size_t)k]), n_rhs), dim3(SC_THREADS), 0, st, (const double*)T, D, k, nc, yv, x);
     }
+};
+
+// the launches of the selected inverse, walked by sc_selinv_steps.  G: the panel scratch (ScPlan::scratch_doubles() holds max |s_k| tiles)
+struct ScSelLaunch {
+    const double* T; double* Z; ScDev D; const ScPlan* P; double* G; hipStream_t st;
+    void ginv(int k) { hipLaunchKernelGGL(sc_sel_ginv_kernel, dim3((unsigned)P->s_size(k)), dim3(SC_THREADS), 0, st, T, D, k, G); }
+    void column(int k) { hipLaunchKernelGGL(sc_sel_column_kernel, dim3((unsigned)P->s_size(k)), dim3(SC_THREADS), 0, st, Z, D, k, (const double*)G); }
+    void diag(int k) { hipLaunchKernelGGL(sc_sel_diag_kernel, dim3(1), dim3(SC_THREADS), 0, st, Z, D, k, (const double*)G); }
+    void inverses() { hipLaunchKernelGGL(sc_sel_inverses_kernel, dim3((unsigned)P->nt), dim3(SC_THREADS), 0, st, T, Z, D); }
 };
 
 // a device, a stream, a plan with its tables, tile storage and panel scratch
@@ -363,13 +550,14 @@ struct pgo_sparse_chol {
     int64_t N = 0, n_pairs = 0;
     int used = 0;
     bool factored = false;
+    bool selected = false;      // Z holds the selected inverse of the present factor
     std::vector<uint8_t> in_system;
     std::vector<int32_t> order, pos;
-    DevBuf d_in, d_pos, d_hi, d_lo, d_diag, d_blocks, d_at, d_val, d_pr, d_out;
+    DevBuf d_in, d_pos, d_hi, d_lo, d_diag, d_blocks, d_at, d_val, d_pr, d_out, Z, d_na, d_nb, d_flag;
     void release() {
         if (c.device >= 0) (void)hipSetDevice(c.device);
         if (c.st) (void)hipStreamSynchronize(c.st);
-        for (DevBuf* b : {&d_in, &d_pos, &d_hi, &d_lo, &d_diag, &d_blocks, &d_at, &d_val, &d_pr, &d_out}) b->release();
+        for (DevBuf* b : {&d_in, &d_pos, &d_hi, &d_lo, &d_diag, &d_blocks, &d_at, &d_val, &d_pr, &d_out, &Z, &d_na, &d_nb, &d_flag}) b->release();
         c.close();
     }
 };
@@ -490,6 +678,7 @@ int pgo_sparse_chol_factor(pgo_sparse_chol* h, const double* diag, const double*
     int rc;
     if ((rc = c.use()) != PGO_OK) return rc;
     h->factored = false;
+    h->selected = false;      // (Z, if there is one, belongs to the factor before)
     const int nc = c.nc();
     SCHIP(c.err, hipMemcpyAsync(h->d_diag.p, diag, (size_t)h->N * 36 * sizeof(double), hipMemcpyHostToDevice, c.st));
     if (h->n_pairs) SCHIP(c.err, hipMemcpyAsync(h->d_blocks.p, pair_blocks, (size_t)h->n_pairs * 36 * sizeof(double), hipMemcpyHostToDevice, c.st));
@@ -581,6 +770,68 @@ int pgo_sparse_chol_inverse_blocks(pgo_sparse_chol* h, int64_t n_groups, const i
     SCHIP(c.err, hipMemcpyAsync(blocks.data(), h->d_out.p, blocks.size() * sizeof(double), hipMemcpyDeviceToHost, c.st));
     if ((rc = c.finish()) != PGO_OK) return rc;
     std::copy(blocks.begin(), blocks.end(), out);
+    return PGO_OK;
+}
+
+int pgo_sparse_chol_selected_inverse(pgo_sparse_chol* h) {
+    if (!h) return PGO_ERR_INVALID_ARG;
+    ScCore& c = h->c;
+    c.err.clear();
+    if (!h->factored) { c.err = "pgo_sparse_chol_selected_inverse: no factor (pgo_sparse_chol_factor has not succeeded)"; return PGO_ERR_STATE; }
+    int rc;
+    if ((rc = c.use()) != PGO_OK) return rc;
+    h->selected = false;
+    SCHIP(c.err, h->Z.ensure((size_t)c.P.tiles() * SC_TILE * sizeof(double)));      // (every tile is written by the step of its column: no memset)
+    ScSelLaunch L{c.T.as<const double>(), h->Z.as<double>(), c.D, &c.P, c.LT.as<double>(), c.st};
+    SCHIP(c.err, hipEventRecord(c.e0, c.st));
+    sc_selinv_steps(c.P, L);
+    SCHIP(c.err, hipEventRecord(c.e1, c.st));
+    if ((rc = c.finish()) != PGO_OK) return rc;
+    h->selected = true;
+    return PGO_OK;
+}
+
+int pgo_sparse_chol_selected_info(const pgo_sparse_chol* h, int64_t* info4) {
+    if (!h || !info4) return PGO_ERR_INVALID_ARG;
+    const ScPlan& P = h->c.P;
+    const int64_t v[4] = {P.selinv_launches(), P.selinv_products(), (int64_t)(P.tiles() * (int64_t)SC_TILE * 8), h->selected ? 1 : 0};
+    std::copy(v, v + 4, info4);
+    return PGO_OK;
+}
+
+int pgo_sparse_chol_selected_blocks(pgo_sparse_chol* h, int64_t n_blocks, const int32_t* node_a, const int32_t* node_b, double* out, uint8_t* in_pattern) {
+    if (!h) return PGO_ERR_INVALID_ARG;
+    ScCore& c = h->c;
+    c.err.clear();
+    if (n_blocks < 0 || n_blocks > (int64_t)50000000 || (n_blocks > 0 && (!node_a || !node_b || !out))) { c.err = "pgo_sparse_chol_selected_blocks: null pointer or count out of range"; return PGO_ERR_INVALID_ARG; }
+    for (int64_t k = 0; k < n_blocks; ++k)
+        if (node_a[k] < 0 || node_a[k] >= h->N || node_b[k] < 0 || node_b[k] >= h->N) { c.err = "pgo_sparse_chol_selected_blocks: block " + std::to_string(k) + " names a keyframe out of range"; return PGO_ERR_INVALID_ARG; }
+    if (!h->selected) { c.err = "pgo_sparse_chol_selected_blocks: no selected inverse of the present factor (pgo_sparse_chol_selected_inverse has not succeeded since the last pgo_sparse_chol_factor)"; return PGO_ERR_STATE; }
+    if (n_blocks == 0) return PGO_OK;
+    int rc;
+    if ((rc = c.use()) != PGO_OK) return rc;
+    const size_t nb = (size_t)n_blocks;
+    SCHIP(c.err, h->d_na.ensure(nb * sizeof(int32_t))); SCHIP(c.err, h->d_nb.ensure(nb * sizeof(int32_t)));
+    SCHIP(c.err, h->d_out.ensure(nb * 36 * sizeof(double))); SCHIP(c.err, h->d_flag.ensure(nb));
+    SCHIP(c.err, hipMemcpyAsync(h->d_na.p, node_a, nb * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
+    SCHIP(c.err, hipMemcpyAsync(h->d_nb.p, node_b, nb * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
+    SCHIP(c.err, hipEventRecord(c.e0, c.st));
+    hipLaunchKernelGGL(sc_sel_gather_kernel, dim3((unsigned)((nb * 36 + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, c.st, h->Z.as<const double>(), c.D, n_blocks, h->d_na.as<const int32_t>(),
+                       h->d_nb.as<const int32_t>(), h->d_in.as<const uint8_t>(), h->d_pos.as<const int32_t>(), h->d_out.as<double>(), h->d_flag.as<uint8_t>());
+    SCHIP(c.err, hipEventRecord(c.e1, c.st));
+    std::vector<double> blocks(nb * 36);
+    std::vector<uint8_t> flag(nb);
+    SCHIP(c.err, hipMemcpyAsync(blocks.data(), h->d_out.p, blocks.size() * sizeof(double), hipMemcpyDeviceToHost, c.st));
+    SCHIP(c.err, hipMemcpyAsync(flag.data(), h->d_flag.p, nb, hipMemcpyDeviceToHost, c.st));
+    if ((rc = c.finish()) != PGO_OK) return rc;
+    if (!in_pattern)
+        for (size_t k = 0; k < nb; ++k)
+            if (!flag[k]) {
+                c.err = "pgo_sparse_chol_selected_blocks: block " + std::to_string(k) + " (keyframes " + std::to_string(node_a[k]) + ", " + std::to_string(node_b[k]) + ") is not wholly in the pattern of the factor";
+                return PGO_ERR_INVALID_ARG;
+            }
+    std::copy(blocks.begin(), blocks.end(), out);
+    if (in_pattern) std::copy(flag.begin(), flag.end(), in_pattern);
     return PGO_OK;
 }
 

@@ -1,7 +1,8 @@
 // pgo_sparse_blocks.hpp — the host side of libpgo_sparse.so's block interface (include/pgo_sparse.h) that needs no GPU: the undamped Schur complement S of a handle as
 // 6 x 6 blocks from pgo_get_normal_blocks' arrays (sc_reduce_normal_blocks), the checks and the adjacency of a caller's pair list (sc_check_pairs, sc_pair_adjacency),
 // where a 6 x 6 block lands in the permuted tile matrix (sc_block_entry: what the fill kernel computes per entry) and the right-hand sides of
-// pgo_sparse_chol_inverse_blocks from its CSR rows (ScRows).  tests/native/sparse_companion_host.cpp runs all of it on the host.
+// pgo_sparse_chol_inverse_blocks from its CSR rows (ScRows).  tests/native/sparse_companion_host.cpp runs all of it on the host.  For the selected inverse: where an
+// entry of a 6 x 6 block of the inverse is stored (sc_sigma_entry) and the gather of a block on the host (sc_selected_block_host; tests/native/sparse_selinv_host.cpp).
 //
 // S, per entry, is pgo_dense_math.hpp's arithmetic for a matrix-free handle (DcMfPlan, dc_mf_diag_entry, dc_mf_offdiag_entry): per keyframe H_ii minus c c^T / h over
 // its switch sides in edge order; per pair of keyframes the sum in edge order (relative-pose before switchable) of J1^T J2 — transposed where the edge's c1 is the lower
@@ -90,6 +91,30 @@ inline void sc_fill_blocks_host(const ScPlan& P, int64_t N, const uint8_t* in_sy
     for (int64_t k = 0; k < n_pairs; ++k)
         for (int a = 0; a < 6; ++a)
             for (int c = 0; c < 6; ++c) { sc_block_entry(pos[hi[k]], pos[lo[k]], a, c, &row, &col); put(row, col, blocks[(size_t)k * 36 + a * 6 + c]); }
+}
+
+// Entry (i, j) of the 6 x 6 block of the inverse with its rows at keyframe position pr and its columns at position pc: the row and column of the permuted matrix's
+// LOWER triangle that hold it (the inverse is symmetric; the selected inverse stores the lower tiles, and in a diagonal tile this is the lower half).  (pc, pr, j, i)
+// gives the same place: (b, a) is the exact transpose of (a, b), a diagonal block is exactly symmetric.
+PGO_DC_HD void sc_sigma_entry(int32_t pr, int32_t pc, int i, int j, int* row, int* col) {
+    const int r = pr * 6 + i, q = pc * 6 + j;
+    *row = r > q ? r : q; *col = r > q ? q : r;
+}
+// One block of the selected inverse Z (ScSelHost's tiles) on the host, as the gather kernel reads it: rows of keyframe a, columns of keyframe b, the caller's keyframe
+// order.  A keyframe outside the system: a zero block (true).  A block may straddle up to four tiles — those of its four corners; false and zeros when one of them is
+// not in the pattern.
+inline bool sc_selected_block_host(const ScPlan& P, const double* Z, const uint8_t* in_system, const int32_t* pos, int32_t a, int32_t b, double* out36) {
+    std::fill(out36, out36 + 36, 0.0);
+    if (!in_system[a] || !in_system[b]) return true;
+    int row, col;
+    for (int i = 0; i < 6; i += 5)
+        for (int j = 0; j < 6; j += 5) { sc_sigma_entry(pos[a], pos[b], i, j, &row, &col); if (P.find(row / DC_NB, col / DC_NB) < 0) return false; }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            sc_sigma_entry(pos[a], pos[b], i, j, &row, &col);
+            out36[i * 6 + j] = Z[(size_t)P.find(row / DC_NB, col / DC_NB) * SC_TILE + (size_t)(row % DC_NB) * DC_NB + col % DC_NB];
+        }
+    return true;
 }
 
 // The right-hand sides of pgo_sparse_chol_inverse_blocks: groups of 1 or 6 sparse rows in CSR over the 6 N coordinates of the caller's keyframe order.  Per non-zero its

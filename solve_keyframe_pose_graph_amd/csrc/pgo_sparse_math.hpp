@@ -1,6 +1,7 @@
 // pgo_sparse_math.hpp — the host side of a tile-sparse exact Cholesky solver for graphs above the dense solver's limit (pgo_dense.hip stops at PGO_DENSE_MAX_KEYFRAMES
 // because it stores all n^2 entries): the ordering of the keyframes, the tile pattern of the system, the symbolic factorisation, the order of the block steps and a serial
-// host instantiation of the whole factor and solve (tests/native/sparse_chol_host.cpp).  The arithmetic is pgo_dense_math.hpp's: the same 64 x 64 block routines, the same
+// host instantiation of the whole factor and solve (tests/native/sparse_chol_host.cpp) and of the selected inverse on the factor's tiles (sc_selinv_steps, ScSelHost;
+// tests/native/sparse_selinv_host.cpp).  The arithmetic is pgo_dense_math.hpp's: the same 64 x 64 block routines, the same
 // panel substitution, the same update.  libpgo.so does not include this header and no option of pgo_options uses it (DESIGN.md section 3.4 says why); the kernels that run
 // this plan and this step order are the companion library's, libpgo_sparse.so (pgo_sparse.hip, include/pgo_sparse.h).
 //
@@ -93,7 +94,11 @@ struct ScPlan {
     int64_t factor_launches() const { int64_t l = 1; for (int k = 0; k + 1 < nt; ++k) l += s_size(k) > 0 ? (ahead[(size_t)k] ? 2 : 3) : 1; return l; }
     int64_t solve_launches() const { return 2 * (int64_t)nt; }
     int64_t tile_updates() const { int64_t u = 0; for (int k = 0; k < nt; ++k) { const int64_t m = s_size(k); u += m * (m + 1) / 2; } return u; }
-    size_t scratch_doubles() const { return (size_t)DC_NB * ((size_t)max_s() * DC_NB + 16); }      // the k-major copy of one panel, compact by position in s_k
+    // the selected inverse (sc_selinv_steps): one launch for the inverses of all diagonal tiles, then ginv + column + diag per column with a non-empty s_k; tile products:
+    // |s_k|^2 of column(k) and |s_k| of diag(k)
+    int64_t selinv_launches() const { int64_t l = 1; for (int k = 0; k < nt; ++k) l += s_size(k) > 0 ? 3 : 0; return l; }
+    int64_t selinv_products() const { int64_t u = 0; for (int k = 0; k < nt; ++k) { const int64_t m = s_size(k); u += m * m + m; } return u; }
+    size_t scratch_doubles() const { return (size_t)DC_NB * ((size_t)max_s() * DC_NB + 16); }      // the k-major copy of one panel, compact by position in s_k (>= max_s tiles: the selected inverse keeps G there)
     int ldu() const { return max_s() * DC_NB + 16; }
 };
 
@@ -188,6 +193,22 @@ template <class Ops>
 inline void sc_solve_steps(const ScPlan& P, Ops& o) {
     for (int k = 0; k < P.nt; ++k) o.forward(k);
     for (int k = P.nt - 1; k >= 0; --k) o.backward(k);
+}
+// The selected inverse (Takahashi's recurrence on the tiles of L): every tile of Z = A^-1 that lies in the pattern of L, one backward pass over the block columns.
+// With A = L L^T and s = s_k:
+//   inverses() Z_kk = L_kk^-T L_kk^-1 for EVERY k, the entries i >= j, mirrored: it reads L alone, so it is one step of nt independent parts ahead of the chain of
+//              dependent steps (on the device one launch of nt workgroups: the 64-step substitutions are the longest block routine of the recurrence);
+// then for k = nt - 1 .. 0 with a non-empty s_k:
+//   ginv(k)    G_e = L_{s[e],k} L_kk^-1 for every tile of s, by substitution, compact by position e;
+//   column(k)  Z_{s[a],k} = - sum_b Z(s[a], s[b]) G_b, b ascending; Z(s[a], s[b]) = Z(s[b], s[a])^T where a < b — every tile (s[a], s[b]), a >= b, is in the pattern by
+//              the argument the update relies on, and it was finished by the steps of the columns s[b] > k;
+//   diag(k)    Z_kk -= sum_a G_a^T Z_{s[a],k}, the entries i >= j, mirrored: a diagonal tile of Z holds both triangles with equal bits.
+// An empty s_k has no step: Z_kk = L_kk^-T L_kk^-1 alone.  Z is a second tile array with the ids of L's tiles; L is only read.
+template <class Ops>
+inline void sc_selinv_steps(const ScPlan& P, Ops& o) {
+    o.inverses();
+    for (int k = P.nt - 1; k >= 0; --k)
+        if (P.s_size(k) > 0) { o.ginv(k); o.column(k); o.diag(k); }
 }
 
 // The plan of a dense host matrix (n x n row-major, padded to nc = a multiple of 64 by identity rows): the tile pattern is that of the exact non-zeros of its lower
@@ -285,6 +306,84 @@ struct ScHost {
         }
     }
 };
+
+// ---- serial host instantiation of the selected inverse on the factored tiles T: Z [tiles][4096] receives every tile, T is only read.  G and L_kk^-T L_kk^-1 come from
+// the block substitutions (a row of G: L_kk^T g = l; a column of the inverse: L_kk y = e_c, L_kk^T x = y), never from a product with an explicit inverse; every product
+// is a sum formed from zero in ascending order (b or a outermost, then the 64 terms) and subtracted once, as the kernels' accumulators are.
+struct ScSelHost {
+    const ScPlan& P; const double* T; double* Z;
+    std::vector<double> G = std::vector<double>((size_t)std::max(P.max_s(), 1) * SC_TILE, 0.0);      // G_e row-major, compact by position in s_k
+    std::vector<double> blk = std::vector<double>((size_t)DC_NB * DC_LD, 0.0), X = std::vector<double>((size_t)DC_NB * DC_LD, 0.0), acc = std::vector<double>(SC_TILE, 0.0);
+    double vec[DC_NB], sol[DC_NB];
+    double* ztile(int id) const { return Z + (size_t)id * SC_TILE; }
+    void load_diag(int k) { const double* t = T + (size_t)P.diag(k) * SC_TILE; for (int i = 0; i < DC_NB; ++i) for (int j = 0; j < DC_NB; ++j) blk[(size_t)i * DC_LD + j] = t[i * DC_NB + j]; }
+    void ginv(int k) {
+        load_diag(k);
+        const int32_t c0 = P.col_ptr[(size_t)k], m = P.s_size(k);
+        for (int e = 0; e < m; ++e) {
+            const double* t = T + (size_t)P.col_tile[(size_t)(c0 + e)] * SC_TILE;
+            double* g = G.data() + (size_t)e * SC_TILE;
+            for (int r = 0; r < DC_NB; ++r) {
+                for (int c = 0; c < DC_NB; ++c) vec[c] = t[r * DC_NB + c];
+                dc_backward_block(DcSerial{}, blk.data(), vec, sol);
+                for (int c = 0; c < DC_NB; ++c) g[r * DC_NB + c] = sol[c];
+            }
+        }
+    }
+    void column(int k) {
+        const int32_t c0 = P.col_ptr[(size_t)k], m = P.s_size(k);
+        for (int a = 0; a < m; ++a) {
+            std::fill(acc.begin(), acc.end(), 0.0);
+            const int ra = P.col_row[(size_t)(c0 + a)];
+            for (int b = 0; b < m; ++b) {
+                const int rb = P.col_row[(size_t)(c0 + b)];
+                const bool tr = a < b;                                           // the stored tile is (s[b], s[a]): read transposed
+                const double* z = ztile(tr ? P.find(rb, ra) : P.find(ra, rb));      // in the pattern by construction
+                const double* g = G.data() + (size_t)b * SC_TILE;
+                for (int i = 0; i < DC_NB; ++i)
+                    for (int n = 0; n < DC_NB; ++n) {
+                        double s = acc[(size_t)i * DC_NB + n];
+                        for (int kk = 0; kk < DC_NB; ++kk) s += (tr ? z[kk * DC_NB + i] : z[i * DC_NB + kk]) * g[kk * DC_NB + n];
+                        acc[(size_t)i * DC_NB + n] = s;
+                    }
+            }
+            double* out = ztile(P.col_tile[(size_t)(c0 + a)]);
+            for (size_t e = 0; e < SC_TILE; ++e) out[e] = -acc[e];
+        }
+    }
+    void inverses() {
+        for (int k = 0; k < P.nt; ++k) {
+            load_diag(k);
+            for (int c = 0; c < DC_NB; ++c) {      // column c of L_kk^-T L_kk^-1 from the unit right-hand side e_c
+                for (int i = 0; i < DC_NB; ++i) vec[i] = i == c ? 1.0 : 0.0;
+                dc_forward_block(DcSerial{}, blk.data(), vec, sol);
+                for (int i = 0; i < DC_NB; ++i) vec[i] = sol[i];
+                dc_backward_block(DcSerial{}, blk.data(), vec, sol);
+                for (int i = 0; i < DC_NB; ++i) X[(size_t)c * DC_LD + i] = sol[i];
+            }
+            double* out = ztile(P.diag(k));
+            for (int i = 0; i < DC_NB; ++i) for (int j = 0; j <= i; ++j) out[i * DC_NB + j] = out[j * DC_NB + i] = X[(size_t)j * DC_LD + i];
+        }
+    }
+    void diag(int k) {
+        const int32_t c0 = P.col_ptr[(size_t)k], m = P.s_size(k);
+        double* out = ztile(P.diag(k));
+        for (int i = 0; i < DC_NB; ++i)
+            for (int j = 0; j <= i; ++j) {
+                double s = 0.0;
+                for (int a = 0; a < m; ++a) {
+                    const double* g = G.data() + (size_t)a * SC_TILE; const double* z = ztile(P.col_tile[(size_t)(c0 + a)]);
+                    for (int x = 0; x < DC_NB; ++x) s += g[x * DC_NB + i] * z[x * DC_NB + j];
+                }
+                out[i * DC_NB + j] = out[j * DC_NB + i] = out[i * DC_NB + j] - s;
+            }
+    }
+};
+// Z [tiles][4096] from the factored tiles T
+inline void sc_host_selected_inverse(const ScPlan& P, const double* T, double* Z) {
+    ScSelHost H{P, T, Z};
+    sc_selinv_steps(P, H);
+}
 
 // Solves A x = b for the symmetric positive definite n x n matrix `a` with the tile-sparse factorisation, row i at position pos[i] < n (a permutation of 0 .. n - 1;
 // nullptr: the identity).  Returns false — and leaves x alone — when a pivot failed.  info8 (may be null): nt, tiles of the matrix, tiles of L, 0, bytes of the tile

@@ -2,7 +2,8 @@
 covariance blocks from it.
 
 The library is a companion of libpgo.so: it takes no Problem.  covariance() below carries a Problem's system across with Problem.normal_blocks() — every handle has
-them, matrix-free ones too — and returns what Problem.covariance returns where that runs.  As capi: no CPU fallback, a missing library or device is an error."""
+them, matrix-free ones too — and returns what Problem.covariance returns where that runs; covariance_all() returns every keyframe's marginal and every edge's joint
+covariance from one selected inverse of the factor (SparseCholesky.selected_inverse / selected_blocks).  As capi: no CPU fallback, a missing library or device is an error."""
 import ctypes as C
 import dataclasses
 
@@ -16,6 +17,7 @@ MAX_RHS, MAX_GROUPS = 65535, 64                      # PGO_SPARSE_MAX_RHS, PGO_S
 ERR_INVALID_ARG, ERR_STATE, ERR_NUMERIC = -1, -5, -7
 # what info() and spd_solve() report of a plan
 INFO = ("nt", "a_tiles", "l_tiles", "ordering", "bytes", "factor_launches", "solve_launches", "tile_updates")
+SELECTED_INFO = ("launches", "tile_products", "bytes", "current")      # selected_info()
 
 _dp, _ip, _lp, _bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
 _lib = None
@@ -44,6 +46,9 @@ def load(build=True):
     lib.pgo_sparse_chol_factor.argtypes = [C.c_void_p, _dp, _dp]
     lib.pgo_sparse_chol_solve.argtypes = [C.c_void_p, C.c_int64, _dp, _dp]
     lib.pgo_sparse_chol_inverse_blocks.argtypes = [C.c_void_p, C.c_int64, _lp, _lp, _ip, _dp, C.c_int64, _ip, _ip, _dp]
+    lib.pgo_sparse_chol_selected_inverse.argtypes = [C.c_void_p]
+    lib.pgo_sparse_chol_selected_info.argtypes = [C.c_void_p, _lp]
+    lib.pgo_sparse_chol_selected_blocks.argtypes = [C.c_void_p, C.c_int64, _ip, _ip, _dp, _bp]
     lib.pgo_sparse_reduce_normal_blocks.argtypes = [C.c_int64, _bp, _dp, _dp, _dp, _dp, C.c_int64, _ip, _ip, C.c_int64, _ip, _ip, _lp, _ip, _ip, _dp, _dp]
     _lib = lib
     return lib
@@ -95,7 +100,8 @@ def reduce_normal_blocks(n_nodes, node_free, diag, offdiag, sw_c, sw_hss, rel_c1
 
 
 class SparseCholesky:
-    """pgo_sparse_chol: the symbolic phase at construction (the keyframes of the system and the pairs that share a block), then factor / solve / inverse_blocks"""
+    """pgo_sparse_chol: the symbolic phase at construction (the keyframes of the system and the pairs that share a block), then factor / solve / inverse_blocks,
+    and selected_inverse / selected_blocks for many blocks at once"""
 
     def __init__(self, n_nodes, in_system, pair_hi, pair_lo, ordering=ORDER_AUTO, device_id=0):
         self.lib = load()
@@ -125,7 +131,7 @@ class SparseCholesky:
         return dict(zip(INFO, [int(v) for v in info])), order
 
     def last_ms(self):
-        """HIP-event milliseconds of the launches of the last factor, solve or inverse_blocks"""
+        """HIP-event milliseconds of the launches of the last factor, solve, inverse_blocks, selected_inverse or selected_blocks"""
         return self.lib.pgo_sparse_chol_last_ms(self.h)
 
     def factor(self, diag, pair_blocks):
@@ -158,6 +164,25 @@ class SparseCholesky:
         _check(self.lib.pgo_sparse_chol_inverse_blocks(self.h, len(groups), gp.ctypes.data_as(_lp), rp.ctypes.data_as(_lp), _p(cc, _ip), _p(vv, _dp), len(pr), _p(ga, _ip), _p(gb, _ip), _p(out, _dp)), self.h)
         dim = lambda g: len(groups[g])
         return [out[k, :dim(a) * dim(b)].reshape(dim(a), dim(b)).copy() for k, (a, b) in enumerate(pr)]
+
+    def selected_inverse(self):
+        """every tile of A^-1 in the pattern of the factor (Takahashi's recurrence), kept in the object until the next factor(); the factor itself is only read"""
+        _check(self.lib.pgo_sparse_chol_selected_inverse(self.h), self.h)
+
+    def selected_info(self):
+        """launches and tile products of one selected_inverse(), bytes of its tile array, whether a selected inverse of the present factor exists"""
+        info = np.zeros(4, np.int64)
+        _check(self.lib.pgo_sparse_chol_selected_info(self.h, info.ctypes.data_as(_lp)), self.h)
+        return dict(zip(SELECTED_INFO, [int(v) for v in info]))
+
+    def selected_blocks(self, node_a, node_b):
+        """the blocks of A^-1 with the rows of keyframe node_a[k] and the columns of keyframe node_b[k], from the selected inverse -> (blocks (k, 6, 6), in_pattern
+        (k,) bool).  A keyframe outside the system: a zero block; a block not wholly in the factor's pattern: zeros and in_pattern False."""
+        a, b = _i(node_a).reshape(-1), _i(node_b).reshape(-1)
+        assert a.shape == b.shape
+        out, flag = np.zeros((len(a), 6, 6)), np.zeros(len(a), np.uint8)
+        _check(self.lib.pgo_sparse_chol_selected_blocks(self.h, len(a), _p(a, _ip), _p(b, _ip), _p(out, _dp), _p(flag, _bp)), self.h)
+        return out, flag.astype(bool)
 
 
 @dataclasses.dataclass
@@ -254,3 +279,84 @@ def covariance(P, edges, quat, t, sw, pairs, ordering=ORDER_AUTO, device_id=None
     finally:
         F.close()
     return out
+
+
+@dataclasses.dataclass
+class AllCovariances:
+    """what covariance_all() returns; n_rel, n_sw: the relative-pose and the switchable edges in the order they were added"""
+    pose: np.ndarray           # (N, 6, 6): every keyframe's marginal covariance; a constant keyframe: zeros; a keyframe referenced by no residual block: NaN
+    rel_cross: np.ndarray      # (n_rel, 6, 6): cov(c1, c2) of every relative-pose edge, rows of c1
+    sw_cross: np.ndarray       # (n_sw, 6, 6): cov(c1, c2) of every switchable edge, rows of c1
+    switch_var: np.ndarray     # (n_sw,): the variance of every switchable edge's switch
+    switch_pose: np.ndarray    # (n_sw, 2, 6): cov(switch e, keyframe c1), cov(switch e, keyframe c2)
+
+
+def all_block_requests(n_nodes, edges):
+    """(node_a, node_b) of the blocks covariance_all gathers: every keyframe with itself, then (c1, c2) of every relative-pose edge, then of every switchable edge —
+    all of them blocks of the system, hence in the factor's pattern"""
+    own = np.arange(n_nodes, dtype=np.int32)
+    return _i(np.concatenate([own, _i(edges.rel_c1), _i(edges.sw_c1)])), _i(np.concatenate([own, _i(edges.rel_c2), _i(edges.sw_c2)]))
+
+
+def assemble_all(n_nodes, in_system, referenced, edges, sw_c, sw_hss, blocks):
+    """AllCovariances from the gathered blocks of all_block_requests (zero where a keyframe is outside the system), in fp64 numpy.  Switch e is the row v_e = -c_e / h_e
+    on the edge's free endpoints: var = 1 / h_e + v_e^T Sigma v_e, cov(switch e, keyframe k) = v_c1^T Sigma(c1, k) + v_c2^T Sigma(c2, k) — all of it from the three
+    blocks (c1, c1), (c1, c2), (c2, c2)."""
+    N, n_rel, n_sw = n_nodes, len(edges.rel_c1), len(edges.sw_c1)
+    blocks = np.asarray(blocks, dtype=np.float64).reshape(-1, 6, 6)
+    assert len(blocks) == N + n_rel + n_sw
+    ins = np.asarray(in_system).astype(bool)
+    pose = blocks[:N].copy()
+    pose[~np.asarray(referenced, dtype=bool)] = np.nan
+    rel_cross, sw_cross = blocks[N:N + n_rel].copy(), blocks[N + n_rel:].copy()
+    c1, c2 = np.asarray(edges.sw_c1, dtype=np.int64), np.asarray(edges.sw_c2, dtype=np.int64)
+    c, h = _d(sw_c).reshape(n_sw, 12), _d(sw_hss).reshape(n_sw)
+    v1 = np.where(ins[c1][:, None], -c[:, :6] / h[:, None], 0.0)
+    v2 = np.where(ins[c2][:, None], -c[:, 6:] / h[:, None], 0.0)
+    S11, S22, S12 = blocks[:N][c1], blocks[:N][c2], sw_cross
+    quad = lambda u, S, w: np.einsum("ei,eij,ej->e", u, S, w)
+    switch_var = 1.0 / h + (quad(v1, S11, v1) + 2.0 * quad(v1, S12, v2) + quad(v2, S22, v2))
+    switch_pose = np.zeros((n_sw, 2, 6))
+    switch_pose[:, 0] = np.einsum("ei,eij->ej", v1, S11) + np.einsum("ei,eji->ej", v2, S12)
+    switch_pose[:, 1] = np.einsum("ei,eij->ej", v1, S12) + np.einsum("ei,eij->ej", v2, S22)
+    return AllCovariances(pose, rel_cross, sw_cross, switch_var, switch_pose)
+
+
+def covariance_all(P, edges, quat, t, sw, ordering=ORDER_AUTO, device_id=None, timings=None):
+    """Every keyframe's marginal covariance and every edge's joint covariance (pose, pose, switch) at the given point, for graphs of any size: AllCovariances.  The
+    linearisation, the reduction and the system are covariance()'s; instead of a forward sweep per requested row, one selected inverse (SparseCholesky.selected_inverse:
+    about twice the factor's tile products, no dense array) and one gather of the N + n_rel + n_sw blocks; the switch quantities are formed on the host from them.
+    This is an all-blocks call: a keyframe referenced by no residual block does not raise, its `pose` block is NaN; a constant keyframe's blocks are zero.
+    PgoError(PGO_ERR_NUMERIC): the system is not positive definite (is the gauge fixed?), or some switchable edge's h is not a positive finite number.
+    timings (a dict): HIP-event milliseconds of the factor, the selected inverse and the gather."""
+    q = np.asarray(quat, dtype=np.float64).reshape(-1, 4)
+    N = len(q)
+    free = np.ones(N, np.uint8); free[np.asarray(edges.constant, dtype=np.int64)] = 0
+    referenced = np.zeros(N, bool)
+    for c in (edges.rel_c1, edges.rel_c2, edges.sw_c1, edges.sw_c2, edges.reg_node):
+        referenced[np.asarray(c, dtype=np.int64)] = True
+    P.evaluate(quat, t, sw, want_residuals=False, want_gradient=True)
+    diag, _, off, c, hss, _ = P.normal_blocks()
+    for e in range(len(edges.sw_c1)):
+        if not (hss[e] > 0.0 and np.isfinite(hss[e])):
+            raise PgoError(ERR_NUMERIC, "switch %d: J_s^T J_s = %r is not a positive finite number" % (int(edges.sw_idx[e]), hss[e]))
+    in_system = (free != 0) & referenced
+    hi, lo, sd, sb = reduce_normal_blocks(N, free, diag, off, c, hss, edges.rel_c1, edges.rel_c2, edges.sw_c1, edges.sw_c2)
+    F = SparseCholesky(N, in_system, hi, lo, ordering, P.options.device_id if device_id is None else device_id)
+    try:
+        F.factor(sd, sb)
+        if timings is not None:
+            timings["factor_ms"] = F.last_ms(); timings["info"] = F.info()[0]
+        F.selected_inverse()
+        if timings is not None:
+            timings["selected_ms"] = F.last_ms(); timings["selected_info"] = F.selected_info()
+        na, nb = all_block_requests(N, edges)
+        blocks, in_pattern = F.selected_blocks(na, nb)
+        if timings is not None:
+            timings["gather_ms"] = F.last_ms()
+        if not in_pattern.all():      # (every request is a block of the system)
+            k = int(np.flatnonzero(~in_pattern)[0])
+            raise RuntimeError("covariance_all: the block of keyframes (%d, %d) is not in the factor's pattern" % (na[k], nb[k]))
+    finally:
+        F.close()
+    return assemble_all(N, in_system, referenced, edges, c, hss, blocks)
