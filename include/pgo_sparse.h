@@ -88,6 +88,25 @@ int pgo_sparse_chol_selected_info(const pgo_sparse_chol* h, int64_t* info4);
  * PGO_ERR_STATE: no selected inverse of the present factor. */
 int pgo_sparse_chol_selected_blocks(pgo_sparse_chol* h, int64_t n_blocks, const int32_t* node_a, const int32_t* node_b, double* out /*[n_blocks][36]*/, uint8_t* in_pattern /*[n_blocks], may be NULL*/);
 
+/* Blocks of A^-1 between ANY keyframes, in number — the blocks outside the pattern of L, which the selected inverse has not: the cross-covariance of two keyframes
+ * that share no edge yet (a loop-closure candidate).  col_node [n_cols]: distinct keyframes; out[36 k] = the 6 x 6 block, row-major, with the rows of keyframe
+ * row_node[k] and the columns of keyframe col_node[col_index[k]].  The six unit columns of every column keyframe that a block asks for are solved by both sweeps as
+ * the ROWS of a workspace W [m_pad][nc], in ascending position, 64 rows (a panel) per workgroup, the 64 x 64 x 64 tile products on the fp64 MFMA (sc_panel_steps):
+ *   launches: per chunk 1 (the unit entries) + nt - k0 (forward, from the first tile k0 that holds a one) + nt - k_stop (backward, down to the lowest tile that holds
+ *             a requested row) + 1 (gather): info4[0] of pgo_sparse_chol_columns_info; tile products: info4[1].
+ *   memory:   W, at most the workspace limit (PGO_SPARSE_WORKSPACE_BYTES unless set): more columns than fit are served in chunks of whole keyframes, one after the
+ *             other (info4[3]); allocated by the first call, grown on demand (info4[2]: bytes of the largest chunk of the last call), freed by _destroy.
+ * A right-hand side gets the bits it gets alone, whatever the batch, the chunks and the rows asked for; no atomics, every sum in a fixed order.  The factor is only
+ * read: pgo_sparse_chol_solve, _inverse_blocks and the selected inverse give afterwards the bits they gave before.  A block with a keyframe outside the system, as
+ * row or as column: zeros.  The block of (b, a) through column a and that of (a, b) through column b are two computations: ask one and transpose it.
+ * PGO_ERR_STATE: no factor.  PGO_ERR_INVALID_ARG, out left alone: a keyframe out of range, col_node not distinct, col_index out of range. */
+#define PGO_SPARSE_WORKSPACE_BYTES ((int64_t)1 << 30)
+int pgo_sparse_chol_inverse_columns(pgo_sparse_chol* h, int64_t n_cols, const int32_t* col_node, int64_t n_blocks, const int32_t* row_node, const int32_t* col_index, double* out /*[n_blocks][36]*/);
+/* of the last pgo_sparse_chol_inverse_columns: launches, tile products, workspace bytes, chunks.  No launch. */
+int pgo_sparse_chol_columns_info(const pgo_sparse_chol* h, int64_t* info4);
+/* the most W may take from the next pgo_sparse_chol_inverse_columns on; at least one panel, 64 rows of 64 nt doubles, else PGO_ERR_INVALID_ARG */
+int pgo_sparse_chol_set_workspace_limit(pgo_sparse_chol* h, int64_t bytes);
+
 /* Host only: the undamped Schur complement S of a handle's last linearisation as blocks, from pgo_get_normal_blocks' arrays (diag [n_nodes][36], offdiag
  * [n_rel + n_sw][36]: J1^T J2 per edge, relative-pose then switchable, internal order; sw_c [n_sw][12]; sw_hss [n_sw]), the edges' endpoints in the same
  * order and node_free [n_nodes] (0: constant).  Per free keyframe H_ii - sum c c^T / h over its switch sides; per pair of free keyframes the sum in edge order
@@ -97,7 +116,7 @@ int pgo_sparse_reduce_normal_blocks(int64_t n_nodes, const uint8_t* node_free, c
                                     int64_t n_rel, const int32_t* rel_c1, const int32_t* rel_c2, int64_t n_sw, const int32_t* swe_c1, const int32_t* swe_c2,
                                     int64_t* n_pairs, int32_t* pair_hi, int32_t* pair_lo, double* s_diag, double* s_blocks);
 
-/* HIP-event milliseconds of the launches of the object's last pgo_sparse_chol_factor (fill included), _solve, _inverse_blocks, _selected_inverse or _selected_blocks */
+/* HIP-event milliseconds of the launches of the object's last pgo_sparse_chol_factor (fill included), _solve, _inverse_blocks, _selected_inverse, _selected_blocks or _inverse_columns */
 double pgo_sparse_chol_last_ms(const pgo_sparse_chol* h);
 
 const char* pgo_sparse_strerror(int code);

@@ -93,7 +93,7 @@ SPARSE_HEADERS = ["pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_mat
 SPARSE_OBJ_DIR = os.path.join(_ROOT, "build", "obj_sparse")
 # every symbol include/pgo_sparse.h declares
 SPARSE_EXPORTS = ["pgo_sparse_spd_solve", "pgo_sparse_chol_create", "pgo_sparse_chol_destroy", "pgo_sparse_chol_info", "pgo_sparse_chol_factor", "pgo_sparse_chol_solve",
-                  "pgo_sparse_chol_inverse_blocks", "pgo_sparse_chol_selected_inverse", "pgo_sparse_chol_selected_info", "pgo_sparse_chol_selected_blocks", "pgo_sparse_reduce_normal_blocks", "pgo_sparse_chol_last_ms", "pgo_sparse_strerror", "pgo_sparse_last_error"]
+                  "pgo_sparse_chol_inverse_blocks", "pgo_sparse_chol_selected_inverse", "pgo_sparse_chol_selected_info", "pgo_sparse_chol_selected_blocks", "pgo_sparse_chol_inverse_columns", "pgo_sparse_chol_columns_info", "pgo_sparse_chol_set_workspace_limit", "pgo_sparse_reduce_normal_blocks", "pgo_sparse_chol_last_ms", "pgo_sparse_strerror", "pgo_sparse_last_error"]
 
 
 def compile_libpgo_sparse(target, verbose=False, obj_dir=None):

@@ -9,6 +9,9 @@
 //
 // The selected inverse (sc_selinv_steps: sc_sel_inverses_kernel, sc_sel_ginv_kernel, sc_sel_column_kernel, sc_sel_diag_kernel, then sc_sel_gather_kernel for 6 x 6 blocks)
 // has no counterpart in pgo_dense.hip: Takahashi's recurrence on the tiles of L into a second tile array, under the same rules.
+//
+// The columns of the inverse in number (sc_panel_steps: sc_pcol_rhs_kernel, sc_pfwd_kernel, sc_pbwd_kernel, sc_pgather_kernel) are the tile-sparse counterpart of
+// dcv_solve_kernel / dcv_update_kernel — right-hand sides as the rows of W, 64 per workgroup — in the pull form and for both sweeps: blocks outside the pattern of L.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -434,8 +437,152 @@ __global__ __launch_bounds__(SC_THREADS) void sc_sel_gather_kernel(const double*
     out[gid] = v;
 }
 
+// ---- columns of the inverse in number (sc_panel_steps): W [m_pad][nc], the right-hand sides as rows, a workgroup per panel of 64 rows, a wavefront per 16 of them.
+// A lane (lr, lk) holds row 16 wave + lr of the panel and the columns 16 jb + lk + 4 reg of the block W_pk — sc_panel_kernel's layout, so the product sums feed the
+// substitution without a transposition.  For that the products are formed transposed, D^T = L W^T: the tile of L is the A operand (A[i][k], i the column of W_pk),
+// the rows of W the B operand (B[k][n], n the row), and D comes back as col = lane & 15 = the row of W, row = (lane >> 4) + 4 reg = the column inside the 16-wide
+// block.  The tile of L goes through LDS (all four wavefronts read all of it; the stride of 65 makes the row walk of the forward sweep and the column walk of the
+// backward sweep conflict-free) and the diagonal tile follows it into the same 33 KB.  The rows of W are read directly, not through LDS: a wavefront reads its own 16
+// rows and nobody else's, four consecutive doubles of each per load — staging them would take a second 33 KB array and the kernel past 64 KB of LDS per workgroup.
+
+// rhs: the one of every unit row into the zeroed W; col[r] = -1: a padding row
+__global__ __launch_bounds__(SC_THREADS) void sc_pcol_rhs_kernel(double* __restrict__ W, int nc, int rows, const int32_t* __restrict__ col) {
+    const int r = (int)(blockIdx.x * SC_THREADS + threadIdx.x);
+    if (r < rows && col[r] >= 0) W[(size_t)r * nc + col[r]] = 1.0;
+}
+
+// pfwd(k): one workgroup per started panel (the grid).  acc = sum_j W_pj L_kj^T over the stored tiles (k, j), first[p] <= j < k, ascending; W_pk - acc, then
+// sc_panel_kernel's substitution with L_kk.
+__global__ __launch_bounds__(SC_THREADS) void sc_pfwd_kernel(const double* __restrict__ T, ScDev P, int k, int nc, double* __restrict__ W, const int32_t* __restrict__ first) {
+    __shared__ double l[DC_NB * DC_LD];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int p = (int)blockIdx.x, fp = first[p];
+    double* __restrict__ wrow = W + ((size_t)p * DC_NB + wave * DC_SUB + lr) * nc;
+    const int diag = P.row_ptr[k + 1] - 1;
+    sc_d4 acc[DC_NB / DC_SUB];
+#pragma unroll
+    for (int jb = 0; jb < DC_NB / DC_SUB; ++jb) acc[jb] = sc_d4{0.0, 0.0, 0.0, 0.0};
+    for (int id = P.row_ptr[k]; id < diag; ++id) {
+        const int j = P.row_col[id];
+        if (j < fp) continue;                                              // (the same for every thread of the workgroup) W_pj is all zero
+        __syncthreads();                                                   // the products of the tile before are done with l
+        sc_load_tile(T + (size_t)id * SC_TILE, l);
+        __syncthreads();
+        const double* __restrict__ wj = wrow + (size_t)j * DC_NB;
+#pragma unroll
+        for (int kk = 0; kk < DC_NB / 4; ++kk) {
+            const double b = wj[kk * 4 + lk];
+#pragma unroll
+            for (int jb = 0; jb < DC_NB / DC_SUB; ++jb) acc[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(jb * DC_SUB + lr) * DC_LD + kk * 4 + lk], b, acc[jb], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+    sc_load_tile(T + (size_t)diag * SC_TILE, l);
+    __syncthreads();
+    double* __restrict__ arow = wrow + (size_t)k * DC_NB;
+    sc_d4 Y[DC_NB / DC_SUB];
+#pragma unroll
+    for (int j = 0; j < DC_NB / DC_SUB; ++j) {
+        double r[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = arow[j * DC_SUB + lk + 4 * reg] - acc[j][reg];
+        sc_d4 sub = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int m = 0; m < j; ++m)
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+                sub = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(j * DC_SUB + lr) * DC_LD + m * DC_SUB + 4 * kk + lk], Y[m][kk], sub, 0, 0, 0);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = r[reg] - sub[reg];
+#pragma unroll
+        for (int q = 0; q < DC_SUB; ++q) {
+            const double yq = __shfl(r[q >> 2], (q & 3) * 16 + lr) / l[(j * DC_SUB + q) * DC_LD + j * DC_SUB + q];
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int c = lk + 4 * reg;
+                const double lcq = l[(j * DC_SUB + (c > q ? c : q)) * DC_LD + j * DC_SUB + q];      // (c <= q: the diagonal entry, unused)
+                r[reg] = c == q ? yq : (c > q ? r[reg] - lcq * yq : r[reg]);
+            }
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            Y[j][reg] = r[reg];
+            arow[j * DC_SUB + lk + 4 * reg] = r[reg];
+        }
+    }
+}
+
+// pbwd(k): one workgroup per panel (the grid).  acc = sum_{i in s_k} W_pi L_ik, i ascending; W_pk - acc, then sc_sel_ginv_kernel's substitution with L_kk.
+__global__ __launch_bounds__(SC_THREADS) void sc_pbwd_kernel(const double* __restrict__ T, ScDev P, int k, int nc, double* __restrict__ W) {
+    __shared__ double l[DC_NB * DC_LD];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    double* __restrict__ wrow = W + ((size_t)blockIdx.x * DC_NB + wave * DC_SUB + lr) * nc;
+    sc_d4 acc[DC_NB / DC_SUB];
+#pragma unroll
+    for (int jb = 0; jb < DC_NB / DC_SUB; ++jb) acc[jb] = sc_d4{0.0, 0.0, 0.0, 0.0};
+    for (int e = P.col_ptr[k]; e < P.col_ptr[k + 1]; ++e) {
+        __syncthreads();                                                   // the products of the tile before are done with l
+        sc_load_tile(T + (size_t)P.col_tile[e] * SC_TILE, l);
+        __syncthreads();
+        const double* __restrict__ wi = wrow + (size_t)P.col_row[e] * DC_NB;
+#pragma unroll
+        for (int kk = 0; kk < DC_NB / 4; ++kk) {
+            const double b = wi[kk * 4 + lk];
+#pragma unroll
+            for (int jb = 0; jb < DC_NB / DC_SUB; ++jb) acc[jb] = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(kk * 4 + lk) * DC_LD + jb * DC_SUB + lr], b, acc[jb], 0, 0, 0);
+        }
+    }
+    __syncthreads();
+    sc_load_tile(T + (size_t)(P.row_ptr[k + 1] - 1) * SC_TILE, l);
+    __syncthreads();
+    double* __restrict__ arow = wrow + (size_t)k * DC_NB;
+    sc_d4 Y[DC_NB / DC_SUB];
+#pragma unroll
+    for (int j = DC_NB / DC_SUB - 1; j >= 0; --j) {
+        double r[4];
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = arow[j * DC_SUB + lk + 4 * reg] - acc[j][reg];
+        sc_d4 sub = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int m = DC_NB / DC_SUB - 1; m > j; --m)
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+                sub = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(m * DC_SUB + 4 * kk + lk) * DC_LD + j * DC_SUB + lr], Y[m][kk], sub, 0, 0, 0);
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) r[reg] = r[reg] - sub[reg];
+#pragma unroll
+        for (int q = DC_SUB - 1; q >= 0; --q) {
+            const double gq = __shfl(r[q >> 2], (q & 3) * 16 + lr) / l[(j * DC_SUB + q) * DC_LD + j * DC_SUB + q];
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int c = lk + 4 * reg;
+                const double lqc = l[(j * DC_SUB + q) * DC_LD + j * DC_SUB + (c < q ? c : q)];      // (c >= q: the diagonal entry, unused)
+                r[reg] = c == q ? gq : (c < q ? r[reg] - lqc * gq : r[reg]);
+            }
+        }
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            Y[j][reg] = r[reg];
+            arow[j * DC_SUB + lk + 4 * reg] = r[reg];
+        }
+    }
+}
+
+// gather: one thread per entry of a requested block out of one chunk's W: entry (i, j) = row 6 pos[row keyframe] + i of the solution of right-hand side j of the column
+// keyframe (sc_columns_gather_host).  row0[c] < 0: the column has no rows in this chunk — another chunk's, or a block with a keyframe outside the system, which stays
+// as the zero it was set to.
+__global__ __launch_bounds__(SC_THREADS) void sc_pgather_kernel(const double* __restrict__ W, int nc, int64_t n_blocks, const int32_t* __restrict__ row_node, const int32_t* __restrict__ col_index,
+                                                                const int32_t* __restrict__ row0, const uint8_t* __restrict__ in_system, const int32_t* __restrict__ pos, double* __restrict__ out) {
+    const int64_t gid = (int64_t)blockIdx.x * SC_THREADS + threadIdx.x, blk = gid / 36;
+    if (blk >= n_blocks) return;
+    const int e = (int)(gid - blk * 36), i = e / 6, j = e - i * 6;
+    const int32_t a = row_node[blk], r0 = row0[col_index[blk]];            // both in range: the host checked
+    if (r0 < 0 || !in_system[a]) return;
+    out[gid] = W[(size_t)(r0 + j) * nc + (size_t)pos[a] * 6 + i];
+}
+
 // ---- host side
-thread_local std::string g_err;     // the last error of a call without an object
+thread_local std::string g_err;    // the last error of a call without an object
 
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
@@ -473,6 +620,13 @@ struct ScSelLaunch {
     void column(int k) { hipLaunchKernelGGL(sc_sel_column_kernel, dim3((unsigned)P->s_size(k)), dim3(SC_THREADS), 0, st, Z, D, k, (const double*)G); }
     void diag(int k) { hipLaunchKernelGGL(sc_sel_diag_kernel, dim3(1), dim3(SC_THREADS), 0, st, Z, D, k, (const double*)G); }
     void inverses() { hipLaunchKernelGGL(sc_sel_inverses_kernel, dim3((unsigned)P->nt), dim3(SC_THREADS), 0, st, T, Z, D); }
+};
+
+// the launches of the panel sweeps, walked by sc_panel_steps
+struct ScPanelLaunch {
+    const double* T; ScDev D; int nc; double* W; const int32_t* first; hipStream_t st;
+    void pfwd(int k, int started) { hipLaunchKernelGGL(sc_pfwd_kernel, dim3((unsigned)started), dim3(SC_THREADS), 0, st, T, D, k, nc, W, first); }
+    void pbwd(int k, int panels) { hipLaunchKernelGGL(sc_pbwd_kernel, dim3((unsigned)panels), dim3(SC_THREADS), 0, st, T, D, k, nc, W); }
 };
 
 // a device, a stream, a plan with its tables, tile storage and panel scratch
@@ -554,10 +708,13 @@ struct pgo_sparse_chol {
     std::vector<uint8_t> in_system;
     std::vector<int32_t> order, pos;
     DevBuf d_in, d_pos, d_hi, d_lo, d_diag, d_blocks, d_at, d_val, d_pr, d_out, Z, d_na, d_nb, d_flag;
+    DevBuf ws, d_req;                                      // pgo_sparse_chol_inverse_columns: W of one chunk, the chunk's tables
+    int64_t ws_limit = PGO_SPARSE_WORKSPACE_BYTES;
+    int64_t cols_info[4] = {0, 0, 0, 0};                   // of the last pgo_sparse_chol_inverse_columns
     void release() {
         if (c.device >= 0) (void)hipSetDevice(c.device);
         if (c.st) (void)hipStreamSynchronize(c.st);
-        for (DevBuf* b : {&d_in, &d_pos, &d_hi, &d_lo, &d_diag, &d_blocks, &d_at, &d_val, &d_pr, &d_out, &Z, &d_na, &d_nb, &d_flag}) b->release();
+        for (DevBuf* b : {&d_in, &d_pos, &d_hi, &d_lo, &d_diag, &d_blocks, &d_at, &d_val, &d_pr, &d_out, &Z, &d_na, &d_nb, &d_flag, &ws, &d_req}) b->release();
         c.close();
     }
 };
@@ -832,6 +989,75 @@ int pgo_sparse_chol_selected_blocks(pgo_sparse_chol* h, int64_t n_blocks, const 
             }
     std::copy(blocks.begin(), blocks.end(), out);
     if (in_pattern) std::copy(flag.begin(), flag.end(), in_pattern);
+    return PGO_OK;
+}
+
+int pgo_sparse_chol_inverse_columns(pgo_sparse_chol* h, int64_t n_cols, const int32_t* col_node, int64_t n_blocks, const int32_t* row_node, const int32_t* col_index, double* out) {
+    if (!h) return PGO_ERR_INVALID_ARG;
+    ScCore& c = h->c;
+    c.err.clear();
+    if (n_cols < 0 || n_cols > h->N || n_blocks < 0 || n_blocks > (int64_t)50000000 || (n_cols > 0 && !col_node) || (n_blocks > 0 && (!row_node || !col_index || !out))) {
+        c.err = "pgo_sparse_chol_inverse_columns: null pointer or count out of range"; return PGO_ERR_INVALID_ARG;
+    }
+    if (!h->factored) { c.err = "pgo_sparse_chol_inverse_columns: no factor (pgo_sparse_chol_factor has not succeeded)"; return PGO_ERR_STATE; }
+    const int nc = c.nc();
+    const ScColumns Q(c.P, h->N, h->in_system.data(), h->pos.data(), n_cols, col_node, n_blocks, row_node, col_index, h->ws_limit);
+    if (Q.error) { c.err = std::string("pgo_sparse_chol_inverse_columns: ") + Q.error; return PGO_ERR_INVALID_ARG; }
+    const int64_t info[4] = {Q.launches, Q.products, Q.workspace, (int64_t)Q.chunks.size()};
+    std::copy(info, info + 4, h->cols_info);
+    if (n_blocks == 0) return PGO_OK;
+    int rc;
+    if ((rc = c.use()) != PGO_OK) return rc;
+    const size_t nb = (size_t)n_blocks;
+    std::vector<int32_t> tab;                              // every chunk's tables, one upload: rhs_col | first | row0
+    std::vector<size_t> at;
+    for (const ScColumnChunk& C : Q.chunks) {
+        at.push_back(tab.size());
+        tab.insert(tab.end(), C.rhs_col.begin(), C.rhs_col.end());
+        tab.insert(tab.end(), C.first.begin(), C.first.end());
+        tab.insert(tab.end(), C.row0.begin(), C.row0.end());
+    }
+    SCHIP(c.err, h->ws.ensure((size_t)Q.workspace));
+    SCHIP(c.err, h->d_req.ensure(tab.size() * sizeof(int32_t)));
+    SCHIP(c.err, h->d_na.ensure(nb * sizeof(int32_t))); SCHIP(c.err, h->d_nb.ensure(nb * sizeof(int32_t)));
+    SCHIP(c.err, h->d_out.ensure(nb * 36 * sizeof(double)));
+    SCHIP(c.err, hipMemcpyAsync(h->d_na.p, row_node, nb * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
+    SCHIP(c.err, hipMemcpyAsync(h->d_nb.p, col_index, nb * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
+    if (!tab.empty()) SCHIP(c.err, hipMemcpyAsync(h->d_req.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
+    SCHIP(c.err, hipEventRecord(c.e0, c.st));
+    SCHIP(c.err, hipMemsetAsync(h->d_out.p, 0, nb * 36 * sizeof(double), c.st));
+    double* W = h->ws.as<double>();
+    for (size_t q = 0; q < Q.chunks.size(); ++q) {
+        const ScColumnChunk& C = Q.chunks[q];
+        const int32_t* d_col = h->d_req.as<const int32_t>() + at[q];
+        const int32_t* d_first = d_col + C.rhs_col.size();
+        const int32_t* d_row0 = d_first + C.first.size();
+        SCHIP(c.err, hipMemsetAsync(W, 0, (size_t)C.m_pad * nc * sizeof(double), c.st));
+        hipLaunchKernelGGL(sc_pcol_rhs_kernel, dim3((unsigned)((C.m_pad + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, c.st, W, nc, C.m_pad, d_col);
+        ScPanelLaunch L{c.T.as<const double>(), c.D, nc, W, d_first, c.st};
+        sc_panel_steps(c.P, C.first, Q.k_stop, L);
+        hipLaunchKernelGGL(sc_pgather_kernel, dim3((unsigned)((nb * 36 + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, c.st, (const double*)W, nc, n_blocks, h->d_na.as<const int32_t>(),
+                           h->d_nb.as<const int32_t>(), d_row0, h->d_in.as<const uint8_t>(), h->d_pos.as<const int32_t>(), h->d_out.as<double>());
+    }
+    SCHIP(c.err, hipEventRecord(c.e1, c.st));
+    std::vector<double> blocks(nb * 36);
+    SCHIP(c.err, hipMemcpyAsync(blocks.data(), h->d_out.p, blocks.size() * sizeof(double), hipMemcpyDeviceToHost, c.st));
+    if ((rc = c.finish()) != PGO_OK) return rc;
+    std::copy(blocks.begin(), blocks.end(), out);
+    return PGO_OK;
+}
+
+int pgo_sparse_chol_columns_info(const pgo_sparse_chol* h, int64_t* info4) {
+    if (!h || !info4) return PGO_ERR_INVALID_ARG;
+    std::copy(h->cols_info, h->cols_info + 4, info4);
+    return PGO_OK;
+}
+
+int pgo_sparse_chol_set_workspace_limit(pgo_sparse_chol* h, int64_t bytes) {
+    if (!h) return PGO_ERR_INVALID_ARG;
+    h->c.err.clear();
+    if (bytes < sc_panel_bytes(h->c.nc())) { h->c.err = "pgo_sparse_chol_set_workspace_limit: below one panel of right-hand sides, 64 rows of " + std::to_string(h->c.nc()) + " doubles"; return PGO_ERR_INVALID_ARG; }
+    h->ws_limit = bytes;
     return PGO_OK;
 }
 

@@ -3,6 +3,8 @@
 // where a 6 x 6 block lands in the permuted tile matrix (sc_block_entry: what the fill kernel computes per entry) and the right-hand sides of
 // pgo_sparse_chol_inverse_blocks from its CSR rows (ScRows).  tests/native/sparse_companion_host.cpp runs all of it on the host.  For the selected inverse: where an
 // entry of a 6 x 6 block of the inverse is stored (sc_sigma_entry) and the gather of a block on the host (sc_selected_block_host; tests/native/sparse_selinv_host.cpp).
+// For the columns of the inverse in number (pgo_sparse_chol_inverse_columns): the chunks of column keyframes that fit the workspace (sc_column_chunks), the checked and
+// laid-out request with its counts (ScColumns), the gather and the whole call on the host (sc_host_inverse_columns; tests/native/sparse_panel_host.cpp).
 //
 // S, per entry, is pgo_dense_math.hpp's arithmetic for a matrix-free handle (DcMfPlan, dc_mf_diag_entry, dc_mf_offdiag_entry): per keyframe H_ii minus c c^T / h over
 // its switch sides in edge order; per pair of keyframes the sum in edge order (relative-pose before switchable) of J1^T J2 — transposed where the edge's c1 is the lower
@@ -116,6 +118,98 @@ inline bool sc_selected_block_host(const ScPlan& P, const double* Z, const uint8
         }
     return true;
 }
+
+// ---- pgo_sparse_chol_inverse_columns: blocks of the inverse between ANY keyframes, by the panel sweeps (sc_panel_steps) on the unit rows of the column keyframes.
+// W of one chunk must fit the workspace limit; a panel of W is 64 rows of nc doubles, the least a limit may be.
+inline int64_t sc_panel_bytes(int nc) { return (int64_t)DC_NB * nc * (int64_t)sizeof(double); }
+// runs [begin, end) of the n_cols column keyframes (six rows each) whose W — whole panels — fits workspace_bytes; boundaries on whole keyframes.  Empty: the limit is
+// below one panel.
+inline std::vector<std::pair<int64_t, int64_t>> sc_column_chunks(int64_t n_cols, int nc, int64_t workspace_bytes) {
+    std::vector<std::pair<int64_t, int64_t>> runs;
+    const int64_t per = workspace_bytes / sc_panel_bytes(nc) * DC_NB / 6;      // >= 10 keyframes per panel
+    if (per < 1) return runs;
+    for (int64_t s = 0; s < n_cols; s += per) runs.emplace_back(s, std::min(n_cols, s + per));
+    return runs;
+}
+struct ScColumnChunk {
+    int m_pad = 0;                    // rows of W: a multiple of 64
+    std::vector<int32_t> rhs_col;     // [m_pad]: the column of the row's one, ascending; -1: a padding row
+    std::vector<int32_t> first;       // [m_pad / 64]: the tile of the panel's first one
+    std::vector<int32_t> row0;        // [n_cols]: the first of the six rows of column keyframe col_node[c] in this chunk's W; -1: it has none here
+};
+// A request checked and laid out.  The column keyframes that a block with two keyframes of the system asks for get six unit rows each, in ascending POSITION (a keyframe
+// may straddle two panels), dealt out in chunks; a block with a keyframe outside the system is zero and asks for nothing.  launches: per chunk the right-hand sides, the
+// steps of the two sweeps and the gather; products: ScPlan::panel_products; workspace: bytes of the largest chunk's W.
+struct ScColumns {
+    const char* error = nullptr;
+    std::vector<ScColumnChunk> chunks;
+    int k_stop = 0;
+    int64_t launches = 0, products = 0, workspace = 0;
+    ScColumns(const ScPlan& P, int64_t N, const uint8_t* in_system, const int32_t* pos, int64_t n_cols, const int32_t* col_node, int64_t n_blocks, const int32_t* row_node,
+              const int32_t* col_index, int64_t workspace_bytes) {
+        const int nc = P.nt * DC_NB;
+        std::vector<uint8_t> seen((size_t)N, 0), used((size_t)n_cols, 0);
+        for (int64_t c = 0; c < n_cols; ++c) {
+            if (col_node[c] < 0 || col_node[c] >= N) { error = "a column keyframe is out of range"; return; }
+            if (seen[(size_t)col_node[c]]) { error = "a column keyframe is listed twice"; return; }
+            seen[(size_t)col_node[c]] = 1;
+        }
+        for (int64_t k = 0; k < n_blocks; ++k) {
+            if (row_node[k] < 0 || row_node[k] >= N) { error = "a row keyframe is out of range"; return; }
+            if (col_index[k] < 0 || col_index[k] >= n_cols) { error = "a column index is out of range"; return; }
+        }
+        if (workspace_bytes < sc_panel_bytes(nc)) { error = "the workspace limit is below one panel of right-hand sides"; return; }
+        k_stop = P.nt;
+        for (int64_t k = 0; k < n_blocks; ++k)
+            if (in_system[row_node[k]] && in_system[col_node[col_index[k]]]) { k_stop = std::min(k_stop, pos[row_node[k]] * 6 / DC_NB); used[(size_t)col_index[k]] = 1; }
+        std::vector<int32_t> live;
+        for (int64_t c = 0; c < n_cols; ++c) if (used[(size_t)c]) live.push_back((int32_t)c);
+        std::sort(live.begin(), live.end(), [&](int32_t a, int32_t b) { return pos[col_node[a]] < pos[col_node[b]]; });
+        for (const auto& run : sc_column_chunks((int64_t)live.size(), nc, workspace_bytes)) {
+            ScColumnChunk C;
+            C.m_pad = (int)(((run.second - run.first) * 6 + DC_NB - 1) / DC_NB * DC_NB);
+            C.rhs_col.assign((size_t)C.m_pad, -1);
+            C.row0.assign((size_t)n_cols, -1);
+            int32_t r = 0;
+            for (int64_t q = run.first; q < run.second; ++q) {
+                const int32_t c = live[(size_t)q];
+                C.row0[(size_t)c] = r;
+                for (int a = 0; a < 6; ++a) C.rhs_col[(size_t)r++] = pos[col_node[c]] * 6 + a;
+            }
+            for (int p = 0; p < C.m_pad / DC_NB; ++p) C.first.push_back(C.rhs_col[(size_t)p * DC_NB] / DC_NB);
+            launches += 2 + P.panel_launches(C.first.data(), (int)C.first.size(), k_stop);
+            products += P.panel_products(C.first.data(), (int)C.first.size(), k_stop);
+            workspace = std::max(workspace, (int64_t)C.m_pad * nc * (int64_t)sizeof(double));
+            chunks.push_back(std::move(C));
+        }
+    }
+};
+// entry (i, j) of block k out of one chunk's W, as the gather kernel reads it: rows of keyframe row_node[k], the six right-hand sides of column col_index[k].  out is
+// zeroed before the first chunk: a block with a keyframe outside the system stays zero.
+inline void sc_columns_gather_host(const ScColumnChunk& C, const double* W, int nc, const uint8_t* in_system, const int32_t* pos, int64_t n_blocks, const int32_t* row_node,
+                                   const int32_t* col_index, double* out) {
+    for (int64_t k = 0; k < n_blocks; ++k) {
+        const int32_t r0 = C.row0[(size_t)col_index[k]];
+        if (r0 < 0 || !in_system[row_node[k]]) continue;
+        for (int i = 0; i < 6; ++i)
+            for (int j = 0; j < 6; ++j) out[k * 36 + i * 6 + j] = W[(size_t)(r0 + j) * nc + (size_t)pos[row_node[k]] * 6 + i];
+    }
+}
+#if !defined(__HIP_DEVICE_COMPILE__)
+// the whole call on the host, on the factored tiles T: what pgo_sparse_chol_inverse_columns does chunk by chunk
+inline void sc_host_inverse_columns(const ScPlan& P, const double* T, const ScColumns& Q, const uint8_t* in_system, const int32_t* pos, int64_t n_blocks, const int32_t* row_node,
+                                    const int32_t* col_index, double* out) {
+    const int nc = P.nt * DC_NB;
+    std::fill(out, out + n_blocks * 36, 0.0);
+    for (const ScColumnChunk& C : Q.chunks) {
+        std::vector<double> W((size_t)C.m_pad * nc, 0.0);
+        for (int r = 0; r < C.m_pad; ++r) if (C.rhs_col[(size_t)r] >= 0) W[(size_t)r * nc + C.rhs_col[(size_t)r]] = 1.0;
+        ScPanelHost H{P, T, W.data(), nc, C.first.data()};
+        sc_panel_steps(P, C.first, Q.k_stop, H);
+        sc_columns_gather_host(C, W.data(), nc, in_system, pos, n_blocks, row_node, col_index, out);
+    }
+}
+#endif
 
 // The right-hand sides of pgo_sparse_chol_inverse_blocks: groups of 1 or 6 sparse rows in CSR over the 6 N coordinates of the caller's keyframe order.  Per non-zero its
 // place in W [rows][nc] under the permutation; first_tile: the first tile that holds a non-zero of any row (nt: there is none).

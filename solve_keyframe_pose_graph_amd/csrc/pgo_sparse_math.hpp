@@ -1,7 +1,7 @@
 // pgo_sparse_math.hpp — the host side of a tile-sparse exact Cholesky solver for graphs above the dense solver's limit (pgo_dense.hip stops at PGO_DENSE_MAX_KEYFRAMES
 // because it stores all n^2 entries): the ordering of the keyframes, the tile pattern of the system, the symbolic factorisation, the order of the block steps and a serial
-// host instantiation of the whole factor and solve (tests/native/sparse_chol_host.cpp) and of the selected inverse on the factor's tiles (sc_selinv_steps, ScSelHost;
-// tests/native/sparse_selinv_host.cpp).  The arithmetic is pgo_dense_math.hpp's: the same 64 x 64 block routines, the same
+// host instantiation of the whole factor and solve (tests/native/sparse_chol_host.cpp), of the selected inverse on the factor's tiles (sc_selinv_steps, ScSelHost;
+// tests/native/sparse_selinv_host.cpp) and of both sweeps over panels of 64 right-hand sides (sc_panel_steps, ScPanelHost; tests/native/sparse_panel_host.cpp).  The arithmetic is pgo_dense_math.hpp's: the same 64 x 64 block routines, the same
 // panel substitution, the same update.  libpgo.so does not include this header and no option of pgo_options uses it (DESIGN.md section 3.4 says why); the kernels that run
 // this plan and this step order are the companion library's, libpgo_sparse.so (pgo_sparse.hip, include/pgo_sparse.h).
 //
@@ -98,6 +98,17 @@ struct ScPlan {
     // |s_k|^2 of column(k) and |s_k| of diag(k)
     int64_t selinv_launches() const { int64_t l = 1; for (int k = 0; k < nt; ++k) l += s_size(k) > 0 ? 3 : 0; return l; }
     int64_t selinv_products() const { int64_t u = 0; for (int k = 0; k < nt; ++k) { const int64_t m = s_size(k); u += m * m + m; } return u; }
+    // the panel sweeps (sc_panel_steps) of n_panels panels with first[] ascending and the lowest requested tile k_stop: one launch per step of the two sweeps; tile
+    // products: forward, per step k and started panel p the stored tiles (k, j) with first[p] <= j < k; backward, |s_k| per step k >= k_stop and panel
+    int64_t panel_launches(const int32_t* first, int n_panels, int k_stop) const { return n_panels > 0 ? (int64_t)(nt - first[0]) + (nt - k_stop) : 0; }
+    int64_t panel_products(const int32_t* first, int n_panels, int k_stop) const {
+        int64_t u = 0;
+        for (int p = 0; p < n_panels; ++p)
+            for (int k = first[p]; k < nt; ++k)
+                u += (row_col.begin() + diag(k)) - std::lower_bound(row_col.begin() + row_ptr[(size_t)k], row_col.begin() + diag(k), first[p]);
+        for (int k = k_stop; k < nt; ++k) u += (int64_t)n_panels * s_size(k);
+        return u;
+    }
     size_t scratch_doubles() const { return (size_t)DC_NB * ((size_t)max_s() * DC_NB + 16); }      // the k-major copy of one panel, compact by position in s_k (>= max_s tiles: the selected inverse keeps G there)
     int ldu() const { return max_s() * DC_NB + 16; }
 };
@@ -209,6 +220,29 @@ inline void sc_selinv_steps(const ScPlan& P, Ops& o) {
     o.inverses();
     for (int k = P.nt - 1; k >= 0; --k)
         if (P.s_size(k) > 0) { o.ginv(k); o.column(k); o.diag(k); }
+}
+
+// Columns of A^-1 in number — the blocks OUTSIDE the pattern of L, which the selected inverse has not: both sweeps with many right-hand sides at once.  The right-hand
+// sides are the ROWS of W [m_pad][nc], m_pad a multiple of 64 (the dense covariance kernels' layout); a panel is 64 consecutive rows, W_pk the 64 x 64 block of panel p
+// in the columns of tile k.  Row r starts as the unit row e_c^T; the forward sweep leaves y^T = e_c^T L^-T in it, the backward sweep x^T = y^T L^-1 = (A^-1 e_c)^T, in place.
+// first[p]: the tile that holds the first non-zero of panel p; the rows are sorted by the column of their one, so first[] ascends and the panels that have started at
+// step k are a prefix.  k_stop: the lowest tile that holds a requested entry of x — x_k needs x_i for i > k only, so the backward sweep ends there.
+//   forward   k = first[0] .. nt - 1, every started panel p:   W_pk -= sum_j W_pj L_kj^T over the stored tiles (k, j), j < k, j ascending, j >= first[p];  W_pk <- W_pk L_kk^-T
+//   backward  k = nt - 1 .. k_stop, every panel p:             W_pk -= sum_{i in s_k} W_pi L_ik, i ascending;                                              W_pk <- W_pk L_kk^-1
+// The pull form: block W_pk has one writer, the step (k, p), which reads blocks of its own panel that earlier steps finished — no atomics, and one launch per k with a
+// workgroup per panel.  Each sum is formed from zero in the order above and subtracted once; a product that is skipped (j < first[p], a panel that has not started) has
+// an all-zero W_pj and would have added +0, and row r of a product reads row r of W alone: a right-hand side gets the same bits alone, in any batch and in any chunk,
+// and whatever k_stop is.  pfwd(k, started) / pbwd(k, panels): one op per (k, panel), handed over per k.
+template <class Ops>
+inline void sc_panel_steps(const ScPlan& P, const std::vector<int32_t>& first, int k_stop, Ops& o) {
+    const int np = (int)first.size();
+    if (np == 0) return;
+    int started = 0;
+    for (int k = first[0]; k < P.nt; ++k) {
+        while (started < np && first[(size_t)started] <= k) ++started;
+        o.pfwd(k, started);
+    }
+    for (int k = P.nt - 1; k >= k_stop; --k) o.pbwd(k, np);
 }
 
 // The plan of a dense host matrix (n x n row-major, padded to nc = a multiple of 64 by identity rows): the tile pattern is that of the exact non-zeros of its lower
@@ -384,6 +418,64 @@ inline void sc_host_selected_inverse(const ScPlan& P, const double* T, double* Z
     ScSelHost H{P, T, Z};
     sc_selinv_steps(P, H);
 }
+
+// ---- serial host instantiation of the panel sweeps (sc_panel_steps) on the factored tiles T: W [panels x 64][nc] in place, T is only read.  The substitutions are the
+// block routines of pgo_dense_math.hpp, per row (forward: DcHost::substitute_row, the panel's; backward: dc_backward_block, as ScSelHost::ginv), never a product with an
+// inverse; every product sum is formed from zero in the walker's order and subtracted once.
+struct ScPanelHost {
+    const ScPlan& P; const double* T; double* W; int nc; const int32_t* first;
+    std::vector<double> blk = std::vector<double>((size_t)DC_NB * DC_LD, 0.0), acc = std::vector<double>(SC_TILE, 0.0);
+    double vec[DC_NB], sol[DC_NB];
+    void load_diag(int k) { const double* t = T + (size_t)P.diag(k) * SC_TILE; for (int i = 0; i < DC_NB; ++i) for (int j = 0; j < DC_NB; ++j) blk[(size_t)i * DC_LD + j] = t[i * DC_NB + j]; }
+    double* row(int p, int r) const { return W + ((size_t)p * DC_NB + r) * nc; }
+    void pfwd(int k, int started) {
+        load_diag(k);
+        for (int p = 0; p < started; ++p) {
+            std::fill(acc.begin(), acc.end(), 0.0);
+            for (int32_t id = P.row_ptr[(size_t)k]; id < P.diag(k); ++id) {
+                const int j = P.row_col[(size_t)id];
+                if (j < first[p]) continue;
+                const double* t = T + (size_t)id * SC_TILE;
+                for (int r = 0; r < DC_NB; ++r) {
+                    const double* w = row(p, r) + (size_t)j * DC_NB;
+                    for (int c = 0; c < DC_NB; ++c) {
+                        double s = acc[(size_t)r * DC_NB + c];
+                        for (int kk = 0; kk < DC_NB; ++kk) s += w[kk] * t[c * DC_NB + kk];
+                        acc[(size_t)r * DC_NB + c] = s;
+                    }
+                }
+            }
+            for (int r = 0; r < DC_NB; ++r) {
+                double* w = row(p, r) + (size_t)k * DC_NB;
+                for (int c = 0; c < DC_NB; ++c) w[c] -= acc[(size_t)r * DC_NB + c];
+                DcHost::substitute_row(blk.data(), w);
+            }
+        }
+    }
+    void pbwd(int k, int panels) {
+        load_diag(k);
+        for (int p = 0; p < panels; ++p) {
+            std::fill(acc.begin(), acc.end(), 0.0);
+            for (int32_t e = P.col_ptr[(size_t)k]; e < P.col_ptr[(size_t)k + 1]; ++e) {
+                const double* t = T + (size_t)P.col_tile[(size_t)e] * SC_TILE;
+                for (int r = 0; r < DC_NB; ++r) {
+                    const double* w = row(p, r) + (size_t)P.col_row[(size_t)e] * DC_NB;
+                    for (int c = 0; c < DC_NB; ++c) {
+                        double s = acc[(size_t)r * DC_NB + c];
+                        for (int kk = 0; kk < DC_NB; ++kk) s += w[kk] * t[kk * DC_NB + c];
+                        acc[(size_t)r * DC_NB + c] = s;
+                    }
+                }
+            }
+            for (int r = 0; r < DC_NB; ++r) {
+                double* w = row(p, r) + (size_t)k * DC_NB;
+                for (int c = 0; c < DC_NB; ++c) vec[c] = w[c] - acc[(size_t)r * DC_NB + c];
+                dc_backward_block(DcSerial{}, blk.data(), vec, sol);
+                for (int c = 0; c < DC_NB; ++c) w[c] = sol[c];
+            }
+        }
+    }
+};
 
 // Solves A x = b for the symmetric positive definite n x n matrix `a` with the tile-sparse factorisation, row i at position pos[i] < n (a permutation of 0 .. n - 1;
 // nullptr: the identity).  Returns false — and leaves x alone — when a pivot failed.  info8 (may be null): nt, tiles of the matrix, tiles of L, 0, bytes of the tile

@@ -3,7 +3,9 @@ covariance blocks from it.
 
 The library is a companion of libpgo.so: it takes no Problem.  covariance() below carries a Problem's system across with Problem.normal_blocks() — every handle has
 them, matrix-free ones too — and returns what Problem.covariance returns where that runs; covariance_all() returns every keyframe's marginal and every edge's joint
-covariance from one selected inverse of the factor (SparseCholesky.selected_inverse / selected_blocks).  As capi: no CPU fallback, a missing library or device is an error."""
+covariance from one selected inverse of the factor (SparseCholesky.selected_inverse / selected_blocks); cross_covariance() returns the blocks of ANY keyframe pairs, in
+any number — those of keyframes that share no edge yet, outside the factor's pattern — from SparseCholesky.inverse_columns, and loop_candidate_gate() the chi-square gate
+of loop-closure candidates built on them.  As capi: no CPU fallback, a missing library or device is an error."""
 import ctypes as C
 import dataclasses
 
@@ -18,6 +20,8 @@ ERR_INVALID_ARG, ERR_STATE, ERR_NUMERIC = -1, -5, -7
 # what info() and spd_solve() report of a plan
 INFO = ("nt", "a_tiles", "l_tiles", "ordering", "bytes", "factor_launches", "solve_launches", "tile_updates")
 SELECTED_INFO = ("launches", "tile_products", "bytes", "current")      # selected_info()
+COLUMNS_INFO = ("launches", "tile_products", "bytes", "chunks")        # columns_info()
+WORKSPACE_BYTES = 1 << 30                                               # PGO_SPARSE_WORKSPACE_BYTES
 
 _dp, _ip, _lp, _bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
 _lib = None
@@ -49,6 +53,9 @@ def load(build=True):
     lib.pgo_sparse_chol_selected_inverse.argtypes = [C.c_void_p]
     lib.pgo_sparse_chol_selected_info.argtypes = [C.c_void_p, _lp]
     lib.pgo_sparse_chol_selected_blocks.argtypes = [C.c_void_p, C.c_int64, _ip, _ip, _dp, _bp]
+    lib.pgo_sparse_chol_inverse_columns.argtypes = [C.c_void_p, C.c_int64, _ip, C.c_int64, _ip, _ip, _dp]
+    lib.pgo_sparse_chol_columns_info.argtypes = [C.c_void_p, _lp]
+    lib.pgo_sparse_chol_set_workspace_limit.argtypes = [C.c_void_p, C.c_int64]
     lib.pgo_sparse_reduce_normal_blocks.argtypes = [C.c_int64, _bp, _dp, _dp, _dp, _dp, C.c_int64, _ip, _ip, C.c_int64, _ip, _ip, _lp, _ip, _ip, _dp, _dp]
     _lib = lib
     return lib
@@ -131,7 +138,7 @@ class SparseCholesky:
         return dict(zip(INFO, [int(v) for v in info])), order
 
     def last_ms(self):
-        """HIP-event milliseconds of the launches of the last factor, solve, inverse_blocks, selected_inverse or selected_blocks"""
+        """HIP-event milliseconds of the launches of the last factor, solve, inverse_blocks, selected_inverse, selected_blocks or inverse_columns"""
         return self.lib.pgo_sparse_chol_last_ms(self.h)
 
     def factor(self, diag, pair_blocks):
@@ -183,6 +190,26 @@ class SparseCholesky:
         out, flag = np.zeros((len(a), 6, 6)), np.zeros(len(a), np.uint8)
         _check(self.lib.pgo_sparse_chol_selected_blocks(self.h, len(a), _p(a, _ip), _p(b, _ip), _p(out, _dp), _p(flag, _bp)), self.h)
         return out, flag.astype(bool)
+
+    def inverse_columns(self, col_nodes, row_nodes, col_index):
+        """blocks of A^-1 between ANY keyframes, in the factor's pattern or not: block k has the rows of keyframe row_nodes[k] and the columns of keyframe
+        col_nodes[col_index[k]] -> (k, 6, 6).  col_nodes: distinct keyframes; their unit columns are solved by both sweeps, 64 at a time per workgroup, in chunks where
+        they exceed the workspace limit.  A keyframe outside the system, as row or column: a zero block."""
+        cn, rn, ci = _i(col_nodes).reshape(-1), _i(row_nodes).reshape(-1), _i(col_index).reshape(-1)
+        assert rn.shape == ci.shape
+        out = np.zeros((len(rn), 6, 6))
+        _check(self.lib.pgo_sparse_chol_inverse_columns(self.h, len(cn), _p(cn, _ip), len(rn), _p(rn, _ip), _p(ci, _ip), _p(out, _dp)), self.h)
+        return out
+
+    def columns_info(self):
+        """of the last inverse_columns(): launches, tile products, bytes of the workspace, chunks"""
+        info = np.zeros(4, np.int64)
+        _check(self.lib.pgo_sparse_chol_columns_info(self.h, info.ctypes.data_as(_lp)), self.h)
+        return dict(zip(COLUMNS_INFO, [int(v) for v in info]))
+
+    def set_workspace_limit(self, nbytes):
+        """the most the right-hand sides of one chunk of inverse_columns() may take; at least one panel (64 rows of 64 nt doubles)"""
+        _check(self.lib.pgo_sparse_chol_set_workspace_limit(self.h, int(nbytes)), self.h)
 
 
 @dataclasses.dataclass
@@ -360,3 +387,165 @@ def covariance_all(P, edges, quat, t, sw, ordering=ORDER_AUTO, device_id=None, t
     finally:
         F.close()
     return assemble_all(N, in_system, referenced, edges, c, hss, blocks)
+
+
+def cross_blocks(F, pairs):
+    """The blocks of A^-1 of any keyframe pairs [(a, b), ...] from F.inverse_columns (a SparseCholesky with a factor, or anything with that method) -> (n_pairs, 6, 6),
+    rows of a, columns of b.  The column side — the keyframes whose unit columns are solved — is the side of the list with fewer distinct keyframes, the second elements
+    on a tie.  Every block is gathered once: a pair asked again gets the same block, a pair asked the other way round its transpose, and a diagonal block is read
+    once and its lower triangle mirrored — (b, a) is the exact transpose of (a, b), (a, a) exactly symmetric."""
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    out = np.zeros((len(pr), 6, 6))
+    if not len(pr):
+        return out
+    side = 0 if len(np.unique(pr[:, 0])) < len(np.unique(pr[:, 1])) else 1
+    cols = np.unique(pr[:, side])
+    col_at = {int(c): k for k, c in enumerate(cols)}
+    asked, rows, cidx = {}, [], []      # (row keyframe, column keyframe) -> index of the request
+    take = []                           # per pair: (request, transposed)
+    for a, b in pr:
+        a, b = int(a), int(b)
+        if (a, b) in asked:
+            take.append((asked[(a, b)], False))
+        elif (b, a) in asked:
+            take.append((asked[(b, a)], True))
+        else:
+            r, c, tr = (a, b, False) if side == 1 else (b, a, True)
+            asked[(r, c)] = len(rows); rows.append(r); cidx.append(col_at[c])
+            take.append((asked[(r, c)], tr))
+    got = F.inverse_columns(cols, rows, cidx)
+    for (r, c), k in asked.items():
+        if r == c:
+            got[k] = np.tril(got[k]) + np.tril(got[k], -1).T
+    for k, (q, tr) in enumerate(take):
+        out[k] = got[q].T if tr else got[q]
+    return out
+
+
+SOLVE_BELOW_COLUMNS = 100      # see _Routed
+
+
+class _Routed:
+    """inverse_columns of a SparseCholesky for cross_blocks, with the measured rule: a request with fewer than SOLVE_BELOW_COLUMNS column keyframes goes to
+    SparseCholesky.solve of their unit columns.  The panel sweeps pay a chain of 2 nt launches whose steps walk the tiles of a row one after the other in one workgroup
+    per 64 right-hand sides, whatever the number of right-hand sides; the solve pays per right-hand side.  profiles/sparse_panel_solve_times.txt (HIP events; 1 100,
+    3 000 and 10 000 keyframes, both orders): at 6, 60, 150 and 300 right-hand sides the solve takes 0.06 - 1.00 x the panel sweeps' time (300: 0.62 - 1.00), at 600
+    it takes 1.19 - 1.60 x, at 6 000 4.8 - 14.7 x.  The two meet between 300 and 600 right-hand sides — 50 and 100 keyframes; 100 is the first measured count at which
+    the panel sweeps win on every graph and order.  `ms`: HIP-event milliseconds of the calls; `route`: what served the last one."""
+
+    def __init__(self, F):
+        self.F, self.ms, self.route = F, 0.0, None
+
+    def inverse_columns(self, col_nodes, row_nodes, col_index):
+        cn, rn, ci = _i(col_nodes).reshape(-1), _i(row_nodes).reshape(-1), _i(col_index).reshape(-1)
+        if len(cn) >= SOLVE_BELOW_COLUMNS:
+            out = self.F.inverse_columns(cn, rn, ci)
+            self.route = "columns"
+        else:
+            B = np.zeros((6 * len(cn), 6 * self.F.n_nodes))
+            B[np.arange(6 * len(cn)), (6 * cn[:, None].astype(np.int64) + np.arange(6)).reshape(-1)] = 1.0
+            X = self.F.solve(B).reshape(len(cn), 6, self.F.n_nodes, 6)      # [column keyframe, right-hand side j, row keyframe, entry i]
+            out = np.ascontiguousarray(X[ci, :, rn, :].transpose(0, 2, 1))
+            self.route = "solve"
+        self.ms += self.F.last_ms()
+        return out
+
+
+def _pose_system(P, edges, quat, t, sw, nodes):
+    """covariance()'s linearisation, checks and reduction for requests on keyframes alone: (N, in_system, pair_hi, pair_lo, s_diag, s_blocks)"""
+    N = len(np.asarray(quat, dtype=np.float64).reshape(-1, 4))
+    free = np.ones(N, np.uint8); free[np.asarray(edges.constant, dtype=np.int64)] = 0
+    referenced = np.zeros(N, bool)
+    for c in (edges.rel_c1, edges.rel_c2, edges.sw_c1, edges.sw_c2, edges.reg_node):
+        referenced[np.asarray(c, dtype=np.int64)] = True
+    for i in np.unique(np.asarray(nodes, dtype=np.int64)):
+        if i < 0 or i >= N:
+            raise ValueError("keyframe %d out of range (0 .. n_nodes - 1)" % i)
+        if not referenced[i]:
+            raise ValueError("keyframe %d is referenced by no residual block: it has no covariance" % i)
+    P.evaluate(quat, t, sw, want_residuals=False, want_gradient=True)
+    diag, _, off, c, hss, _ = P.normal_blocks()
+    hi, lo, sd, sb = reduce_normal_blocks(N, free, diag, off, c, hss, edges.rel_c1, edges.rel_c2, edges.sw_c1, edges.sw_c2)
+    return N, (free != 0) & referenced, hi, lo, sd, sb
+
+
+def cross_covariance(P, edges, quat, t, sw, pairs, ordering=ORDER_AUTO, device_id=None, timings=None):
+    """The 6 x 6 covariance blocks of ANY keyframe pairs [(a, b), ...], rows of a and columns of b, in any number -> (n_pairs, 6, 6): what covariance() gives for
+    pairs of keyframes, for the blocks outside the factor's pattern too and without its limit of groups per call — the cross-covariances of loop-closure candidates.
+    The linearisation, the reduction, the id checks and the rules are covariance()'s: a pair with a constant keyframe is a zero block, an unreferenced keyframe raises
+    ValueError, PgoError(PGO_ERR_NUMERIC) a system that is not positive definite.  One factor, then cross_blocks (its rules on the column side and on transposes) on
+    SparseCholesky.inverse_columns — or, below SOLVE_BELOW_COLUMNS column keyframes, on SparseCholesky.solve of their unit columns, which is measured faster there
+    (_Routed).  timings (a dict): HIP-event milliseconds of the factor and the columns, and which of the two served them."""
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    N, in_system, hi, lo, sd, sb = _pose_system(P, edges, quat, t, sw, pr)
+    F = SparseCholesky(N, in_system, hi, lo, ordering, P.options.device_id if device_id is None else device_id)
+    try:
+        F.factor(sd, sb)
+        if timings is not None:
+            timings["factor_ms"] = F.last_ms(); timings["info"] = F.info()[0]
+        R = _Routed(F)
+        out = cross_blocks(R, pr)
+        if timings is not None:
+            timings["columns_ms"] = R.ms; timings["route"] = R.route; timings["columns_info"] = F.columns_info()
+    finally:
+        F.close()
+    return out
+
+
+@dataclasses.dataclass
+class LoopGate:
+    """what loop_candidate_gate() returns, per candidate"""
+    residual: np.ndarray           # (n, 6): the candidates' weighted residuals at the given point
+    cross: np.ndarray              # (n, 6, 6): cov(c1, c2), rows of c1
+    innovation_cov: np.ndarray     # (n, 6, 6): S, the covariance of the residual under the posterior plus its own unit noise
+    mahalanobis2: np.ndarray       # (n,): d^2 = r^T S^-1 r — chi-square with 6 degrees of freedom for a true loop closure
+
+
+def gate_from_blocks(r, J1, J2, S_aa, S_bb, S_ab):
+    """the gate's arithmetic, in fp64 numpy: S = J1 S_aa J1^T + J1 S_ab J2^T + J2 S_ab^T J1^T + J2 S_bb J2^T + I per candidate (the residual is weighted: its noise is
+    the identity), d^2 = r^T S^-1 r by a solve"""
+    r, J1, J2 = _d(r).reshape(-1, 6), _d(J1).reshape(-1, 6, 6), _d(J2).reshape(-1, 6, 6)
+    S_aa, S_bb, S_ab = _d(S_aa).reshape(-1, 6, 6), _d(S_bb).reshape(-1, 6, 6), _d(S_ab).reshape(-1, 6, 6)
+    T = lambda M: M.transpose(0, 2, 1)
+    cross = J1 @ S_ab @ T(J2)
+    S = J1 @ S_aa @ T(J1) + cross + T(cross) + J2 @ S_bb @ T(J2) + np.eye(6)
+    S = 0.5 * (S + T(S))      # (the two congruences round their two triangles apart)
+    d2 = np.einsum("ei,ei->e", r, np.linalg.solve(S, r[:, :, None])[:, :, 0]) if len(r) else np.zeros(0)
+    return LoopGate(r, S_ab, S, d2)
+
+
+def loop_candidate_gate(P, edges, quat, t, sw, c1, c2, c1_T_c2, weight, ordering=ORDER_AUTO, device_id=None, timings=None):
+    """The chi-square gate of loop-closure candidates: relative-pose edges (c1, c2, c1_T_c2, weight as add_relpose_edges takes them) that are NOT in the graph, judged
+    under the posterior of the graph that is (P and `edges`, at the given point): LoopGate.  Residual and Jacobians come from a scratch capi.Problem with P's options
+    that holds only the candidates — the tangent order and the weighting are the library's own; cov(c1, c1) and cov(c2, c2) come from the selected inverse, cov(c1, c2)
+    through cross_covariance's
+    path, on one factor.  A candidate between keyframes that are both constant has S = I.  Errors as cross_covariance's."""
+    from . import capi
+    c1, c2 = _i(c1).reshape(-1), _i(c2).reshape(-1)
+    n = len(c1)
+    assert len(c2) == n
+    N, in_system, hi, lo, sd, sb = _pose_system(P, edges, quat, t, sw, np.concatenate([c1, c2]))
+    scratch = capi.Problem(P.options)
+    try:
+        scratch.add_relpose_edges(c1, c2, c1_T_c2, weight)
+        _, res, _ = scratch.evaluate(quat, t, None, want_residuals=True, want_gradient=True)
+        J1, J2, _ = scratch.jacobian_blocks(0)
+    finally:
+        scratch.close()
+    F = SparseCholesky(N, in_system, hi, lo, ordering, P.options.device_id if device_id is None else device_id)
+    try:
+        F.factor(sd, sb)
+        if timings is not None:
+            timings["factor_ms"] = F.last_ms(); timings["info"] = F.info()[0]
+        F.selected_inverse()
+        if timings is not None:
+            timings["selected_ms"] = F.last_ms()
+        own, in_pattern = F.selected_blocks(np.concatenate([c1, c2]), np.concatenate([c1, c2]))
+        assert in_pattern.all()      # (diagonal blocks)
+        R = _Routed(F)
+        S_ab = cross_blocks(R, np.stack([c1, c2], axis=1))
+        if timings is not None:
+            timings["columns_ms"] = R.ms; timings["route"] = R.route; timings["columns_info"] = F.columns_info()
+    finally:
+        F.close()
+    return gate_from_blocks(res.reshape(n, 6), J1, J2, own[:n], own[n:], S_ab)
