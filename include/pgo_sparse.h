@@ -1,5 +1,5 @@
 /* pgo_sparse.h — C-ABI of libpgo_sparse.so: a tile-sparse exact Cholesky factorisation on the GPU (gfx950, fp64) for pose-graph systems above
- * PGO_DENSE_MAX_KEYFRAMES, and covariance blocks from it.  A companion of libpgo.so, not a part of it: it links no libpgo.so, takes no pgo_problem and has no
+ * PGO_DENSE_MAX_KEYFRAMES, covariance blocks from it, and the exact Levenberg-Marquardt step and solve on it (pgo_sparse_lm_*, further down).  A companion of libpgo.so, not a part of it: it links no libpgo.so, takes no pgo_problem and has no
  * option in pgo_options.  A caller carries a handle's system across with pgo_get_normal_blocks (every handle has it, matrix-free ones too) and
  * pgo_sparse_reduce_normal_blocks below.  Error codes are pgo.h's PGO_ERR_*.
  *
@@ -118,6 +118,62 @@ int pgo_sparse_reduce_normal_blocks(int64_t n_nodes, const uint8_t* node_free, c
 
 /* HIP-event milliseconds of the launches of the object's last pgo_sparse_chol_factor (fill included), _solve, _inverse_blocks, _selected_inverse, _selected_blocks or _inverse_columns */
 double pgo_sparse_chol_last_ms(const pgo_sparse_chol* h);
+
+/* ---- The exact Levenberg-Marquardt step and solve on the factor: Ceres' trust-region solve with every step the backward-stable solution of its system — what
+ * PGO_LINEAR_DENSE_CHOLESKY gives up to PGO_DENSE_MAX_KEYFRAMES — for graphs of any size, beside the library: the linearisation comes through the hooks every handle has
+ * (pgo_evaluate, pgo_get_normal_blocks, pgo_manifold_plus), the controller's decisions are csrc/pgo_lm.hpp's, the linear algebra of every step runs on the device here.
+ * There is no option of pgo_options for it.
+ *
+ * One LM system (csrc/pgo_sparse_lm_math.hpp has the arithmetic per entry, shared by the kernels and a serial host instantiation):
+ *   S_j = 1 / (1 + sqrt(H_jj)) per column, from the diagonals of `diag` (pose columns, before the switch elimination) and `sw_hss`, fixed at iteration 0;
+ *   lambda_j = clamp(S_j^2 H_jj, min_lm_diagonal, max_lm_diagonal) / (radius S_j^2);   a_e = 1 / (h_e + lambda_e);
+ *   (H_pp + diag(lambda_p) - sum_e c_e a_e c_e^T) dp = -(g_p - sum_e c_e a_e g_s,e);   ds_e = -a_e (g_s,e + c_e^T dp);
+ *   model_cost_change = -d^T (g + H d / 2) with the full undamped H.
+ * The damped Schur complement is written straight into the factor's zeroed tiles, each entry once as a sum in internal edge order; no atomics, every sum in a fixed
+ * order: two calls give the same bits. */
+typedef struct pgo_sparse_lm pgo_sparse_lm;
+
+/* The step plan of a graph on `chol` (it must outlive the object, and both are used from one thread at a time).  node_free [n_nodes]: 0 for a constant keyframe; the
+ * keyframes of the system are those with node_free != 0 that pgo_sparse_chol_create took with in_system != 0.  The edges in internal order — relative-pose in add order,
+ * then switchable: the order of pgo_get_normal_blocks' offdiag.  Several edges may lie on one pair of keyframes, in either direction; an edge side on a keyframe outside
+ * the system drops out, a switch with both endpoints outside keeps its pivot alone.  PGO_ERR_INVALID_ARG (text: pgo_sparse_last_error(NULL)): n_nodes is not the
+ * factor's, a keyframe out of range, an edge from a keyframe to itself, a free endpoint that the factor keeps outside the system, or two keyframes of the system joined
+ * by an edge that are no pair of the factor's pair list.  No launch. */
+int pgo_sparse_lm_create(pgo_sparse_chol* chol, int64_t n_nodes, const uint8_t* node_free, int64_t n_rel, const int32_t* rel_c1, const int32_t* rel_c2,
+                         int64_t n_sw, const int32_t* swe_c1, const int32_t* swe_c2, pgo_sparse_lm** out);
+void pgo_sparse_lm_destroy(pgo_sparse_lm* lm);
+
+/* The Jacobi scale S from a linearisation's diag [n_nodes][36] and sw_hss [n_sw]: at iteration 0 only.  diag = NULL: no scaling, S = 1 (pgo_options.jacobi_scaling = 0). */
+int pgo_sparse_lm_set_scale(pgo_sparse_lm* lm, const double* diag, const double* sw_hss);
+
+/* One exact LM step from pgo_get_normal_blocks' host arrays as they come: one upload, the launches — damping, fill, right-hand side, 1 + 1 + 1; the factor, info8[5];
+ * the sweeps, info8[6]; back-substitution, model, its reduction, 1 + 1 + 1 — and one download.  delta_pose [6 n_nodes] in the caller's keyframe order, exactly 0 for a
+ * keyframe outside the system; delta_sw [n_sw] per switchable edge; out3: model_cost_change, the tangent norm |d| (pose and switch entries), HIP-event milliseconds of
+ * the factor.  PGO_ERR_NUMERIC: a pivot of the factor or a damped switch pivot is not > 0 (or NaN) — nothing but out3[2] is written, and the object takes the next step.
+ * PGO_ERR_STATE: no scale.  The factor in `chol` is the damped system's afterwards: its covariance calls want a new pgo_sparse_chol_factor.
+ * Error texts: pgo_sparse_last_error(chol). */
+int pgo_sparse_lm_step(pgo_sparse_lm* lm, const double* diag, const double* grad, const double* offdiag, const double* sw_c, const double* sw_hss, const double* sw_gs,
+                       double radius, double min_lm_diagonal, double max_lm_diagonal, double* delta_pose, double* delta_sw, double* out3);
+/* HIP-event milliseconds of the last pgo_sparse_lm_step: upload, damping + fill + right-hand side, factor, sweeps, back-substitution + model, download.  No launch. */
+int pgo_sparse_lm_last_times(const pgo_sparse_lm* lm, double* ms6);
+
+/* pgo_evaluate, pgo_get_normal_blocks and pgo_manifold_plus without the handle; `user` is handed through.  A return other than 0 ends the solve with that code. */
+typedef struct pgo_sparse_lm_callbacks {
+    int (*evaluate)(void* user, const double* quat_xyzw, const double* t, const double* sw, int64_t n_nodes, int64_t n_switch, double* cost, double* residuals, double* gradient);
+    int (*normal_blocks)(void* user, double* diag, double* grad, double* offdiag, double* sw_c, double* sw_hss, double* sw_gs);
+    int (*manifold_plus)(void* user, int64_t n, const double* quat_xyzw, const double* t, const double* delta, double* quat_out, double* t_out);      /* t, t_out may be NULL */
+} pgo_sparse_lm_callbacks;
+
+/* The whole solve = pgo_solve with every step exact: lm_begin, lm_pre_step, lm_step_outcome, lm_outcome_stop and lm_finish_step of csrc/pgo_lm.hpp around
+ * pgo_sparse_lm_step.  quat [4 n_nodes], t [3 n_nodes], sw [n_switch] hold the start and receive the result; swe_index [n_sw]: the switch index of every switchable
+ * edge (NULL: edge e uses switch e).  Per iteration: the step; the candidate Plus(x, dp) through the callback and sw + ds, evaluated for its cost alone; an accepted
+ * step is linearised again (evaluate with a gradient, then normal_blocks).  A failed factorisation is an invalid step (PGO_STEP_INVALID_FACTORIZATION) and the radius
+ * halves: the dense solver's rule; the point's blocks are then fetched again (evaluate with a gradient, normal_blocks: a handle gives the numbers it gave before).  There is no pause plan — every step is exact.  The controller's step norm and x_norm are the handle's: ambient, 4 + 3 numbers per
+ * keyframe of the system and one per switchable edge's switch.  `summary` is filled as the handle's dense solve fills it: preconditioner = PGO_PRECOND_DIRECT, zero CG
+ * counts, seconds_system = the factor's HIP-event time.  The options read: max_num_iterations, jacobi_scaling, max_num_consecutive_invalid_steps, the trust-region
+ * radii, min_relative_decrease, the LM diagonal's clamps and the three tolerances.  On PGO_FAILURE, and on any error return, the arrays are left unmodified. */
+int pgo_sparse_lm_solve(pgo_sparse_lm* lm, const pgo_sparse_lm_callbacks* callbacks, void* user, int64_t n_switch, const int32_t* swe_index, double* quat_xyzw, double* t, double* sw,
+                        const pgo_options* options, pgo_summary* summary);
 
 const char* pgo_sparse_strerror(int code);
 /* the text of the last error of this object; h = NULL: of the calling thread's last call that had no object (pgo_sparse_spd_solve, pgo_sparse_chol_create, ...) */

@@ -89,11 +89,14 @@ def build_libpgo(force=False, verbose=False):
 
 LIBSPARSE = os.path.join(_HERE, "libpgo_sparse.so")
 SPARSE_SOURCE = "pgo_sparse.hip"
-SPARSE_HEADERS = ["pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_math.hpp"]
+SPARSE_HEADERS = ["pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_math.hpp", "pgo_sparse_lm.hpp", "pgo_sparse_lm_math.hpp"]
+# a header of libpgo.so that the companion includes unchanged (the LM controller: one copy of Ceres' rules); it belongs to HIP_HEADERS, here it is only a dependency
+SPARSE_SHARED_HEADERS = ["pgo_lm.hpp"]
 SPARSE_OBJ_DIR = os.path.join(_ROOT, "build", "obj_sparse")
 # every symbol include/pgo_sparse.h declares
 SPARSE_EXPORTS = ["pgo_sparse_spd_solve", "pgo_sparse_chol_create", "pgo_sparse_chol_destroy", "pgo_sparse_chol_info", "pgo_sparse_chol_factor", "pgo_sparse_chol_solve",
-                  "pgo_sparse_chol_inverse_blocks", "pgo_sparse_chol_selected_inverse", "pgo_sparse_chol_selected_info", "pgo_sparse_chol_selected_blocks", "pgo_sparse_chol_inverse_columns", "pgo_sparse_chol_columns_info", "pgo_sparse_chol_set_workspace_limit", "pgo_sparse_reduce_normal_blocks", "pgo_sparse_chol_last_ms", "pgo_sparse_strerror", "pgo_sparse_last_error"]
+                  "pgo_sparse_chol_inverse_blocks", "pgo_sparse_chol_selected_inverse", "pgo_sparse_chol_selected_info", "pgo_sparse_chol_selected_blocks", "pgo_sparse_chol_inverse_columns", "pgo_sparse_chol_columns_info", "pgo_sparse_chol_set_workspace_limit", "pgo_sparse_reduce_normal_blocks", "pgo_sparse_chol_last_ms", "pgo_sparse_strerror", "pgo_sparse_last_error",
+                  "pgo_sparse_lm_create", "pgo_sparse_lm_destroy", "pgo_sparse_lm_set_scale", "pgo_sparse_lm_step", "pgo_sparse_lm_last_times", "pgo_sparse_lm_solve"]
 
 
 def compile_libpgo_sparse(target, verbose=False, obj_dir=None):
@@ -112,7 +115,7 @@ def compile_libpgo_sparse(target, verbose=False, obj_dir=None):
 
 
 def build_libpgo_sparse(force=False, verbose=False):
-    deps = [os.path.join(CSRC, f) for f in [SPARSE_SOURCE] + SPARSE_HEADERS] + [os.path.join(INCLUDE, "pgo_sparse.h"), os.path.join(INCLUDE, "pgo.h")]
+    deps = [os.path.join(CSRC, f) for f in [SPARSE_SOURCE] + SPARSE_HEADERS + SPARSE_SHARED_HEADERS] + [os.path.join(INCLUDE, "pgo_sparse.h"), os.path.join(INCLUDE, "pgo.h")]
     if force or _stale(LIBSPARSE, deps):
         compile_libpgo_sparse(LIBSPARSE, verbose=verbose)
     return LIBSPARSE

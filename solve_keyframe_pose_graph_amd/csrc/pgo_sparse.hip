@@ -12,6 +12,9 @@
 //
 // The columns of the inverse in number (sc_panel_steps: sc_pcol_rhs_kernel, sc_pfwd_kernel, sc_pbwd_kernel, sc_pgather_kernel) are the tile-sparse counterpart of
 // dcv_solve_kernel / dcv_update_kernel — right-hand sides as the rows of W, 64 per workgroup — in the pull form and for both sweeps: blocks outside the pattern of L.
+//
+// The exact LM step and solve on this factor (pgo_sparse_lm_*: sc_lm_scale_kernel, sc_lm_fill_kernel, sc_lm_rhs_kernel, sc_lm_backsub_kernel, sc_lm_model_kernel,
+// sc_lm_reduce_kernel) are in pgo_sparse_lm.hpp, included at the end of this file: still one translation unit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -707,6 +710,7 @@ struct pgo_sparse_chol {
     bool selected = false;      // Z holds the selected inverse of the present factor
     std::vector<uint8_t> in_system;
     std::vector<int32_t> order, pos;
+    std::vector<int32_t> h_hi, h_lo;                       // the pair list as pgo_sparse_chol_create took it (pgo_sparse_lm_create reads it)
     DevBuf d_in, d_pos, d_hi, d_lo, d_diag, d_blocks, d_at, d_val, d_pr, d_out, Z, d_na, d_nb, d_flag;
     DevBuf ws, d_req;                                      // pgo_sparse_chol_inverse_columns: W of one chunk, the chunk's tables
     int64_t ws_limit = PGO_SPARSE_WORKSPACE_BYTES;
@@ -791,6 +795,7 @@ int pgo_sparse_chol_create(int32_t device_id, int64_t n_nodes, const uint8_t* in
     if ((rc = h->c.open(device_id)) != PGO_OK) return rc;
     h->N = n_nodes; h->n_pairs = n_pairs;
     h->in_system.assign(in_system, in_system + n_nodes);
+    if (n_pairs) { h->h_hi.assign(pair_hi, pair_hi + n_pairs); h->h_lo.assign(pair_lo, pair_lo + n_pairs); }
     std::vector<int64_t> adj_ptr; std::vector<int32_t> adj;
     sc_pair_adjacency(n_nodes, n_pairs, pair_hi, pair_lo, adj_ptr, adj);
     h->c.P = sc_plan_graph(n_nodes, adj_ptr.data(), adj.data(), in_system, ordering, h->order, &h->used);
@@ -1080,3 +1085,6 @@ int pgo_sparse_reduce_normal_blocks(int64_t n_nodes, const uint8_t* node_free, c
 }
 
 }  // extern "C"
+
+// the exact Levenberg-Marquardt step and solve on this factor (pgo_sparse_lm_*): kernels, object and entry points
+#include "pgo_sparse_lm.hpp"

@@ -5,7 +5,9 @@ The library is a companion of libpgo.so: it takes no Problem.  covariance() belo
 them, matrix-free ones too — and returns what Problem.covariance returns where that runs; covariance_all() returns every keyframe's marginal and every edge's joint
 covariance from one selected inverse of the factor (SparseCholesky.selected_inverse / selected_blocks); cross_covariance() returns the blocks of ANY keyframe pairs, in
 any number — those of keyframes that share no edge yet, outside the factor's pattern — from SparseCholesky.inverse_columns, and loop_candidate_gate() the chi-square gate
-of loop-closure candidates built on them.  As capi: no CPU fallback, a missing library or device is an error."""
+of loop-closure candidates built on them.  solve_exact() is Problem.solve with every LM step exact, at any keyframe count: the Problem linearises and steps on the manifold
+through its hooks (as callbacks), SparseLm solves every damped system on the factor's tiles, the decisions are csrc/pgo_lm.hpp's.  As capi: no CPU fallback, a missing
+library or device is an error."""
 import ctypes as C
 import dataclasses
 
@@ -25,6 +27,16 @@ WORKSPACE_BYTES = 1 << 30                                               # PGO_SP
 
 _dp, _ip, _lp, _bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
 _lib = None
+
+# pgo_sparse_lm_callbacks: pgo_evaluate, pgo_get_normal_blocks and pgo_manifold_plus without the handle
+EVALUATE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64, _dp, _dp, _dp)
+NORMAL_BLOCKS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp)
+MANIFOLD_PLUS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp)
+LM_TIMES = ("upload_ms", "fill_ms", "factor_ms", "solve_ms", "backsub_model_ms", "download_ms")      # pgo_sparse_lm_last_times
+
+
+class LmCallbacks(C.Structure):
+    _fields_ = [("evaluate", EVALUATE_FN), ("normal_blocks", NORMAL_BLOCKS_FN), ("manifold_plus", MANIFOLD_PLUS_FN)]
 
 
 def load(build=True):
@@ -57,6 +69,13 @@ def load(build=True):
     lib.pgo_sparse_chol_columns_info.argtypes = [C.c_void_p, _lp]
     lib.pgo_sparse_chol_set_workspace_limit.argtypes = [C.c_void_p, C.c_int64]
     lib.pgo_sparse_reduce_normal_blocks.argtypes = [C.c_int64, _bp, _dp, _dp, _dp, _dp, C.c_int64, _ip, _ip, C.c_int64, _ip, _ip, _lp, _ip, _ip, _dp, _dp]
+    lib.pgo_sparse_lm_create.argtypes = [C.c_void_p, C.c_int64, _bp, C.c_int64, _ip, _ip, C.c_int64, _ip, _ip, C.POINTER(C.c_void_p)]
+    lib.pgo_sparse_lm_destroy.restype = None
+    lib.pgo_sparse_lm_destroy.argtypes = [C.c_void_p]
+    lib.pgo_sparse_lm_set_scale.argtypes = [C.c_void_p, _dp, _dp]
+    lib.pgo_sparse_lm_step.argtypes = [C.c_void_p] + [_dp] * 6 + [C.c_double] * 3 + [_dp] * 3
+    lib.pgo_sparse_lm_last_times.argtypes = [C.c_void_p, _dp]
+    lib.pgo_sparse_lm_solve.argtypes = [C.c_void_p, C.POINTER(LmCallbacks), C.c_void_p, C.c_int64, _ip, _dp, _dp, _dp, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -212,6 +231,62 @@ class SparseCholesky:
         _check(self.lib.pgo_sparse_chol_set_workspace_limit(self.h, int(nbytes)), self.h)
 
 
+class SparseLm:
+    """pgo_sparse_lm: the exact LM step on a SparseCholesky's factor.  node_free: 0 for a constant keyframe; the edges in internal order (relative-pose in add order,
+    then switchable).  F must stay open while this object is used; its factor is the damped system's after a step."""
+
+    def __init__(self, F, node_free, rel_c1, rel_c2, sw_c1, sw_c2):
+        self.lib, self.F = load(), F
+        self.h = C.c_void_p()
+        free = np.ascontiguousarray(node_free, dtype=np.uint8)
+        rc1, rc2, sc1, sc2 = _i(rel_c1), _i(rel_c2), _i(sw_c1), _i(sw_c2)
+        assert free.shape == (F.n_nodes,) and rc1.shape == rc2.shape and sc1.shape == sc2.shape
+        self.n_nodes, self.n_rel, self.n_sw = F.n_nodes, len(rc1), len(sc1)
+        _check(self.lib.pgo_sparse_lm_create(F.h, self.n_nodes, _p(free, _bp), self.n_rel, _p(rc1, _ip), _p(rc2, _ip), self.n_sw, _p(sc1, _ip), _p(sc2, _ip), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.pgo_sparse_lm_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_scale(self, diag, sw_hss, jacobi_scaling=True):
+        """the Jacobi scale of a linearisation's diag (n_nodes, 6, 6) and sw_hss: at iteration 0 only.  jacobi_scaling=False: S = 1"""
+        d, h = _d(diag), _d(sw_hss)
+        assert d.size == 36 * self.n_nodes and h.size == self.n_sw
+        _check(self.lib.pgo_sparse_lm_set_scale(self.h, _p(d, _dp) if jacobi_scaling else None, _p(h, _dp)), self.F.h)
+
+    def step(self, diag, grad, offdiag, sw_c, sw_hss, sw_gs, radius, min_lm_diagonal=1e-6, max_lm_diagonal=1e32):
+        """one exact LM step from Problem.normal_blocks()' arrays -> (delta_pose (n_nodes, 6), delta_sw (n_sw,), model_cost_change, |d|, factor milliseconds).
+        PgoError(PGO_ERR_NUMERIC): a pivot is not > 0; the object takes the next step."""
+        a = [_d(x) for x in (diag, grad, offdiag, sw_c, sw_hss, sw_gs)]
+        assert [x.size for x in a] == [36 * self.n_nodes, 6 * self.n_nodes, 36 * (self.n_rel + self.n_sw), 12 * self.n_sw, self.n_sw, self.n_sw]
+        dpose, dsw, out3 = np.zeros((self.n_nodes, 6)), np.zeros(self.n_sw), np.zeros(3)
+        _check(self.lib.pgo_sparse_lm_step(self.h, *[_p(x, _dp) for x in a], radius, min_lm_diagonal, max_lm_diagonal, _p(dpose, _dp), _p(dsw, _dp), _p(out3, _dp)), self.F.h)
+        return dpose, dsw, float(out3[0]), float(out3[1]), float(out3[2])
+
+    def last_times(self):
+        """HIP-event milliseconds of the last step: upload, damping + fill + right-hand side, factor, sweeps, back-substitution + model, download"""
+        ms = np.zeros(6)
+        _check(self.lib.pgo_sparse_lm_last_times(self.h, _p(ms, _dp)), self.F.h)
+        return dict(zip(LM_TIMES, [float(v) for v in ms]))
+
+    def solve(self, callbacks, n_switch, swe_index, quat, t, sw, options):
+        """pgo_sparse_lm_solve -> (quat, t, sw, capi.Summary); callbacks: an LmCallbacks; options: a capi.Options"""
+        from . import capi
+        q, tt, s = capi.Problem._state(quat, t, sw)
+        idx = _i(swe_index)
+        assert idx.size == self.n_sw and s.size == n_switch and q.size == 4 * self.n_nodes
+        summ = capi.Summary()
+        _check(self.lib.pgo_sparse_lm_solve(self.h, C.byref(callbacks), None, n_switch, _p(idx, _ip), _p(q, _dp), _p(tt, _dp), _p(s, _dp), C.cast(C.byref(options), C.c_void_p), C.cast(C.byref(summ), C.c_void_p)), self.F.h)
+        return q, tt, s, summ
+
+
 @dataclasses.dataclass
 class Edges:
     """what covariance() has to know of a Problem's residual blocks, in the order they were added: the relative-pose edges' endpoints, the switchable edges' endpoints and
@@ -303,6 +378,93 @@ def covariance(P, edges, quat, t, sw, pairs, ordering=ORDER_AUTO, device_id=None
                 if a >= N and a == b:
                     blk = blk + 1.0 / hss[edge_of[a - N]]
                 out[k] = blk
+    finally:
+        F.close()
+    return out
+
+
+def handle_callbacks(P, hooks=None):
+    """LmCallbacks over a capi.Problem: ctypes wrappers of P.evaluate, P.normal_blocks and P.manifold_plus that hand the solve's host pointers straight to
+    pgo_evaluate, pgo_get_normal_blocks and pgo_manifold_plus.  hooks (a dict, optional): "normal_blocks": called as f(call index, diag (N, 6, 6), grad, offdiag,
+    sw_c, sw_hss, sw_gs) on writable views after every fetch — tests disturb a linearisation through it.  No exception crosses the C boundary: it is printed and the
+    callback returns PGO_ERR_INVALID_ARG."""
+    hooks = hooks or {}
+    calls = {"normal_blocks": 0}
+
+    def guarded(f):
+        def g(*a):
+            try:
+                return int(f(*a))
+            except Exception:
+                import traceback
+                traceback.print_exc()
+                return ERR_INVALID_ARG
+        return g
+
+    def evaluate(user, q, t, sw, n_nodes, n_switch, cost, res, grad):
+        P._shape = (int(n_nodes), int(n_switch))
+        return P.lib.pgo_evaluate(P.h, q, t, sw, C.c_int64(n_nodes), C.c_int64(n_switch), cost, res, grad)
+
+    def normal_blocks(user, diag, grad, off, c, hss, gs):
+        rc = P.lib.pgo_get_normal_blocks(P.h, diag, grad, off, c, hss, gs)
+        if rc == 0 and "normal_blocks" in hooks:
+            N, _ = P._shape
+            view = lambda p, shape: np.ctypeslib.as_array(p, shape=shape) if p else None
+            hooks["normal_blocks"](calls["normal_blocks"], view(diag, (N, 6, 6)), view(grad, (N, 6)), view(off, (P.n_rel + P.n_sw, 6, 6)), view(c, (P.n_sw, 12)), view(hss, (P.n_sw,)), view(gs, (P.n_sw,)))
+        calls["normal_blocks"] += 1
+        return rc
+
+    def manifold_plus(user, n, q, t, d, qo, to):
+        return P.lib.pgo_manifold_plus(P.h, C.c_int64(n), q, t, d, qo, to)
+
+    return LmCallbacks(EVALUATE_FN(guarded(evaluate)), NORMAL_BLOCKS_FN(guarded(normal_blocks)), MANIFOLD_PLUS_FN(guarded(manifold_plus)))
+
+
+def _refuse_busy_handle(P, n_nodes):
+    """PgoError(PGO_ERR_STATE) for a handle inside an open solve or with a communicator attached: pgo_get_linear_solution names both states before it does anything"""
+    x = np.zeros(6 * n_nodes)
+    rc = P.lib.pgo_get_linear_solution(P.h, _p(x, _dp))
+    text = P.lib.pgo_last_error(P.h).decode()
+    if rc == ERR_STATE and "communicator" in text:
+        raise PgoError(ERR_STATE, "solve_exact: one GPU only: a communicator is attached to the handle")
+    if not (rc == ERR_STATE and "needs an open solve" in text):
+        raise PgoError(ERR_STATE, "solve_exact inside a solve of the handle (between solve_begin and solve_end)")
+
+
+def solve_exact(P, edges, quat, t, sw, ordering=ORDER_AUTO, device_id=None, timings=None, hooks=None, **options):
+    """Problem.solve with every LM step exact, for graphs of any size: Ceres' trust-region solve on the tile-sparse Cholesky factor of every damped system —
+    what linear_solver = LINEAR_DENSE_CHOLESKY gives up to DENSE_MAX_KEYFRAMES keyframes -> (quat, t, sw, capi.Summary); the inputs are not modified.
+    P: a capi.Problem of any linear_solver on one GPU whose residual blocks `edges` describes; it linearises (evaluate, normal_blocks) and steps on the manifold
+    (manifold_plus), its own solver does not run and its summary and trust-region state stay what they were.  options: fields of capi.Options that replace P's for
+    this solve (max_num_iterations, function_tolerance, initial_trust_region_radius, ...).  PgoError(PGO_ERR_STATE): P is inside an open solve or has a communicator.
+    timings (a dict): the plan's figures and the HIP-event milliseconds of the last step's phases (LM_TIMES)."""
+    from . import capi
+    q, tt, s = capi.Problem._state(quat, t, sw)
+    N, S = q.size // 4, s.size
+    _refuse_busy_handle(P, N)
+    o = capi.Options.from_buffer_copy(P.options)
+    for k, v in options.items():
+        if not hasattr(o, k):
+            raise TypeError("unknown option %r" % k)
+        setattr(o, k, v)
+    free = np.ones(N, np.uint8); free[np.asarray(edges.constant, dtype=np.int64)] = 0
+    referenced = np.zeros(N, bool)
+    for c in (edges.rel_c1, edges.rel_c2, edges.sw_c1, edges.sw_c2, edges.reg_node):
+        referenced[np.asarray(c, dtype=np.int64)] = True
+    in_system = (free != 0) & referenced
+    ends = np.concatenate([np.stack([_i(edges.rel_c1), _i(edges.rel_c2)], axis=1), np.stack([_i(edges.sw_c1), _i(edges.sw_c2)], axis=1)]).astype(np.int64)
+    ends = ends[(ends[:, 0] != ends[:, 1]) & in_system[ends[:, 0]] & in_system[ends[:, 1]]]
+    pairs = np.unique(np.stack([ends.max(axis=1), ends.min(axis=1)], axis=1), axis=0) if len(ends) else np.zeros((0, 2), np.int64)
+    F = SparseCholesky(N, in_system, pairs[:, 0], pairs[:, 1], ordering, P.options.device_id if device_id is None else device_id)
+    try:
+        L = SparseLm(F, free, edges.rel_c1, edges.rel_c2, edges.sw_c1, edges.sw_c2)
+        try:
+            cb = handle_callbacks(P, hooks)
+            out = L.solve(cb, S, edges.sw_idx, q, tt, s, o)
+            if timings is not None:
+                timings["info"] = F.info()[0]; timings.update(L.last_times())
+        finally:
+            L.close()
     finally:
         F.close()
     return out
