@@ -89,7 +89,7 @@ def build_libpgo(force=False, verbose=False):
 
 LIBSPARSE = os.path.join(_HERE, "libpgo_sparse.so")
 SPARSE_SOURCE = "pgo_sparse.hip"
-SPARSE_HEADERS = ["pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_math.hpp", "pgo_sparse_lm.hpp", "pgo_sparse_lm_math.hpp"]
+SPARSE_HEADERS = ["pgo_sparse_kernels.hpp", "pgo_sparse_tile_ops.hpp", "pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_math.hpp", "pgo_sparse_lm.hpp", "pgo_sparse_lm_math.hpp"]
 # a header of libpgo.so that the companion includes unchanged (the LM controller: one copy of Ceres' rules); it belongs to HIP_HEADERS, here it is only a dependency
 SPARSE_SHARED_HEADERS = ["pgo_lm.hpp"]
 SPARSE_OBJ_DIR = os.path.join(_ROOT, "build", "obj_sparse")

@@ -91,16 +91,17 @@ struct pgo_sparse_lm {
     pgo_sparse_chol* chol = nullptr;
     ScLmPlan plan;
     ScLmView V{};                                          // device pointers
-    DevBuf tables, d_insys, num, scale, out, part;
+    DevBufs bufs;
+    DevBuf tables{bufs}, d_insys{bufs}, num{bufs}, scale{bufs}, out{bufs}, part{bufs};
     std::vector<double> h_scale, stage, h_out;
     bool scale_set = false;
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     double ms[6] = {0, 0, 0, 0, 0, 0};                     // upload, scale + fill + rhs, factor, sweeps, back-substitution + model, download
-    int blocks() const { return (int)((plan.N + plan.n_sw + SC_THREADS - 1) / SC_THREADS); }
+    int blocks() const { return (int)sc_grid(plan.N + plan.n_sw).x; }
     void release() {
         if (chol && chol->c.device >= 0) (void)hipSetDevice(chol->c.device);
         if (chol && chol->c.st) (void)hipStreamSynchronize(chol->c.st);
-        for (DevBuf* b : {&tables, &d_insys, &num, &scale, &out, &part}) b->release();
+        release_all(bufs);
         for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     }
 };
@@ -209,22 +210,21 @@ int pgo_sparse_lm_step(pgo_sparse_lm* lm, const double* diag, const double* grad
     double* dp = lm->out.as<double>();
     double* ds = dp + N * 6;
     double* d3 = ds + Es;
-    auto grid = [](int64_t threads) { return dim3((unsigned)((threads + SC_THREADS - 1) / SC_THREADS)); };
     SCHIP(c.err, hipEventRecord(lm->ev[0], c.st));
     SCHIP(c.err, hipMemcpyAsync(lm->num.p, st, lm->stage.size() * sizeof(double), hipMemcpyHostToDevice, c.st));
     SCHIP(c.err, hipEventRecord(lm->ev[1], c.st));
     SCHIP(c.err, hipMemsetAsync(c.fail.p, 0, sizeof(int32_t), c.st));
     SCHIP(c.err, hipMemsetAsync(c.T.p, 0, (size_t)c.P.tiles() * SC_TILE * sizeof(double), c.st));
-    hipLaunchKernelGGL(sc_lm_scale_kernel, grid((int64_t)(N * 6 + Es)), dim3(SC_THREADS), 0, c.st, V, radius, min_lm_diagonal, max_lm_diagonal, c.fail.as<int32_t>());
-    hipLaunchKernelGGL(sc_lm_fill_kernel, grid(sc_lm_fill_threads(V)), dim3(SC_THREADS), 0, c.st, c.T.as<double>(), c.D, V);
-    hipLaunchKernelGGL(sc_lm_rhs_kernel, grid(nc), dim3(SC_THREADS), 0, c.st, V, w);
+    hipLaunchKernelGGL(sc_lm_scale_kernel, sc_grid((int64_t)(N * 6 + Es)), dim3(SC_THREADS), 0, c.st, V, radius, min_lm_diagonal, max_lm_diagonal, c.fail.as<int32_t>());
+    hipLaunchKernelGGL(sc_lm_fill_kernel, sc_grid(sc_lm_fill_threads(V)), dim3(SC_THREADS), 0, c.st, c.T.as<double>(), c.D, V);
+    hipLaunchKernelGGL(sc_lm_rhs_kernel, sc_grid(nc), dim3(SC_THREADS), 0, c.st, V, w);
     SCHIP(c.err, hipEventRecord(lm->ev[2], c.st));
     ScLaunch Ln = c.launcher(1, w, w + nc, x, 0, true);
     sc_factor_steps(c.P, Ln);
     SCHIP(c.err, hipEventRecord(lm->ev[3], c.st));
     sc_solve_steps(c.P, Ln);      // (a failed factor: the sweeps and what follows run on numbers nobody reads — every address comes from the plan, none from the numbers)
     SCHIP(c.err, hipEventRecord(lm->ev[4], c.st));
-    hipLaunchKernelGGL(sc_lm_backsub_kernel, grid((int64_t)(N * 6 + Es)), dim3(SC_THREADS), 0, c.st, V, (const double*)x, dp, ds);
+    hipLaunchKernelGGL(sc_lm_backsub_kernel, sc_grid((int64_t)(N * 6 + Es)), dim3(SC_THREADS), 0, c.st, V, (const double*)x, dp, ds);
     hipLaunchKernelGGL(sc_lm_model_kernel, dim3((unsigned)lm->blocks()), dim3(SC_THREADS), 0, c.st, V, (const double*)dp, (const double*)ds, lm->part.as<double>());
     hipLaunchKernelGGL(sc_lm_reduce_kernel, dim3(1), dim3(64), 0, c.st, lm->part.as<const double>(), lm->blocks(), d3);
     SCHIP(c.err, hipEventRecord(lm->ev[5], c.st));
