@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Are the kernels of two checkouts the same machine code?  Compiles every HIP source of both trees for gfx950 to assembly (device side only, the build's own flags, no GPU
+"""Are the kernels of two checkouts the same machine code?  Compiles every HIP source of both trees (libpgo.so's, and the companion library's where the tree has one) for gfx950 to assembly (device side only, the build's own flags, no GPU
 needed) and compares, kernel by kernel, the instruction stream and the kernel descriptor (registers, LDS, scratch, kernel-argument size ...).  Comments, debug line directives and
 the numbering of local labels are dropped.  Kernels are matched by name: where a change adds a trailing template parameter with a default, DROPPED_DEFAULTS below has to be
 edited for that comparison so that an instantiation is matched with the one it was before.
@@ -25,6 +25,8 @@ def assemble(root, out_dir):
             del sys.modules[m]
         from solve_keyframe_pose_graph_amd import _build
         flags, sources, hipcc = list(_build.HIP_FLAGS), list(_build.HIP_SOURCES), _build.hipcc_path()
+        if hasattr(_build, "SPARSE_SOURCE"):      # libpgo_sparse.so's one translation unit
+            sources.append(_build.SPARSE_SOURCE)
     finally:
         sys.path.pop(0)
     procs = []

@@ -11,7 +11,7 @@ LIBPGO = os.path.join(_HERE, "libpgo.so")
 LIBGEN = os.path.join(_HERE, "libpgo_graphgen.so")
 
 HIP_SOURCES = ["pgo_kernels.hip", "pgo_solver.hip", "pgo_graph.hip", "pgo_shard.hip", "pgo_measure.hip", "pgo_pcg.hip", "pgo_multigrid.hip", "pgo_comm.hip", "pgo_dense.hip"]
-HIP_HEADERS = ["pgo_handle.hpp", "pgo_internal.hpp", "pgo_lm.hpp", "pgo_mg_cycle.hpp", "pgo_device_math.hpp", "pgo_mg_kernels.hpp", "pgo_mg_host.hpp", "pgo_comm.hpp", "pgo_dense_math.hpp"]
+HIP_HEADERS = ["pgo_handle.hpp", "pgo_internal.hpp", "pgo_lm.hpp", "pgo_mg_cycle.hpp", "pgo_device_math.hpp", "pgo_mg_kernels.hpp", "pgo_mg_host.hpp", "pgo_comm.hpp", "pgo_dense_math.hpp", "pgo_tile_ops.hpp"]
 
 
 def _stale(target, deps):
@@ -89,9 +89,10 @@ def build_libpgo(force=False, verbose=False):
 
 LIBSPARSE = os.path.join(_HERE, "libpgo_sparse.so")
 SPARSE_SOURCE = "pgo_sparse.hip"
-SPARSE_HEADERS = ["pgo_sparse_kernels.hpp", "pgo_sparse_tile_ops.hpp", "pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_math.hpp", "pgo_sparse_lm.hpp", "pgo_sparse_lm_math.hpp"]
-# a header of libpgo.so that the companion includes unchanged (the LM controller: one copy of Ceres' rules); it belongs to HIP_HEADERS, here it is only a dependency
-SPARSE_SHARED_HEADERS = ["pgo_lm.hpp"]
+SPARSE_HEADERS = ["pgo_sparse_kernels.hpp", "pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_math.hpp", "pgo_sparse_lm.hpp", "pgo_sparse_lm_math.hpp"]
+# headers of libpgo.so that the companion includes unchanged (the LM controller: one copy of Ceres' rules; the fp64 MFMA tile bodies: one copy of the operand maps and
+# the summation order); they belong to HIP_HEADERS, here they are only dependencies
+SPARSE_SHARED_HEADERS = ["pgo_lm.hpp", "pgo_tile_ops.hpp"]
 SPARSE_OBJ_DIR = os.path.join(_ROOT, "build", "obj_sparse")
 # every symbol include/pgo_sparse.h declares
 SPARSE_EXPORTS = ["pgo_sparse_spd_solve", "pgo_sparse_chol_create", "pgo_sparse_chol_destroy", "pgo_sparse_chol_info", "pgo_sparse_chol_factor", "pgo_sparse_chol_solve",

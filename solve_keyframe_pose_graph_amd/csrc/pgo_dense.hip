@@ -16,12 +16,12 @@
 
 #include "pgo_handle.hpp"
 #include "pgo_dense_math.hpp"
+#include "pgo_tile_ops.hpp"
 
 namespace pgo {
 
 namespace {
 
-typedef double dc_d4 __attribute__((ext_vector_type(4)));
 constexpr int DC_THREADS = 256;
 
 struct DcTeam {
@@ -58,46 +58,19 @@ __global__ __launch_bounds__(DC_THREADS) void dc_first_block_kernel(double* __re
 // Panel of step k: one workgroup per tile row i > k, one wavefront per 16 rows x of it.  The wavefront solves L_kk Y = (A_xk)^T by 16-wide block rows j: the products with
 // the block rows solved before it on the MFMA — Y_m leaves the accumulator in the D layout (row lk + 4 reg, column lr), which IS the B layout of the next product's k = 4 kk + lk
 // for reg = kk, so it never leaves the registers — then 16 substitution steps inside the 16 x 16 diagonal sub-block, the pivot row's value fetched with one cross-lane shuffle.
-// Writes L_ik over A_ik and, k-major, into LT[64][ldu] for the update's coalesced operand loads.
+// Writes L_ik over A_ik and, k-major, into LT[64][ldu] for the update's coalesced operand loads.  The body is TILE_RSUB_FORWARD (pgo_tile_ops.hpp), which
+// dcv_solve_kernel and the tile-sparse kernels expand too.
 __global__ __launch_bounds__(DC_THREADS) void dc_panel_kernel(double* __restrict__ A, int n, int ldu, int k, double* __restrict__ LT) {
     __shared__ double l[DC_NB * DC_LD];
     const int k0 = k * DC_NB;
     dc_load_block(A, n, k0, l);
     __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    TILE_LANE;
     const int x0 = (k + 1 + (int)blockIdx.x) * DC_NB + wave * DC_SUB;      // < n: the grid has nt - k - 1 workgroups
     double* __restrict__ arow = A + (size_t)(x0 + lr) * n + k0;
-    dc_d4 Y[DC_NB / DC_SUB];
-#pragma unroll
-    for (int j = 0; j < DC_NB / DC_SUB; ++j) {
-        double r[4];
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) r[reg] = arow[j * DC_SUB + lk + 4 * reg];
-        dc_d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int m = 0; m < j; ++m)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(j * DC_SUB + lr) * DC_LD + m * DC_SUB + 4 * kk + lk], Y[m][kk], acc, 0, 0, 0);
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) r[reg] = r[reg] - acc[reg];
-#pragma unroll
-        for (int p = 0; p < DC_SUB; ++p) {
-            const double yp = __shfl(r[p >> 2], (p & 3) * 16 + lr) / l[(j * DC_SUB + p) * DC_LD + j * DC_SUB + p];
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int q = lk + 4 * reg;
-                const double lqp = l[(j * DC_SUB + (q > p ? q : p)) * DC_LD + j * DC_SUB + p];      // (q <= p: the diagonal entry, unused)
-                r[reg] = q == p ? yp : (q > p ? r[reg] - lqp * yp : r[reg]);
-            }
-        }
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            Y[j][reg] = r[reg];
-            arow[j * DC_SUB + lk + 4 * reg] = r[reg];
-            LT[(size_t)(j * DC_SUB + lk + 4 * reg) * ldu + x0 + lr] = r[reg];
-        }
-    }
+    TILE_RSUB_FORWARD(l, arow[j * DC_SUB + lk + 4 * reg],
+                      arow[j * DC_SUB + lk + 4 * reg] = r[reg];
+                      LT[(size_t)(j * DC_SUB + lk + 4 * reg) * ldu + x0 + lr] = r[reg])
 }
 
 // Trailing update of step k: one workgroup per 64 x 64 tile (bi, bj), k < bj <= bi, 32 x 32 per wavefront as 2 x 2 MFMA tiles over K = 64, operands from the k-major
@@ -107,42 +80,20 @@ __global__ __launch_bounds__(DC_THREADS) void dc_update_kernel(double* __restric
     __shared__ double a[DC_NB * DC_LD];
     const int bi = k + 1 + (int)blockIdx.y, bj = k + 1 + (int)blockIdx.x;      // < nt: the grid is (nt - k - 1)^2
     if (bj > bi) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    TILE_LANE;
     const int wr = wave >> 1, wc = wave & 1;
     const int i0 = bi * DC_NB + wr * 32, j0 = bj * DC_NB + wc * 32;
     const int k1 = (k + 1) * DC_NB;
     const bool ahead = bi == k + 1 && bj == k + 1;                 // this workgroup owns the next diagonal block
     if (!(bi == bj && wr == 0 && wc == 1)) {                       // (that quadrant lies above the diagonal)
-        dc_d4 acc[2][2];
+        tile_d4 acc[2][2];
         double old[2][2][4];                                       // the tile's current values: all 16 loads in flight before the first store
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                acc[s][t] = dc_d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) old[s][t][reg] = A[(size_t)(i0 + s * 16 + lk + 4 * reg) * n + j0 + t * 16 + lr];
-            }
-#pragma unroll
-        for (int kk = 0; kk < DC_NB / 4; ++kk) {
-            const size_t row = (size_t)(kk * 4 + lk) * ldu;
-            const double a0 = LT[row + i0 + lr], a1 = LT[row + i0 + 16 + lr], b0 = LT[row + j0 + lr], b1 = LT[row + j0 + 16 + lr];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int i = i0 + s * 16 + lk + 4 * reg, j = j0 + t * 16 + lr;
-                    const double v = old[s][t][reg] - acc[s][t][reg];
-                    if (ahead) a[(i - k1) * DC_LD + (j - k1)] = v;      // (written to A once, as the factor)
-                    else A[(size_t)i * n + j] = v;
-                }
+        TILE_WALK_2X2(i0, j0, acc[s][u] = TILE_D4_ZERO, old[s][u][reg] = A[(size_t)i * n + j0 + u * 16 + lr])
+        TILE_MFMA_2X2(acc, DC_NB / 4, const size_t row = (size_t)(kk * 4 + lk) * ldu, LT[row + i0 + lr], LT[row + i0 + 16 + lr], LT[row + j0 + lr], LT[row + j0 + 16 + lr])
+        TILE_WALK_2X2(i0, j0, ,
+                      const double v = old[s][u][reg] - acc[s][u][reg];
+                      if (ahead) a[(i - k1) * DC_LD + (j - k1)] = v;      // (written to A once, as the factor)
+                      else A[(size_t)i * n + j] = v)
     }
     if (!ahead) return;
     __syncthreads();
@@ -223,47 +174,19 @@ __global__ __launch_bounds__(DC_THREADS) void dc_scatter_kernel(GraphDev G, CgDe
 
 // ---- covariance blocks: forward substitution with many right-hand sides (the rows of W[m][n]), then one Gram product per requested pair
 
-// Solve of step k: dc_panel_kernel's substitution on the tile rows of W instead of the tile rows of A below the diagonal (a copy, so that the factor's kernel keeps its
-// machine code): one workgroup per tile row that has started, one wavefront per 16 right-hand sides, Y = W_.k L_kk^-T over W_.k and, k-major, into YT[64][ldm].
+// Solve of step k: dc_panel_kernel's substitution (TILE_RSUB_FORWARD) on the tile rows of W instead of the tile rows of A below the diagonal: one workgroup per tile
+// row that has started, one wavefront per 16 right-hand sides, Y = W_.k L_kk^-T over W_.k and, k-major, into YT[64][ldm].
 __global__ __launch_bounds__(DC_THREADS) void dcv_solve_kernel(const double* __restrict__ A, int n, int k, double* __restrict__ W, int ldm, double* __restrict__ YT) {
     __shared__ double l[DC_NB * DC_LD];
     const int k0 = k * DC_NB;
     dc_load_block(A, n, k0, l);
     __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    TILE_LANE;
     const int x0 = (int)blockIdx.x * DC_NB + wave * DC_SUB;                // < m: the grid has at most m / 64 workgroups
     double* __restrict__ wrow = W + (size_t)(x0 + lr) * n + k0;
-    dc_d4 Y[DC_NB / DC_SUB];
-#pragma unroll
-    for (int j = 0; j < DC_NB / DC_SUB; ++j) {
-        double r[4];
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) r[reg] = wrow[j * DC_SUB + lk + 4 * reg];
-        dc_d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int m = 0; m < j; ++m)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(j * DC_SUB + lr) * DC_LD + m * DC_SUB + 4 * kk + lk], Y[m][kk], acc, 0, 0, 0);
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) r[reg] = r[reg] - acc[reg];
-#pragma unroll
-        for (int p = 0; p < DC_SUB; ++p) {
-            const double yp = __shfl(r[p >> 2], (p & 3) * 16 + lr) / l[(j * DC_SUB + p) * DC_LD + j * DC_SUB + p];
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int q = lk + 4 * reg;
-                const double lqp = l[(j * DC_SUB + (q > p ? q : p)) * DC_LD + j * DC_SUB + p];      // (q <= p: the diagonal entry, unused)
-                r[reg] = q == p ? yp : (q > p ? r[reg] - lqp * yp : r[reg]);
-            }
-        }
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            Y[j][reg] = r[reg];
-            wrow[j * DC_SUB + lk + 4 * reg] = r[reg];
-            YT[(size_t)(j * DC_SUB + lk + 4 * reg) * ldm + x0 + lr] = r[reg];
-        }
-    }
+    TILE_RSUB_FORWARD(l, wrow[j * DC_SUB + lk + 4 * reg],
+                      wrow[j * DC_SUB + lk + 4 * reg] = r[reg];
+                      YT[(size_t)(j * DC_SUB + lk + 4 * reg) * ldm + x0 + lr] = r[reg])
 }
 
 // Update of step k: one workgroup per 64 x 64 tile (tile row R of W, block column bi > k), W_Ri -= Y_R L_ik^T, 32 x 32 per wavefront as 2 x 2 MFMA tiles over K = 64.
@@ -272,41 +195,19 @@ __global__ __launch_bounds__(DC_THREADS) void dcv_update_kernel(const double* __
     __shared__ double l[DC_NB * DC_LD];
     const int bi = k + 1 + (int)blockIdx.y;                                // < nt: the grid is rows x (nt - k - 1)
     const int k0 = k * DC_NB;
-    for (int idx = threadIdx.x; idx < DC_NB * DC_NB; idx += DC_THREADS) {
+    for (int idx = threadIdx.x; idx < DC_NB * DC_NB; idx += DC_THREADS) {      // (through dc_load_block with a row and a column origin the kernel gets other instructions)
         const int r = idx >> 6, c = idx & 63;
         l[r * DC_LD + c] = A[(size_t)(bi * DC_NB + r) * n + k0 + c];
     }
     __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    TILE_LANE;
     const int wr = wave >> 1, wc = wave & 1;
     const int i0 = (int)blockIdx.x * DC_NB + wr * 32, j0 = wc * 32;        // rows of W (< m), columns inside the block column
-    dc_d4 acc[2][2];
+    tile_d4 acc[2][2];
     double old[2][2][4];
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            acc[s][t] = dc_d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) old[s][t][reg] = W[(size_t)(i0 + s * 16 + lk + 4 * reg) * n + bi * DC_NB + j0 + t * 16 + lr];
-        }
-#pragma unroll
-    for (int kk = 0; kk < DC_NB / 4; ++kk) {
-        const size_t row = (size_t)(kk * 4 + lk) * ldm;
-        const double a0 = YT[row + i0 + lr], a1 = YT[row + i0 + 16 + lr];
-        const double b0 = l[(j0 + lr) * DC_LD + kk * 4 + lk], b1 = l[(j0 + 16 + lr) * DC_LD + kk * 4 + lk];
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg)
-                W[(size_t)(i0 + s * 16 + lk + 4 * reg) * n + bi * DC_NB + j0 + t * 16 + lr] = old[s][t][reg] - acc[s][t][reg];
+    TILE_WALK_2X2(i0, j0, acc[s][u] = TILE_D4_ZERO, old[s][u][reg] = W[(size_t)i * n + bi * DC_NB + j0 + u * 16 + lr])
+    TILE_MFMA_2X2(acc, DC_NB / 4, const size_t row = (size_t)(kk * 4 + lk) * ldm, YT[row + i0 + lr], YT[row + i0 + 16 + lr], l[(j0 + lr) * DC_LD + kk * 4 + lk], l[(j0 + 16 + lr) * DC_LD + kk * 4 + lk])
+    TILE_WALK_2X2(i0, j0, , W[(size_t)i * n + bi * DC_NB + j0 + u * 16 + lr] = old[s][u][reg] - acc[s][u][reg])
 }
 
 // ---- the right-hand sides and the Gram products of pose and switch blocks (the algebra and the plan: pgo_dense_math.hpp)

@@ -11,6 +11,7 @@
 
 #include "pgo_internal.hpp"
 #include "pgo_mg_cycle.hpp"
+#include "pgo_tile_ops.hpp"
 
 namespace pgo {
 
@@ -2470,7 +2471,6 @@ void launch_coarse_apply(const GraphDev& G, const CgDev& C, const CoarseDev& K, 
 // v_mfma_f64_16x16x4_f64 operand maps: A[l & 15][k = l >> 4], B[k = l >> 4][l & 15], D[row = (l >> 4) + 4 reg][col = l & 15].
 // ------------------------------------------------------------------------------------------------
 constexpr int GJ_NB = 32;
-typedef double gj_d4 __attribute__((ext_vector_type(4)));
 
 // 32 x 32 Gauss-Jordan of the symmetric block in `a` (LDS), called by all 256 threads of a workgroup; writes the symmetrised inverse to
 // Pinv.  The 32 pivots are a sequential chain, so the elimination runs in the registers of ONE wavefront without barriers: lane (br, bc) of
@@ -2520,6 +2520,36 @@ __device__ inline void gj_block_inverse(double (*a)[GJ_NB + 1], double* __restri
     for (int q = 0; q < 4; ++q) Pinv[r * GJ_NB + c0 + q] = 0.5 * (a[r][c0 + q] + a[c0 + q][r]);
 }
 
+// the tail of the workgroup that owns the next pivot block: only the upper triangle of the block in `a` is maintained, so mirror it, then invert.  (__forceinline__:
+// out of line, both kernels that end in it get other instructions.)
+__device__ __forceinline__ void gj_mirror_and_invert(double (*a)[GJ_NB + 1], double* __restrict__ Pinv, int32_t* __restrict__ fail) {
+    __syncthreads();
+    const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * 4;
+    double m[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const int c = c0 + q; m[q] = r <= c ? a[r][c] : a[c][r]; }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[r][c0 + q] = m[q];
+    __syncthreads();
+    gj_block_inverse(a, Pinv, fail);
+}
+
+// acc0, acc1 = rows 0 .. 15 and 16 .. 31 of P u for 16 indices x (D row lk + 4 reg, column lr = x): declares them and u[kk] = U_ENTRY, the lane's coupling of index
+// lr to entry k = kk * 4 + lk of the pivot block, an expression in kk and k; eight steps of two MFMAs.  lr, lk in scope.
+#define GJ_PIVOT_TIMES_U(P, U_ENTRY)                                                                                     \
+    double u[GJ_NB / 4];                                                                                                 \
+    _Pragma("unroll") for (int kk = 0; kk < GJ_NB / 4; ++kk) {                                                           \
+        const int k = kk * 4 + lk;                                                                                       \
+        u[kk] = U_ENTRY;                                                                                                 \
+    }                                                                                                                    \
+    tile_d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};                                                    \
+    _Pragma("unroll") for (int kk = 0; kk < GJ_NB / 4; ++kk) {                                                           \
+        const int k = kk * 4 + lk;                                                                                       \
+        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(P[lr * GJ_NB + k], u[kk], acc0, 0, 0, 0);                            \
+        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(P[(16 + lr) * GJ_NB + k], u[kk], acc1, 0, 0, 0);                     \
+    }
+
 // the first pivot block (the later ones are inverted by gj_update_kernel one step ahead)
 __global__ __launch_bounds__(256) void gj_pivot_kernel(const double* __restrict__ A, int n, int k0, double* __restrict__ Pinv, int32_t* __restrict__ fail) {
     __shared__ double a[GJ_NB][GJ_NB + 1];
@@ -2548,19 +2578,7 @@ __global__ __launch_bounds__(256) void gj_panels_kernel(double* __restrict__ A, 
         return;
     }
     const bool before = x0 < k0;
-    double u[GJ_NB / 4];
-#pragma unroll
-    for (int kk = 0; kk < GJ_NB / 4; ++kk) {
-        const int k = kk * 4 + lk;
-        u[kk] = before ? A[(size_t)(x0 + lr) * n + k0 + k] : A[(size_t)(k0 + k) * n + x0 + lr];
-    }
-    gj_d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < GJ_NB / 4; ++kk) {
-        const int k = kk * 4 + lk;
-        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(Pinv[lr * GJ_NB + k], u[kk], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(Pinv[(16 + lr) * GJ_NB + k], u[kk], acc1, 0, 0, 0);
-    }
+    GJ_PIVOT_TIMES_U(Pinv, before ? A[(size_t)(x0 + lr) * n + k0 + k] : A[(size_t)(k0 + k) * n + x0 + lr])
     const double sgn = before ? -1.0 : 1.0;
 #pragma unroll
     for (int kk = 0; kk < GJ_NB / 4; ++kk) UT[(size_t)(kk * 4 + lk) * n + x0 + lr] = u[kk];
@@ -2584,56 +2602,22 @@ __global__ __launch_bounds__(256) void gj_update_kernel(double* __restrict__ A, 
     if (bi == 0 && bj == 0) bi = bj = kt;                             // the tile of the next pivot block is dispatched first: its
     else if (bi == kt && bj == kt) bi = bj = 0;                       // in-LDS inversion overlaps with the other tiles
     if (bj < bi) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    TILE_LANE;
     const int wr = wave >> 1, wc = wave & 1;
     const int i0 = bi * 64 + wr * 32, j0 = bj * 64 + wc * 32;
     const bool ahead = k1 < n && bi == bj && bi == kt;                // this workgroup owns the next pivot block
     if (!(bi == bj && wr == 1 && wc == 0)) {                          // (that quadrant lies below the diagonal)
-        gj_d4 acc[2][2];
+        tile_d4 acc[2][2];
         double old[2][2][4];                                          // the tile's current values: all 16 loads in flight before the first store
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                acc[s][t] = gj_d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) old[s][t][reg] = A[(size_t)(i0 + s * 16 + lk + 4 * reg) * n + j0 + t * 16 + lr];
-            }
-#pragma unroll
-        for (int kk = 0; kk < GJ_NB / 4; ++kk) {
-            const size_t row = (size_t)(kk * 4 + lk) * n;
-            const double a0 = UT[row + i0 + lr], a1 = UT[row + i0 + 16 + lr], b0 = VT[row + j0 + lr], b1 = VT[row + j0 + 16 + lr];
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        TILE_WALK_2X2(i0, j0, acc[s][u] = TILE_D4_ZERO, old[s][u][reg] = A[(size_t)i * n + j0 + u * 16 + lr])
+        TILE_MFMA_2X2(acc, GJ_NB / 4, const size_t row = (size_t)(kk * 4 + lk) * n, UT[row + i0 + lr], UT[row + i0 + 16 + lr], VT[row + j0 + lr], VT[row + j0 + 16 + lr])
         const bool mine = ahead && i0 == k1 && j0 == k1;
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const int i = i0 + s * 16 + lk + 4 * reg, j = j0 + t * 16 + lr;
-                    const double v = old[s][t][reg] - acc[s][t][reg];
-                    A[(size_t)i * n + j] = v;
-                    if (mine) a[i - k1][j - k1] = v;
-                }
+        TILE_WALK_2X2(i0, j0, ,
+                      const double v = old[s][u][reg] - acc[s][u][reg];
+                      A[(size_t)i * n + j] = v;
+                      if (mine) a[i - k1][j - k1] = v)
     }
-    if (!ahead) return;
-    __syncthreads();
-    {   // only the upper triangle of the block is maintained: mirror it
-        const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * 4;
-        double m[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const int c = c0 + q; m[q] = r <= c ? a[r][c] : a[c][r]; }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a[r][c0 + q] = m[q];
-        __syncthreads();
-    }
-    gj_block_inverse(a, Pinv, fail);
+    if (ahead) gj_mirror_and_invert(a, Pinv, fail);
 }
 
 // ONE launch per block step (default; -DPGO_GJ_TWO_LAUNCHES keeps the panels + update pair).  What the panels kernel did is done by the update's own wavefronts:
@@ -2658,7 +2642,7 @@ __global__ __launch_bounds__(256) void gj_step_kernel(double* __restrict__ A, in
     if (bi == 0 && bj == 0) bi = bj = kt;                             // the tile of the next pivot block is dispatched first: its
     else if (bi == kt && bj == kt) bi = bj = 0;                       // in-LDS inversion overlaps with the other tiles
     if (bj < bi) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    TILE_LANE;
     const int wr = wave >> 1, wc = wave & 1;
     const int i0 = bi * 64 + wr * 32, j0 = bj * 64 + wc * 32;
     const bool ahead = k1 < n && bi == bj && bi == kt;                // this workgroup owns the next pivot block
@@ -2676,16 +2660,7 @@ __global__ __launch_bounds__(256) void gj_step_kernel(double* __restrict__ A, in
         } else if (cols_pivot) {                                      // rows before the pivot block: A[x][k] = -v_x, v_x = P u_x
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                gj_d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-                double u[GJ_NB / 4];
-#pragma unroll
-                for (int kk = 0; kk < GJ_NB / 4; ++kk) u[kk] = UT[(size_t)(kk * 4 + lk) * ldu + i0 + s * 16 + lr];
-#pragma unroll
-                for (int kk = 0; kk < GJ_NB / 4; ++kk) {
-                    const int k = kk * 4 + lk;
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(Pin[lr * GJ_NB + k], u[kk], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(Pin[(16 + lr) * GJ_NB + k], u[kk], acc1, 0, 0, 0);
-                }
+                GJ_PIVOT_TIMES_U(Pin, UT[(size_t)(kk * 4 + lk) * ldu + i0 + s * 16 + lr])
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -2696,20 +2671,11 @@ __global__ __launch_bounds__(256) void gj_step_kernel(double* __restrict__ A, in
             }
         } else {
             // s_j v_j of this quadrant's columns: vj[t][h][reg] = row (h 16 + lk + 4 reg), column (j0 + 16 t + lr)
-            gj_d4 vj[2][2];
+            tile_d4 vj[2][2];
             const double sgn = j0 < k0 ? -1.0 : 1.0;
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                gj_d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-                double u[GJ_NB / 4];
-#pragma unroll
-                for (int kk = 0; kk < GJ_NB / 4; ++kk) u[kk] = UT[(size_t)(kk * 4 + lk) * ldu + j0 + t * 16 + lr];
-#pragma unroll
-                for (int kk = 0; kk < GJ_NB / 4; ++kk) {
-                    const int k = kk * 4 + lk;
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(Pin[lr * GJ_NB + k], u[kk], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(Pin[(16 + lr) * GJ_NB + k], u[kk], acc1, 0, 0, 0);
-                }
+                GJ_PIVOT_TIMES_U(Pin, UT[(size_t)(kk * 4 + lk) * ldu + j0 + t * 16 + lr])
 #pragma unroll
                 for (int reg = 0; reg < 4; ++reg) { vj[t][0][reg] = sgn * acc0[reg]; vj[t][1][reg] = sgn * acc1[reg]; }
             }
@@ -2726,57 +2692,23 @@ __global__ __launch_bounds__(256) void gj_step_kernel(double* __restrict__ A, in
                             if (next_cols) UTn[(size_t)(t * 16 + lr) * ldu + k0 + c] = w;      // (j0 == k1: these rows' couplings to the next pivot block)
                         }
             } else {
-                gj_d4 acc[2][2];
+                tile_d4 acc[2][2];
                 double old[2][2][4];                                  // the tile's current values: all 16 loads in flight before the first store
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        acc[s][t] = gj_d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                        for (int reg = 0; reg < 4; ++reg) old[s][t][reg] = A[(size_t)(i0 + s * 16 + lk + 4 * reg) * n + j0 + t * 16 + lr];
-                    }
-#pragma unroll
-                for (int kk = 0; kk < GJ_NB / 4; ++kk) {
-                    const size_t row = (size_t)(kk * 4 + lk) * ldu;
-                    const double a0 = UT[row + i0 + lr], a1 = UT[row + i0 + 16 + lr];
-                    const double b0 = vj[0][kk >> 2][kk & 3], b1 = vj[1][kk >> 2][kk & 3];
-                    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-                    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-                    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-                    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-                }
+                TILE_WALK_2X2(i0, j0, acc[s][u] = TILE_D4_ZERO, old[s][u][reg] = A[(size_t)i * n + j0 + u * 16 + lr])
+                TILE_MFMA_2X2(acc, GJ_NB / 4, const size_t row = (size_t)(kk * 4 + lk) * ldu, UT[row + i0 + lr], UT[row + i0 + 16 + lr], vj[0][kk >> 2][kk & 3], vj[1][kk >> 2][kk & 3])
                 const bool mine = ahead && i0 == k1 && j0 == k1;
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-#pragma unroll
-                        for (int reg = 0; reg < 4; ++reg) {
-                            const int i = i0 + s * 16 + lk + 4 * reg, j = j0 + t * 16 + lr;
-                            const double v = old[s][t][reg] - acc[s][t][reg];
-                            A[(size_t)i * n + j] = v;
-                            if (mine) a[i - k1][j - k1] = v;
-                            if (next_cols) UTn[(size_t)(j - k1) * ldu + i] = v;
-                            if (next_rows) UTn[(size_t)(i - k1) * ldu + j] = v;
-                        }
+                TILE_WALK_2X2(i0, j0, ,
+                              const double v = old[s][u][reg] - acc[s][u][reg];
+                              A[(size_t)i * n + j] = v;
+                              if (mine) a[i - k1][j - k1] = v;
+                              if (next_cols) UTn[(size_t)(j - k1) * ldu + i] = v;
+                              if (next_rows) UTn[(size_t)(i - k1) * ldu + j] = v)
             }
         }
     }
-    if (!ahead) return;
-    __syncthreads();
-    {   // only the upper triangle of the block is maintained: mirror it
-        const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * 4;
-        double m[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const int c = c0 + q; m[q] = r <= c ? a[r][c] : a[c][r]; }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a[r][c0 + q] = m[q];
-        __syncthreads();
-    }
-    gj_block_inverse(a, Pout, fail);
+    if (ahead) gj_mirror_and_invert(a, Pout, fail);
 }
+#undef GJ_PIVOT_TIMES_U
 
 __global__ void coarse_pad_identity_kernel(CoarseDev K) {    // rows/columns beyond 6 n_agg: a decoupled identity block
     const int i = 6 * K.n_agg + blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,5 +1,5 @@
 // pgo_sparse.hip — libpgo_sparse.so (include/pgo_sparse.h): the tile-sparse exact Cholesky solver on the device, host side and C entry points.  The kernels are in
-// pgo_sparse_kernels.hpp (what they share: pgo_sparse_tile_ops.hpp); the exact LM step and solve on this factor (pgo_sparse_lm_*) in pgo_sparse_lm.hpp, included at the end of this file: one translation unit.
+// pgo_sparse_kernels.hpp (what they share: pgo_tile_ops.hpp); the exact LM step and solve on this factor (pgo_sparse_lm_*) in pgo_sparse_lm.hpp, included at the end of this file: one translation unit.
 // This library neither links nor changes libpgo.so.
 //
 // The step order is sc_factor_steps / sc_solve_steps / sc_selinv_steps / sc_panel_steps (pgo_sparse_math.hpp), nowhere else: the structs ScLaunch, ScSelLaunch and

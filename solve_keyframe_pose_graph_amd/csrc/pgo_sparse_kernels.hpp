@@ -1,13 +1,13 @@
 // pgo_sparse_kernels.hpp — the device side of pgo_sparse_chol_* (include/pgo_sparse.h), included by pgo_sparse.hip: the companion library stays one translation unit.
 // The six kernels of pgo_dense.hip with the matrix addressed through an ScPlan (pgo_sparse_math.hpp): tile storage `tiles` x 4096 doubles, the plan's tables on the
-// device as int32 (ScDev).  The arithmetic of the diagonal tile, the panel, the update and the two sweeps is COPIED from dc_first_block_kernel, dc_panel_kernel,
-// dc_update_kernel, dc_forward_kernel and dc_backward_kernel — the same MFMA operand maps (the comment above dc_panel_kernel), the same summation order, the block
-// routines of pgo_dense_math.hpp — on purpose: the originals live in an anonymous namespace of a translation unit of libpgo.so, which this library neither links nor
-// changes.  In natural order the results are the dense solver's as numbers.
+// device as int32 (ScDev).  The arithmetic of the diagonal tile, the panel, the update and the two sweeps is that of dc_first_block_kernel, dc_panel_kernel,
+// dc_update_kernel, dc_forward_kernel and dc_backward_kernel: the block routines of pgo_dense_math.hpp and the MFMA tile bodies of pgo_tile_ops.hpp, two headers of
+// libpgo.so that both libraries include — the same operand maps (the comment above dc_panel_kernel), the same summation order; this library still links no libpgo.so.
+// In natural order the results are the dense solver's as numbers.
 //
-// What several kernels here share — the substitution with a diagonal tile (sc_panel_kernel, sc_pfwd_kernel; backwards in sc_sel_ginv_kernel, sc_pbwd_kernel), the
-// 2 x 2 MFMA product over K = 64 with its zeroing and store walk (sc_update_kernel, sc_sel_column_kernel, sc_sel_diag_kernel), the 16 x 64 row-panel product
-// (sc_pfwd_kernel, sc_pbwd_kernel) and the lane decomposition — is written once, in pgo_sparse_tile_ops.hpp, and expanded here.
+// The bodies of pgo_tile_ops.hpp that the kernels here expand: the substitution with a diagonal tile (sc_panel_kernel, sc_pfwd_kernel; backwards in sc_sel_ginv_kernel,
+// sc_pbwd_kernel), the 2 x 2 MFMA product over K = 64 with its zeroing and store walk (sc_update_kernel, sc_sel_column_kernel, sc_sel_diag_kernel), the 16 x 64
+// row-panel product (sc_pfwd_kernel, sc_pbwd_kernel) and the lane decomposition.
 //
 // Nothing waits on another workgroup inside a launch, there are no atomics, every sum has a fixed order.  The update finds its target tile by ScPlan::find's binary
 // search in row_col, in device code (sc_find): no per-step pair table.
@@ -18,7 +18,7 @@
 // The columns of the inverse in number (sc_pcol_rhs_kernel, sc_pfwd_kernel, sc_pbwd_kernel, sc_pgather_kernel) are the tile-sparse counterpart of dcv_solve_kernel /
 // dcv_update_kernel — right-hand sides as the rows of W, 64 per workgroup — in the pull form and for both sweeps: blocks outside the pattern of L.
 #include "pgo_sparse_blocks.hpp"
-#include "pgo_sparse_tile_ops.hpp"
+#include "pgo_tile_ops.hpp"
 
 namespace pgo {
 
@@ -73,11 +73,11 @@ __global__ __launch_bounds__(SC_THREADS) void sc_panel_kernel(double* __restrict
     __shared__ double l[DC_NB * DC_LD];
     sc_load_tile(T + (size_t)(P.row_ptr[k + 1] - 1) * SC_TILE, l);
     __syncthreads();
-    SC_LANE;
+    TILE_LANE;
     const int e = (int)blockIdx.x;                                         // < |s_k|: the grid
     const int x0 = e * DC_NB + wave * DC_SUB;
     double* __restrict__ arow = T + (size_t)P.col_tile[P.col_ptr[k] + e] * SC_TILE + (size_t)(wave * DC_SUB + lr) * DC_NB;
-    SC_RSUB_FORWARD(l, arow[j * DC_SUB + lk + 4 * reg],
+    TILE_RSUB_FORWARD(l, arow[j * DC_SUB + lk + 4 * reg],
                     arow[j * DC_SUB + lk + 4 * reg] = r[reg];
                     LT[(size_t)(j * DC_SUB + lk + 4 * reg) * ldu + x0 + lr] = r[reg])
 }
@@ -95,17 +95,17 @@ __global__ __launch_bounds__(SC_THREADS) void sc_update_kernel(double* __restric
     const int id = sc_find(P, P.col_row[c0 + pa], P.col_row[c0 + pb]);      // in the pattern by construction of the symbolic factorisation
     if (id < 0) return;
     double* __restrict__ t = T + (size_t)id * SC_TILE;
-    SC_LANE;
+    TILE_LANE;
     const int wr = wave >> 1, wc = wave & 1;
     const int i0 = wr * 32, j0 = wc * 32;                                  // inside the tile
     const int ia = pa * DC_NB + i0, jb = pb * DC_NB + j0;                  // columns of the k-major copy
     const bool ahead = p == 0 && P.ahead[k] != 0;                          // this workgroup owns the next diagonal tile
     if (!(pa == pb && wr == 0 && wc == 1)) {                               // (that quadrant lies above the diagonal)
-        sc_d4 acc[2][2];
+        tile_d4 acc[2][2];
         double old[2][2][4];
-        SC_WALK_2X2(i0, j0, acc[s][u] = SC_D4_ZERO, old[s][u][reg] = t[i * DC_NB + j])
-        SC_MFMA_2X2(acc, const size_t row = (size_t)(kk * 4 + lk) * ldu, LT[row + ia + lr], LT[row + ia + 16 + lr], LT[row + jb + lr], LT[row + jb + 16 + lr])
-        SC_WALK_2X2(i0, j0, ,
+        TILE_WALK_2X2(i0, j0, acc[s][u] = TILE_D4_ZERO, old[s][u][reg] = t[i * DC_NB + j])
+        TILE_MFMA_2X2(acc, DC_NB / 4, const size_t row = (size_t)(kk * 4 + lk) * ldu, LT[row + ia + lr], LT[row + ia + 16 + lr], LT[row + jb + lr], LT[row + jb + 16 + lr])
+        TILE_WALK_2X2(i0, j0, ,
                     const double v = old[s][u][reg] - acc[s][u][reg];
                     if (ahead) a[i * DC_LD + j] = v;      // (written to the tile once, as the factor)
                     else t[i * DC_NB + j] = v)
@@ -220,11 +220,11 @@ __global__ __launch_bounds__(SC_THREADS) void sc_sel_ginv_kernel(const double* _
     __shared__ double l[DC_NB * DC_LD];
     sc_load_tile(T + (size_t)(P.row_ptr[k + 1] - 1) * SC_TILE, l);
     __syncthreads();
-    SC_LANE;
+    TILE_LANE;
     const int e = (int)blockIdx.x;                                         // < |s_k|: the grid
     const double* __restrict__ arow = T + (size_t)P.col_tile[P.col_ptr[k] + e] * SC_TILE + (size_t)(wave * DC_SUB + lr) * DC_NB;
     double* __restrict__ grow = G + (size_t)e * SC_TILE + (size_t)(wave * DC_SUB + lr) * DC_NB;
-    SC_RSUB_BACKWARD(l, arow[j * DC_SUB + lk + 4 * reg], grow[j * DC_SUB + lk + 4 * reg] = r[reg])
+    TILE_RSUB_BACKWARD(l, arow[j * DC_SUB + lk + 4 * reg], grow[j * DC_SUB + lk + 4 * reg] = r[reg])
 }
 
 // column(k): one workgroup per position a; Z_{s[a],k} = - sum_b Z(s[a], s[b]) G_b.  2 x 2 MFMA tiles per wavefront over K = 64 (sc_update_kernel's layout), the
@@ -234,10 +234,10 @@ __global__ __launch_bounds__(SC_THREADS) void sc_sel_column_kernel(double* __res
     __shared__ double z[DC_NB * DC_LD];
     const int a = (int)blockIdx.x;                                         // < |s_k|: the grid
     const int c0 = P.col_ptr[k], m = P.col_ptr[k + 1] - c0, ra = P.col_row[c0 + a];
-    SC_LANE;
+    TILE_LANE;
     const int i0 = (wave >> 1) * 32, j0 = (wave & 1) * 32;                 // inside the tile
-    sc_d4 acc[2][2];
-    SC_ZERO_2X2(acc)
+    tile_d4 acc[2][2];
+    TILE_ZERO_2X2(acc)
     for (int b = 0; b < m; ++b) {
         const int rb = P.col_row[c0 + b];
         const bool tr = a < b;
@@ -248,10 +248,10 @@ __global__ __launch_bounds__(SC_THREADS) void sc_sel_column_kernel(double* __res
         __syncthreads();
         const int si = tr ? 1 : DC_LD, sk = tr ? DC_LD : 1;
         const double* __restrict__ g = G + (size_t)b * SC_TILE;
-        SC_MFMA_2X2(acc, const int kx = kk * 4 + lk, z[(i0 + lr) * si + kx * sk], z[(i0 + 16 + lr) * si + kx * sk], g[kx * DC_NB + j0 + lr], g[kx * DC_NB + j0 + 16 + lr])
+        TILE_MFMA_2X2(acc, DC_NB / 4, const int kx = kk * 4 + lk, z[(i0 + lr) * si + kx * sk], z[(i0 + 16 + lr) * si + kx * sk], g[kx * DC_NB + j0 + lr], g[kx * DC_NB + j0 + 16 + lr])
     }
     double* __restrict__ t = Z + (size_t)P.col_tile[c0 + a] * SC_TILE;      // a tile of column k: none of those read above
-    SC_WALK_2X2(i0, j0, , t[i * DC_NB + j] = -acc[s][u][reg])
+    TILE_WALK_2X2(i0, j0, , t[i * DC_NB + j] = -acc[s][u][reg])
 }
 
 // inverses: one workgroup per diagonal tile k (the grid: nt), Z_kk = L_kk^-T L_kk^-1 in LDS from the 64 unit right-hand sides, thread c substituting column c in place
@@ -280,18 +280,18 @@ __global__ __launch_bounds__(SC_THREADS) void sc_sel_inverses_kernel(const doubl
 // i >= j, each written to both triangles by the one lane that holds it.
 __global__ __launch_bounds__(SC_THREADS) void sc_sel_diag_kernel(double* __restrict__ Z, ScDev P, int k, const double* __restrict__ G) {
     const int c0 = P.col_ptr[k], m = P.col_ptr[k + 1] - c0;
-    SC_LANE;
+    TILE_LANE;
     const int i0 = (wave >> 1) * 32, j0 = (wave & 1) * 32;
     if (i0 == 0 && j0 == 32) return;                                       // (that quadrant lies above the diagonal)
-    sc_d4 acc[2][2];
-    SC_ZERO_2X2(acc)
+    tile_d4 acc[2][2];
+    TILE_ZERO_2X2(acc)
     for (int a = 0; a < m; ++a) {
         const double* __restrict__ g = G + (size_t)a * SC_TILE;
         const double* __restrict__ zt = Z + (size_t)P.col_tile[c0 + a] * SC_TILE;
-        SC_MFMA_2X2(acc, const int kx = (kk * 4 + lk) * DC_NB, g[kx + i0 + lr], g[kx + i0 + 16 + lr], zt[kx + j0 + lr], zt[kx + j0 + 16 + lr])
+        TILE_MFMA_2X2(acc, DC_NB / 4, const int kx = (kk * 4 + lk) * DC_NB, g[kx + i0 + lr], g[kx + i0 + 16 + lr], zt[kx + j0 + lr], zt[kx + j0 + 16 + lr])
     }
     double* t = Z + (size_t)(P.row_ptr[k + 1] - 1) * SC_TILE;              // the diagonal tile: none of those read above
-    SC_WALK_2X2(i0, j0, ,
+    TILE_WALK_2X2(i0, j0, ,
                 if (i >= j) {
                     const double v = t[i * DC_NB + j] - acc[s][u][reg];
                     t[i * DC_NB + j] = v;
@@ -337,27 +337,27 @@ __global__ __launch_bounds__(SC_THREADS) void sc_pcol_rhs_kernel(double* __restr
 }
 
 // one tile of pfwd's / pbwd's carried sum: once every thread of the workgroup is done with what l held, tile `id` of T into l, then acc += (the wavefront's rows of
-// W in tile column w_col) x (the tile, by rows or by columns: SC_ROW_PANEL_MFMA).  The caller walks its own list of tiles.
+// W in tile column w_col) x (the tile, by rows or by columns: TILE_ROW_PANEL_MFMA).  The caller walks its own list of tiles.
 #define SC_PANEL_TILE(acc, id, w_col, BY_COLUMNS)                      \
     {                                                                  \
         __syncthreads();                                               \
         sc_load_tile(T + (size_t)(id) * SC_TILE, l);                   \
         __syncthreads();                                               \
         const double* __restrict__ wt = wrow + (size_t)(w_col) * DC_NB; \
-        SC_ROW_PANEL_MFMA(acc, l, wt, BY_COLUMNS)                      \
+        TILE_ROW_PANEL_MFMA(acc, l, wt, BY_COLUMNS)                      \
     }
 
 // pfwd(k): one workgroup per started panel (the grid).  acc = sum_j W_pj L_kj^T over the stored tiles (k, j), first[p] <= j < k, ascending; W_pk - acc, then
 // sc_panel_kernel's substitution with L_kk.
 __global__ __launch_bounds__(SC_THREADS) void sc_pfwd_kernel(const double* __restrict__ T, ScDev P, int k, int nc, double* __restrict__ W, const int32_t* __restrict__ first) {
     __shared__ double l[DC_NB * DC_LD];
-    SC_LANE;
+    TILE_LANE;
     const int p = (int)blockIdx.x, fp = first[p];
     double* __restrict__ wrow = W + ((size_t)p * DC_NB + wave * DC_SUB + lr) * nc;
     const int diag = P.row_ptr[k + 1] - 1;
-    sc_d4 acc[DC_NB / DC_SUB];
+    tile_d4 acc[DC_NB / DC_SUB];
 #pragma unroll
-    for (int jb = 0; jb < DC_NB / DC_SUB; ++jb) acc[jb] = sc_d4{0.0, 0.0, 0.0, 0.0};
+    for (int jb = 0; jb < DC_NB / DC_SUB; ++jb) acc[jb] = tile_d4{0.0, 0.0, 0.0, 0.0};
     for (int id = P.row_ptr[k]; id < diag; ++id) {
         const int j = P.row_col[id];
         if (j < fp) continue;                                              // (the same for every thread of the workgroup) W_pj is all zero
@@ -367,23 +367,23 @@ __global__ __launch_bounds__(SC_THREADS) void sc_pfwd_kernel(const double* __res
     sc_load_tile(T + (size_t)diag * SC_TILE, l);
     __syncthreads();
     double* __restrict__ arow = wrow + (size_t)k * DC_NB;
-    SC_RSUB_FORWARD(l, arow[j * DC_SUB + lk + 4 * reg] - acc[j][reg], arow[j * DC_SUB + lk + 4 * reg] = r[reg])
+    TILE_RSUB_FORWARD(l, arow[j * DC_SUB + lk + 4 * reg] - acc[j][reg], arow[j * DC_SUB + lk + 4 * reg] = r[reg])
 }
 
 // pbwd(k): one workgroup per panel (the grid).  acc = sum_{i in s_k} W_pi L_ik, i ascending; W_pk - acc, then sc_sel_ginv_kernel's substitution with L_kk.
 __global__ __launch_bounds__(SC_THREADS) void sc_pbwd_kernel(const double* __restrict__ T, ScDev P, int k, int nc, double* __restrict__ W) {
     __shared__ double l[DC_NB * DC_LD];
-    SC_LANE;
+    TILE_LANE;
     double* __restrict__ wrow = W + ((size_t)blockIdx.x * DC_NB + wave * DC_SUB + lr) * nc;
-    sc_d4 acc[DC_NB / DC_SUB];
+    tile_d4 acc[DC_NB / DC_SUB];
 #pragma unroll
-    for (int jb = 0; jb < DC_NB / DC_SUB; ++jb) acc[jb] = sc_d4{0.0, 0.0, 0.0, 0.0};
+    for (int jb = 0; jb < DC_NB / DC_SUB; ++jb) acc[jb] = tile_d4{0.0, 0.0, 0.0, 0.0};
     for (int e = P.col_ptr[k]; e < P.col_ptr[k + 1]; ++e) SC_PANEL_TILE(acc, P.col_tile[e], P.col_row[e], true)
     __syncthreads();
     sc_load_tile(T + (size_t)(P.row_ptr[k + 1] - 1) * SC_TILE, l);
     __syncthreads();
     double* __restrict__ arow = wrow + (size_t)k * DC_NB;
-    SC_RSUB_BACKWARD(l, arow[j * DC_SUB + lk + 4 * reg] - acc[j][reg], arow[j * DC_SUB + lk + 4 * reg] = r[reg])
+    TILE_RSUB_BACKWARD(l, arow[j * DC_SUB + lk + 4 * reg] - acc[j][reg], arow[j * DC_SUB + lk + 4 * reg] = r[reg])
 }
 
 // gather: one thread per entry of a requested block out of one chunk's W: entry (i, j) = row 6 pos[row keyframe] + i of the solution of right-hand side j of the column

@@ -1,13 +1,19 @@
-// pgo_sparse_tile_ops.hpp — the arithmetic that several kernels of libpgo_sparse.so (pgo_sparse_kernels.hpp) share, each body written once.  The bodies are MACROS, not
-// functions: the kernels' instruction sequences are pinned to those of the copies these bodies replace (profiles/sparse_kernel_refactor_check.txt), and a body that the
-// compiler sees as a function — inlined, with functor arguments or without — is scheduled differently (profiles/sparse_kernel_refactor_times.txt).  A macro's expansion is
-// the text the kernel had.  Every body expects `SC_LANE;` in scope (lr, lk); its other operands are arguments.  `-ffp-contract=on`: keep every expression as it stands.
-//   SC_RSUB_FORWARD / SC_RSUB_BACKWARD       X L_kk^T = R / X L_kk = R, a wavefront's 16 rows: sc_panel_kernel, sc_pfwd_kernel / sc_sel_ginv_kernel, sc_pbwd_kernel
-//   SC_ZERO_2X2, SC_MFMA_2X2, SC_WALK_2X2    a wavefront's 32 x 32 quadrant of a 64 x 64 x 64 product: sc_update_kernel, sc_sel_column_kernel, sc_sel_diag_kernel
-//   SC_ROW_PANEL_MFMA                        a wavefront's 16 rows of W times a tile of L, read by rows or by columns: sc_pfwd_kernel, sc_pbwd_kernel
-// The operand maps and the summation order are dc_panel_kernel's and dc_update_kernel's (pgo_dense.hip; the comment above dc_panel_kernel derives them).  Those dense
-// kernels KEEP THEIR OWN COPIES of the substitution and of the 2 x 2 product, on purpose: they live in an anonymous namespace of a translation unit of libpgo.so, which
-// this library neither links nor changes — a fix made here that the dense solver needs too is made there by hand.
+// pgo_tile_ops.hpp — the fp64 MFMA tile arithmetic (v_mfma_f64_16x16x4_f64) that kernels of both libraries share, each body written once: the dense Cholesky solver
+// (pgo_dense.hip) and the coarse operator's Gauss-Jordan inverse (pgo_kernels.hip) of libpgo.so, and the tile-sparse Cholesky kernels (pgo_sparse_kernels.hpp) of
+// libpgo_sparse.so.  The bodies are MACROS, not functions: the kernels' instruction sequences are pinned to those of the copies these bodies replaced
+// (profiles/sparse_kernel_refactor_check.txt, profiles/tile_ops_refactor_check.txt), and a body that the compiler sees as a function — inlined, with functor arguments or
+// without — is scheduled differently (profiles/sparse_kernel_refactor_times.txt).  A macro's expansion is the text the kernel had.  Every body expects `TILE_LANE;` in
+// scope (lr, lk); its other operands are arguments.  `-ffp-contract=on`: keep every expression as it stands.  The spelling of an address expression in an argument
+// decides the instructions too: (size_t)i * n + j0 + u * 16 + lr adds the column terms one by one in 64 bits, (size_t)i * n + j adds the walk's int j once.
+//   TILE_RSUB_FORWARD                          X L_kk^T = R, a wavefront's 16 rows: dc_panel_kernel, dcv_solve_kernel; sc_panel_kernel, sc_pfwd_kernel
+//   TILE_RSUB_BACKWARD                         X L_kk = R: sc_sel_ginv_kernel, sc_pbwd_kernel
+//   TILE_ZERO_2X2, TILE_MFMA_2X2, TILE_WALK_2X2  a wavefront's 32 x 32 quadrant of a 64 x 64 x K product.  K = 64: dc_update_kernel, dcv_update_kernel; sc_update_kernel,
+//                                              sc_sel_column_kernel, sc_sel_diag_kernel.  K = 32: gj_update_kernel, gj_step_kernel
+//   TILE_ROW_PANEL_MFMA                        a wavefront's 16 rows of W times a tile of L, read by rows or by columns: sc_pfwd_kernel, sc_pbwd_kernel
+// The comment above dc_panel_kernel (pgo_dense.hip) derives the operand maps and the summation order; the one above gj_block_inverse (pgo_kernels.hip) states the
+// instruction's.  Deliberately not here: the Gauss-Jordan kernels' product P u of the pivot inverse with 16 couplings (two accumulators over K = 32, no quadrant),
+// which only they use — GJ_PIVOT_TIMES_U, beside them in pgo_kernels.hip; and dcv_update_kernel's own loop that loads L_ik into LDS, which through dc_load_block with a
+// row and a column origin gave that kernel other instructions.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,23 +23,23 @@ namespace pgo {
 
 namespace {
 
-typedef double sc_d4 __attribute__((ext_vector_type(4)));
-#define SC_D4_ZERO sc_d4{0.0, 0.0, 0.0, 0.0}
+typedef double tile_d4 __attribute__((ext_vector_type(4)));
+#define TILE_D4_ZERO tile_d4{0.0, 0.0, 0.0, 0.0}
 
 // a thread's place in its workgroup of four wavefronts: a lane (lr, lk) holds, of a 16 x 16 MFMA tile, the entries lk + 4 reg (reg = 0 .. 3) of line lr.  (As the
-// members of a struct the same four values gave all seven kernels other instructions.)
-#define SC_LANE const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4
+// members of a struct the same four values gave the sparse kernels other instructions.)
+#define TILE_LANE const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4
 
 // X L^T = R for the wavefront's 16 rows, l = the lower triangular L in LDS (stride DC_LD): dc_panel_kernel's scheme.  The 16-wide block columns j from the first to the
 // last: r[reg] = R_ENTRY — the lane's entry of R in column j * DC_SUB + lk + 4 * reg, an expression in j and reg —, minus the MFMA products with the block columns
-// already solved (m = 0 .. j - 1), then the substitution inside the diagonal sub-block from its first column to its last, one __shfl per column; STORE: statements in
-// j and reg that put r[reg] where the solved entry goes.
-#define SC_RSUB_FORWARD(l, R_ENTRY, ...)                                                                                                                    \
-    sc_d4 Y[DC_NB / DC_SUB];                                                                                                                                \
+// already solved (m = 0 .. j - 1), then the substitution inside the diagonal sub-block from its first column to its last, one __shfl per column; the remaining
+// arguments: statements in j and reg that put r[reg] where the solved entry goes.
+#define TILE_RSUB_FORWARD(l, R_ENTRY, ...)                                                                                                                    \
+    tile_d4 Y[DC_NB / DC_SUB];                                                                                                                                \
     _Pragma("unroll") for (int j = 0; j < DC_NB / DC_SUB; ++j) {                                                                                            \
         double r[4];                                                                                                                                        \
         _Pragma("unroll") for (int reg = 0; reg < 4; ++reg) r[reg] = R_ENTRY;                                                                               \
-        sc_d4 sub = {0.0, 0.0, 0.0, 0.0};                                                                                                                   \
+        tile_d4 sub = {0.0, 0.0, 0.0, 0.0};                                                                                                                   \
         _Pragma("unroll") for (int m = 0; m < j; ++m)                                                                                                       \
             _Pragma("unroll") for (int kk = 0; kk < 4; ++kk)                                                                                                \
                 sub = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(j * DC_SUB + lr) * DC_LD + m * DC_SUB + 4 * kk + lk], Y[m][kk], sub, 0, 0, 0);          \
@@ -52,15 +58,15 @@ typedef double sc_d4 __attribute__((ext_vector_type(4)));
         }                                                                                                                                                   \
     }
 
-// X L = R: SC_RSUB_FORWARD run backwards — the block columns from the last to the first, MFMA products with the block columns already solved (m = 3 .. j + 1),
+// X L = R: TILE_RSUB_FORWARD run backwards — the block columns from the last to the first, MFMA products with the block columns already solved (m = 3 .. j + 1),
 // substitution inside the diagonal sub-block from its last column to its first.  Operand map: A[i][k] = L[16 m + k][16 j + i], B[k][n] = X[row n][16 m + k],
 // D[i][n] = (X_m L_mj)[row n][16 j + i]; a lane holds row lr, columns lk + 4 reg.
-#define SC_RSUB_BACKWARD(l, R_ENTRY, ...)                                                                                                                   \
-    sc_d4 Y[DC_NB / DC_SUB];                                                                                                                                \
+#define TILE_RSUB_BACKWARD(l, R_ENTRY, ...)                                                                                                                   \
+    tile_d4 Y[DC_NB / DC_SUB];                                                                                                                                \
     _Pragma("unroll") for (int j = DC_NB / DC_SUB - 1; j >= 0; --j) {                                                                                       \
         double r[4];                                                                                                                                        \
         _Pragma("unroll") for (int reg = 0; reg < 4; ++reg) r[reg] = R_ENTRY;                                                                               \
-        sc_d4 sub = {0.0, 0.0, 0.0, 0.0};                                                                                                                   \
+        tile_d4 sub = {0.0, 0.0, 0.0, 0.0};                                                                                                                   \
         _Pragma("unroll") for (int m = DC_NB / DC_SUB - 1; m > j; --m)                                                                                      \
             _Pragma("unroll") for (int kk = 0; kk < 4; ++kk)                                                                                                \
                 sub = __builtin_amdgcn_mfma_f64_16x16x4f64(l[(m * DC_SUB + 4 * kk + lk) * DC_LD + j * DC_SUB + lr], Y[m][kk], sub, 0, 0, 0);          \
@@ -79,14 +85,15 @@ typedef double sc_d4 __attribute__((ext_vector_type(4)));
         }                                                                                                                                                   \
     }
 
-// the 2 x 2 MFMA tiles of a wavefront's 32 x 32 quadrant: sc_d4 acc[2][2], acc[s][u] = rows 16 s .., columns 16 u .. of the quadrant
-#define SC_ZERO_2X2(acc)                                                                                                                                    \
+// the 2 x 2 MFMA tiles of a wavefront's 32 x 32 quadrant: tile_d4 acc[2][2], acc[s][u] = rows 16 s .., columns 16 u .. of the quadrant
+#define TILE_ZERO_2X2(acc)                                                                                                                                    \
     _Pragma("unroll") for (int s = 0; s < 2; ++s)                                                                                                           \
-        _Pragma("unroll") for (int u = 0; u < 2; ++u) acc[s][u] = SC_D4_ZERO;
-// acc += A B over K = 64.  Per step kk = 0 .. 15: STEP, a declaration of what the operand expressions share (the inner index (kk * 4 + lk), scaled as the caller's
-// operands need it); A0, A1: the lane's entries of A in rows lr and 16 + lr of the quadrant; B0, B1: of B in columns lr and 16 + lr
-#define SC_MFMA_2X2(acc, STEP, A0, A1, B0, B1)                                                                                                              \
-    _Pragma("unroll") for (int kk = 0; kk < DC_NB / 4; ++kk) {                                                                                              \
+        _Pragma("unroll") for (int u = 0; u < 2; ++u) acc[s][u] = TILE_D4_ZERO;
+// acc += A B over K = 4 STEPS (DC_NB / 4 steps for a 64-wide tile, GJ_NB / 4 for the Gauss-Jordan block).  Per step kk: STEP, a declaration of what the operand
+// expressions share (the inner index (kk * 4 + lk), scaled as the caller's operands need it); A0, A1: the lane's entries of A in rows lr and 16 + lr of the quadrant;
+// B0, B1: of B in columns lr and 16 + lr
+#define TILE_MFMA_2X2(acc, STEPS, STEP, A0, A1, B0, B1)                                                                                                       \
+    _Pragma("unroll") for (int kk = 0; kk < STEPS; ++kk) {                                                                                                  \
         STEP;                                                                                                                                               \
         const double a0 = A0, a1 = A1, b0 = B0, b1 = B1;                                                                                                    \
         acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);                                                                       \
@@ -96,7 +103,7 @@ typedef double sc_d4 __attribute__((ext_vector_type(4)));
     }
 // the lane's sixteen entries (i, j) of the quadrant at (i0, j0) of the tile: PER_TILE, statements in s and u (may be empty), then for reg = 0 .. 3 the statements
 // that follow, in s, u, reg, i and j
-#define SC_WALK_2X2(i0, j0, PER_TILE, ...)                                                                                                                  \
+#define TILE_WALK_2X2(i0, j0, PER_TILE, ...)                                                                                                                  \
     _Pragma("unroll") for (int s = 0; s < 2; ++s)                                                                                                           \
         _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                                                                     \
             PER_TILE;                                                                                                                                       \
@@ -106,10 +113,10 @@ typedef double sc_d4 __attribute__((ext_vector_type(4)));
             }                                                                                                                                               \
         }
 
-// sc_d4 acc[4]: acc[jb] += (the wavefront's row w of W, 64 entries) x (the tile l in LDS, stride DC_LD), block column jb of the result.  BY_COLUMNS false: W L^T, the
+// tile_d4 acc[4]: acc[jb] += (the wavefront's row w of W, 64 entries) x (the tile l in LDS, stride DC_LD), block column jb of the result.  BY_COLUMNS false: W L^T, the
 // tile read by rows (the forward sweep, tile (k, j)); true: W L, by columns (the backward sweep, tile (i, k)).  Formed transposed, D^T = L W^T, so that the sums arrive
-// in SC_RSUB_*'s layout.
-#define SC_ROW_PANEL_MFMA(acc, l, w, BY_COLUMNS)                                                                                                            \
+// in TILE_RSUB_*'s layout.
+#define TILE_ROW_PANEL_MFMA(acc, l, w, BY_COLUMNS)                                                                                                            \
     _Pragma("unroll") for (int kk = 0; kk < DC_NB / 4; ++kk) {                                                                                              \
         const double b = w[kk * 4 + lk];                                                                                                                 \
         _Pragma("unroll") for (int jb = 0; jb < DC_NB / DC_SUB; ++jb)                                                                                       \

@@ -1,5 +1,5 @@
 """GPU: the bits libpgo_sparse.so returns on the cases of tests/sparse_bits_cases.py against tests/golden/sparse_kernel_bits.json, which
-scripts/record_sparse_kernel_bits.py wrote from the library as it stood before its kernels' shared arithmetic was written once (csrc/pgo_sparse_tile_ops.hpp).  No
+scripts/record_sparse_kernel_bits.py wrote from the library as it stood before its kernels' shared arithmetic was written once (csrc/pgo_tile_ops.hpp, which the dense kernels of libpgo.so expand too).  No
 tolerance: the library has no atomics and every sum has a fixed order, so a change that is not meant to alter a number leaves every digest as it is."""
 import json
 import os
