@@ -11,7 +11,7 @@ LIBPGO = os.path.join(_HERE, "libpgo.so")
 LIBGEN = os.path.join(_HERE, "libpgo_graphgen.so")
 
 HIP_SOURCES = ["pgo_kernels.hip", "pgo_solver.hip", "pgo_graph.hip", "pgo_shard.hip", "pgo_measure.hip", "pgo_pcg.hip", "pgo_multigrid.hip", "pgo_comm.hip", "pgo_dense.hip"]
-HIP_HEADERS = ["pgo_handle.hpp", "pgo_internal.hpp", "pgo_lm.hpp", "pgo_mg_cycle.hpp", "pgo_device_math.hpp", "pgo_mg_kernels.hpp", "pgo_mg_host.hpp", "pgo_comm.hpp", "pgo_dense_math.hpp", "pgo_tile_ops.hpp"]
+HIP_HEADERS = ["pgo_handle.hpp", "pgo_internal.hpp", "pgo_lm.hpp", "pgo_mg_cycle.hpp", "pgo_device_math.hpp", "pgo_mg_kernels.hpp", "pgo_mg_host.hpp", "pgo_comm.hpp", "pgo_dense_math.hpp", "pgo_tile_ops.hpp", "pgo_pcg_ops.hpp"]
 
 
 def _stale(target, deps):

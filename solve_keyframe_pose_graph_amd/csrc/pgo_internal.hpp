@@ -220,7 +220,7 @@ struct CgDev {
 // update RIDES in two of the cycle's sparse-level launches, as `riders` extra workgroups behind the launch's own (cg_update's workgroup -> keyframe mapping and r.u slots):
 //   kind & 1  direction and solution  p = u + beta p, x += alpha p     (reads u in z: a launch BEFORE the one that carries kind & 2)
 //   kind & 2  block-Jacobi part       z = D^-1 r, partials of r.z      (a launch before the one that adds P_0 x_1 to z)
-// alpha and gamma are the head's (scal[9 + 2 parity], scal[8 + 2 parity]); beta = gamma / gamma_prev is formed again from the same two doubles.
+// alpha and gamma are the head's (scal[9 + 2 parity], scal[8 + 2 parity]); beta is formed again from the same two doubles by the head's own text (sr_beta, pgo_pcg_ops.hpp).
 struct UpdRiderDev {
     int32_t kind, riders, parity, first;      // kind 0: the launch carries nothing
     int64_t N;

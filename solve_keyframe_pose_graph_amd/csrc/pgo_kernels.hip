@@ -26,124 +26,11 @@ __device__ __forceinline__ int wave_in_grid() { return (int)(((int64_t)blockIdx.
 __device__ __forceinline__ int wave_in_block() { return (int)(threadIdx.x >> 6); }
 #endif
 
-// ------------------------------------------------------------------------------------------------
-// reductions (fixed-shape trees: results are bitwise reproducible run to run)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-    return v;
-}
-// This thread's share of a partial-sum array, p[threadIdx.x + k blockDim.x]: up to 12 entries per thread (2 048 partials on 192 lanes) REQUESTED TOGETHER — the loop form
-// `for (i = tid; i < n; i += blockDim) v += p[i]` has a run-time trip count, is not unrolled, and waits for every load before it issues the next: four to eleven dependent
-// round trips at the head of every PCG kernel, where the whole workgroup waits for alpha / beta (timeline build: 5 us of the matvec's 26).  Same summation order as the loop.
-#ifndef PGO_SERIAL_HEAD
-__device__ __forceinline__ double strided_share(const double* __restrict__ p, int n) {
-    constexpr int MAXK = 12;
-    double v[MAXK];
-#pragma unroll
-    for (int k = 0; k < MAXK; ++k) { const int i = (int)threadIdx.x + k * (int)blockDim.x; v[k] = i < n ? p[i] : 0.0; }
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < MAXK; ++k) s += v[k];
-    for (int i = (int)threadIdx.x + MAXK * (int)blockDim.x; i < n; i += blockDim.x) s += p[i];
-    return s;
-}
-#else      // A/B aid (variant build): the loop form
-__device__ __forceinline__ double strided_share(const double* __restrict__ p, int n) { double s = 0.0; for (int i = threadIdx.x; i < n; i += blockDim.x) s += p[i]; return s; }
-#endif
-// sum over the workgroup; valid in thread 0.  `buf` holds blockDim/64 doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double* buf) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) buf[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0) for (int i = 0; i < nw; ++i) s += buf[i];
-    return s;
-}
-// every thread gets sum(partials[0..n)); n <= a few thousand, read through L2
-__device__ __forceinline__ double block_total(const double* __restrict__ partials, int n, double* buf) {
-    double v = strided_share(partials, n);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) buf[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < nw; ++i) s += buf[i];
-    return s;
-}
+#include "pgo_pcg_ops.hpp"      // the reductions and what the PCG iteration's kernels share
 
 // 6x6 blocks of the BSR matrix and of the preconditioner are stored PAIR-MAJOR: element (r, c) lives at (c/2)*12 + r*2 + (c&1),
 // so the 6 lanes (rows) of one keyframe read consecutive 16-B words: every SpMV load is a contiguous 96-B run per keyframe.
 __device__ __forceinline__ int pm(int r, int c) { return (c >> 1) * 12 + r * 2 + (c & 1); }
-
-// two totals in one pass (one barrier pair instead of two): every PCG kernel starts by re-reducing two partial arrays
-__device__ __forceinline__ void block_total2(const double* __restrict__ pa, int na, const double* __restrict__ pb, int nb, double* buf /*2 x nwaves*/, double& sa, double& sb) {
-    double va = strided_share(pa, na), vb = strided_share(pb, nb);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    va = wave_sum(va); vb = wave_sum(vb);
-    __syncthreads();
-    if (lane == 0) { buf[wave] = va; buf[nw + wave] = vb; }
-    __syncthreads();
-    sa = 0.0; sb = 0.0;
-    for (int i = 0; i < nw; ++i) { sa += buf[i]; sb += buf[nw + i]; }
-}
-
-// three totals in one pass: the two-level method's matvec keeps the block-Jacobi part and the coarse part of r.z apart (below)
-__device__ __forceinline__ void block_total3(const double* __restrict__ pa, int na, const double* __restrict__ pb, int nb, const double* __restrict__ pc, int nc, double* buf /*3 x nwaves*/,
-                                             double& sa, double& sb, double& sc) {
-    double va = strided_share(pa, na), vb = strided_share(pb, nb), vc = strided_share(pc, nc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    va = wave_sum(va); vb = wave_sum(vb); vc = wave_sum(vc);
-    __syncthreads();
-    if (lane == 0) { buf[wave] = va; buf[nw + wave] = vb; buf[2 * nw + wave] = vc; }
-    __syncthreads();
-    sa = 0.0; sb = 0.0; sc = 0.0;
-    for (int i = 0; i < nw; ++i) { sa += buf[i]; sb += buf[nw + i]; sc += buf[2 * nw + i]; }
-}
-
-// The head of every PCG kernel: "has the PCG stopped?" and the re-reduction of two (three) partial-sum arrays.  Measured with the timeline build (scripts/dev/mf_timeline.py, C3):
-// as two steps — flag -> barrier -> partial sums -> barrier — the head took 5 us of the matvec's 26, two dependent round trips to cold L2s.  Here ONE lane requests the flag
-// BEFORE the partial sums are requested and hands it over through the reduction's own LDS buffer: one round trip, one barrier pair.  (The flag may be raised by workgroup 0 of
-// a matvec while other workgroups of the same launch are starting: one lane reads, LDS broadcasts, nobody diverges around a barrier.)  buf: 2 (3) x nwaves + 1 doubles.
-__device__ __forceinline__ bool block_total2_done(const int32_t* __restrict__ flags, const double* __restrict__ pa, int na, const double* __restrict__ pb, int nb, double* buf,
-                                                  double& sa, double& sb) {
-    int f = 0;
-    if (threadIdx.x == 0) f = flags[0];
-    double va = strided_share(pa, na), vb = strided_share(pb, nb);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    va = wave_sum(va); vb = wave_sum(vb);
-    __syncthreads();
-    if (lane == 0) { buf[wave] = va; buf[nw + wave] = vb; }
-    if (threadIdx.x == 0) buf[2 * nw] = (double)f;
-    __syncthreads();
-    sa = 0.0; sb = 0.0;
-    for (int i = 0; i < nw; ++i) { sa += buf[i]; sb += buf[nw + i]; }
-    return buf[2 * nw] != 0.0;
-}
-__device__ __forceinline__ bool block_total3_done(const int32_t* __restrict__ flags, const double* __restrict__ pa, int na, const double* __restrict__ pb, int nb, const double* __restrict__ pc, int nc,
-                                                  double* buf, double& sa, double& sb, double& sc) {
-    int f = 0;
-    if (threadIdx.x == 0) f = flags[0];
-    double va = strided_share(pa, na), vb = strided_share(pb, nb), vc = strided_share(pc, nc);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    va = wave_sum(va); vb = wave_sum(vb); vc = wave_sum(vc);
-    __syncthreads();
-    if (lane == 0) { buf[wave] = va; buf[nw + wave] = vb; buf[2 * nw + wave] = vc; }
-    if (threadIdx.x == 0) buf[3 * nw] = (double)f;
-    __syncthreads();
-    sa = 0.0; sb = 0.0; sc = 0.0;
-    for (int i = 0; i < nw; ++i) { sa += buf[i]; sb += buf[nw + i]; sc += buf[2 * nw + i]; }
-    return buf[3 * nw] != 0.0;
-}
 
 __device__ __forceinline__ size_t tile_elem(int doubles_per_edge, int64_t e, int k) {
     return (size_t)(e >> 6) * (size_t)(doubles_per_edge * TILE) + (size_t)(k >> 1) * (2 * TILE) + (size_t)(e & 63) * 2 + (k & 1);
@@ -742,8 +629,7 @@ __global__ __launch_bounds__(256) void build_rows_kernel(GraphDev G, LinDev L, S
 
 // Block-Jacobi preconditioner in FACTORED form: the lower Cholesky factor L of every (Schur-reduced, damped) 6x6 diagonal block, packed
 // (21 entries, diagonal stored as 1/L_ii) and rounded to fp32 — 96 B per keyframe instead of 288 B for an fp64 inverse.  M = L~ L~^T
-// is symmetric positive definite whatever the rounding did, so PCG stays valid; the arithmetic applying it is fp64.
-constexpr int LF_STRIDE = 24;   // floats per keyframe (21 used): 6 x 16-B loads
+// is symmetric positive definite whatever the rounding did, so PCG stays valid; the arithmetic applying it is fp64.  (LF_STRIDE floats per keyframe: pgo_pcg_ops.hpp)
 __device__ __forceinline__ int lf_idx(int i, int j) { return i * (i + 1) / 2 + j; }   // i >= j
 
 __global__ __launch_bounds__(256) void invert_rows_kernel(GraphDev G, CgDev C, int32_t* fail) {
@@ -861,8 +747,8 @@ void launch_invert_rows(const GraphDev& G, const CgDev& C, int32_t* fail_flag, h
 // One thread per (keyframe, row): 192-thread workgroups = 32 keyframes x 6 rows; blocks are pair-major so each load
 // instruction reads a contiguous 96-B run per keyframe.  Dot products: per-workgroup partials (grid capped at MAX_PARTIALS),
 // re-reduced in a fixed order by every workgroup of the consuming kernel -> no atomics, bitwise reproducible.
+// The heads, the vector update of a row pair and the staging of a trip's block-Jacobi factors: pgo_pcg_ops.hpp (CG_BLOCK = 192 there).
 // ------------------------------------------------------------------------------------------------
-constexpr int CG_BLOCK = 192;   // 32 keyframes x 6 lanes = 3 wavefronts
 
 // workgroup-uniform read of the convergence flag (it may be raised by workgroup 0 of cg_spmv while other workgroups of the
 // same launch are starting: one lane reads, LDS broadcasts, nobody diverges around a barrier)
@@ -920,14 +806,8 @@ __global__ __launch_bounds__(CG_BLOCK) void cg_spmv_kernel(GraphDev G, CgDev C, 
     if (first) { if (cg_done(C)) return; }
     else {
         double rz_new, rz_old;
-        if (block_total2_done(C.flags, C.part_rz + parity * RZ_STRIDE, nparts + C.extra_rz, C.part_rz + (parity ^ 1) * RZ_STRIDE, nparts + C.extra_rz, red, rz_new, rz_old)) return;
-        const bool breakdown = C.flags[1] != 0;
-        // convergence on the preconditioned residual norm: every workgroup evaluates the same numbers -> uniform exit
-        if (breakdown || !(rz_new > C.scal[3] * C.scal[0])) {
-            // (r.z clearly negative: the preconditioner is not positive definite — a breakdown, never convergence)
-            if (blockIdx.x == 0 && threadIdx.x == 0) { C.flags[0] = 1; if (!breakdown) { C.scal[1] = rz_new; if (!(rz_new >= -C.scal[3] * C.scal[0])) C.flags[1] = 1; } }
-            return;
-        }
+        if (block_totals<true>(C.flags, red, C.part_rz + parity * RZ_STRIDE, nparts + C.extra_rz, rz_new, C.part_rz + (parity ^ 1) * RZ_STRIDE, nparts + C.extra_rz, rz_old)) return;
+        if (pcg_stopped(C, rz_new, false)) return;
         beta = rz_new / rz_old;
         if (blockIdx.x == 0 && threadIdx.x == 0) C.scal[1] = rz_new;
     }
@@ -1043,57 +923,12 @@ __global__ void cg_scalars_init_kernel(CgDev C, int nparts, int nparts_bb, doubl
     }
 }
 
-// The head of the single-reduction (Chronopoulos-Gear) update on one GPU: delta = u.w (the matvec's partials) and gamma = r.u (the previous update's) are re-reduced
-// TOGETHER — the iteration's only reduction point — then the convergence test the classic form runs at the head of its matvec, beta = gamma / gamma_prev,
-// alpha = gamma / (delta - beta gamma / alpha_prev).  Scalars in C.scal[8 + 2 parity] (gamma), [9 + 2 parity] (alpha) of the iteration with that parity (as the multi-rank
-// kernel keeps them).  Returns false when the workgroup has nothing to do (stopped, converged, broken down).
-// split_coarse (the two-level method's fused iteration): the slots behind the update kernel's `nparts` hold the coarse part rc.Ac^-1 rc of r.u (coarse_solve_dot_kernel); a
-// convergence that the block-Jacobi part alone does not confirm is a breakdown of the fp32-rounded coarse inverse, never a converged step (the classic form runs the same
-// test at the head of its matvec: mf_spmv_kernel<true, true>); coarse_only: one aggregate per keyframe, u is the coarse term alone.  red: 3 x waves + 1 doubles then.
-__device__ __forceinline__ bool sr_head(const CgDev& C, int parity, int first, int nparts_pq, int nparts, double* red, double& alpha, double& beta, bool split_coarse = false, bool coarse_only = false) {
-    double delta, gamma;
-    bool coarse_negative = false;
-    if (split_coarse) {
-        double g_bj, g_c;
-        if (block_total3_done(C.flags, C.part_pq, nparts_pq, C.part_rz + parity * RZ_STRIDE, nparts, C.part_rz + parity * RZ_STRIDE + nparts, C.extra_rz, red, delta, g_bj, g_c)) return false;
-        gamma = g_bj + g_c;
-        coarse_negative = !coarse_only && !(gamma > C.scal[3] * C.scal[0]) && g_bj > C.scal[3] * C.scal[0];
-    } else if (block_total2_done(C.flags, C.part_pq, nparts_pq, C.part_rz + parity * RZ_STRIDE, nparts + C.extra_rz, red, delta, gamma)) return false;
-    const bool breakdown = C.flags[1] != 0;
-    if (breakdown || !(gamma > C.scal[3] * C.scal[0])) {      // converged (or broken down): the state stays that of the last completed update
-        if (blockIdx.x == 0 && threadIdx.x == 0) { C.flags[0] = 1; if (!breakdown) { C.scal[1] = gamma; if (coarse_negative || !(gamma >= -C.scal[3] * C.scal[0])) C.flags[1] = 1; } }
-        return false;
-    }
-    beta = 0.0;
-    double den = delta;
-    if (!first) {
-        const double gamma_prev = C.scal[8 + 2 * (parity ^ 1)], alpha_prev = C.scal[9 + 2 * (parity ^ 1)];
-        beta = gamma / gamma_prev;
-        den = delta - beta * gamma / alpha_prev;
-    }
-    if (!(den > 0.0)) {      // not positive definite along the direction (or NaN): x is left untouched
-        if (blockIdx.x == 0 && threadIdx.x == 0) { C.flags[1] = 1; C.flags[0] = 1; }
-        return false;
-    }
-    alpha = gamma / den;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { C.scal[8 + 2 * parity] = gamma; C.scal[9 + 2 * parity] = alpha; C.scal[1] = gamma; C.flags[2] += 1; }
-    return true;
-}
-
 // classic form (SR = false):   alpha = rz/pq ; x += alpha p ; r' = r - alpha q ; z = Minv r' ; partial r'.z -> part_rz[parity^1]
 // single-reduction form (SR):  p = u + beta p ; s = w + beta s ; x += alpha p ; r -= alpha s ; u = Minv r ; partial r.u -> part_rz[parity^1]     (u in C.z, w in C.q, s in C.p2, r in place)
 template <bool SR>
 __global__ __launch_bounds__(CG_BLOCK) void cg_update_kernel(GraphDev G, CgDev C, int parity, int nparts_pq, int nparts, int first) {
     __shared__ double red[2 * (CG_BLOCK / 64) + 1];
-    const double2* __restrict__ rin = reinterpret_cast<const double2*>(SR ? C.r : (parity ? C.r2 : C.r));
-    double2* __restrict__ rout = reinterpret_cast<double2*>(SR ? C.r : (parity ? C.r : C.r2));
-    const double2* __restrict__ pcur = reinterpret_cast<const double2*>(SR ? C.p : (parity ? C.p2 : C.p));
-    const double2* __restrict__ qv = reinterpret_cast<const double2*>(C.q);
-    double2* __restrict__ xv = reinterpret_cast<double2*>(C.x);
-    double2* __restrict__ zv = reinterpret_cast<double2*>(C.z);
-    double2* __restrict__ pout = reinterpret_cast<double2*>(C.p);      // (SR only)
-    double2* __restrict__ sv = reinterpret_cast<double2*>(C.p2);       // (SR only) s = A p
-    // one lane per (keyframe, ROW PAIR): every vector access is 16 B/lane (8-B accesses reach only ~0.6x of the streaming rate);
+    const UpdateViews<SR> V(C, parity);
     // a workgroup covers CG_BLOCK/3 = 64 keyframes per trip
     constexpr int KF = CG_BLOCK / 3;
     const int64_t pairs = G.N * 3;
@@ -1108,59 +943,33 @@ __global__ __launch_bounds__(CG_BLOCK) void cg_update_kernel(GraphDev G, CgDev C
         const int64_t i = base + threadIdx.x;
         r_ = make_double2(0.0, 0.0); q_ = r_; p_ = r_; x_ = r_; l0 = make_float4(0.f, 0.f, 0.f, 0.f); l1 = l0;
         if (SR) { u0 = r_; s0 = r_; }
-        if (i < pairs) { r_ = rin[i]; q_ = qv[i]; p_ = pcur[i]; x_ = xv[i]; if (SR) { u0 = zv[i]; s0 = sv[i]; } }
+        if (i < pairs) { r_ = V.rin[i]; q_ = V.qv[i]; p_ = V.pcur[i]; x_ = V.xv[i]; if (SR) { u0 = V.zv[i]; s0 = V.sv[i]; } }
         const int64_t first_node = base / 3;
-        const float4* lp = reinterpret_cast<const float4*>(C.Lf + (size_t)first_node * LF_STRIDE);
-        if (first_node + threadIdx.x / 6 < G.N) l0 = lp[threadIdx.x];
-        if (first_node + (threadIdx.x + CG_BLOCK) / 6 < G.N) l1 = lp[threadIdx.x + CG_BLOCK];
+        LF_TRIP_LOAD(C.Lf, first_node, G.N, threadIdx.x, l0, l1)
     };
     double2 r0, q0, p0, x0; float4 lf0, lf1;
     load_trip((int64_t)blockIdx.x * CG_BLOCK, r0, q0, p0, x0, lf0, lf1);
     double alpha = 0.0, beta = 0.0;
     // (after the first trip's loads are in flight: the flag's and the partial sums' round trip overlaps with theirs)
-    if (SR) { if (!sr_head(C, parity, first, nparts_pq, nparts, red, alpha, beta)) return; }
-    else {
-        double pq, rz;   // pq partials are produced by the matvec kernel (its own grid size)
-        if (block_total2_done(C.flags, C.part_pq, nparts_pq, C.part_rz + parity * RZ_STRIDE, nparts + C.extra_rz, red, pq, rz)) return;
-        if (!(pq > 0.0)) {   // breakdown: matrix not positive definite along p (or NaN); x is left untouched, the next spmv raises done
-            if (blockIdx.x == 0 && threadIdx.x == 0) C.flags[1] = 1;
-            if (threadIdx.x == 0) C.part_rz[(parity ^ 1) * RZ_STRIDE + blockIdx.x] = 0.0;
-            return;
-        }
-        alpha = rz / pq;
-    }
+    PCG_UPDATE_HEAD_OR_RETURN(SR, C, parity, first, nparts_pq, nparts, red, alpha, beta)
     __shared__ double2 rnew[CG_BLOCK];
     __shared__ __attribute__((aligned(16))) float lfs[KF * LF_STRIDE];
-    static_assert(KF * LF_STRIDE / 4 == 2 * CG_BLOCK, "two 16-B loads per lane stage a trip's factors");
     double acc = 0.0;
     for (int64_t it = 0; it < trips; ++it) {
         const int64_t base = it * stride + (int64_t)blockIdx.x * CG_BLOCK;
         const int64_t i = base + threadIdx.x;
         const bool live = i < pairs;
         double2 rr = make_double2(0.0, 0.0);
-        if (live) {
-            if (SR) {
-                p0.x = u0.x + beta * p0.x; p0.y = u0.y + beta * p0.y;
-                s0.x = q0.x + beta * s0.x; s0.y = q0.y + beta * s0.y;
-                rr = make_double2(r0.x - alpha * s0.x, r0.y - alpha * s0.y);
-                x0.x += alpha * p0.x; x0.y += alpha * p0.y;
-                pout[i] = p0; sv[i] = s0;
-            } else {
-                rr = make_double2(r0.x - alpha * q0.x, r0.y - alpha * q0.y);
-                x0.x += alpha * p0.x; x0.y += alpha * p0.y;
-            }
-            rout[i] = rr; xv[i] = x0;
-        }
+        if (live) PCG_UPDATE_PAIR(SR, false, V, i, alpha, beta, r0, q0, p0, x0, u0, s0, rr)
         reinterpret_cast<float4*>(lfs)[threadIdx.x] = lf0; reinterpret_cast<float4*>(lfs)[threadIdx.x + CG_BLOCK] = lf1;
         rnew[threadIdx.x] = rr;
         __syncthreads();
         if (it + 1 < trips) load_trip(base + stride, r0, q0, p0, x0, lf0, lf1);
         if (live) {
             const int j = (int)(i % 3);
-            const double2 z = lf_apply_pair(lfs + (threadIdx.x / 3) * LF_STRIDE, reinterpret_cast<const double*>(rnew + (threadIdx.x - j)), j);
-            zv[i] = z;
+            LF_TRIP_APPLY(lfs + (threadIdx.x / 3) * LF_STRIDE, reinterpret_cast<const double*>(rnew + (threadIdx.x - j)), j, rr, V.zv[i], rz)
             const double w = G.own ? G.own[i / 3] : 1.0;
-            acc += w * (rr.x * z.x + rr.y * z.y);
+            acc += w * rz;
         }
         if (it + 1 < trips) __syncthreads();      // the LDS buffers are rewritten by the next trip
     }
@@ -1194,7 +1003,7 @@ __global__ void cg_reduce2_live_kernel(CgDev C, const double* __restrict__ pa, i
     __shared__ double red[8];
     const bool stopped = C.flags[0] != 0;
     double a = 0.0, b = 0.0;
-    if (!stopped) block_total2(pa, na, pb, nb, red, a, b);
+    if (!stopped) block_totals<false>(nullptr, red, pa, na, a, pb, nb, b);
     if (threadIdx.x == 0) { out[0] = a; out[1] = b; }
 }
 // xq / sh_of / two (fused exchange): the summed rows of w for shared keyframes are read straight from the exchange buffer (sh_of[keyframe] = its position there, or -1)
@@ -1203,23 +1012,8 @@ __global__ __launch_bounds__(CG_BLOCK) void cgcg_update_kernel(GraphDev G, CgDev
                                                                const double* __restrict__ two = nullptr) {
     if (cg_done(C)) return;
     const double delta = two ? two[0] : C.scal[12], gamma = two ? two[1] : C.scal[13];
-    double beta = 0.0, den = delta;
-    const bool breakdown = C.flags[1] != 0;
-    if (breakdown || !(gamma > C.scal[3] * C.scal[0])) {   // converged (or broken down): the state stays that of the last completed update
-        if (blockIdx.x == 0 && threadIdx.x == 0) { C.flags[0] = 1; if (!breakdown) { C.scal[1] = gamma; if (!(gamma >= -C.scal[3] * C.scal[0])) C.flags[1] = 1; } }
-        return;
-    }
-    if (!first) {
-        const double gamma_prev = C.scal[8 + 2 * (parity ^ 1)], alpha_prev = C.scal[9 + 2 * (parity ^ 1)];
-        beta = gamma / gamma_prev;
-        den = delta - beta * gamma / alpha_prev;
-    }
-    if (!(den > 0.0)) {   // not positive definite along the direction (or NaN)
-        if (blockIdx.x == 0 && threadIdx.x == 0) { C.flags[1] = 1; C.flags[0] = 1; }
-        return;
-    }
-    const double alpha = gamma / den;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { C.scal[8 + 2 * parity] = gamma; C.scal[9 + 2 * parity] = alpha; C.scal[1] = gamma; C.flags[2] += 1; }
+    double alpha = 0.0, beta = 0.0;
+    if (!sr_scalars(C, parity, first, delta, gamma, false, alpha, beta)) return;
     __shared__ double red[CG_BLOCK / 64];
     constexpr int KF = CG_BLOCK / 3;
     __shared__ double2 rnew[CG_BLOCK];
@@ -1245,10 +1039,10 @@ __global__ __launch_bounds__(CG_BLOCK) void cgcg_update_kernel(GraphDev G, CgDev
             if (xq) { const int32_t pos = sh_of[i / 3]; if (pos >= 0) w = reinterpret_cast<const double2*>(xq)[(size_t)pos * 3 + (i % 3)]; }
             double2 pp = pv[i], ss = sv[i], xx = xv[i];
             rr = rv[i];
-            pp.x = u.x + beta * pp.x; pp.y = u.y + beta * pp.y;
-            ss.x = w.x + beta * ss.x; ss.y = w.y + beta * ss.y;
-            xx.x += alpha * pp.x; xx.y += alpha * pp.y;
-            rr.x -= alpha * ss.x; rr.y -= alpha * ss.y;
+            PAIR_XPBY(beta, u, pp)
+            PAIR_XPBY(beta, w, ss)
+            PAIR_AXPY(alpha, pp, xx)
+            PAIR_MINUS(rr, alpha, rr, ss)
             pv[i] = pp; sv[i] = ss; xv[i] = xx; rv[i] = rr;
         }
         __syncthreads();
@@ -1257,10 +1051,9 @@ __global__ __launch_bounds__(CG_BLOCK) void cgcg_update_kernel(GraphDev G, CgDev
         __syncthreads();
         if (live) {
             const int j = (int)(i % 3);
-            const double2 u = lf_apply_pair(lfs + (threadIdx.x / 3) * LF_STRIDE, reinterpret_cast<const double*>(rnew + (threadIdx.x - j)), j);
-            uv[i] = u;
+            LF_TRIP_APPLY(lfs + (threadIdx.x / 3) * LF_STRIDE, reinterpret_cast<const double*>(rnew + (threadIdx.x - j)), j, rr, uv[i], ru)
             const double wgt = G.own ? G.own[i / 3] : 1.0;
-            acc += wgt * (rr.x * u.x + rr.y * u.y);
+            acc += wgt * ru;
         }
     }
     const double sum = block_sum(acc, red);
@@ -1359,6 +1152,7 @@ __global__ __launch_bounds__(256) void mf_compact_kernel(GraphDev G, MfDev F, co
 }
 
 // component r of B_i y_a, the pending coarse correction of keyframe i (dtheta_i = dtheta_a ; dt_i = dt_a - 2 d_i x dtheta_a); 0 for fixed keyframes
+// (B_i y_a keeps a text of its own here, in mf_spmv_kernel's far gather, in coarse_prolong_kernel and in cg_update_restrict_kernel: pgo_pcg_ops.hpp says why)
 __device__ __forceinline__ double coarse_pending(const CoarseDev& K, const uint8_t* __restrict__ node_free, int64_t node, int r) {
     // every load is issued unconditionally (no load depends on another one's value): one round trip
     const double fr = node_free[node] ? 1.0 : 0.0;
@@ -1432,16 +1226,11 @@ __global__ __launch_bounds__(MF_BLOCK, PGO_MF_WAVES) void mf_spmv_kernel(GraphDe
                 // tolerance — or through zero — while the residual is still large.  So convergence that the block-Jacobi part alone does not confirm is a BREAKDOWN
                 // (lm_step then finishes the system with plain block-Jacobi from the current iterate), never a converged step.  K.m == 1: z is the coarse term alone.
                 double rz_bj, rz_c;
-                stopped = block_total3_done(C.flags, C.part_rz + parity * RZ_STRIDE, nparts, C.part_rz + parity * RZ_STRIDE + nparts, C.extra_rz, C.part_rz + (parity ^ 1) * RZ_STRIDE, nparts + C.extra_rz, red, rz_bj, rz_c, rz_old);
+                stopped = block_totals<true, 3>(C.flags, red, C.part_rz + parity * RZ_STRIDE, nparts, rz_bj, C.part_rz + parity * RZ_STRIDE + nparts, C.extra_rz, rz_c, C.part_rz + (parity ^ 1) * RZ_STRIDE, nparts + C.extra_rz, rz_old);
                 rz_new = rz_bj + rz_c;
                 coarse_negative = K.m != 1 && !(rz_new > C.scal[3] * C.scal[0]) && rz_bj > C.scal[3] * C.scal[0];
-            } else stopped = block_total2_done(C.flags, C.part_rz + parity * RZ_STRIDE, nparts + C.extra_rz, C.part_rz + (parity ^ 1) * RZ_STRIDE, nparts + C.extra_rz, red, rz_new, rz_old);
-            if (stopped) return;
-            const bool breakdown = C.flags[1] != 0;
-            if (breakdown || !(rz_new > C.scal[3] * C.scal[0])) {
-                if (blockIdx.x == 0 && threadIdx.x == 0) { C.flags[0] = 1; if (!breakdown) { C.scal[1] = rz_new; if (coarse_negative || !(rz_new >= -C.scal[3] * C.scal[0])) C.flags[1] = 1; } }
-                return;
-            }
+            } else stopped = block_totals<true>(C.flags, red, C.part_rz + parity * RZ_STRIDE, nparts + C.extra_rz, rz_new, C.part_rz + (parity ^ 1) * RZ_STRIDE, nparts + C.extra_rz, rz_old);
+            if (stopped || pcg_stopped(C, rz_new, coarse_negative)) return;
             beta = rz_new / rz_old;
             if (blockIdx.x == 0 && threadIdx.x == 0) C.scal[1] = rz_new;
         }
@@ -2288,14 +2077,7 @@ __global__ __launch_bounds__(CG_BLOCK) void coarse_prolong_kernel(GraphDev G, Co
 template <bool SR>
 __global__ __launch_bounds__(CG_BLOCK) void cg_update_restrict_kernel(GraphDev G, CgDev C, CoarseDev K, int parity, int nparts_pq, int nparts, int kft, int first, int pending) {
     __shared__ double red[3 * (CG_BLOCK / 64) + 1];
-    const double2* __restrict__ rin = reinterpret_cast<const double2*>(SR ? C.r : (parity ? C.r2 : C.r));
-    double2* __restrict__ rout = reinterpret_cast<double2*>(SR ? C.r : (parity ? C.r : C.r2));
-    const double2* __restrict__ pcur = reinterpret_cast<const double2*>(SR ? C.p : (parity ? C.p2 : C.p));
-    const double2* __restrict__ qv = reinterpret_cast<const double2*>(C.q);
-    double2* __restrict__ xv = reinterpret_cast<double2*>(C.x);
-    double2* __restrict__ zv = reinterpret_cast<double2*>(C.z);
-    double2* __restrict__ pout = reinterpret_cast<double2*>(C.p);      // (SR only)
-    double2* __restrict__ sv = reinterpret_cast<double2*>(C.p2);       // (SR only) s = A p
+    const UpdateViews<SR> V(C, parity);
     double2 u0 = make_double2(0.0, 0.0), s0 = u0;
     // the lane's row pair of the pending coarse correction P y: dtheta_i = dtheta_a ; dt_i = dt_a - 2 d_i x dtheta_a (0 for fixed keyframes)
     auto pending_pair = [&](int64_t node, int j, double e0, double e1, double e2, double free_) -> double2 {
@@ -2317,26 +2099,16 @@ __global__ __launch_bounds__(CG_BLOCK) void cg_update_restrict_kernel(GraphDev G
     double d0 = 0.0, d1 = 0.0, d2 = 0.0, fr = 0.0;      // the lane's keyframe: offset from its aggregate's centroid, free flag
     const bool direct = K.m == 1;
     auto load_u = [&](int64_t i, int64_t node, int j) {      // (SR) u = z_bj + P y (direct: the coarse term alone), s
-        u0 = zv[i]; s0 = sv[i];
+        u0 = V.zv[i]; s0 = V.sv[i];
         if (pending) { const double2 c = pending_pair(node, j, d0, d1, d2, fr); if (direct) u0 = c; else { u0.x += c.x; u0.y += c.y; } }
     };
     if (live_first) {
-        r0 = rin[i_first]; q0 = qv[i_first]; p0 = pcur[i_first]; x0 = xv[i_first];
+        r0 = V.rin[i_first]; q0 = V.qv[i_first]; p0 = V.pcur[i_first]; x0 = V.xv[i_first];
         const double* d = K.d + (size_t)kf_first * 3; d0 = d[0]; d1 = d[1]; d2 = d[2]; fr = G.node_free[kf_first] ? 1.0 : 0.0;
         if (SR) load_u(i_first, kf_first, t % 3);
     }
     double alpha = 0.0, beta = 0.0;
-    if (SR) { if (!sr_head(C, parity, first, nparts_pq, nparts, red, alpha, beta, true, direct)) return; }
-    else {
-        double pq, rz;
-        if (block_total2_done(C.flags, C.part_pq, nparts_pq, C.part_rz + parity * RZ_STRIDE, nparts + C.extra_rz, red, pq, rz)) return;
-        if (!(pq > 0.0)) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) C.flags[1] = 1;
-            if (threadIdx.x == 0) C.part_rz[(parity ^ 1) * RZ_STRIDE + blockIdx.x] = 0.0;
-            return;
-        }
-        alpha = rz / pq;
-    }
+    PCG_UPDATE_HEAD_OR_RETURN(SR, C, parity, first, nparts_pq, nparts, red, alpha, beta, true, direct)
     __shared__ double2 btr[CG_BLOCK];       // B_i^T r'_i, row pair j of keyframe t / 3 at [t]
     __shared__ double2 rnew[CG_BLOCK];
     __shared__ __attribute__((aligned(16))) float lfs[(CG_BLOCK / 3) * LF_STRIDE];
@@ -2348,21 +2120,11 @@ __global__ __launch_bounds__(CG_BLOCK) void cg_update_restrict_kernel(GraphDev G
         double2 rr = make_double2(0.0, 0.0);
         if (live) {
             if (g != (int64_t)blockIdx.x) {
-                r0 = rin[i]; q0 = qv[i]; p0 = pcur[i]; x0 = xv[i];
+                r0 = V.rin[i]; q0 = V.qv[i]; p0 = V.pcur[i]; x0 = V.xv[i];
                 const double* d = K.d + (size_t)(base + t / 3) * 3; d0 = d[0]; d1 = d[1]; d2 = d[2]; fr = G.node_free[base + t / 3] ? 1.0 : 0.0;
                 if (SR) load_u(i, base + t / 3, t % 3);
             }
-            if (SR) {
-                p0.x = u0.x + beta * p0.x; p0.y = u0.y + beta * p0.y;
-                s0.x = q0.x + beta * s0.x; s0.y = q0.y + beta * s0.y;
-                rr = make_double2(r0.x - alpha * s0.x, r0.y - alpha * s0.y);
-                x0.x += alpha * p0.x; x0.y += alpha * p0.y;
-                pout[i] = p0; sv[i] = s0;
-            } else {
-                rr = make_double2(r0.x - alpha * q0.x, r0.y - alpha * q0.y);
-                x0.x += alpha * p0.x; x0.y += alpha * p0.y;
-            }
-            rout[i] = rr; xv[i] = x0;
+            PCG_UPDATE_PAIR(SR, false, V, i, alpha, beta, r0, q0, p0, x0, u0, s0, rr)
         }
         __syncthreads();
         for (int f4 = t; f4 < kft * 6; f4 += CG_BLOCK) {
@@ -2374,9 +2136,8 @@ __global__ __launch_bounds__(CG_BLOCK) void cg_update_restrict_kernel(GraphDev G
         __syncthreads();
         if (live) {
             const int j = t % 3;
-            const double2 z = lf_apply_pair(lfs + (t / 3) * LF_STRIDE, reinterpret_cast<const double*>(rnew + (t - j)), j);
-            zv[i] = z;
-            if (!direct) acc += rr.x * z.x + rr.y * z.y;
+            LF_TRIP_APPLY(lfs + (t / 3) * LF_STRIDE, reinterpret_cast<const double*>(rnew + (t - j)), j, rr, V.zv[i], rz)
+            if (!direct) acc += rz;
         }
         // rc = P^T r' for the aggregates of this group: B_i^T r'_i = [r_theta + 2 d_i x r_t ; r_t] per keyframe (its three lanes, operands from LDS),
         // then a fixed-order sum over each aggregate's keyframes (deterministic)
@@ -2385,9 +2146,7 @@ __global__ __launch_bounds__(CG_BLOCK) void cg_update_restrict_kernel(GraphDev G
             if (live) {
                 const int j = t % 3;
                 const double* r6 = reinterpret_cast<const double*>(rnew + (t - j));
-                if (j == 0) b = make_double2(r6[0] + 2.0 * (d1 * r6[5] - d2 * r6[4]), r6[1] + 2.0 * (d2 * r6[3] - d0 * r6[5]));
-                else if (j == 1) b = make_double2(r6[2] + 2.0 * (d0 * r6[4] - d1 * r6[3]), r6[3]);
-                else b = make_double2(r6[4], r6[5]);
+                RIGID_RESTRICT_PAIR(b, r6, j, d0, d1, d2)
                 b.x *= fr; b.y *= fr;
             }
             btr[t] = b;

@@ -588,11 +588,11 @@ __global__ __launch_bounds__(CG_BLOCK) void mg_smooth_step_kernel(MgLevelDev A, 
     mg_smooth_step_tile(A, (int)blockIdx.x + A.tile0, in_r, in_x, out_w, add1, add2, out, cs, stop, xch, tb);
 }
 // ---- riders: the half of the split single-reduction update that nothing waits for until the level-1 up-sweep (UpdRiderDev, pgo_internal.hpp) ----
-// Rider workgroup `rb` of `U.riders` takes the keyframes workgroup rb of cg_update_mg_kernel takes.  The expressions are those of cg_update_mg_body, statement by statement.
+// Rider workgroup `rb` of `U.riders` takes the keyframes workgroup rb of cg_update_mg_kernel takes.  The statements are those cg_update_mg_body expands (pgo_pcg_ops.hpp: sr_beta,
+// PAIR_XPBY, PAIR_AXPY, LF_TRIP_LOAD, LF_TRIP_APPLY): one text, not two that have to be kept alike.
 __device__ __forceinline__ void upd_rider_direction(const UpdRiderDev& U, int rb) {
     const double alpha = U.scal[9 + 2 * U.parity], gamma = U.scal[8 + 2 * U.parity];
-    double beta = 0.0;
-    if (!U.first) { const double gamma_prev = U.scal[8 + 2 * (U.parity ^ 1)]; beta = gamma / gamma_prev; }
+    const double beta = sr_beta(U.scal, U.parity, U.first, gamma);
     const double2* __restrict__ zv = reinterpret_cast<const double2*>(U.z);
     double2* __restrict__ pout = reinterpret_cast<double2*>(U.p);
     double2* __restrict__ xv = reinterpret_cast<double2*>(U.x);
@@ -600,14 +600,13 @@ __device__ __forceinline__ void upd_rider_direction(const UpdRiderDev& U, int rb
     for (int64_t i = (int64_t)rb * CG_BLOCK + threadIdx.x; i < pairs; i += (int64_t)U.riders * CG_BLOCK) {
         const double2 u0 = zv[i];
         double2 p0 = pout[i], x0 = xv[i];
-        p0.x = u0.x + beta * p0.x; p0.y = u0.y + beta * p0.y;
-        x0.x += alpha * p0.x; x0.y += alpha * p0.y;
+        PAIR_XPBY(beta, u0, p0)
+        PAIR_AXPY(alpha, p0, x0)
         pout[i] = p0; xv[i] = x0;
     }
 }
 // lds: 2 CG_BLOCK doubles (the trip's residual) + CG_BLOCK / 3 x LF_STRIDE floats (its block-Jacobi factors), 16-B aligned: 9 KB of the host kernel's buffers; red: CG_BLOCK / 64 doubles
 __device__ __forceinline__ void upd_rider_jacobi(const UpdRiderDev& U, int rb, double* lds, double* red) {
-    constexpr int KF = CG_BLOCK / 3;
     double2* rnew = reinterpret_cast<double2*>(lds);
     float* lfs = reinterpret_cast<float*>(lds + 2 * CG_BLOCK);
     const double2* __restrict__ rin = reinterpret_cast<const double2*>(U.r);
@@ -625,24 +624,20 @@ __device__ __forceinline__ void upd_rider_jacobi(const UpdRiderDev& U, int rb, d
         float4 lf0 = make_float4(0.f, 0.f, 0.f, 0.f), lf1 = lf0;
         if (live) rr = rin[i];
         const int64_t first_node = base / 3;
-        const float4* lp = reinterpret_cast<const float4*>(U.Lf + (size_t)first_node * LF_STRIDE);
-        if (first_node + t / 6 < U.N) lf0 = lp[t];
-        if (first_node + (t + CG_BLOCK) / 6 < U.N) lf1 = lp[t + CG_BLOCK];
+        LF_TRIP_LOAD(U.Lf, first_node, U.N, t, lf0, lf1)
         reinterpret_cast<float4*>(lfs)[t] = lf0; reinterpret_cast<float4*>(lfs)[t + CG_BLOCK] = lf1;
         rnew[t] = rr;
         __syncthreads();
         if (live) {
             const int j = t % 3;
             const double* r6 = reinterpret_cast<const double*>(rnew + (t - j));
-            const double2 z = lf_apply_pair(lfs + (t / 3) * LF_STRIDE, r6, j);
-            zv[i] = z;
-            acc += rr.x * z.x + rr.y * z.y;
+            LF_TRIP_APPLY(lfs + (t / 3) * LF_STRIDE, r6, j, rr, zv[i], rz)
+            acc += rz;
         }
         if (it + 1 < trips) __syncthreads();      // the LDS buffers are rewritten by the next trip
     }
     const double s = block_sum(acc, red);
     if (threadIdx.x == 0) U.part_rz[rb] = s;
-    static_assert(KF * LF_STRIDE / 4 == 2 * CG_BLOCK, "two 16-B loads per lane stage a trip's factors");
 }
 // the workgroups of a level launch behind its own `own` tiles; true: this workgroup was a rider (it has nothing else to do)
 __device__ __forceinline__ bool upd_riders(const UpdRiderDev& U, int own, const int32_t* __restrict__ stop, double* lds, double* red) {
@@ -1244,22 +1239,15 @@ __global__ __launch_bounds__(CG_BLOCK) void mg_prolong0_kernel(GraphDev G, MgDev
 #define PGO_SR_MG_WAVES 3
 #endif
 // CRIT (single-reduction form only): the half of the update the cycle waits for — the head, s = w + beta s, r -= alpha s, r_1, x_1.  The other half (p, x, the block-Jacobi
-// part of the next u and the partials of r.u) rides in two of the cycle's sparse-level launches: upd_rider_direction / upd_rider_jacobi above evaluate the SAME source
-// expressions (-ffp-contract=on fuses inside one expression only), so every vector entry and every partial-sum slot holds the bits the unsplit kernel leaves.
+// part of the next u and the partials of r.u) rides in two of the cycle's sparse-level launches: upd_rider_direction / upd_rider_jacobi above expand the SAME statements
+// of pgo_pcg_ops.hpp (-ffp-contract=on fuses inside one expression only), so every vector entry and every partial-sum slot holds the bits the unsplit kernel leaves.
 template <bool SR, bool CRIT>
 __device__ __forceinline__ void cg_update_mg_body(GraphDev G, CgDev C, MgDev M, double* __restrict__ r1_out, double* __restrict__ x1_out, const double* __restrict__ Dinv1,
                                                   int parity, int nparts_pq, int nparts, int first) {
     static_assert(SR || !CRIT, "the split update exists in the single-reduction form only");
     static_assert(CG_BLOCK / 3 == MG_BLOCK0, "one workgroup trip of the vector update = one run of the slot table");
     __shared__ double red[2 * (CG_BLOCK / 64) + 1];
-    const double2* __restrict__ rin = reinterpret_cast<const double2*>(SR ? C.r : (parity ? C.r2 : C.r));
-    double2* __restrict__ rout = reinterpret_cast<double2*>(SR ? C.r : (parity ? C.r : C.r2));
-    const double2* __restrict__ pcur = reinterpret_cast<const double2*>(SR ? C.p : (parity ? C.p2 : C.p));
-    const double2* __restrict__ qv = reinterpret_cast<const double2*>(C.q);
-    double2* __restrict__ xv = reinterpret_cast<double2*>(C.x);
-    double2* __restrict__ zv = reinterpret_cast<double2*>(C.z);
-    double2* __restrict__ pout = reinterpret_cast<double2*>(C.p);      // (SR only)
-    double2* __restrict__ sv = reinterpret_cast<double2*>(C.p2);       // (SR only) s = A p
+    const UpdateViews<SR> V(C, parity);
     double2 u0 = make_double2(0.0, 0.0), s0 = u0;
     constexpr int KF = CG_BLOCK / 3;
     const int t = threadIdx.x;
@@ -1281,17 +1269,13 @@ __device__ __forceinline__ void cg_update_mg_body(GraphDev G, CgDev C, MgDev M, 
             tab1 = M.blk_tab[(size_t)run * MG_BLOCK0 + (t + CG_BLOCK) / 6];
         }
         if (i < pairs) {
-            r0 = rin[i]; q0 = qv[i];
-            if (!CRIT) { p0 = pcur[i]; x0 = xv[i]; }
-            if (SR) { if (!CRIT) u0 = zv[i]; s0 = sv[i]; }
+            r0 = V.rin[i]; q0 = V.qv[i];
+            if (!CRIT) { p0 = V.pcur[i]; x0 = V.xv[i]; }
+            if (SR) { if (!CRIT) u0 = V.zv[i]; s0 = V.sv[i]; }
             const double* d = M.d0 + (size_t)(i / 3) * 3; d0 = d[0]; d1 = d[1]; d2 = d[2];
         }
         const int64_t first_node = base / 3;
-        if (!CRIT) {
-            const float4* lp = reinterpret_cast<const float4*>(C.Lf + (size_t)first_node * LF_STRIDE);
-            if (first_node + t / 6 < G.N) lf0 = lp[t];
-            if (first_node + (t + CG_BLOCK) / 6 < G.N) lf1 = lp[t + CG_BLOCK];
-        }
+        if (!CRIT) LF_TRIP_LOAD(C.Lf, first_node, G.N, t, lf0, lf1)
 #pragma unroll
         for (int jj = 0; jj < 6; ++jj) { Dk0[jj] = 0.0; Dk1[jj] = 0.0; }
         if (x1_out) {
@@ -1301,22 +1285,11 @@ __device__ __forceinline__ void cg_update_mg_body(GraphDev G, CgDev C, MgDev M, 
     };
     load_trip((int64_t)blockIdx.x);
     double alpha = 0.0, beta = 0.0;
-    if (SR) { if (!sr_head(C, parity, first, nparts_pq, nparts, red, alpha, beta)) return; }
-    else {
-        double pq, rz;
-        if (block_total2_done(C.flags, C.part_pq, nparts_pq, C.part_rz + parity * RZ_STRIDE, nparts + C.extra_rz, red, pq, rz)) return;
-        if (!(pq > 0.0)) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) C.flags[1] = 1;
-            if (threadIdx.x == 0) C.part_rz[(parity ^ 1) * RZ_STRIDE + blockIdx.x] = 0.0;
-            return;
-        }
-        alpha = rz / pq;
-    }
+    PCG_UPDATE_HEAD_OR_RETURN(SR, C, parity, first, nparts_pq, nparts, red, alpha, beta)
     __shared__ double2 rnew[CG_BLOCK];
     __shared__ double2 btr[CG_BLOCK];
     __shared__ double rs[2 * CG_BLOCK];
     __shared__ __attribute__((aligned(16))) float lfs[KF * LF_STRIDE];
-    static_assert(KF * LF_STRIDE / 4 == 2 * CG_BLOCK, "two 16-B loads per lane stage a trip's factors");
     double acc = 0.0;
     for (int64_t it = 0; it < trips; ++it) {
         const int64_t run = it * gridDim.x + blockIdx.x;
@@ -1324,20 +1297,7 @@ __device__ __forceinline__ void cg_update_mg_body(GraphDev G, CgDev C, MgDev M, 
         const int64_t i = base + t;
         const bool live = i < pairs;
         double2 rr = make_double2(0.0, 0.0);
-        if (live) {
-            if (SR) {
-                if (!CRIT) { p0.x = u0.x + beta * p0.x; p0.y = u0.y + beta * p0.y; }
-                s0.x = q0.x + beta * s0.x; s0.y = q0.y + beta * s0.y;
-                rr = make_double2(r0.x - alpha * s0.x, r0.y - alpha * s0.y);
-                if (!CRIT) { x0.x += alpha * p0.x; x0.y += alpha * p0.y; pout[i] = p0; }
-                sv[i] = s0;
-            } else {
-                rr = make_double2(r0.x - alpha * q0.x, r0.y - alpha * q0.y);
-                x0.x += alpha * p0.x; x0.y += alpha * p0.y;
-            }
-            rout[i] = rr;
-            if (!CRIT) xv[i] = x0;
-        }
+        if (live) PCG_UPDATE_PAIR(SR, CRIT, V, i, alpha, beta, r0, q0, p0, x0, u0, s0, rr)
         if (!CRIT) { reinterpret_cast<float4*>(lfs)[t] = lf0; reinterpret_cast<float4*>(lfs)[t + CG_BLOCK] = lf1; }
         rnew[t] = rr;
         const double e0 = d0, e1 = d1, e2 = d2;
@@ -1347,14 +1307,11 @@ __device__ __forceinline__ void cg_update_mg_body(GraphDev G, CgDev C, MgDev M, 
             const int j = t % 3;
             const double* r6 = reinterpret_cast<const double*>(rnew + (t - j));
             double2 b;
-            if (j == 0) b = make_double2(r6[0] + 2.0 * (e1 * r6[5] - e2 * r6[4]), r6[1] + 2.0 * (e2 * r6[3] - e0 * r6[5]));
-            else if (j == 1) b = make_double2(r6[2] + 2.0 * (e0 * r6[4] - e1 * r6[3]), r6[3]);
-            else b = make_double2(r6[4], r6[5]);
+            RIGID_RESTRICT_PAIR(b, r6, j, e0, e1, e2)
             btr[t] = b;
             if (!CRIT && live) {
-                const double2 z = lf_apply_pair(lfs + (t / 3) * LF_STRIDE, r6, j);
-                zv[i] = z;
-                acc += rr.x * z.x + rr.y * z.y;
+                LF_TRIP_APPLY(lfs + (t / 3) * LF_STRIDE, r6, j, rr, V.zv[i], rz)
+                acc += rz;
             }
         }
         __syncthreads();

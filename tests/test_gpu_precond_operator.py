@@ -211,24 +211,7 @@ def test_multigrid_smoothed_keyframe_transition_is_symmetric_positive_definite(r
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 # the forms that actually run: x_k of a k-step PCG
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
-MG1 = dict(pc.MG_BASE, **pc.MG_CASES["one_sparse"][0])
-MG3 = dict(pc.MG_BASE, **pc.MG_CASES["three_levels"][0])
-FORMS = {
-    # label: (graph, options, preconditioner, single-reduction form expected, multigrid case)
-    "block-Jacobi single-reduction":    ("bj300", dict(coarse_aggregates=0), BJ, 1, None),
-    "block-Jacobi classic (tolerance)": ("bj300", dict(coarse_aggregates=0, cg_rel_tolerance=1e-12), BJ, 0, None),
-    "block-Jacobi classic (option)":    ("bj300", dict(coarse_aggregates=0, cg_single_reduction=0), BJ, 0, None),
-    "block-Jacobi block-CSR":           ("bj300", dict(coarse_aggregates=0, linear_solver=0), BJ, 0, None),
-    "two-level fused sr_coarse":        ("tl600", dict(coarse_aggregates=64), TL, 1, None),
-    "two-level fused classic_coarse":   ("tl600", dict(coarse_aggregates=64, cg_single_reduction=0), TL, 0, None),
-    "two-level unfused m=75":           ("tl600", dict(coarse_aggregates=8, coarse_min_radius=0.0), TL, 0, None),
-    "two-level unfused block-CSR":      ("tl600", dict(coarse_aggregates=64, linear_solver=0), TL, 0, None),
-    "multigrid restricted update":      ("mg640", MG1, MG, 1, "one_sparse"),
-    "multigrid restricted classic":     ("mg640", dict(MG1, cg_single_reduction=0), MG, 0, "one_sparse"),
-    "multigrid split update":           ("mg640", MG3, MG, 1, "three_levels"),      # two sparse levels: three launches can carry riders, choose_split takes two of them
-    "multigrid block-CSR":              ("mg640", dict(MG1, linear_solver=0), MG, 0, "one_sparse"),
-}
-KS = (1, 2, 3, 6)
+FORMS, KS = pc.FORMS, pc.KS      # (the table lives in tests/precond_cases.py: tests/pcg_bits_cases.py records the bits of the same forms)
 
 
 def reference_iterates(graph, opt, precond, mg_case, radius, handle_for_hierarchy, kmax):
