@@ -57,8 +57,9 @@ void* mgh_build_regroup(long long N, const unsigned char* node_free, long long E
 }
 // Smoothed transition keyframes -> level 1: the keyframe level's block pattern built as pgo_graph.hip's incident_lists builds it (row i: block (i, i), then one block per incident
 // edge — relative-pose edges first, in edge order —, parallel edges repeating a column), handed to build_hierarchy with level0_block as the solver does.
-void* mgh_build_fine(long long N, const unsigned char* node_free, long long Er, const int* rc1, const int* rc2, const double* rw, long long Es, const int* sc1, const int* sc2,
-                     int passes0, int passes, int dense_max, int tile_rows, int max_levels, int smoothed_levels, int level0_block) {
+// sw_w (null: every switch weight 1) and loop_discount: what pgo_multigrid.hip hands build_hierarchy beside the pattern — the aggregates are then the solver's
+void* mgh_build_fine_sw(long long N, const unsigned char* node_free, long long Er, const int* rc1, const int* rc2, const double* rw, long long Es, const int* sc1, const int* sc2,
+                        const double* sw_w, int passes0, int passes, int dense_max, int tile_rows, int max_levels, int smoothed_levels, double loop_discount, int level0_block) {
     std::vector<uint8_t> nf(node_free, node_free + N);
     std::vector<int32_t> a(rc1, rc1 + Er), b(rc2, rc2 + Er), c(sc1, sc1 + Es), d(sc2, sc2 + Es);
     std::vector<double> w(rw, rw + Er);
@@ -72,8 +73,12 @@ void* mgh_build_fine(long long N, const unsigned char* node_free, long long Er, 
     for (long long e = 0; e < Er; ++e) { col[fill[a[e]]++] = b[e]; col[fill[b[e]]++] = a[e]; }
     for (long long e = 0; e < Es; ++e) { col[fill[c[e]]++] = d[e]; col[fill[d[e]]++] = c[e]; }
     pgo_mg::Hierarchy* H = new pgo_mg::Hierarchy();
-    if (!pgo_mg::build_hierarchy(N, nf, a, b, w.data(), 1, c, d, nullptr, passes0, passes, dense_max, tile_rows, max_levels, *H, false, level0_block, nullptr, smoothed_levels, 0.0, nullptr, &rowptr, &col)) { delete H; return nullptr; }
+    if (!pgo_mg::build_hierarchy(N, nf, a, b, w.data(), 1, c, d, sw_w, passes0, passes, dense_max, tile_rows, max_levels, *H, false, level0_block, nullptr, smoothed_levels, loop_discount, nullptr, &rowptr, &col)) { delete H; return nullptr; }
     return H;
+}
+void* mgh_build_fine(long long N, const unsigned char* node_free, long long Er, const int* rc1, const int* rc2, const double* rw, long long Es, const int* sc1, const int* sc2,
+                     int passes0, int passes, int dense_max, int tile_rows, int max_levels, int smoothed_levels, int level0_block) {
+    return mgh_build_fine_sw(N, node_free, Er, rc1, rc2, rw, Es, sc1, sc2, nullptr, passes0, passes, dense_max, tile_rows, max_levels, smoothed_levels, 0.0, level0_block);
 }
 // (level -1 in the accessors below = the keyframe level F of a hierarchy built with the smoothed keyframe transition)
 static const pgo_mg::HostLevel& level_of(void* h, int l) { pgo_mg::Hierarchy* H = (pgo_mg::Hierarchy*)h; return l < 0 ? H->F : H->L[l]; }

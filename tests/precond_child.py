@@ -7,12 +7,13 @@ import sys
 import numpy as np
 
 
-def linear_iterate(graph, k, radius, constant=(), drop_last=0, handle=None, **opt):
-    """-> (x [6 N], pgo_iteration of the step, the handle).  One handle serves several k: cg_max_iterations is set per solve."""
+def linear_iterate(graph, k, radius, constant=(), drop_last=0, handle=None, regroup=None, **opt):
+    """-> (x [6 N], pgo_iteration of the step, the handle).  One handle serves several k: cg_max_iterations is set per solve.  regroup: the start values are
+    precond_cases.state(g, regroup) — a solve from "B" on a handle that last solved from "A" starts with a regroup."""
     from tests import precond_cases as pc
     from tests import util
     g = pc.graph(graph, drop_last)
-    q, t, s = pc.state(g)
+    q, t, s = pc.state(g, regroup)
     base = dict(cg_early_tolerance=0.0, cg_mid_tolerance=0.0, mg_switch_iterations=0, initial_trust_region_radius=radius, cg_max_iterations=k)
     base.update(opt)
     if handle is None:

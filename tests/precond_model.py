@@ -12,9 +12,11 @@ Everything is a dense matrix over the FREE keyframes (6 rows each, global keyfra
   multigrid   M^-1 = D^-1 + s P_0 V(P_0^T r), V = the V(1,1) cycle of csrc/pgo_mg_kernels.hpp's header comment over Galerkin levels, damped block-Jacobi
               (omega) on every sparse level, every coarse correction scaled by s (launch_mg_apply), the top level inverted densely; a smoothed transition:
               Ps = (I - c Dinv A) P with c = omega_p / omega, Dinv = omega D^-1, level above = Ps^T A Ps, applied implicitly or through the
-              explicit transfer operator R^T = Ps - Dinv A Ps
+              explicit transfer operator R^T = Ps - Dinv A Ps; the smoother's safety rescaling: a level whose estimate omega * lambda (power_estimate) exceeds 1.75 gets
+              its Dinv scaled to omega * lambda = 1.5 before anything above it is formed; the smoothed keyframe transition (smoothed_fine): Ps_0 = (I - omega_p D^-1 A) P_0,
+              level 1 = Ps_0^T A Ps_0, M^-1 = D^-1 + s Ps_0 V Ps_0^T
 
-fp32 mode: every object the device streams in fp32 — the level matrices inside the cycle, R^T, the dense inverse, the two-level Ac^-1, the packed block-Jacobi
+fp32 mode: every object the device streams in fp32 — the level matrices inside the cycle, R^T, Ps_0, the dense inverse, the two-level Ac^-1, the packed block-Jacobi
 Cholesky factors — is rounded with astype(np.float32) and accumulated in fp64.  `variant` switches in the deliberately wrong forms the CPU tests use to show that
 the GPU test's tolerance would catch them."""
 import numpy as np
@@ -183,11 +185,21 @@ def power_estimate(Dinv_unit, A, steps=8):
     return np.sqrt((v @ v) / (w @ w))
 
 
-def multigrid(lin, A, agg0, parents, fp32=False, omega=OMEGA, scale=1.0, omega_p=OMEGA_P, smoothed_levels=0, explicit=False, variant=None):
+def multigrid(lin, A, agg0, parents, fp32=False, omega=OMEGA, scale=1.0, omega_p=OMEGA_P, smoothed_levels=0, explicit=False, smoothed_fine=False, variant=None):
     """agg0 [N]: level-1 node of every keyframe (-1 outside the system); parents[l - 1] (l = 1 .. n_levels - 1): level-(l+1) node of every level-l node.
+    smoothed_fine: the transition keyframes -> level 1 is smoothed as well (launch_mg_assemble_fine): Ps_0 = P_0 - c (omega D^-1) A P_0 with D the diagonal
+    blocks of A itself (mg_dinv_kernel on the keyframe level: fp64, no power estimate, no rescaling), level 1 = Ps_0^T (A Ps_0), M^-1 = D^-1 + s Ps_0 V Ps_0^T; the cycle
+    streams Ps_0 as fp32 blocks, the same rounded numbers in both orientations (mg_ps_f32_kernel).
     -> dict(M, C = M - D^-1, V [the cycle as a matrix on level 1], A1 [level 1], levels, lam_max [exact lambda_max(D^-1 A) per sparse level], lam_est [the device's
-    estimate of it], limit_active [that estimate rescales some level's smoother])"""
+    estimate of it], rescaled [per sparse level: that estimate exceeds the limit], limit_active [any of them])
+    variant: the wrong devices of tests/test_precond_model.py.  Rescaling: no_rescale (the limit is never applied), rescale_every_level (the factor of the first level that
+    triggers on all sparse levels), ps_before_rescale (Ps, W and R^T of a smoothed transition from the unrescaled Dinv, the cycle with the rescaled one).  Smoothed keyframe
+    transition: fine_restrict_plain (restriction with P_0^T), fine_level1_plain (level 1 = P_0^T A P_0), fine_omega_p (omega in omega_p's place in Ps_0)."""
     v = variant or {}
+    if v.get("rescale_every_level") and "_factor_all" not in v:
+        base = multigrid(lin, A, agg0, parents, fp32, omega, scale, omega_p, smoothed_levels, explicit, smoothed_fine, {k: x for k, x in v.items() if k != "rescale_every_level"})
+        first = [omega * e for e, on in zip(base["lam_est"], base["rescaled"]) if on]
+        v = dict(v, _factor_all=SMOOTHER_TARGET / first[0] if first else 1.0)
     factor = v.get("factor", 2.0)
     idx, t = lin.idx, lin.t
     a0 = np.asarray(agg0)[idx]
@@ -197,10 +209,18 @@ def multigrid(lin, A, agg0, parents, fp32=False, omega=OMEGA, scale=1.0, omega_p
     P0 = prolongation(t[idx] - pos[a0], a0, n1, factor=factor)
     R0 = prolongation(t[idx] - pos[a0], a0, n1, factor=factor, cross=not v.get("restrict_no_cross")).T
     levels = []
-    Al = P0.T @ A @ P0
-    A1 = 0.5 * (Al + Al.T)
-    lam_max, lam_est, limit_active = [], [], False
     cs = omega_p / omega
+    T0 = P0                                                  # what the cycle prolongs to the keyframes with; R0: what it restricts with
+    if smoothed_fine:
+        Dinv0 = omega * block_diag(np.linalg.inv(diag_blocks(A)))
+        Ps0 = P0 - (1.0 if v.get("fine_omega_p") else cs) * Dinv0 @ (A @ P0)
+        Al = P0.T @ A @ P0 if v.get("fine_level1_plain") else Ps0.T @ (A @ Ps0)
+        T0 = f32(Ps0) if fp32 else Ps0
+        R0 = P0.T if v.get("fine_restrict_plain") else T0.T
+    else:
+        Al = P0.T @ A @ P0
+    A1 = 0.5 * (Al + Al.T)
+    lam_max, lam_est, rescaled = [], [], []
     for li, par in enumerate(parents):                       # sparse level li + 1
         par = np.asarray(par)
         n_next = int(par.max()) + 1
@@ -213,15 +233,18 @@ def multigrid(lin, A, agg0, parents, fp32=False, omega=OMEGA, scale=1.0, omega_p
         lam_max.append(float(np.linalg.eigvalsh(Dh @ Al @ Dh.T)[-1]))
         est = power_estimate(Dunit, Af)
         lam_est.append(float(est))
-        Dinv = omega * Dunit
-        if omega * est > SMOOTHER_LIMIT:
-            limit_active = True
+        Dinv = Dplain = omega * Dunit
+        rescaled.append(bool(omega * est > SMOOTHER_LIMIT))
+        if "_factor_all" in v:
+            Dinv = Dinv * v["_factor_all"]
+        elif rescaled[-1] and not v.get("no_rescale"):
             Dinv = Dinv * (SMOOTHER_TARGET / (omega * est))
         L = dict(A=Al, Af=Af, Dinv=Dinv, P=P, smoothed=li < smoothed_levels, explicit=explicit)
         if L["smoothed"]:
-            Ps = P - cs * Dinv @ (Al @ P)
+            Dps = Dplain if v.get("ps_before_rescale") else Dinv
+            Ps = P - cs * Dps @ (Al @ P)
             W = Al @ Ps
-            RT = Ps - Dinv @ W
+            RT = Ps - Dps @ W
             L.update(Ps=Ps, RTf=f32(RT) if fp32 else RT)
             A_next = Ps.T @ W
         else:
@@ -258,9 +281,9 @@ def multigrid(lin, A, agg0, parents, fp32=False, omega=OMEGA, scale=1.0, omega_p
         return y + post * (Dinv @ (r - Af @ y))
 
     V = cycle(0, np.eye(6 * n1))                             # the cycle is linear: applied to the identity of level 1
-    C = scale * (P0 @ V @ R0)
+    C = scale * (T0 @ V @ R0)
     M = block_jacobi(A, fp32) + C
-    return dict(M=M, C=C, V=V, A1=A1, levels=levels, lam_max=lam_max, lam_est=lam_est, limit_active=limit_active, n_levels=len(levels) + 1)
+    return dict(M=M, C=C, V=V, A1=A1, levels=levels, lam_max=lam_max, lam_est=lam_est, rescaled=rescaled, limit_active=any(rescaled), n_levels=len(levels) + 1)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------

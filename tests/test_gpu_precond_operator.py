@@ -10,6 +10,9 @@ dense inverses, packed block-Jacobi factors) costs IN THE MODEL; the device, whi
 8 e_ref + 1e-10, and 8 e_ref <= 1e-3 is asserted for every case so that the bound stays a bound.  Symmetry: exact transposes in fp32 with fp64 accumulation leave fp64 noise
 (~1e-13); one asymmetric fp32 rounding would show at 6e-8 or more: 1e-10 separates the two.
 
+The multigrid is also compared on the paths the library takes by default on real graphs (tests/precond_cases.py: MG_PATH_CASES, MG_REGROUP_CASES): a hierarchy one of whose
+levels gets the smoother's safety rescaling, the smoothed keyframe transition, and the hierarchy a handle installs when its next solve starts from other switch values (regroup).
+
 Every test prints its figures (`PRECOND ...`) before it asserts; profiles/precond_operator_check.txt records them.  PRECOND_REPORT_EIGENVALUES=1 in the environment adds the
 smallest eigenvalue of sym(M_dev) to the line (seconds per case: not part of the suite's run)."""
 import json
@@ -198,7 +201,7 @@ def test_multigrid_operator_with_constant_keyframes(radius):
 
 @pytest.mark.parametrize("radius", pc.RADII)
 def test_multigrid_smoothed_keyframe_transition_is_symmetric_positive_definite(radius):
-    """mg_smoothed_fine = 1: model-free properties only (the model does not cover the smoothed keyframe transition)"""
+    """mg_smoothed_fine = 1: model-free properties only (against the model: test_multigrid_smoothed_keyframe_transition_operator)"""
     lin = pc.linearisation("mg640")
     A, _ = pc.system("mg640", radius)
     P = open_solve("mg640", **dict(pc.MG_BASE, mg_smoothed_fine=1, mg_smoothed_levels=1, mg_dense_max_nodes=64))
@@ -206,6 +209,100 @@ def test_multigrid_smoothed_keyframe_transition_is_symmetric_positive_definite(r
     P.solve_end(); P.close()
     D = pm.block_jacobi(A)
     check_operator("multigrid smoothed keyframes", radius, M, lin, dict(M=D), dict(M=D), against_model=False)
+
+
+# ---- the paths the library takes by default on real graphs: the smoother's safety rescaling, the smoothed keyframe transition, a hierarchy after a regroup ----
+def mg_models_expecting(lin, A, agg0, parents, margs, rescaled):
+    """mg_models for the cases whose smoother limit IS active on some level: every sparse level of the DEVICE's hierarchy lies on the side of the limit the case names,
+    and clear of it by the same 0.01 — level by level, so the model and the device take the same branch on each"""
+    kw = pc.model_arguments(margs)
+    m64, m32 = pm.multigrid(lin, A, agg0, parents, **kw), pm.multigrid(lin, A, agg0, parents, fp32=True, **kw)
+    for m in (m64, m32):
+        assert m["rescaled"] == list(rescaled) and all(pc.limit_margin(dict(lam_est=[e])) >= 0.01 for e in m["lam_est"]), (m64["lam_est"], m32["lam_est"])
+    return m64, m32
+
+
+def path_operator(case, radius):
+    graph, opt, margs, n_levels, rescaled = pc.MG_PATH_CASES[case]
+    lin = pc.linearisation(graph)
+    A, _ = pc.system(graph, radius)
+    P = open_solve(graph, **dict(pc.MG_BASE, **opt))
+    M = dense_operator(P, MG, radius, lin)
+    agg0, parents = device_hierarchy(P)
+    P.solve_end(); P.close()
+    assert len(parents) + 1 == n_levels, [len(p) for p in parents]
+    assert np.array_equal(agg0 >= 0, lin.free)
+    m64, m32 = mg_models_expecting(lin, A, agg0, parents, margs, rescaled)
+    return lin, M, m64, m32
+
+
+@pytest.mark.parametrize("radius", pc.RADII)
+@pytest.mark.parametrize("case", ["rescaled_plain", "fine_rescaled"])
+def test_multigrid_rescaled_operator(case, radius):
+    """one sparse level's smoother is rescaled (mg_rescale_dinv_kernel) and the other's is not — rescaled_plain: level 2; fine_rescaled: level 1 = Ps_0^T A Ps_0, whose
+    unrescaled smoother would leave M^-1 indefinite, with the smoothed transition above it formed from the rescaled Dinv"""
+    lin, M, m64, m32 = path_operator(case, radius)
+    check_operator("multigrid " + case, radius, M, lin, m64, m32)
+
+
+@pytest.mark.parametrize("radius", pc.RADII)
+def test_multigrid_rescaled_smoothed_operator_implicit_and_explicit(radius):
+    """a smoothed transition below the rescaled level, both forms, against the model and against each other"""
+    lin, Mi, m64, m32i = path_operator("rescaled_smoothed_impl", radius)
+    _, Me, m64e, m32e = path_operator("rescaled_smoothed_expl", radius)
+    Mdi = check_operator("multigrid rescaled_smoothed_impl", radius, Mi, lin, m64, m32i)
+    Mde = check_operator("multigrid rescaled_smoothed_expl", radius, Me, lin, m64e, m32e)
+    norm = pm.maxnorm(m64["M"])
+    e_i, e_e = pm.maxnorm(m32i["M"] - m64["M"]) / norm, pm.maxnorm(m32e["M"] - m64e["M"]) / norm
+    diff = pm.maxnorm(Mdi - Mde) / norm
+    print("PRECOND rescaled implicit vs explicit  radius %.0e  |M_impl - M_expl| %.3e  (e_ref %.3e / %.3e)" % (radius, diff, e_i, e_e))
+    assert diff <= 8 * (e_i + e_e) + 1e-10
+
+
+@pytest.mark.parametrize("radius", pc.RADII)
+def test_multigrid_smoothed_keyframe_transition_operator(radius):
+    """mg_smoothed_fine = 1 against the model: Ps_0 = (I - w_p D^-1 A) P_0 in both orientations, level 1 = Ps_0^T A Ps_0"""
+    lin, M, m64, m32 = path_operator("fine640", radius)
+    check_operator("multigrid fine640", radius, M, lin, m64, m32)
+
+
+def same_hierarchy(a, b):
+    return np.array_equal(a[0], b[0]) and len(a[1]) == len(b[1]) and all(np.array_equal(x, y) for x, y in zip(a[1], b[1]))
+
+
+def entries_moved(a, b):
+    return [int((x != y).sum()) if len(x) == len(y) else -1 for x, y in zip([a[0]] + list(a[1]), [b[0]] + list(b[1]))]
+
+
+@pytest.mark.parametrize("radius", pc.RADII)
+@pytest.mark.parametrize("case", sorted(pc.MG_REGROUP_CASES))
+def test_multigrid_operator_after_a_regroup(case, radius):
+    """One handle opens a solve at state A, closes it and opens the next at state B (the outlier loop closures switched off): regroup_if_moved "for the new start" rebuilds
+    the hierarchy from the cache and installs it (regroup_commit, mg_install).  What is installed then is what a fresh handle installs at B, and the operators built on the
+    re-installed pools are those of the new aggregates: M_dev against the model built from the regrouped handle's own parents at B's linearisation."""
+    opt, margs, n_levels = pc.MG_REGROUP_CASES[case]
+    g = pc.graph("mg640")
+    opts = dict(pc.MG_BASE, **opt)
+    lin = pc.linearisation("mg640", regroup="B")
+    A, _ = pc.system("mg640", radius, regroup="B")
+    P = util.pgo_problem(g, True, **opts)
+    P.solve_begin(*pc.state(g))
+    at_a = device_hierarchy(P)
+    P.solve_end()
+    P.solve_begin(*pc.state(g, "B"))
+    regrouped = device_hierarchy(P)
+    M = dense_operator(P, MG, radius, lin)
+    P.solve_end(); P.close()
+    F = util.pgo_problem(g, True, **opts)
+    F.solve_begin(*pc.state(g, "B"))
+    fresh = device_hierarchy(F)
+    F.solve_end(); F.close()
+    print("PRECOND regroup %-24s radius %.0e  entries moved per level A -> B %s  regrouped vs fresh at B %s" % (case, radius, entries_moved(at_a, regrouped), entries_moved(regrouped, fresh)))
+    assert not same_hierarchy(at_a, regrouped)
+    assert same_hierarchy(regrouped, fresh)
+    assert len(regrouped[1]) + 1 == n_levels and np.array_equal(regrouped[0] >= 0, lin.free)
+    m64, m32 = mg_models_expecting(lin, A, regrouped[0], regrouped[1], margs, (False,) * (n_levels - 1))
+    check_operator("multigrid " + case, radius, M, lin, m64, m32)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -253,6 +350,33 @@ def test_iterates_of_the_forms_that_run(label, radius):
     P.close()
     for k in KS:
         check_iterate(label, radius, k, got[k][0], got[k][1], lin, x64, x32, precond, sr)
+
+
+@pytest.mark.parametrize("radius", pc.RADII)
+@pytest.mark.parametrize("label", sorted(pc.PATH_FORMS))
+def test_iterates_of_the_new_paths(label, radius):
+    """x_k of the form that runs by default (single reduction, explicit transfer) on a hierarchy with a rescaled level, and on a handle that regrouped at this solve's start"""
+    graph, opt, sr, case, regroup = pc.PATH_FORMS[label]
+    P, got = None, {}
+    if regroup:      # a solve from state A first: the first of the solves from B below then starts with the regroup, the later ones find the hierarchy already B's
+        _, _, P = linear_iterate(graph, 1, radius, regroup="A", **opt)
+        at_a = device_hierarchy(P)
+    for k in KS:
+        x, it, P = linear_iterate(graph, k, radius, handle=P, regroup="B" if regroup else None, **opt)
+        got[k] = (x, it)
+    agg0, parents = device_hierarchy(P)
+    P.close()
+    lin = pc.linearisation(graph, regroup="B" if regroup else None)
+    A, b = pc.system(graph, radius, regroup="B" if regroup else None)
+    if regroup:
+        assert not same_hierarchy(at_a, (agg0, parents))
+        margs, rescaled = pc.MG_REGROUP_CASES[case][1], (False,) * (pc.MG_REGROUP_CASES[case][2] - 1)
+    else:
+        margs, rescaled = pc.MG_PATH_CASES[case][2], pc.MG_PATH_CASES[case][4]
+    m64, m32 = mg_models_expecting(lin, A, agg0, parents, margs, rescaled)
+    x64, x32 = pm.pcg(A, b, m64["M"], max(KS)), pm.pcg(A, b, m32["M"], max(KS))
+    for k in KS:
+        check_iterate(label, radius, k, got[k][0], got[k][1], lin, x64, x32, MG, sr)
 
 
 def test_iterate_out_of_a_captured_chunk():
