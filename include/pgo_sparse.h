@@ -175,6 +175,56 @@ typedef struct pgo_sparse_lm_callbacks {
 int pgo_sparse_lm_solve(pgo_sparse_lm* lm, const pgo_sparse_lm_callbacks* callbacks, void* user, int64_t n_switch, const int32_t* swe_index, double* quat_xyzw, double* t, double* sw,
                         const pgo_options* options, pgo_summary* summary);
 
+/* ---- A pose graph that linearises itself: relative-pose, switchable and regulariser blocks with their own kernels in this library, so that the exact solve above needs no
+ * pgo_problem — and the one place where yaw/pitch/roll-weighted edges (the reference's FourDOFError and FourDOFErrorWithSwitchingConstraints, src/CeresResidues.h:252-422) run
+ * on the device.  It takes no pgo_problem and links no libpgo.so.  Conventions, residual order, internal edge order (relative-pose in add order, then switchable) and the tangent
+ * layout are include/pgo.h's; robust blocks follow Problem::Evaluate with apply_loss_function = true, as on a handle.
+ *
+ * Edge kinds.  ypr_gains = NULL, or an edge's three gains (0, 0, 0): a SixDOFError edge, r6 = w [dt ; 2 dq.vec].  Three gains > 0: a yaw/pitch/roll edge,
+ * r6 = w [dt ; g_y yaw ; g_p pitch ; g_r roll] in degrees (the reference's own gains: 4, 10, 10); pitch error +-90 degrees is the Euler singularity of the reference's functor and
+ * is not handled: the block turns non-finite.  A switchable edge ignores the weight and multiplies all seven rows by s, as the reference does: r = [s r6 ; s (1 - s)].
+ *
+ * One linearisation = pgo_sparse_graph_evaluate with a gradient: a block kernel (one thread per residual block), a one-workgroup cost reduction, a node kernel (one thread per
+ * keyframe over its incident list in list order: internal edge order, regularisers last).  A cost-only evaluation: the block kernel without Jacobians and the reduction.  No
+ * atomics, one writer per address, nothing waits on another workgroup, every address from the tables of _finalize: two calls give the same bits.  All arrays are host arrays.
+ *
+ * PGO_ERR_INVALID_ARG — nothing is added, nothing is launched, the text in pgo_sparse_last_error(NULL): a keyframe out of range, an edge from a keyframe to itself, gains that
+ * are neither all zero nor all > 0 and finite, an unknown loss, a loss_a that is not finite or <= 0 on a non-trivial loss, a switch index used twice, a non-finite measurement.
+ * PGO_ERR_STATE: blocks added after _finalize, an evaluation before it, _normal_blocks / _jacobian_blocks before an evaluation with a gradient. */
+typedef struct pgo_sparse_graph pgo_sparse_graph;
+
+int pgo_sparse_graph_create(int64_t n_nodes, int32_t device_id, pgo_sparse_graph** out);
+void pgo_sparse_graph_destroy(pgo_sparse_graph* g);
+/* c1_T_c2: n x 16 doubles (column-major Matrix4d); weight [n]; ypr_gains [3 n] (yaw, pitch, roll per edge) or NULL; loss: PGO_LOSS_*, loss_a its parameter */
+int pgo_sparse_graph_add_relpose_edges(pgo_sparse_graph* g, int64_t n, const int32_t* c1, const int32_t* c2, const double* c1_T_c2, const double* weight, const double* ypr_gains, int32_t loss,
+                                       double loss_a);
+int pgo_sparse_graph_add_switchable_edges(pgo_sparse_graph* g, int64_t n, const int32_t* c1, const int32_t* c2, const double* c1_T_c2, const int32_t* switch_idx, const double* ypr_gains,
+                                          int32_t loss, double loss_a);
+/* pgo_set_node_regularizers' contract: REPLACES the regulariser set */
+int pgo_sparse_graph_set_node_regularizers(pgo_sparse_graph* g, int64_t n, const int32_t* node, const double* target, const double* weight);
+/* cumulative */
+int pgo_sparse_graph_set_nodes_constant(pgo_sparse_graph* g, int64_t n, const int32_t* node);
+/* builds the tables (incident lists, free flags, the factor's pair list) and uploads them; allocates the arrays of one linearisation.  No launch. */
+int pgo_sparse_graph_finalize(pgo_sparse_graph* g);
+/* pgo_evaluate's contract and orders; n_switch: at least every switch index in use + 1.  The gradient of a constant keyframe is zero. */
+int pgo_sparse_graph_evaluate(pgo_sparse_graph* g, const double* quat_xyzw, const double* t, const double* sw, int64_t n_nodes, int64_t n_switch, double* cost, double* residuals, double* gradient);
+/* pgo_get_normal_blocks' contract and orders, of the last evaluation with a gradient; any pointer may be NULL.  diag and grad of a constant keyframe are zero; grad and sw_gs
+ * are the bits pgo_sparse_graph_evaluate returned as the gradient. */
+int pgo_sparse_graph_normal_blocks(pgo_sparse_graph* g, double* diag, double* grad, double* offdiag, double* sw_c, double* sw_hss, double* sw_gs);
+/* pgo_get_jacobian_blocks' contract, of the last evaluation with a gradient: kind 0 relative-pose, 1 switchable, 2 regulariser */
+int pgo_sparse_graph_jacobian_blocks(pgo_sparse_graph* g, int32_t kind, int64_t first, int64_t count, double* J1, double* J2, double* dr_ds);
+/* pgo_manifold_plus' contract */
+int pgo_sparse_graph_manifold_plus(pgo_sparse_graph* g, int64_t n, const double* quat_xyzw, const double* t, const double* delta, double* quat_out, double* t_out);
+/* the three calls above as the callbacks pgo_sparse_lm_solve takes; *user = g */
+int pgo_sparse_graph_lm_callbacks(pgo_sparse_graph* g, pgo_sparse_lm_callbacks* cb, void** user);
+/* What pgo_sparse_chol_create and pgo_sparse_lm_create need of a finalised graph; any pointer may be NULL (ask counts6 first).  counts6: n_nodes, n_rel, n_sw, n_pairs, the
+ * least n_switch, regularisers.  node_free [n_nodes]: 0 for a constant keyframe; in_system [n_nodes]: free and referenced by a block; the edges' endpoints in internal order and
+ * every switchable edge's switch index; the pairs of keyframes of the system that an edge joins, each once, pair_hi > pair_lo, sorted.  PGO_ERR_STATE before _finalize. */
+int pgo_sparse_graph_edge_lists(const pgo_sparse_graph* g, int64_t* counts6, uint8_t* node_free, uint8_t* in_system, int32_t* rel_c1, int32_t* rel_c2, int32_t* swe_c1, int32_t* swe_c2,
+                                int32_t* swe_index, int32_t* pair_hi, int32_t* pair_lo);
+/* HIP-event milliseconds of the last pgo_sparse_graph_evaluate: upload of the state, block kernel + cost reduction, node kernel, download.  No launch. */
+int pgo_sparse_graph_last_times(const pgo_sparse_graph* g, double* ms4);
+
 const char* pgo_sparse_strerror(int code);
 /* the text of the last error of this object; h = NULL: of the calling thread's last call that had no object (pgo_sparse_spd_solve, pgo_sparse_chol_create, ...) */
 const char* pgo_sparse_last_error(const pgo_sparse_chol* h);

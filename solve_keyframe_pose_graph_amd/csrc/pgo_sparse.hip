@@ -1,5 +1,5 @@
 // pgo_sparse.hip — libpgo_sparse.so (include/pgo_sparse.h): the tile-sparse exact Cholesky solver on the device, host side and C entry points.  The kernels are in
-// pgo_sparse_kernels.hpp (what they share: pgo_tile_ops.hpp); the exact LM step and solve on this factor (pgo_sparse_lm_*) in pgo_sparse_lm.hpp, included at the end of this file: one translation unit.
+// pgo_sparse_kernels.hpp (what they share: pgo_tile_ops.hpp); the exact LM step and solve on this factor (pgo_sparse_lm_*) in pgo_sparse_lm.hpp and the self-linearising graph (pgo_sparse_graph_*) in pgo_sparse_graph.hpp, both included at the end of this file: one translation unit.
 // This library neither links nor changes libpgo.so.
 //
 // The step order is sc_factor_steps / sc_solve_steps / sc_selinv_steps / sc_panel_steps (pgo_sparse_math.hpp), nowhere else: the structs ScLaunch, ScSelLaunch and
@@ -541,3 +541,6 @@ int pgo_sparse_reduce_normal_blocks(int64_t n_nodes, const uint8_t* node_free, c
 
 // the exact Levenberg-Marquardt step and solve on this factor (pgo_sparse_lm_*): kernels, object and entry points
 #include "pgo_sparse_lm.hpp"
+
+// a pose graph that linearises itself (pgo_sparse_graph_*): yaw/pitch/roll-weighted edges, and the exact LM solve without a pgo_problem handle
+#include "pgo_sparse_graph.hpp"

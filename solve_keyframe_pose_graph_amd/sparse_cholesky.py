@@ -5,7 +5,8 @@ The library is a companion of libpgo.so: it takes no Problem.  covariance() belo
 them, matrix-free ones too — and returns what Problem.covariance returns where that runs; covariance_all() returns every keyframe's marginal and every edge's joint
 covariance from one selected inverse of the factor (SparseCholesky.selected_inverse / selected_blocks); cross_covariance() returns the blocks of ANY keyframe pairs, in
 any number — those of keyframes that share no edge yet, outside the factor's pattern — from SparseCholesky.inverse_columns, and loop_candidate_gate() the chi-square gate
-of loop-closure candidates built on them.  solve_exact() is Problem.solve with every LM step exact, at any keyframe count: the Problem linearises and steps on the manifold
+of loop-closure candidates built on them.  Graph is a pose graph that linearises itself in this library (yaw/pitch/roll-weighted edges included), solve_graph() the
+exact solve on it without a Problem.  solve_exact() is Problem.solve with every LM step exact, at any keyframe count: the Problem linearises and steps on the manifold
 through its hooks (as callbacks), SparseLm solves every damped system on the factor's tiles, the decisions are csrc/pgo_lm.hpp's.  As capi: no CPU fallback, a missing
 library or device is an error."""
 import ctypes as C
@@ -76,6 +77,21 @@ def load(build=True):
     lib.pgo_sparse_lm_step.argtypes = [C.c_void_p] + [_dp] * 6 + [C.c_double] * 3 + [_dp] * 3
     lib.pgo_sparse_lm_last_times.argtypes = [C.c_void_p, _dp]
     lib.pgo_sparse_lm_solve.argtypes = [C.c_void_p, C.POINTER(LmCallbacks), C.c_void_p, C.c_int64, _ip, _dp, _dp, _dp, C.c_void_p, C.c_void_p]
+    lib.pgo_sparse_graph_create.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.pgo_sparse_graph_destroy.restype = None
+    lib.pgo_sparse_graph_destroy.argtypes = [C.c_void_p]
+    lib.pgo_sparse_graph_add_relpose_edges.argtypes = [C.c_void_p, C.c_int64, _ip, _ip, _dp, _dp, _dp, C.c_int32, C.c_double]
+    lib.pgo_sparse_graph_add_switchable_edges.argtypes = [C.c_void_p, C.c_int64, _ip, _ip, _dp, _ip, _dp, C.c_int32, C.c_double]
+    lib.pgo_sparse_graph_set_node_regularizers.argtypes = [C.c_void_p, C.c_int64, _ip, _dp, _dp]
+    lib.pgo_sparse_graph_set_nodes_constant.argtypes = [C.c_void_p, C.c_int64, _ip]
+    lib.pgo_sparse_graph_finalize.argtypes = [C.c_void_p]
+    lib.pgo_sparse_graph_evaluate.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int64, C.c_int64, _dp, _dp, _dp]
+    lib.pgo_sparse_graph_normal_blocks.argtypes = [C.c_void_p] + [_dp] * 6
+    lib.pgo_sparse_graph_jacobian_blocks.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, _dp, _dp, _dp]
+    lib.pgo_sparse_graph_manifold_plus.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp]
+    lib.pgo_sparse_graph_lm_callbacks.argtypes = [C.c_void_p, C.POINTER(LmCallbacks), C.POINTER(C.c_void_p)]
+    lib.pgo_sparse_graph_edge_lists.argtypes = [C.c_void_p, _lp, _bp, _bp] + [_ip] * 7
+    lib.pgo_sparse_graph_last_times.argtypes = [C.c_void_p, _dp]
     _lib = lib
     return lib
 
@@ -276,14 +292,14 @@ class SparseLm:
         _check(self.lib.pgo_sparse_lm_last_times(self.h, _p(ms, _dp)), self.F.h)
         return dict(zip(LM_TIMES, [float(v) for v in ms]))
 
-    def solve(self, callbacks, n_switch, swe_index, quat, t, sw, options):
-        """pgo_sparse_lm_solve -> (quat, t, sw, capi.Summary); callbacks: an LmCallbacks; options: a capi.Options"""
+    def solve(self, callbacks, n_switch, swe_index, quat, t, sw, options, user=None):
+        """pgo_sparse_lm_solve -> (quat, t, sw, capi.Summary); callbacks: an LmCallbacks; options: a capi.Options; user: what the callbacks get as their first argument"""
         from . import capi
         q, tt, s = capi.Problem._state(quat, t, sw)
         idx = _i(swe_index)
         assert idx.size == self.n_sw and s.size == n_switch and q.size == 4 * self.n_nodes
         summ = capi.Summary()
-        _check(self.lib.pgo_sparse_lm_solve(self.h, C.byref(callbacks), None, n_switch, _p(idx, _ip), _p(q, _dp), _p(tt, _dp), _p(s, _dp), C.cast(C.byref(options), C.c_void_p), C.cast(C.byref(summ), C.c_void_p)), self.F.h)
+        _check(self.lib.pgo_sparse_lm_solve(self.h, C.byref(callbacks), user, n_switch, _p(idx, _ip), _p(q, _dp), _p(tt, _dp), _p(s, _dp), C.cast(C.byref(options), C.c_void_p), C.cast(C.byref(summ), C.c_void_p)), self.F.h)
         return q, tt, s, summ
 
 
@@ -461,6 +477,190 @@ def solve_exact(P, edges, quat, t, sw, ordering=ORDER_AUTO, device_id=None, timi
         try:
             cb = handle_callbacks(P, hooks)
             out = L.solve(cb, S, edges.sw_idx, q, tt, s, o)
+            if timings is not None:
+                timings["info"] = F.info()[0]; timings.update(L.last_times())
+        finally:
+            L.close()
+    finally:
+        F.close()
+    return out
+
+
+GRAPH_TIMES = ("upload_ms", "blocks_ms", "nodes_ms", "download_ms")      # pgo_sparse_graph_last_times
+REFERENCE_YPR_GAINS = (4.0, 10.0, 10.0)                                   # the reference's FourDOFError, src/CeresResidues.h:303-305
+_LOSSES = {None: 0, "huber": 1, "cauchy": 2}                              # PGO_LOSS_*
+
+
+def _loss(loss):
+    """None / ("huber", a) / ("cauchy", a) -> (PGO_LOSS_*, a); an unknown name goes through as an unknown code"""
+    if loss is None:
+        return 0, 0.0
+    kind, a = loss
+    return _LOSSES.get(kind, 99) if not isinstance(kind, int) else kind, float(a)
+
+
+class Graph:
+    """pgo_sparse_graph: a pose graph that linearises itself on the GPU — relative-pose, switchable and regulariser blocks, SixDOFError or yaw/pitch/roll-weighted
+    (gains = three numbers > 0 per edge; the reference's are REFERENCE_YPR_GAINS), plain or robust — without a capi.Problem.  Add blocks, finalize(), then evaluate /
+    normal_blocks / jacobian_blocks / manifold_plus have the contracts and orders of capi.Problem's; solve_graph() runs the exact LM solve on it."""
+
+    def __init__(self, n_nodes, device_id=0):
+        self.lib = load()
+        self.h = C.c_void_p()
+        self.n_nodes, self.n_rel, self.n_sw, self.n_reg = int(n_nodes), 0, 0, 0
+        self.device_id = device_id
+        _check(self.lib.pgo_sparse_graph_create(self.n_nodes, device_id, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.pgo_sparse_graph_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _gains(gains, n):
+        if gains is None:
+            return None
+        return _d(np.broadcast_to(np.asarray(gains, dtype=np.float64).reshape(-1, 3), (n, 3)))
+
+    def add_relpose_edges(self, c1, c2, c1_T_c2, weight, gains=None, loss=None):
+        """gains: None (SixDOFError), three numbers for every edge, or (n, 3); loss: None, ("huber", a) or ("cauchy", a)"""
+        a, b, T, w = _i(c1), _i(c2), _d(c1_T_c2).reshape(-1, 16), _d(weight)
+        n = len(a)
+        assert b.shape == (n,) and T.shape == (n, 16) and w.shape == (n,)
+        g = self._gains(gains, n)
+        kind, la = _loss(loss)
+        _check(self.lib.pgo_sparse_graph_add_relpose_edges(self.h, n, _p(a, _ip), _p(b, _ip), _p(T, _dp), _p(w, _dp), None if g is None else _p(g, _dp), kind, la))
+        self.n_rel += n
+
+    def add_switchable_edges(self, c1, c2, c1_T_c2, switch_idx, gains=None, loss=None):
+        a, b, T, idx = _i(c1), _i(c2), _d(c1_T_c2).reshape(-1, 16), _i(switch_idx)
+        n = len(a)
+        assert b.shape == (n,) and T.shape == (n, 16) and idx.shape == (n,)
+        g = self._gains(gains, n)
+        kind, la = _loss(loss)
+        _check(self.lib.pgo_sparse_graph_add_switchable_edges(self.h, n, _p(a, _ip), _p(b, _ip), _p(T, _dp), _p(idx, _ip), None if g is None else _p(g, _dp), kind, la))
+        self.n_sw += n
+
+    def set_node_regularizers(self, node, target, weight):
+        """REPLACES the regulariser set"""
+        nd, T, w = _i(node), _d(target).reshape(-1, 16), _d(weight)
+        assert T.shape == (len(nd), 16) and w.shape == (len(nd),)
+        _check(self.lib.pgo_sparse_graph_set_node_regularizers(self.h, len(nd), _p(nd, _ip), _p(T, _dp), _p(w, _dp)))
+        self.n_reg = len(nd)
+
+    def set_nodes_constant(self, node):
+        nd = _i(node)
+        _check(self.lib.pgo_sparse_graph_set_nodes_constant(self.h, len(nd), _p(nd, _ip)))
+
+    def finalize(self):
+        """builds and uploads the tables; no launch"""
+        _check(self.lib.pgo_sparse_graph_finalize(self.h))
+
+    @classmethod
+    def from_pose_graph(cls, g, switchable, loop_gains=None, odom_gains=None, loop_loss=None, constant=(), device_id=0):
+        """capi.problem_from_graph(g, switchable, loop_loss=loop_loss) as a finalised Graph: odometry -> relative-pose edges (odom_gains), loop closures -> switchable
+        edges with switch e on loop e, or relative-pose edges (loop_gains, loop_loss), the regularisers, the constant keyframes"""
+        G = cls(g.n_poses, device_id)
+        try:
+            if g.n_odom:
+                G.add_relpose_edges(g.odom_c1, g.odom_c2, g.odom_T, g.odom_w, odom_gains)
+            if g.n_loops:
+                if switchable:
+                    G.add_switchable_edges(g.loop_c1, g.loop_c2, g.loop_T, np.arange(g.n_loops, dtype=np.int32), loop_gains, loop_loss)
+                else:
+                    G.add_relpose_edges(g.loop_c1, g.loop_c2, g.loop_T, g.loop_w, loop_gains, loop_loss)
+            if len(g.reg_node):
+                G.set_node_regularizers(g.reg_node, g.reg_T, g.reg_w)
+            if len(constant):
+                G.set_nodes_constant(constant)
+            G.finalize()
+        except Exception:
+            G.close()
+            raise
+        return G
+
+    def evaluate(self, quat, t, sw=None, want_residuals=True, want_gradient=True):
+        """capi.Problem.evaluate -> (cost, residuals or None, gradient or None)"""
+        from . import capi
+        q, tt, s = capi.Problem._state(quat, t, sw)
+        N, S = q.size // 4, s.size
+        cost = C.c_double(0)
+        res = np.zeros(6 * self.n_rel + 7 * self.n_sw + 6 * self.n_reg) if want_residuals else None
+        grad = np.zeros(6 * N + S) if want_gradient else None
+        _check(self.lib.pgo_sparse_graph_evaluate(self.h, _p(q, _dp), _p(tt, _dp), _p(s, _dp), N, S, C.byref(cost), None if res is None else res.ctypes.data_as(_dp),
+                                                  None if grad is None else grad.ctypes.data_as(_dp)))
+        return cost.value, res, grad
+
+    def normal_blocks(self):
+        """capi.Problem.normal_blocks of the last evaluation with a gradient -> (diag (N, 6, 6), grad (N, 6), offdiag (E, 6, 6), sw_c (n_sw, 12), sw_hss, sw_gs)"""
+        N, E = self.n_nodes, self.n_rel + self.n_sw
+        diag, grad, off = np.zeros((N, 6, 6)), np.zeros((N, 6)), np.zeros((E, 6, 6))
+        c, hss, gs = np.zeros((self.n_sw, 12)), np.zeros(self.n_sw), np.zeros(self.n_sw)
+        _check(self.lib.pgo_sparse_graph_normal_blocks(self.h, *[_p(a, _dp) for a in (diag, grad, off, c, hss, gs)]))
+        return diag, grad, off, c, hss, gs
+
+    def jacobian_blocks(self, kind, first=0, count=None):
+        """capi.Problem.jacobian_blocks: kind 0 relative-pose, 1 switchable, 2 regulariser -> (J1, J2, dr_ds)"""
+        n = [self.n_rel, self.n_sw, self.n_reg][kind] if 0 <= kind <= 2 else 0
+        count = n - first if count is None else count
+        J1, J2, ds = np.zeros((max(count, 0), 6, 6)), np.zeros((max(count, 0), 6, 6)), np.zeros((max(count, 0), 7))
+        _check(self.lib.pgo_sparse_graph_jacobian_blocks(self.h, kind, first, count, _p(J1, _dp), _p(J2, _dp), _p(ds, _dp)))
+        return J1, J2, ds
+
+    def manifold_plus(self, quat, t, delta):
+        q, tt, d = _d(quat).reshape(-1), _d(t).reshape(-1), _d(delta).reshape(-1)
+        n = q.size // 4
+        assert tt.size == 3 * n and d.size == 6 * n
+        qo, to = np.zeros(4 * n), np.zeros(3 * n)
+        _check(self.lib.pgo_sparse_graph_manifold_plus(self.h, n, _p(q, _dp), _p(tt, _dp), _p(d, _dp), _p(qo, _dp), _p(to, _dp)))
+        return qo.reshape(-1, 4), to.reshape(-1, 3)
+
+    def lm_callbacks(self):
+        """(LmCallbacks, user) for SparseLm.solve: this graph's evaluate, normal_blocks and manifold_plus, called from C without a Python frame in between"""
+        cb, user = LmCallbacks(), C.c_void_p()
+        _check(self.lib.pgo_sparse_graph_lm_callbacks(self.h, C.byref(cb), C.byref(user)))
+        return cb, user
+
+    def edge_lists(self):
+        """of a finalised graph: a dict of node_free, in_system, rel_c1, rel_c2, sw_c1, sw_c2, sw_idx, pair_hi, pair_lo and n_switch (the least the state must have)"""
+        cnt = np.zeros(6, np.int64)
+        _check(self.lib.pgo_sparse_graph_edge_lists(self.h, _p(cnt, _lp), None, None, *([None] * 7)))
+        N, n_rel, n_sw, n_pairs, n_switch, _ = [int(v) for v in cnt]
+        free, ins = np.zeros(N, np.uint8), np.zeros(N, np.uint8)
+        names = ("rel_c1", "rel_c2", "sw_c1", "sw_c2", "sw_idx", "pair_hi", "pair_lo")
+        arrays = [np.zeros(k, np.int32) for k in (n_rel, n_rel, n_sw, n_sw, n_sw, n_pairs, n_pairs)]
+        _check(self.lib.pgo_sparse_graph_edge_lists(self.h, None, _p(free, _bp), _p(ins, _bp), *[_p(a, _ip) for a in arrays]))
+        out = dict(zip(names, arrays))
+        out.update(node_free=free, in_system=ins, n_switch=n_switch)
+        return out
+
+    def last_times(self):
+        """HIP-event milliseconds of the last evaluate: upload of the state, block kernel + cost reduction, node kernel, download"""
+        ms = np.zeros(4)
+        _check(self.lib.pgo_sparse_graph_last_times(self.h, _p(ms, _dp)))
+        return dict(zip(GRAPH_TIMES, [float(v) for v in ms]))
+
+
+def solve_graph(G, quat, t, sw, ordering=ORDER_AUTO, timings=None, **options):
+    """solve_exact with a Graph's own linearisation in place of a handle's: Ceres' trust-region solve with every step exact, for graphs of any size and with
+    yaw/pitch/roll-weighted edges -> (quat, t, sw, capi.Summary); the inputs are not modified.  SparseCholesky and SparseLm are made from G's edge lists, on G's
+    device; options: fields of a default capi.Options (max_num_iterations, function_tolerance, ...)."""
+    from . import capi
+    q, tt, s = capi.Problem._state(quat, t, sw)
+    o = capi.default_options(**options)
+    e = G.edge_lists()
+    F = SparseCholesky(G.n_nodes, e["in_system"], e["pair_hi"], e["pair_lo"], ordering, G.device_id)
+    try:
+        L = SparseLm(F, e["node_free"], e["rel_c1"], e["rel_c2"], e["sw_c1"], e["sw_c2"])
+        try:
+            cb, user = G.lm_callbacks()
+            out = L.solve(cb, s.size, e["sw_idx"], q, tt, s, o, user=user)
             if timings is not None:
                 timings["info"] = F.info()[0]; timings.update(L.last_times())
         finally:
