@@ -225,6 +225,62 @@ int pgo_sparse_graph_edge_lists(const pgo_sparse_graph* g, int64_t* counts6, uin
 /* HIP-event milliseconds of the last pgo_sparse_graph_evaluate: upload of the state, block kernel + cost reduction, node kernel, download.  No launch. */
 int pgo_sparse_graph_last_times(const pgo_sparse_graph* g, double* ms4);
 
+/* ---- The reference's 4-DoF pose graph (__USE_YPR_REP, VINS-Fusion's): every keyframe a yaw angle in DEGREES and a translation, every odometry and loop edge a
+ * QinFourDOFWeightError (src/CeresResidues.h:426-546) with the pitch and roll of its first keyframe as constants, AngleLocalParameterization on the yaw.  It linearises itself
+ * with its own kernels, as pgo_sparse_graph does, and is solved by pgo_sparse_lm_solve as it stands: the graph lives in the six-row slots of the exact LM step.
+ *
+ * Edge (i, j) with the record (t_meas[3], rel_yaw, pitch_i, roll_i, w), R_i = Rz(psi_i) Ry(pitch_i) Rx(roll_i), N the reference's NormalizeAngle (ONE conditional fold by 360:
+ * 180 stays 180, 400 becomes 40, 800 becomes 440):
+ *   r[0..2] = w (R_i^T (t_j - t_i) - t_meas)        r[3] = w N(psi_j - psi_i - rel_yaw) / 10
+ * Jacobians J1 (keyframe i), J2 (keyframe j): 4 x 4 row-major, columns [psi, t(3)], analytic.  The reference fixes w = 1.  No robust loss, no switch, no regulariser: the
+ * reference's 4-DoF path has none.
+ *
+ * The embedding.  Ambient state: quat[4 i] = psi_i, quat[4 i + 1 .. 4 i + 3] exactly 0 (every call here keeps them 0; a state that has them otherwise is
+ * PGO_ERR_INVALID_ARG), t[3 i ..] the translation — so the controller's x_norm, step norm and projected-gradient norm are Ceres' for the parameter blocks (yaw 1, t 3).
+ * Tangent: delta[6 i] = dpsi, delta[6 i + 1] = delta[6 i + 2] = 0 (pad), delta[6 i + 3 .. 5] = dt.  Plus: psi+ = N(psi + dpsi), slots 1 - 3 copied, t+ = t + dt.
+ * Normal blocks in pgo_get_normal_blocks' layout and orders: diag [n_nodes][36], grad [n_nodes][6], offdiag [n_edges][36] = J1^T J2 per edge in add order.  Pad rows and
+ * columns are exactly 0 with ONE exception: on a keyframe of the system (free and referenced by an edge) diag[i][1][1] = diag[i][2][2] = 1.0 exactly — identity rows of the
+ * kind the factor keeps for keyframes outside the system.  They keep the undamped matrix positive definite (pgo_sparse_chol_factor and the covariance calls work on it), make
+ * dpsi_pad = 0 exactly in every step (zero right-hand side, zero coupling) and add nothing to model_cost_change.  grad pad entries are exactly 0; a constant keyframe gets all
+ * zeros.  Cost of the embedding: the factor works on 6 n_nodes rows where a native layout would have 4 n_nodes.
+ *
+ * One linearisation = pgo_sparse_yaw_graph_evaluate with a gradient: a block kernel (one thread per edge), the one-workgroup cost reduction, a node kernel (one thread per
+ * keyframe over its incident list in list order: edge sides in add order).  Cost-only: the block kernel without Jacobians (the same residual bits) and the reduction.  No
+ * atomics, one writer per address, nothing waits on another workgroup, every address from the tables of _finalize: two calls give the same bits.  All arrays are host arrays.
+ *
+ * PGO_ERR_INVALID_ARG — nothing is added, nothing is launched, the text in pgo_sparse_last_error(NULL): a keyframe out of range, an edge from a keyframe to itself, a
+ * non-finite number in a record, a weight that is not finite or <= 0.  PGO_ERR_STATE: edges added after _finalize, an evaluation before it, _normal_blocks /
+ * _jacobian_blocks before an evaluation with a gradient.  Several edges on one pair, in either direction, a keyframe with no edge, and a graph with no free keyframe in an
+ * edge (evaluation works; the solve has an empty system) are all allowed. */
+typedef struct pgo_sparse_yaw_graph pgo_sparse_yaw_graph;
+
+int pgo_sparse_yaw_graph_create(int64_t n_nodes, int32_t device_id, pgo_sparse_yaw_graph** out);
+void pgo_sparse_yaw_graph_destroy(pgo_sparse_yaw_graph* g);
+/* c1: keyframe i (whose pitch and roll the record holds), c2: keyframe j; t_meas [3 n]; rel_yaw, pitch_i, roll_i [n] in degrees; weight [n], NULL: 1 */
+int pgo_sparse_yaw_graph_add_edges(pgo_sparse_yaw_graph* g, int64_t n, const int32_t* c1, const int32_t* c2, const double* t_meas, const double* rel_yaw, const double* pitch_i,
+                                   const double* roll_i, const double* weight);
+/* cumulative */
+int pgo_sparse_yaw_graph_set_nodes_constant(pgo_sparse_yaw_graph* g, int64_t n, const int32_t* node);
+/* builds the tables (incident lists, free flags, the factor's pair list) and uploads them; allocates the arrays of one linearisation.  No launch. */
+int pgo_sparse_yaw_graph_finalize(pgo_sparse_yaw_graph* g);
+/* quat [4 n_nodes], t [3 n_nodes]: the ambient state above; residuals [4 n_edges] in add order, gradient [6 n_nodes] in the tangent layout above; cost, residuals, gradient
+ * may be NULL */
+int pgo_sparse_yaw_graph_evaluate(pgo_sparse_yaw_graph* g, const double* quat, const double* t, int64_t n_nodes, double* cost, double* residuals, double* gradient);
+/* of the last evaluation with a gradient; any pointer may be NULL.  grad is the bits pgo_sparse_yaw_graph_evaluate returned as the gradient. */
+int pgo_sparse_yaw_graph_normal_blocks(pgo_sparse_yaw_graph* g, double* diag, double* grad, double* offdiag);
+/* J1, J2 [count][16] of edges first .. first + count - 1, of the last evaluation with a gradient */
+int pgo_sparse_yaw_graph_jacobian_blocks(pgo_sparse_yaw_graph* g, int64_t first, int64_t count, double* J1, double* J2);
+/* Plus on n keyframes; t and t_out may be NULL */
+int pgo_sparse_yaw_graph_manifold_plus(pgo_sparse_yaw_graph* g, int64_t n, const double* quat, const double* t, const double* delta, double* quat_out, double* t_out);
+/* the three calls above as the callbacks pgo_sparse_lm_solve takes (sw = NULL, n_switch = 0; the adapters ignore the sw_* pointers); *user = g */
+int pgo_sparse_yaw_graph_lm_callbacks(pgo_sparse_yaw_graph* g, pgo_sparse_lm_callbacks* cb, void** user);
+/* What pgo_sparse_chol_create and pgo_sparse_lm_create need of a finalised graph; any pointer may be NULL (ask counts3 first).  counts3: n_nodes, n_edges, n_pairs.
+ * node_free [n_nodes]: 0 for a constant keyframe; in_system [n_nodes]: free and referenced by an edge; c1, c2 [n_edges] in add order (pgo_sparse_lm_create's relative-pose
+ * edges; it has no switchable ones); the pairs of keyframes of the system that an edge joins, each once, pair_hi > pair_lo, sorted.  PGO_ERR_STATE before _finalize. */
+int pgo_sparse_yaw_graph_edge_lists(const pgo_sparse_yaw_graph* g, int64_t* counts3, uint8_t* node_free, uint8_t* in_system, int32_t* c1, int32_t* c2, int32_t* pair_hi, int32_t* pair_lo);
+/* HIP-event milliseconds of the last pgo_sparse_yaw_graph_evaluate: upload of the state, block kernel + cost reduction, node kernel, download.  No launch. */
+int pgo_sparse_yaw_graph_last_times(const pgo_sparse_yaw_graph* g, double* ms4);
+
 const char* pgo_sparse_strerror(int code);
 /* the text of the last error of this object; h = NULL: of the calling thread's last call that had no object (pgo_sparse_spd_solve, pgo_sparse_chol_create, ...) */
 const char* pgo_sparse_last_error(const pgo_sparse_chol* h);

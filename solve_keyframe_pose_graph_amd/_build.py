@@ -89,7 +89,7 @@ def build_libpgo(force=False, verbose=False):
 
 LIBSPARSE = os.path.join(_HERE, "libpgo_sparse.so")
 SPARSE_SOURCE = "pgo_sparse.hip"
-SPARSE_HEADERS = ["pgo_sparse_kernels.hpp", "pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_math.hpp", "pgo_sparse_lm.hpp", "pgo_sparse_lm_math.hpp", "pgo_sparse_graph.hpp", "pgo_sparse_graph_math.hpp"]
+SPARSE_HEADERS = ["pgo_sparse_kernels.hpp", "pgo_sparse_blocks.hpp", "pgo_sparse_math.hpp", "pgo_dense_math.hpp", "pgo_sparse_lm.hpp", "pgo_sparse_lm_math.hpp", "pgo_sparse_graph.hpp", "pgo_sparse_graph_math.hpp", "pgo_sparse_yaw.hpp", "pgo_sparse_yaw_math.hpp"]
 # headers of libpgo.so that the companion includes unchanged (the LM controller: one copy of Ceres' rules; the fp64 MFMA tile bodies: one copy of the operand maps and
 # the summation order; the closed forms of the cost functors); they belong to HIP_HEADERS, here they are only dependencies
 SPARSE_SHARED_HEADERS = ["pgo_lm.hpp", "pgo_tile_ops.hpp", "pgo_device_math.hpp"]
@@ -100,7 +100,10 @@ SPARSE_EXPORTS = ["pgo_sparse_spd_solve", "pgo_sparse_chol_create", "pgo_sparse_
                   "pgo_sparse_lm_create", "pgo_sparse_lm_destroy", "pgo_sparse_lm_set_scale", "pgo_sparse_lm_step", "pgo_sparse_lm_last_times", "pgo_sparse_lm_solve",
                   "pgo_sparse_graph_create", "pgo_sparse_graph_destroy", "pgo_sparse_graph_add_relpose_edges", "pgo_sparse_graph_add_switchable_edges", "pgo_sparse_graph_set_node_regularizers",
                   "pgo_sparse_graph_set_nodes_constant", "pgo_sparse_graph_finalize", "pgo_sparse_graph_evaluate", "pgo_sparse_graph_normal_blocks", "pgo_sparse_graph_jacobian_blocks",
-                  "pgo_sparse_graph_manifold_plus", "pgo_sparse_graph_lm_callbacks", "pgo_sparse_graph_edge_lists", "pgo_sparse_graph_last_times"]
+                  "pgo_sparse_graph_manifold_plus", "pgo_sparse_graph_lm_callbacks", "pgo_sparse_graph_edge_lists", "pgo_sparse_graph_last_times",
+                  "pgo_sparse_yaw_graph_create", "pgo_sparse_yaw_graph_destroy", "pgo_sparse_yaw_graph_add_edges", "pgo_sparse_yaw_graph_set_nodes_constant", "pgo_sparse_yaw_graph_finalize",
+                  "pgo_sparse_yaw_graph_evaluate", "pgo_sparse_yaw_graph_normal_blocks", "pgo_sparse_yaw_graph_jacobian_blocks", "pgo_sparse_yaw_graph_manifold_plus",
+                  "pgo_sparse_yaw_graph_lm_callbacks", "pgo_sparse_yaw_graph_edge_lists", "pgo_sparse_yaw_graph_last_times"]
 
 
 def compile_libpgo_sparse(target, verbose=False, obj_dir=None):

@@ -1,5 +1,5 @@
 // pgo_sparse.hip — libpgo_sparse.so (include/pgo_sparse.h): the tile-sparse exact Cholesky solver on the device, host side and C entry points.  The kernels are in
-// pgo_sparse_kernels.hpp (what they share: pgo_tile_ops.hpp); the exact LM step and solve on this factor (pgo_sparse_lm_*) in pgo_sparse_lm.hpp and the self-linearising graph (pgo_sparse_graph_*) in pgo_sparse_graph.hpp, both included at the end of this file: one translation unit.
+// pgo_sparse_kernels.hpp (what they share: pgo_tile_ops.hpp); the exact LM step and solve on this factor (pgo_sparse_lm_*) in pgo_sparse_lm.hpp, the self-linearising graph (pgo_sparse_graph_*) in pgo_sparse_graph.hpp and the 4-DoF graph (pgo_sparse_yaw_graph_*) in pgo_sparse_yaw.hpp, all three included at the end of this file: one translation unit.
 // This library neither links nor changes libpgo.so.
 //
 // The step order is sc_factor_steps / sc_solve_steps / sc_selinv_steps / sc_panel_steps (pgo_sparse_math.hpp), nowhere else: the structs ScLaunch, ScSelLaunch and
@@ -544,3 +544,6 @@ int pgo_sparse_reduce_normal_blocks(int64_t n_nodes, const uint8_t* node_free, c
 
 // a pose graph that linearises itself (pgo_sparse_graph_*): yaw/pitch/roll-weighted edges, and the exact LM solve without a pgo_problem handle
 #include "pgo_sparse_graph.hpp"
+
+// the reference's 4-DoF pose graph (pgo_sparse_yaw_graph_*): yaw + translation per keyframe, QinFourDOFWeightError edges, in the six-row slots of the exact LM step
+#include "pgo_sparse_yaw.hpp"

@@ -6,7 +6,7 @@ them, matrix-free ones too — and returns what Problem.covariance returns where
 covariance from one selected inverse of the factor (SparseCholesky.selected_inverse / selected_blocks); cross_covariance() returns the blocks of ANY keyframe pairs, in
 any number — those of keyframes that share no edge yet, outside the factor's pattern — from SparseCholesky.inverse_columns, and loop_candidate_gate() the chi-square gate
 of loop-closure candidates built on them.  Graph is a pose graph that linearises itself in this library (yaw/pitch/roll-weighted edges included), solve_graph() the
-exact solve on it without a Problem.  solve_exact() is Problem.solve with every LM step exact, at any keyframe count: the Problem linearises and steps on the manifold
+exact solve on it without a Problem; YawGraph and solve_yaw_graph() are the same for the reference's 4-DoF (yaw + translation) formulation.  solve_exact() is Problem.solve with every LM step exact, at any keyframe count: the Problem linearises and steps on the manifold
 through its hooks (as callbacks), SparseLm solves every damped system on the factor's tiles, the decisions are csrc/pgo_lm.hpp's.  As capi: no CPU fallback, a missing
 library or device is an error."""
 import ctypes as C
@@ -92,6 +92,19 @@ def load(build=True):
     lib.pgo_sparse_graph_lm_callbacks.argtypes = [C.c_void_p, C.POINTER(LmCallbacks), C.POINTER(C.c_void_p)]
     lib.pgo_sparse_graph_edge_lists.argtypes = [C.c_void_p, _lp, _bp, _bp] + [_ip] * 7
     lib.pgo_sparse_graph_last_times.argtypes = [C.c_void_p, _dp]
+    lib.pgo_sparse_yaw_graph_create.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.pgo_sparse_yaw_graph_destroy.restype = None
+    lib.pgo_sparse_yaw_graph_destroy.argtypes = [C.c_void_p]
+    lib.pgo_sparse_yaw_graph_add_edges.argtypes = [C.c_void_p, C.c_int64, _ip, _ip, _dp, _dp, _dp, _dp, _dp]
+    lib.pgo_sparse_yaw_graph_set_nodes_constant.argtypes = [C.c_void_p, C.c_int64, _ip]
+    lib.pgo_sparse_yaw_graph_finalize.argtypes = [C.c_void_p]
+    lib.pgo_sparse_yaw_graph_evaluate.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, _dp, _dp, _dp]
+    lib.pgo_sparse_yaw_graph_normal_blocks.argtypes = [C.c_void_p] + [_dp] * 3
+    lib.pgo_sparse_yaw_graph_jacobian_blocks.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp]
+    lib.pgo_sparse_yaw_graph_manifold_plus.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _dp]
+    lib.pgo_sparse_yaw_graph_lm_callbacks.argtypes = [C.c_void_p, C.POINTER(LmCallbacks), C.POINTER(C.c_void_p)]
+    lib.pgo_sparse_yaw_graph_edge_lists.argtypes = [C.c_void_p, _lp, _bp, _bp] + [_ip] * 4
+    lib.pgo_sparse_yaw_graph_last_times.argtypes = [C.c_void_p, _dp]
     _lib = lib
     return lib
 
@@ -668,6 +681,208 @@ def solve_graph(G, quat, t, sw, ordering=ORDER_AUTO, timings=None, **options):
     finally:
         F.close()
     return out
+
+
+def r2ypr(R):
+    """the reference's R2ypr (src/utils/PoseManipUtils.cpp:143-158): yaw, pitch, roll of a rotation matrix, in degrees; R (..., 3, 3)"""
+    R = np.asarray(R, dtype=np.float64)
+    n, o, a = R[..., :, 0], R[..., :, 1], R[..., :, 2]
+    y = np.arctan2(n[..., 1], n[..., 0])
+    p = np.arctan2(-n[..., 2], n[..., 0] * np.cos(y) + n[..., 1] * np.sin(y))
+    r = np.arctan2(a[..., 0] * np.sin(y) - a[..., 1] * np.cos(y), -o[..., 0] * np.sin(y) + o[..., 1] * np.cos(y))
+    return np.stack([y, p, r], axis=-1) / np.pi * 180.0
+
+
+def ypr2R(yaw, pitch, roll):
+    """the reference's YawPitchRollToRotationMatrix (src/CeresResidues.h:458-476): Rz(yaw) Ry(pitch) Rx(roll), degrees -> (..., 3, 3)"""
+    y, p, r = [np.asarray(x, dtype=np.float64) / 180.0 * np.pi for x in (yaw, pitch, roll)]
+    cy, sy, cp, sp, cr, sr = np.cos(y), np.sin(y), np.cos(p), np.sin(p), np.cos(r), np.sin(r)
+    rows = [[cy * cp, -sy * cr + cy * sp * sr, sy * sr + cy * sp * cr], [sy * cp, cy * cr + sy * sp * sr, -cy * sr + sy * sp * cr], [-sp, cp * sr, cp * cr]]
+    return np.stack([np.stack(np.broadcast_arrays(*row), axis=-1) for row in rows], axis=-2)
+
+
+def _quat_to_rot(q):
+    x, y, z, w = np.moveaxis(np.asarray(q, dtype=np.float64), -1, 0)
+    rows = [[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+            [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]
+    return np.stack([np.stack(row, axis=-1) for row in rows], axis=-2)
+
+
+def yaw_state_to_poses(yaw, t, pitch, roll):
+    """the 4-DoF state with every keyframe's constant pitch and roll (degrees) -> w_T_c (N, 4, 4)"""
+    yaw, t = _d(yaw).reshape(-1), _d(t).reshape(-1, 3)
+    T = np.tile(np.eye(4), (len(yaw), 1, 1))
+    T[:, :3, :3] = ypr2R(yaw, _d(pitch).reshape(-1), _d(roll).reshape(-1))
+    T[:, :3, 3] = t
+    return T
+
+
+def yaw_problem_from_pose_graph(g):
+    """the arrays of YawGraph.from_pose_graph (see there), without a device: a dict of c1, c2, t_meas, rel_yaw, pitch_i, roll_i per edge (odometry, then loops) and
+    yaw, t, pitch, roll per keyframe"""
+    ypr = r2ypr(_quat_to_rot(g.init_q))
+    c1 = np.concatenate([_i(g.odom_c1), _i(g.loop_c1)])
+    c2 = np.concatenate([_i(g.odom_c2), _i(g.loop_c2)])
+    T = np.concatenate([_d(g.odom_T).reshape(-1, 16), _d(g.loop_T).reshape(-1, 16)]).reshape(-1, 4, 4).transpose(0, 2, 1)      # column-major 16 -> (E, 4, 4)
+    return dict(c1=c1, c2=c2, t_meas=_d(T[:, :3, 3]), rel_yaw=r2ypr(T[:, :3, :3])[:, 0].copy(), pitch_i=ypr[c1, 1].copy(), roll_i=ypr[c1, 2].copy(),
+                yaw=ypr[:, 0].copy(), t=_d(g.init_t).reshape(-1, 3).copy(), pitch=ypr[:, 1].copy(), roll=ypr[:, 2].copy())
+
+
+class YawGraph:
+    """pgo_sparse_yaw_graph: the reference's 4-DoF pose graph (__USE_YPR_REP) that linearises itself on the GPU — every keyframe a yaw in DEGREES and a translation, every
+    edge a QinFourDOFWeightError with the pitch and roll of its first keyframe as constants.  Add edges, finalize(), then evaluate / normal_blocks / jacobian_blocks /
+    manifold_plus; solve_yaw_graph() runs the exact LM solve on it.  The state travels as (yaw (N,), t (N, 3)); the library's ambient layout (yaw in slot 0 of a
+    keyframe's four quat slots, the others 0) and the tangent layout (N, 6) = [dyaw, 0, 0, dt] are include/pgo_sparse.h's."""
+
+    def __init__(self, n_nodes, device_id=0):
+        self.lib = load()
+        self.h = C.c_void_p()
+        self.n_nodes, self.n_edges = int(n_nodes), 0
+        self.device_id = device_id
+        _check(self.lib.pgo_sparse_yaw_graph_create(self.n_nodes, device_id, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.pgo_sparse_yaw_graph_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_edges(self, c1, c2, t_meas, rel_yaw, pitch_i, roll_i, weight=None):
+        """edge k from keyframe c1[k] (whose pitch and roll the record holds) to c2[k]; angles in degrees; weight None: 1, the reference's"""
+        a, b, tm, ry, pi, ri = _i(c1), _i(c2), _d(t_meas).reshape(-1, 3), _d(rel_yaw), _d(pitch_i), _d(roll_i)
+        n = len(a)
+        w = None if weight is None else _d(weight)
+        assert b.shape == (n,) and tm.shape == (n, 3) and ry.shape == (n,) and pi.shape == (n,) and ri.shape == (n,) and (w is None or w.shape == (n,))
+        _check(self.lib.pgo_sparse_yaw_graph_add_edges(self.h, n, _p(a, _ip), _p(b, _ip), _p(tm, _dp), _p(ry, _dp), _p(pi, _dp), _p(ri, _dp), None if w is None else _p(w, _dp)))
+        self.n_edges += n
+
+    def set_nodes_constant(self, node):
+        nd = _i(node)
+        _check(self.lib.pgo_sparse_yaw_graph_set_nodes_constant(self.h, len(nd), _p(nd, _ip)))
+
+    def finalize(self):
+        """builds and uploads the tables; no launch"""
+        _check(self.lib.pgo_sparse_yaw_graph_finalize(self.h))
+
+    @classmethod
+    def from_pose_graph(cls, g, constant=(0,), device_id=0):
+        """The reference's 4-DoF problem of a graphgen.PoseGraph and its odometry poses (g.init_q, g.init_t) as a finalised YawGraph -> (G, yaw, t, pitch, roll): the
+        start and every keyframe's constant pitch and roll, in degrees.  For every odometry and loop edge (c1, c2, c1_T_c2): t_meas = c1_T_c2[:3, 3], rel_yaw =
+        R2ypr(c1_T_c2.R)[0], pitch_i, roll_i = R2ypr(w_T_c1.R)[1:] of the odometry pose of the edge's FIRST keyframe (src/PoseGraphSLAM.cpp:1608-1626).  The reference's
+        loop-edge line (src/PoseGraphSLAM.cpp:1542) takes pitch and roll from the edge's other keyframe; this helper follows the functor's own definition (R_i is the
+        rotation of the keyframe whose yaw and translation come first) and VINS-Fusion's.  Every weight is 1; constant: the keyframes held fixed (the gauge)."""
+        p = yaw_problem_from_pose_graph(g)
+        G = cls(g.n_poses, device_id)
+        try:
+            if len(p["c1"]):
+                G.add_edges(p["c1"], p["c2"], p["t_meas"], p["rel_yaw"], p["pitch_i"], p["roll_i"])
+            if len(constant):
+                G.set_nodes_constant(constant)
+            G.finalize()
+        except Exception:
+            G.close()
+            raise
+        return G, p["yaw"], p["t"], p["pitch"], p["roll"]
+
+    @staticmethod
+    def pack(yaw):
+        """yaw (N,) -> the ambient quat array (N, 4): the yaw in slot 0, the others 0"""
+        y = _d(yaw).reshape(-1)
+        q = np.zeros((len(y), 4))
+        q[:, 0] = y
+        return q
+
+    def evaluate(self, yaw, t, want_residuals=True, want_gradient=True):
+        """-> (cost, residuals (4 E,) or None, gradient (6 N,) or None)"""
+        q, tt = self.pack(yaw), _d(t).reshape(-1)
+        N = len(q)
+        assert tt.size == 3 * N
+        cost = C.c_double(0)
+        res = np.zeros(4 * self.n_edges) if want_residuals else None
+        grad = np.zeros(6 * N) if want_gradient else None
+        _check(self.lib.pgo_sparse_yaw_graph_evaluate(self.h, _p(q, _dp), _p(tt, _dp), N, C.byref(cost), None if res is None else res.ctypes.data_as(_dp),
+                                                      None if grad is None else grad.ctypes.data_as(_dp)))
+        return cost.value, res, grad
+
+    def normal_blocks(self):
+        """of the last evaluation with a gradient -> (diag (N, 6, 6), grad (N, 6), offdiag (E, 6, 6)); the pad rows and columns as include/pgo_sparse.h says"""
+        diag, grad, off = np.zeros((self.n_nodes, 6, 6)), np.zeros((self.n_nodes, 6)), np.zeros((self.n_edges, 6, 6))
+        _check(self.lib.pgo_sparse_yaw_graph_normal_blocks(self.h, *[_p(a, _dp) for a in (diag, grad, off)]))
+        return diag, grad, off
+
+    def jacobian_blocks(self, first=0, count=None):
+        """-> (J1, J2) (count, 4, 4): rows r[0..3], columns [yaw, t] of the edge's first / second keyframe"""
+        count = self.n_edges - first if count is None else count
+        J1, J2 = np.zeros((max(count, 0), 4, 4)), np.zeros((max(count, 0), 4, 4))
+        _check(self.lib.pgo_sparse_yaw_graph_jacobian_blocks(self.h, first, count, _p(J1, _dp), _p(J2, _dp)))
+        return J1, J2
+
+    def manifold_plus(self, yaw, t, delta):
+        """delta (N, 6) = [dyaw, 0, 0, dt]; t None: the yaw alone -> (yaw, t or None)"""
+        q, d = self.pack(yaw), _d(delta).reshape(-1)
+        n = len(q)
+        tt = None if t is None else _d(t).reshape(-1)
+        assert d.size == 6 * n and (tt is None or tt.size == 3 * n)
+        qo, to = np.zeros((n, 4)), None if tt is None else np.zeros(3 * n)
+        _check(self.lib.pgo_sparse_yaw_graph_manifold_plus(self.h, n, _p(q, _dp), None if tt is None else _p(tt, _dp), _p(d, _dp), _p(qo, _dp), None if to is None else _p(to, _dp)))
+        assert not qo[:, 1:].any()
+        return qo[:, 0].copy(), None if to is None else to.reshape(-1, 3)
+
+    def lm_callbacks(self):
+        """(LmCallbacks, user) for SparseLm.solve: this graph's evaluate, normal_blocks and manifold_plus, called from C without a Python frame in between"""
+        cb, user = LmCallbacks(), C.c_void_p()
+        _check(self.lib.pgo_sparse_yaw_graph_lm_callbacks(self.h, C.byref(cb), C.byref(user)))
+        return cb, user
+
+    def edge_lists(self):
+        """of a finalised graph: a dict of node_free, in_system, c1, c2, pair_hi, pair_lo"""
+        cnt = np.zeros(3, np.int64)
+        _check(self.lib.pgo_sparse_yaw_graph_edge_lists(self.h, _p(cnt, _lp), None, None, None, None, None, None))
+        N, E, n_pairs = [int(v) for v in cnt]
+        free, ins = np.zeros(N, np.uint8), np.zeros(N, np.uint8)
+        arrays = [np.zeros(k, np.int32) for k in (E, E, n_pairs, n_pairs)]
+        _check(self.lib.pgo_sparse_yaw_graph_edge_lists(self.h, None, _p(free, _bp), _p(ins, _bp), *[_p(a, _ip) for a in arrays]))
+        out = dict(zip(("c1", "c2", "pair_hi", "pair_lo"), arrays))
+        out.update(node_free=free, in_system=ins)
+        return out
+
+    def last_times(self):
+        """HIP-event milliseconds of the last evaluate: upload of the state, block kernel + cost reduction, node kernel, download"""
+        ms = np.zeros(4)
+        _check(self.lib.pgo_sparse_yaw_graph_last_times(self.h, _p(ms, _dp)))
+        return dict(zip(GRAPH_TIMES, [float(v) for v in ms]))
+
+
+def solve_yaw_graph(G, yaw, t, ordering=ORDER_AUTO, timings=None, **options):
+    """solve_graph over a YawGraph: Ceres' trust-region solve of the reference's 4-DoF problem with every step exact, for graphs of any size -> (yaw, t, capi.Summary);
+    the inputs are not modified.  SparseCholesky and SparseLm are made from G's edge lists, on G's device (the factor works on 6 rows per keyframe, two of them identity
+    rows); options: fields of a default capi.Options (max_num_iterations, function_tolerance, ...)."""
+    from . import capi
+    q, tt = G.pack(yaw), np.array(t, dtype=np.float64).reshape(-1).copy()
+    assert tt.size == 3 * G.n_nodes and len(q) == G.n_nodes
+    o = capi.default_options(**options)
+    e = G.edge_lists()
+    none = np.zeros(0, np.int32)
+    F = SparseCholesky(G.n_nodes, e["in_system"], e["pair_hi"], e["pair_lo"], ordering, G.device_id)
+    try:
+        L = SparseLm(F, e["node_free"], e["c1"], e["c2"], none, none)
+        try:
+            cb, user = G.lm_callbacks()
+            qo, to, _, summ = L.solve(cb, 0, none, q, tt, None, o, user=user)
+            if timings is not None:
+                timings["info"] = F.info()[0]; timings.update(L.last_times())
+        finally:
+            L.close()
+    finally:
+        F.close()
+    qo = qo.reshape(-1, 4)
+    assert not qo[:, 1:].any()
+    return qo[:, 0].copy(), to.reshape(-1, 3), summ
 
 
 @dataclasses.dataclass
